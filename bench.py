@@ -15,7 +15,13 @@ product's C++ writer in Pinot's on-disk layout and copied to HBM by pg_segment_o
 
 Launch:  python bench.py --gpus 1 --steps 20 --warmup 3
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
-Prints ONE JSON line on rank 0.  At N=1 the line also carries
+Prints ONE JSON line on rank 0.  A plain run sets up, steps through the clock settle and the W warm-up steps, times the `--steps` steps
+and prints the headline (`value`, `ms_per_step`, `roofline` from the timed launches, the merged `result`); nothing else is measured.
+`--dump-outputs DIR` writes what the last timed step returned as float64 arrays: DIR/segment_sum.npy and DIR/segment_count.npy (each
+segment's SUM(v) and matched docs, segment order) and DIR/sum.npy, DIR/count.npy (the merged result).  The inputs are generated from
+fixed seeds, so two builds run with the same arguments can be compared output for output.
+Everything else needs `--full` (off by default): `overlapped`, the side files below, and at N=1 the entries below (roofline.frac and
+summary, with the headline alone, are in every line):
   cpu_baseline            the C oracle ("port") on one host core over segment 0's full workload -- it doubles as a parity check
   cpu_baseline_all_cores  the same workload split into one segment per host core (how BaseCombineOperator runs segments)
   parity                  every segment's result against the oracle at full size
@@ -67,7 +73,17 @@ def parse_args():
     ap.add_argument("--single-process", action="store_true",
                     help="the deployment shape: ONE process (a Pinot server is one JVM) drives all --gpus N devices -- segment s resident on device s mod N, "
                          "one pg_execute_batch call per step (launch plain `python bench.py --single-process --gpus N`, no torch.distributed.run)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: CPU baselines, parity against the oracle, the variants, "
+                         "the overlapped step, the cold launch, the streaming-read ceiling, and the side files")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-segment and merged SUM / COUNT to DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.variants and not args.full:
+        ap.error("--variants selects among the variants, which only --full runs")
+    return args
 
 
 def v_dictionary(kind, cardinality=100000, seed=20260921):
@@ -239,6 +255,13 @@ def main():
         for i, s in enumerate(owned):
             per_segment[s] = (vals[2 * i], vals[2 * i + 1])
     merged_sum, merged_count = D.merge_sum_count([per_segment[s] for s in range(num_segments)])
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path received in its last step: each segment's partial and the merged SUM / COUNT
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        outputs = {"segment_sum": [per_segment[s][0] for s in range(num_segments)], "segment_count": [per_segment[s][1] for s in range(num_segments)],
+                   "sum": [merged_sum], "count": [merged_count]}
+        for name, vals in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(vals, dtype=np.float64))
     avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
     avg_query_ms = sum(query_ms) / len(query_ms)
     if single and num_devices > 1:
@@ -249,7 +272,7 @@ def main():
 
     # A query after idle: Pinot's queries arrive whenever they arrive.  >= 1 s without a launch, then ONE query, no settle launches.
     cold = None
-    if rank == 0 and world == 1 and not single:
+    if args.full and rank == 0 and world == 1 and not single:
         cold = []
         for _ in range(3):
             time.sleep(1.2)
@@ -265,7 +288,7 @@ def main():
     # launch, larger ones (the 1 B-row segments of the default run) overlap as launches of their own; (b) the same call with the shared
     # launch switched off.  Reported next to the serial step above (which stays `value`).
     overlapped = None
-    if len(gsegs) > 1 and not (single and num_devices > 1):
+    if args.full and len(gsegs) > 1 and not (single and num_devices > 1):
         nseg = len(gsegs)
         handles = (C.c_void_p * nseg)(*[g.handle for g in gsegs])
         queries = (C.POINTER(_abi.pg_query) * nseg)(*[C.pointer(spec.c) for _ in gsegs])
@@ -355,13 +378,13 @@ def main():
             "setup": {"host_generate_s": gen_s, "segment_open_h2d_s": h2d_s, "device_bytes": device_bytes,
                       "h2d_GBps": device_bytes / h2d_s / 1e9, "host_threads": S.host_threads()},
         }
-        if world == 1:
+        if args.full and world == 1:
             peak = C.c_double()
             if lib.pg_measure_stream_read(local_rank, 4 << 30, 6, C.byref(peak)) == _abi.PG_OK:
                 result["roofline"]["empirical_peak"] = peak.value
                 result["roofline"]["frac_of_empirical_peak"] = achieved / peak.value
                 result["roofline"]["empirical_peak_note"] = "best of 6 launches of a pure 16 B/lane read-reduce kernel over 4 GiB, this run, this box"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle
             ores = _abi.pg_result()
             t0 = time.perf_counter()
@@ -395,7 +418,7 @@ def main():
                                 "check_s": time.perf_counter() - t0}
     for g in gsegs[1:]:
         g.close()
-    if rank == 0 and world == 1 and not args.no_variants:
+    if args.full and rank == 0 and world == 1 and not args.no_variants:
         import re
         from tools import bench_variants
         match = re.compile(args.variants) if args.variants else None
@@ -409,7 +432,10 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and not args.full:
+        from tools import bench_line
+        print(json.dumps(bench_line.compact(result)), flush=True)
+    elif rank == 0:
         # ONE line under 8 KB (tools/bench_line.py): the variants array and the uncut result go to side files under gpurun_out/, the
         # line keeps the contract's keys + config / roofline / cpu_baseline / parity / overlapped, and `summary` as its LAST key:
         # {configuration: [frac of 8 TB/s on all kernels of the query, all_kernels_ms, bit exact vs oracle]} for BASELINE.json configs[0]..[4]

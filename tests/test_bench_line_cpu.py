@@ -82,3 +82,27 @@ def test_side_files(tmp_path):
     v, f = bench_line.write_side_files(r, str(tmp_path))
     assert len(json.load(open(v))) == 3 and json.load(open(f))["roofline"]["frac_note"]
     assert json.load(open(v))[0]["cpu_baseline"]["kind"] == "port"          # C1 / C3 / C5 carry a 1-core port figure in the variants file
+
+
+def test_plain_run_line():
+    """A run without --full measures only the headline: no CPU baselines, parity, variants, cold launch or overlapped step."""
+    r = synthetic_result(0)
+    for k in ("cpu_baseline", "cpu_baseline_all_cores", "cpu_baseline_c1", "parity", "variants", "cold_launch"):
+        r.pop(k)
+    r["cold_launch_ms"] = r["overlapped"] = None
+    for k in ("empirical_peak", "frac_of_empirical_peak", "empirical_peak_note"):
+        r["roofline"].pop(k)
+    back = json.loads(json.dumps(bench_line.compact(r)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert back[k] == bench_line._round(r[k])
+    assert "cpu_baseline" not in back and "parity" not in back and list(back)[-1] == "summary"
+
+
+def test_bench_options(monkeypatch):
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "3", "--full", "--variants", "^C5", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.full and args.variants == "^C5" and args.dump_outputs == "out"

@@ -1,9 +1,10 @@
 #!/bin/bash
-# tools/c5_probe.sh <tag>: index-AND tests, then the C5 variants of bench.py's line (parity on), summarised
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/$1
+# tools/c5_probe.sh <out-dir> [variants regexp]: index-AND tests, then the C5 variants of bench.py --full (parity on), summarised;
+# <out-dir> is taken relative to the repository root
+cd "$(dirname "$0")/.."; mkdir -p "$1"
 timeout 900 python -m pytest tests/test_gpu_index_and.py tests/test_gpu_parity.py -m gpu -x -q -k "index or inverted or and_of" 2>&1 | tail -6
-timeout 900 python bench.py --steps 5 --warmup 2 --variants "${2:-C5}" > gpurun_out/$1/bench.json 2> gpurun_out/$1/bench.err || tail -5 gpurun_out/$1/bench.err
-python - gpurun_out/$1/bench.json <<'PY'
+timeout 900 python bench.py --full --steps 5 --warmup 2 --variants "${2:-C5}" > "$1/bench.json" 2> "$1/bench.err" || tail -5 "$1/bench.err"
+python - "$1/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read())
 for v in d.get("variants", []):

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Round-3 GPU sessions: tools/gpu_r3.sh <step>...   (everything lands under gpurun_out/r3/)
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r3
 mkdir -p $OUT
@@ -26,7 +27,7 @@ testfold)
 ab)
   echo "== A/B =="; timeout 1200 python tools/ab_r3.py ${AB_ARGS:---c5 --check} > $OUT/ab.jsonl 2> $OUT/ab.err; tail -3 $OUT/ab.err; summ $OUT/ab.jsonl ;;
 bench)
-  echo "== bench.py (driver command line) =="; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err
+  echo "== bench.py (driver command line) =="; timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err
   python - <<'PY'
 import json, os
 d = json.load(open(os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out/r3/bench.json")))
@@ -37,7 +38,7 @@ PY
   ;;
 prof)
   echo "== rocprofv3 --kernel-trace --stats of the driver command line =="; cd /tmp && export TMPDIR=/tmp
-  rm -rf $OUT/prof; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline ${PROF_ARGS:-} > $OUT/prof_bench.json 2> $OUT/prof.err
+  rm -rf $OUT/prof; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline ${PROF_ARGS:-} > $OUT/prof_bench.json 2> $OUT/prof.err
   tail -2 $OUT/prof.err; find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -r head -12; cd $GRAFT_REPO_ROOT ;;
 *) echo "unknown step $step" ;;
 esac

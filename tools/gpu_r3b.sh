@@ -25,7 +25,7 @@ PY
   ;;
 batchtrace)
   echo "== host phases of pg_execute_batch (C1x64) =="
-  PINOT_GPU_BATCH_TRACE=1 timeout 600 python bench.py --steps 2 --warmup 1 --segments 1 --rows 1000000 --no-cpu-baseline --no-clock-settle --variants "^C1x64" > $OUT/batch_trace.json 2> $OUT/batch_trace.err
+  PINOT_GPU_BATCH_TRACE=1 timeout 600 python bench.py --full --steps 2 --warmup 1 --segments 1 --rows 1000000 --no-cpu-baseline --no-clock-settle --variants "^C1x64" > $OUT/batch_trace.json 2> $OUT/batch_trace.err
   grep -c "pg_execute_batch" $OUT/batch_trace.err
   grep "pg_execute_batch\|run_deferred" $OUT/batch_trace.err | tail -12 ;;
 batchtest)
@@ -33,7 +33,7 @@ batchtest)
   timeout 300 python tools/stress_concurrency.py 2>&1 | tail -3 ;;
 batchbench)
   echo "== C1x64 variants (driver-style bench line, only these variants) =="
-  timeout 600 python bench.py --steps 3 --warmup 1 --segments 1 --rows 1000000 --no-cpu-baseline --no-clock-settle --variants "^C1x64" > $OUT/bench_c1x64.json 2> $OUT/bench_c1x64.err
+  timeout 600 python bench.py --full --steps 3 --warmup 1 --segments 1 --rows 1000000 --no-cpu-baseline --no-clock-settle --variants "^C1x64" > $OUT/bench_c1x64.json 2> $OUT/bench_c1x64.err
   python - <<'PY'
 import json, os
 d = json.load(open(os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out/r3/bench_c1x64.json")))

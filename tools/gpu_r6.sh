@@ -6,7 +6,7 @@
 #   c5_pmc      FETCH_SIZE of the C5 kernels (tools/profile_round.sh c5)
 #   rank        tools/rank_image_probe.py at 1 B rows (raw DOUBLE, 40-bit LONG)
 #   suite       the whole GPU suite
-#   bench       python bench.py (the driver's line)
+#   bench       python bench.py --full (the line with every variant; its side files land in the step's directory)
 cd $GRAFT_REPO_ROOT; TAG=$1; shift; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 for step in "$@"; do
@@ -62,7 +62,7 @@ for l in sys.stdin:
 batch_tests)
   timeout 1500 python -m pytest tests/test_gpu_batch.py tests/test_gpu_index_and.py tests/test_gpu_kernel_coverage.py -m gpu -x -q 2>&1 | tail -12 | tee $OUT/batch_tests.txt ;;
 c5x64)
-  timeout 1500 python bench.py --steps 3 --warmup 1 --segments 1 --rows 100000 --variants "^C5x64" > $OUT/c5x64_line.json 2> $OUT/c5x64.err; tail -3 $OUT/c5x64.err
+  timeout 1500 python bench.py --full --steps 3 --warmup 1 --segments 1 --rows 100000 --variants "^C5x64" > $OUT/c5x64_line.json 2> $OUT/c5x64.err; tail -3 $OUT/c5x64.err
   python - <<'PY'
 import json
 for v in json.load(open("gpurun_out/bench_variants.json")):
@@ -88,7 +88,7 @@ rank)
 suite)
   timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 | tee $OUT/gpu_suite.txt ;;
 bench)
-  timeout 1500 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; tail -c 3600 $OUT/bench_line.json; cp gpurun_out/bench_variants.json $OUT/bench_variants.json 2>/dev/null; cp gpurun_out/bench_full.json $OUT/bench_full.json 2>/dev/null ;;
+  PINOT_BENCH_OUT=$OUT timeout 1500 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; tail -c 3600 $OUT/bench_line.json ;;
 *) echo "unknown step $step" ;;
 esac
 echo "--- $step took $(( $(date +%s) - t0 )) s"

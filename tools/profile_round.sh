@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/profile_round.sh <round> [step...]: the rocprofv3 evidence of a round, left under gpurun_out/<round>/ (copy what is to be judged into profiles/<round>/)
-#   stats     kernel trace + stats of the driver's own command line (python bench.py, all variants)
+#   stats     kernel trace + stats of python bench.py --full (the headline and all variants)
 #   head      HBM traffic of the headline kernel (FETCH_SIZE, TCC) -- separate --pmc passes, as MI355X_MICROARCH.md prescribes
 #   c3        SQ / LDS counters and HBM traffic of the C3 group-by kernel
 #   c5        HBM traffic of the C5 kernels (index_and_kernel, scan_sparse_kernel), one counter per pass
@@ -9,6 +9,7 @@
 # no step = stats head c3 c5
 R=${1:-r2}; shift
 STEPS=${@:-stats head c3 c5}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$R; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 pmc() {   # pmc <tag> <kernel regexp> <bench args> <counters...>
@@ -40,12 +41,12 @@ PY
   done
   find $OUT/pmc_$tag -name "*.csv" -size +8M -delete
 }
-ONE="--steps 3 --warmup 1 --segments 1 --no-cpu-baseline"
+ONE="--full --steps 3 --warmup 1 --segments 1 --no-cpu-baseline"
 for step in $STEPS; do
 case $step in
 stats)
-  echo "== kernel stats, python bench.py (all variants)"
-  timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $GRAFT_REPO_ROOT/bench.py > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+  echo "== kernel stats, python bench.py --full (all variants)"
+  timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python "$ROOT/bench.py" --full > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
   find $OUT/stats -name "*kernel_stats*.csv" -exec cat {} \; | cut -c1-200 | head -24
   find $OUT/stats -name "*kernel_trace*.csv" -size +8M -delete ;;
 head)
@@ -62,11 +63,11 @@ c3lds)
   pmc c3_sq "group_private_kernel" "$ONE --variants ^C3$" SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE ;;
 c5)
   echo "== C5 kernels: HBM traffic (one counter per pass)"
-  pmc c5_fetch "index_and|scan_private_kernel|scan_sparse" "--steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-dense$" FETCH_SIZE
-  pmc c5s_fetch "index_and|scan_private_kernel|scan_sparse" "--steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-sparse$" FETCH_SIZE ;;
+  pmc c5_fetch "index_and|scan_private_kernel|scan_sparse" "--full --steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-dense$" FETCH_SIZE
+  pmc c5s_fetch "index_and|scan_private_kernel|scan_sparse" "--full --steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-sparse$" FETCH_SIZE ;;
 c5s_sq)
   echo "== what index_and_kernel's wavefronts do with their time (C5-sparse-count: the AND alone)"
-  C5S="--steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-sparse-count$"
+  C5S="--full --steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-sparse-count$"
   pmc c5s_sq "index_and_kernel" "$C5S" SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD
   pmc c5s_sq2 "index_and_kernel" "$C5S" SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS
   pmc c5s_sq3 "index_and_kernel" "$C5S" GRBM_GUI_ACTIVE SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_BRANCH ;;
@@ -75,7 +76,7 @@ hist)
   pmc hist_fetch "scan_hist_kernel" "$ONE --variants ^C2b-irregular$" FETCH_SIZE ;;
 narrow)
   echo "== scan_narrow_kernel (C5-scan-count): HBM traffic"
-  pmc narrow_fetch "scan_narrow" "--steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-scan-count$" FETCH_SIZE ;;
+  pmc narrow_fetch "scan_narrow" "--full --steps 2 --warmup 1 --segments 1 --no-cpu-baseline --rows 100000 --rows-c5 1000000000 --variants ^C5-scan-count$" FETCH_SIZE ;;
 lowsel)
   echo "== scan_private_kernel at 1 % (C2b-1pct): HBM traffic"
   PMC_LAST=40 pmc lowsel_fetch "scan_simple_kernel|scan_private_kernel" "$ONE --no-clock-settle --variants ^C2b-1pct$" FETCH_SIZE ;;
@@ -83,7 +84,7 @@ per-variant)
   echo "== kernel stats, one variant per run"
   for v in C2b-irregular C2b-1pct C2a-affine C3 C3-filter COUNT-filter; do
     rm -rf $OUT/stats_$v
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$v -o v -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --segments 1 --no-cpu-baseline --variants "^$v\$" > $OUT/stats_$v.json 2> $OUT/stats_$v.err
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$v -o v -- python "$ROOT/bench.py" --full --steps 3 --warmup 1 --segments 1 --no-cpu-baseline --variants "^$v\$" > $OUT/stats_$v.json 2> $OUT/stats_$v.err
     echo "-- $v"; find $OUT/stats_$v -name "*kernel_stats*.csv" -exec cat {} \; | cut -c1-160 | head -4
     find $OUT/stats_$v -name "*kernel_trace*.csv" -delete
   done ;;
