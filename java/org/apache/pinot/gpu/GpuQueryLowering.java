@@ -529,13 +529,14 @@ final class GpuQueryLowering {
         int u = upperUnbounded ? Integer.MAX_VALUE : Integer.parseInt(upper);
         if (!lowerUnbounded && !lowerInclusive) {
           if (l == Integer.MAX_VALUE) {
-            return constant(exclusive);
+            // Preconditions.checkArgument in the reference's evaluator: the CPU plan raises its "Invalid range"
+            throw new NotOffloadable("Invalid range");
           }
           l++;
         }
         if (!upperUnbounded && !upperInclusive) {
           if (u == Integer.MIN_VALUE) {
-            return constant(exclusive);
+            throw new NotOffloadable("Invalid range");
           }
           u--;
         }
@@ -548,13 +549,14 @@ final class GpuQueryLowering {
         long u = upperUnbounded ? Long.MAX_VALUE : Long.parseLong(upper);
         if (!lowerUnbounded && !lowerInclusive) {
           if (l == Long.MAX_VALUE) {
-            return constant(exclusive);
+            // Preconditions.checkArgument in the reference's evaluator: the CPU plan raises its "Invalid range"
+            throw new NotOffloadable("Invalid range");
           }
           l++;
         }
         if (!upperUnbounded && !upperInclusive) {
           if (u == Long.MIN_VALUE) {
-            return constant(exclusive);
+            throw new NotOffloadable("Invalid range");
           }
           u--;
         }
@@ -567,10 +569,19 @@ final class GpuQueryLowering {
         float l = lowerUnbounded ? Float.NEGATIVE_INFINITY : Float.parseFloat(lower);
         float u = upperUnbounded ? Float.POSITIVE_INFINITY : Float.parseFloat(upper);
         if (!lowerUnbounded && !lowerInclusive) {
-          l = Math.nextUp(l);
+          float up = Math.nextUp(l);
+          if (!(up > l)) {
+            // +inf or NaN does not move: Preconditions.checkArgument in the reference's evaluator, left to the CPU plan
+            throw new NotOffloadable("Invalid range");
+          }
+          l = up;
         }
         if (!upperUnbounded && !upperInclusive) {
-          u = Math.nextDown(u);
+          float down = Math.nextDown(u);
+          if (!(down < u)) {
+            throw new NotOffloadable("Invalid range");
+          }
+          u = down;
         }
         lo = Double.doubleToRawLongBits((double) l);
         hi = Double.doubleToRawLongBits((double) u);
@@ -580,10 +591,19 @@ final class GpuQueryLowering {
         double l = lowerUnbounded ? Double.NEGATIVE_INFINITY : Double.parseDouble(lower);
         double u = upperUnbounded ? Double.POSITIVE_INFINITY : Double.parseDouble(upper);
         if (!lowerUnbounded && !lowerInclusive) {
-          l = Math.nextUp(l);
+          double up = Math.nextUp(l);
+          if (!(up > l)) {
+            // +inf or NaN does not move: Preconditions.checkArgument in the reference's evaluator, left to the CPU plan
+            throw new NotOffloadable("Invalid range");
+          }
+          l = up;
         }
         if (!upperUnbounded && !upperInclusive) {
-          u = Math.nextDown(u);
+          double down = Math.nextDown(u);
+          if (!(down < u)) {
+            throw new NotOffloadable("Invalid range");
+          }
+          u = down;
         }
         lo = Double.doubleToRawLongBits(l);
         hi = Double.doubleToRawLongBits(u);

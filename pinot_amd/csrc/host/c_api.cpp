@@ -465,8 +465,10 @@ char* ph_lower_range_predicate(const void* dict, int32_t cardinality, const char
   return *status == 0 ? strdup(out.c_str()) : nullptr;
 }
 
-// A RangePredicate on a RAW (no-dictionary) INT (data_type 0) or LONG (1) column: RangePredicateEvaluatorFactory.newRawValueBasedEvaluator;
-// the evaluator matches lower <= value <= upper (both inclusive after the exclusive bounds were stepped inwards)
+// A RangePredicate on a RAW (no-dictionary) INT (data_type 0), LONG (1), FLOAT (2) or DOUBLE (3) column:
+// RangePredicateEvaluatorFactory.newRawValueBasedEvaluator; the evaluator matches lower <= value <= upper (both inclusive after the exclusive
+// bounds were stepped inwards).  FLOAT / DOUBLE: rawLower / rawUpper are the bit patterns of the double bounds (as the ABI carries them),
+// "lower" / "upper" the same bounds printed with %.17g.
 char* ph_lower_raw_range_predicate(int32_t data_type, const char* lower, int32_t lower_inclusive, const char* upper, int32_t upper_inclusive, int32_t* status) {
   std::string out;
   *status = guarded([&] {
@@ -478,11 +480,21 @@ char* ph_lower_raw_range_predicate(int32_t data_type, const char* lower, int32_t
     DataSource ds;
     ds.name = p.column;
     ds.hasDictionary = false;
-    ds.dataType = data_type == 1 ? DataType::LONG : DataType::INT;
+    static const DataType types[] = {DataType::INT, DataType::LONG, DataType::FLOAT, DataType::DOUBLE};
+    if (data_type < 0 || data_type > 3) throw QueryException("raw range predicates take data types 0..3 (INT, LONG, FLOAT, DOUBLE)");
+    ds.dataType = types[data_type];
     const PredicateEvaluator ev = getPredicateEvaluator(p, ds);
     std::ostringstream o;
     o << "{\"alwaysTrue\": " << (ev.alwaysTrue ? "true" : "false") << ", \"alwaysFalse\": " << (ev.alwaysFalse ? "true" : "false")
-      << ", \"rawLower\": " << ev.rawLower << ", \"rawUpper\": " << ev.rawUpper << "}";
+      << ", \"rawLower\": " << ev.rawLower << ", \"rawUpper\": " << ev.rawUpper;
+    if (ev.rawFloating) {
+      double lo, hi;
+      char buf[64];
+      memcpy(&lo, &ev.rawLower, 8); memcpy(&hi, &ev.rawUpper, 8);
+      snprintf(buf, sizeof(buf), "%.17g", lo); o << ", \"lower\": \"" << buf << "\"";
+      snprintf(buf, sizeof(buf), "%.17g", hi); o << ", \"upper\": \"" << buf << "\"";
+    }
+    o << "}";
     out = o.str();
   });
   return *status == 0 ? strdup(out.c_str()) : nullptr;

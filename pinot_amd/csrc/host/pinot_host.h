@@ -256,7 +256,8 @@ struct PredicateEvaluator {                          // operator/filter/predicat
   bool isRange = false;                              // dictId range [startDictId, endDictId)
   int startDictId = 0, endDictId = 0;
   std::vector<int> matchingDictIds;                  // sorted (IN / NOT_IN inner set)
-  bool rawRange = false; int64_t rawLower = 0, rawUpper = 0;   // raw INT columns: inclusive bounds
+  bool rawRange = false; int64_t rawLower = 0, rawUpper = 0;   // raw INT / LONG columns: inclusive bounds
+  bool rawFloating = false;                          // raw FLOAT / DOUBLE: rawLower / rawUpper hold the bit patterns of inclusive double bounds
   int getNumMatchingItems() const;
 };
 // PredicateEvaluatorProvider.getPredicateEvaluator (operator/filter/predicate/PredicateEvaluatorProvider.java)

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cctype>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -93,6 +94,36 @@ bool parseFloating(const std::string& s, double* out) {
   char* end = nullptr;
   errno = 0;
   const double v = strtod(s.c_str(), &end);
+  if (*end != 0) return false;
+  *out = v;
+  return true;
+}
+// Float.parseFloat / Double.parseDouble (FloatingDecimal.readJavaFormatString): surrounding blanks trimmed, an optional sign, "Infinity" /
+// "NaN" spelled out (what String.format("%f") prints for the infinities), decimal or hexadecimal digits, an optional f / F / d / D suffix.
+// A float is rounded once, from the decimal text (strtof), never through double.
+bool parseJavaFloating(const std::string& text, bool isFloat, double* out) {
+  size_t b = 0, e = text.size();
+  while (b < e && (unsigned char)text[b] <= ' ') ++b;
+  while (e > b && (unsigned char)text[e - 1] <= ' ') --e;
+  std::string s = text.substr(b, e - b);
+  if (s.empty()) return false;
+  const size_t body = (s[0] == '+' || s[0] == '-') ? 1 : 0;
+  const std::string word = s.substr(body);
+  if (word == "Infinity" || word == "NaN") {
+    const double v = word == "NaN" ? NAN : INFINITY;
+    *out = s[0] == '-' ? -v : v;
+    return true;
+  }
+  const bool hex = word.size() > 1 && word[0] == '0' && (word[1] == 'x' || word[1] == 'X');
+  if (!hex && (s.back() == 'f' || s.back() == 'F' || s.back() == 'd' || s.back() == 'D')) s.pop_back();
+  for (char c : s.substr(body)) {       // strtod's own spellings ("inf", "nan(...)") are not Java's
+    if (!(isdigit((unsigned char)c) || c == '.' || c == 'e' || c == 'E' || c == '+' || c == '-' ||
+          (hex && (isxdigit((unsigned char)c) || c == 'x' || c == 'X' || c == 'p' || c == 'P'))))
+      return false;
+  }
+  if (s.size() == body) return false;
+  char* end = nullptr;
+  const double v = isFloat ? (double)strtof(s.c_str(), &end) : strtod(s.c_str(), &end);
   if (*end != 0) return false;
   *out = v;
   return true;
@@ -501,6 +532,45 @@ PredicateEvaluator getPredicateEvaluator(const Predicate& predicate, const DataS
   // operators over the null value vector (lowerFilter does the same before it gets here)
   if (predicate.type == Predicate::Type::IS_NULL || predicate.type == Predicate::Type::IS_NOT_NULL)
     throw QueryException("IS NULL / IS NOT NULL are evaluated on the null value vector, not through a predicate evaluator");
+  if (!ds.hasDictionary && (ds.dataType == DataType::FLOAT || ds.dataType == DataType::DOUBLE)) {
+    // raw FLOAT / DOUBLE column: Float / DoubleRawValueBasedRangePredicateEvaluator (RangePredicateEvaluatorFactory.java:84-91,446-520)
+    // and the raw EQ / NOT_EQ evaluators (primitive ==, !=).  A FLOAT literal is parsed straight to float (Float.parseFloat, not through
+    // double), an exclusive bound is stepped with Math.nextUp / nextDown in the column's precision and then widened to double; a step
+    // that does not move (+-inf, NaN) is "Invalid range" (Preconditions.checkArgument).  The bounds travel as double bit patterns.
+    const bool isFloat = ds.dataType == DataType::FLOAT;
+    auto toFp = [isFloat](const std::string& s) {
+      double v;
+      if (!parseJavaFloating(s, isFloat, &v)) throw QueryException("Cannot convert value: '" + s + "' to " + (isFloat ? "FLOAT" : "DOUBLE"));
+      return v; };
+    auto step = [isFloat](double v, double toward) { return isFloat ? (double)nextafterf((float)v, (float)toward) : nextafter(v, toward); };
+    double lo = 0.0, hi = 0.0;
+    ev.rawRange = ev.rawFloating = true;
+    if (predicate.type == Predicate::Type::RANGE) {
+      const bool lowerUnbounded = predicate.lowerBound == "*", upperUnbounded = predicate.upperBound == "*";
+      lo = lowerUnbounded ? -INFINITY : toFp(predicate.lowerBound);
+      hi = upperUnbounded ? INFINITY : toFp(predicate.upperBound);
+      if (!lowerUnbounded && !predicate.lowerInclusive) {
+        const double up = step(lo, INFINITY);
+        if (!(up > lo)) throw QueryException("Invalid range");
+        lo = up;
+      }
+      if (!upperUnbounded && !predicate.upperInclusive) {
+        const double down = step(hi, -INFINITY);
+        if (!(down < hi)) throw QueryException("Invalid range");
+        hi = down;
+      }
+    } else if (predicate.type == Predicate::Type::EQ || predicate.type == Predicate::Type::NOT_EQ) {
+      lo = hi = toFp(predicate.values.at(0));
+      ev.exclusive = predicate.type == Predicate::Type::NOT_EQ;
+    } else {
+      throw UnsupportedOperationException("IN / NOT IN on a raw column is not offloaded");
+    }
+    memcpy(&ev.rawLower, &lo, 8);
+    memcpy(&ev.rawUpper, &hi, 8);
+    // compared as doubles: a NaN bound is neither, the device's primitive compares then match nothing (EQ, RANGE) or everything (NOT_EQ)
+    if (lo > hi) { if (ev.exclusive) ev.alwaysTrue = true; else ev.alwaysFalse = true; }
+    return ev;
+  }
   if (!ds.hasDictionary) {
     // raw INT / LONG column: Int / LongRawValueBasedRangePredicateEvaluator (RangePredicateEvaluatorFactory.java:68-81,331-446);
     // EQ is the degenerate range, the other raw evaluators are not offloaded.

@@ -580,8 +580,6 @@ def test_narrow_and_typed_items_share_launches(engine, shapes):
     """Items of scan_narrow_kernel's, scan_narrow_single_kernel's and scan_private_typed_kernel's shape: a launch per kind (the mixed batch
     is five launches), same answers as the oracle and as pg_execute, twice (the second call through the plan cache)."""
     segs = _narrow_typed_segments()
-    if not hasattr(Q, "not_"):
-        pytest.skip("no NOT constructor")
     opened = [engine.open(seg) for seg in segs]
     try:
         specs = [_narrow_typed_spec(seg, s, shapes[s % len(shapes)]) for s, seg in enumerate(segs)]

@@ -185,6 +185,79 @@ def test_raw_range_evaluator_cases_of_the_reference_test(data_type, type_min, ty
     assert all(open_extremes(i) for i in range(-20, 20)) and not open_extremes(type_min) and not open_extremes(type_max)
 
 
+@pytest.mark.parametrize("data_type, np_type", [(2, np.float32), (3, np.float64)])
+def test_raw_floating_range_evaluator_cases_of_the_reference_test(data_type, np_type):
+    """NoDictionaryRangePredicateEvaluatorTest.java:143-250 (testFloatPredicateEvaluator / testDoublePredicateEvaluator): every bound shape of a
+    range on a raw FLOAT / DOUBLE column, applied to -20..19 and to the infinities; (String.format("%f", -inf), String.format("%f", +inf)) is
+    "(-Infinity, Infinity)" and excludes both.  The evaluator's bounds are the double bit patterns the ABI carries."""
+    from test_oracle_range_not_queries import bits_to_f64, lower_raw
+
+    def evaluator(lower, incl_lower, upper, incl_upper):
+        ev = lower_raw(data_type, lower, incl_lower, upper, incl_upper)
+        lo, hi = bits_to_f64(ev["rawLower"]), bits_to_f64(ev["rawUpper"])
+        assert ev["lower"] == "%.17g" % lo and ev["upper"] == "%.17g" % hi
+        return lambda v: (not ev["alwaysFalse"]) and lo <= float(np_type(v)) <= hi
+
+    for bounds, want in (((-10, True, 10, True), lambda i: -10 <= i <= 10), ((-10, False, 10, True), lambda i: -10 < i <= 10),
+                         ((-10, False, 10, False), lambda i: -10 < i < 10), (("*", False, 10, True), lambda i: i <= 10),
+                         (("*", False, 10, False), lambda i: i < 10), ((10, True, "*", True), lambda i: i >= 10),
+                         ((10, False, "*", False), lambda i: i > 10), (("*", False, "*", False), lambda i: True)):
+        apply_sv = evaluator(*bounds)
+        assert all(apply_sv(i) == want(i) for i in range(-20, 20)), bounds
+    unbounded = evaluator("*", False, "*", False)
+    assert unbounded(-np.inf) and unbounded(np.inf)
+    open_infinities = evaluator("-Infinity", False, "Infinity", False)
+    assert all(open_infinities(i) for i in range(-20, 20)) and not open_infinities(-np.inf) and not open_infinities(np.inf)
+    # Math.nextUp / nextDown of an infinity (or NaN) does not move: Preconditions.checkArgument -> "Invalid range"
+    for bounds in (("Infinity", False, "*", False), ("*", False, "-Infinity", False), ("NaN", False, "*", False), ("*", False, "NaN", False)):
+        with pytest.raises(host.HostError, match="Invalid range"):
+            lower_raw(data_type, *bounds)
+
+
+def test_raw_floating_range_precision():
+    """A FLOAT literal is parsed to float (Float.parseFloat) and an exclusive bound stepped in float precision; a DOUBLE stays double.  Expected
+    values: numpy primitive compares on np.float32(literal) / np.float64(literal)."""
+    from test_oracle_range_not_queries import bits_to_f64, lower_raw
+    f32, inf = np.float32, np.inf
+    rng = np.random.default_rng(5)
+    fv = np.concatenate([rng.uniform(-1, 1, 4000).astype(np.float32), np.array([0.1, 0.3, 0.7, -0.0, 0.0, inf, -inf, np.nan], dtype=np.float32)])
+    for x in (f32("0.1"), f32("0.3"), f32("0.7")):
+        fv = np.concatenate([fv, [np.nextafter(x, f32(inf)), np.nextafter(x, f32(-inf)), x]]).astype(np.float32)
+    dv = np.concatenate([fv.astype(np.float64), [0.1, np.nextafter(0.1, inf), np.nextafter(0.1, -inf), 5e-324, -5e-324]])
+
+    def count(dt, values, lower, li, upper, ui):
+        ev = lower_raw(dt, lower, li, upper, ui)
+        lo, hi = bits_to_f64(ev["rawLower"]), bits_to_f64(ev["rawUpper"])
+        wide = values.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            return 0 if ev["alwaysFalse"] else int(((wide >= lo) & (wide <= hi)).sum())
+
+    with np.errstate(invalid="ignore"):
+        assert count(2, fv, "0.1", False, "*", False) == int((fv > f32("0.1")).sum())
+        assert count(2, fv, "*", False, "0.3", True) == int((fv <= f32("0.3")).sum())
+        assert count(2, fv, "0.7", True, "0.7", True) == int((fv == f32("0.7")).sum())
+        assert count(2, fv, "0.1", True, "0.3", True) == int(((fv >= f32("0.1")) & (fv <= f32("0.3"))).sum())
+        assert count(3, dv, "0.1", False, "*", False) == int((dv > 0.1).sum())
+        # the stepped FLOAT bound is nextUp in float precision: a double step would let float32(0.1) itself through
+        assert count(2, fv, "0.1", False, "*", False) != int((fv.astype(np.float64) > float(np.nextafter(np.float64(f32("0.1")), -inf))).sum())
+        for lo_lit in ("0.0", "-0.0"):
+            for li in (True, False):
+                assert count(2, fv, lo_lit, li, "*", False) == int(((fv >= f32(lo_lit)) if li else (fv > f32(lo_lit))).sum()), (lo_lit, li)
+                assert count(3, dv, "*", False, lo_lit, li) == int(((dv <= float(lo_lit)) if li else (dv < float(lo_lit))).sum()), (lo_lit, li)
+    ev = lower_raw(2, "0.1", False, "*", False)
+    assert bits_to_f64(ev["rawLower"]) == float(np.nextafter(f32("0.1"), f32(inf)))
+    with pytest.raises(host.HostError, match="Invalid range"):
+        lower_raw(2, "Infinity", False, "*", False)
+    # NaN bounds compare as doubles (a NaN bound is never greater than the other): not alwaysFalse, and the device's compares match nothing
+    ev = lower_raw(3, "NaN", True, "*", False)
+    assert not ev["alwaysFalse"] and not ev["alwaysTrue"] and np.isnan(bits_to_f64(ev["rawLower"]))
+    # rawLower > rawUpper is decided on doubles: -2.0 < -1.0 although their bit patterns, as int64, order the other way
+    ev = lower_raw(3, "-2.0", True, "-1.0", True)
+    assert not ev["alwaysFalse"] and ev["rawLower"] > ev["rawUpper"]
+    assert lower_raw(3, "1.0", True, "-1.0", True)["alwaysFalse"]
+    assert lower_raw(2, "-0.0", False, "0.0", False)["alwaysFalse"]
+
+
 def test_sql_parser_never_crashes_on_mutated_queries():
     """The SQL subset is a test vehicle, but it reads untrusted text: every mutation of valid queries must come back as a parsed query or as
     one of the three error classes (1 QueryException, 2 UnsupportedOperationException, 3 other std::exception), never a crash."""
