@@ -229,8 +229,8 @@ struct ScanParams {
   int32_t sparse_num_windows;
   int32_t set_leaves_in_lds;       // scan_private_*: 1 = the filter's dictId sets (IN lists) are staged in LDS once per workgroup (pg_kernels.h stage_filter_sets)
   uint8_t fsm_delta[64];                     // [state << 4 | input]: next state | entries << 4 (pg_filter_fsm.h's delta, four input bits wide)
-  int32_t lean_kind;               // pg_execute_batch: 0 the general lane-private body, 1 the item has scan_simple_kernel's shape, 2 scan_raw_kernel's, 13 scan_simple_set_kernel's (3..12: pg_engine.hip "kinds of shared launch")
-                                   // (scan_lean_batch_kernel runs those at five waves per SIMD)
+  int32_t lean_kind;               // pg_execute_batch: the item's kind of shared launch, a value of pg_engine.hip's BatchKind (Private 0, Simple 1, Raw 2,
+                                   // SimpleSet 13: scan_lean_batch_kernel runs those three at five waves per SIMD)
 };
 
 // What a query's scan brings back to the host: the folded record, then a sequence number written after it.

@@ -1609,6 +1609,14 @@ struct Geometry {
 
 constexpr size_t kLdsBudget = 156 * 1024;     // of the 160 KiB per CU; leaves room for the runtime's own use
 
+static long long doc_tiles(const pg_segment* seg) { return ((long long)seg->num_docs + 2047) / 2048; }      // the segment's 2048-doc tiles
+// A persistent grid: one workgroup per `per_block` units of work (tiles, or runs of them), at least one, at most `bpc` per CU.
+// PINOT_GPU_BLOCKS_PER_CU (g_engine.blocks_per_cu) replaces `bpc` unless the launch is not `overridable`.
+static int grid_blocks(const pg_segment* seg, long long units, long long per_block, int bpc, bool overridable = true) {
+  if (overridable && g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
+  return (int)std::max<long long>(1, std::min<long long>((units + per_block - 1) / per_block, (long long)seg->num_cus * bpc));
+}
+
 // Lays out the per-wave LDS region (one staging slot per packed column, 256 bytes per bitmap leaf, the gather queue),
 // then picks tile size (32 or 16 steps) and workgroup size so that the most wavefronts stay resident per CU within the
 // LDS budget, and sizes the grid to exactly what is co-resident (a persistent grid: a grid larger than residency runs
@@ -1713,11 +1721,7 @@ void finish_geometry(const pg_segment* seg, Lowered* lw, size_t table_bytes, boo
   g->threads = best_waves * 64;
   g->lds = (size_t)best_waves * sp.wave_lds_bytes + (best_table ? table_bytes : 0);
   g->lds = std::max(g->lds, sizeof(BlockPartial) * (size_t)best_waves + 16);      // the waves' records + the fold flag (publish_block_partial)
-  int bpc = std::max(1, std::min(wave_cap / best_waves, (int)(kLdsBudget / g->lds)));
-  if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-  const long long want = ((long long)sp.num_tiles + best_waves - 1) / best_waves;
-  const long long cap = (long long)seg->num_cus * bpc;
-  g->blocks = (int)std::max<long long>(1, std::min(want, cap));
+  g->blocks = grid_blocks(seg, sp.num_tiles, best_waves, std::max(1, std::min(wave_cap / best_waves, (int)(kLdsBudget / g->lds))));
   flatten_plan(lw);
 }
 
@@ -2574,6 +2578,38 @@ static void finish_filter_stats(const Lowered& lw, const pg_segment* seg, int64_
 // conversion of the folded record into a pg_result; the batch puts many of them into one launch (scan_private_batch_kernel).
 static const pg_status kDeferred = static_cast<pg_status>(100);      // (internal: never leaves the library)
 static const pg_status kRunAlone = static_cast<pg_status>(101);      // (internal: a batch item whose shared launch could not answer it -- pg_execute_batch runs it by itself)
+static const pg_status kHistRetry = static_cast<pg_status>(102);     // (internal: the histogram's counters could not answer -- execute_impl answers the query again)
+// Kinds of shared launch (ScanParams.lean_kind): pg_execute_batch groups a batch's deferred items by device and kind, one launch each.
+// Private: scan_private_batch_kernel (the general lane-private body); Simple / Raw / SimpleSet: scan_lean_batch_kernel<1 | 2 | 13> (the
+// scan_simple / scan_raw shape, 13 with its one set leaf in LDS); Hist*: scan_hist_batch_kernel<8 | 16 | 32> (plain counters); GroupLds:
+// group_lds_batch_kernel; Narrow*: scan_narrow_batch_kernel<general | single leaf>; Typed*: scan_typed_batch_kernel<1 | 2 | kMaxAggCols>
+// (raw and 8-byte aggregated columns); IndexAnd: index_and_batch_kernel (the item's whole device work is index_and_kernel).
+enum class BatchKind : int32_t { Private = 0, Simple = 1, Raw = 2, Hist8 = 3, Hist16 = 4, Hist32 = 5, GroupLds = 6, Narrow = 7, NarrowSingle = 8,
+                                 Typed1 = 9, Typed2 = 10, TypedMax = 11, IndexAnd = 12, SimpleSet = 13 };
+// What enqueue_deferred needs of a scan kind: workgroup waves, tiles a wave takes per iteration (the narrow kernels walk four / eight), counter
+// bits, typed slots, and the waves per CU its kernel holds (0: Private, sized by PINOT_GPU_BATCH_BLOCKS_PER_CU).  GroupLds / IndexAnd: none.
+struct BatchKindInfo { int block_waves = kBlockThreads / 64, tiles_per_wave = 1, hist_bits = 0, typed_slots = 0, wave_cap = 0; };
+static BatchKindInfo batch_kind_info(BatchKind kind) {
+  BatchKindInfo i;
+  switch (kind) {
+    case BatchKind::Hist8: case BatchKind::Hist16: case BatchKind::Hist32:
+      i.block_waves = kHistBlockThreads / 64; i.hist_bits = kind == BatchKind::Hist8 ? 8 : (kind == BatchKind::Hist16 ? 16 : 32); i.wave_cap = waves_scan_hist_batch(i.hist_bits); break;
+    case BatchKind::Narrow: case BatchKind::NarrowSingle:
+      i.tiles_per_wave = kind == BatchKind::Narrow ? kNarrowTiles : kNarrowSingleTiles; i.wave_cap = waves_scan_narrow_batch(kind == BatchKind::NarrowSingle); break;
+    case BatchKind::Typed1: case BatchKind::Typed2: case BatchKind::TypedMax:
+      i.typed_slots = kind == BatchKind::Typed1 ? 1 : (kind == BatchKind::Typed2 ? 2 : kMaxAggCols); i.wave_cap = waves_scan_typed_batch(i.typed_slots); break;
+    case BatchKind::Simple: case BatchKind::Raw: case BatchKind::SimpleSet: i.wave_cap = waves_scan_lean_batch((int)kind); break;
+    default: break;
+  }
+  return i;
+}
+static void launch_batch_kind(BatchKind kind, const BatchKindInfo& i, bool one_slot, int blocks, size_t lds, hipStream_t stream, const ScanParams* items, const uint32_t* first, int n) {
+  if (i.hist_bits) launch_scan_hist_batch(i.hist_bits, blocks, lds, stream, items, first, n);
+  else if (i.tiles_per_wave > 1) launch_scan_narrow_batch(kind == BatchKind::NarrowSingle, blocks, stream, items, first, n);
+  else if (i.typed_slots) launch_scan_typed_batch(i.typed_slots, blocks, stream, items, first, n);
+  else if (kind != BatchKind::Private) launch_scan_lean_batch((int)kind, blocks, stream, items, first, n);
+  else launch_scan_private_batch(one_slot, blocks, stream, items, first, n);
+}
 // A query lowered for the shared launch of pg_execute_batch: the kernel's parameter block (the launch fills in where this item's records
 // go), the workgroups it would get on its own, and the conversion of its folded record into the reference's holder types.  Immutable
 // once built: the segment's plan_cache hands the same item to later batches.
@@ -2673,625 +2709,525 @@ static inline void exec_mark(int i) {
 
 static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out, unsigned long long* d_out_bitmap_request,
                               uint64_t* host_bitmap, int64_t host_bitmap_words, int64_t* out_cardinality, bool allow_metadata_plan = true,
-                              Deferred* defer = nullptr, FsmSide* side = nullptr) {
-  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
-  if (!seg || !q) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
-  // d_out_bitmap_request: like host_bitmap, but the filter's doc-order bitmap is copied device to device into the caller's
-  // buffer ((num_docs + 63) / 64 words, any stream-ordered device memory) and never visits the host.
-  {
-    pg_query shape = *q;                      // pg_filter_bitmap evaluates the filter only
-    if (host_bitmap != nullptr || d_out_bitmap_request != nullptr) { shape.num_aggregations = 0; shape.num_group_by = 0; }
-    const pg_status eligible = check_query_plan(seg, &shape, 0);
-    if (eligible != PG_OK) return eligible;
+                              Deferred* defer = nullptr, FsmSide* side = nullptr);
+
+// ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
+// preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, Raw, PrivateFsm, Private, PrivateTyped, Agg };
+// per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
+// leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
+static const struct { int id; bool writes_leaves; } kScanKernels[] = {
+  {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
+  {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
+  {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_AGG, false}};
+static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
+// general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
+// specialised kernel that won keeps it: the index handling, the leap-frog count and the batch's fallbacks go by the family.
+struct ScanChoice {
+  ScanKernel kernel = ScanKernel::Agg, general = ScanKernel::Agg;
+  int hist_slot = -1, hist_cw = 0;         // Hist: the aggregation slot the histogram counts, its counter bits ...
+  bool hist_guarded = false;               // ... and whether they are the guarded tier's
+};
+static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, int hist_col, bool typed, bool want_bitmap, bool want_result) {
+  const PlanParams& pl = lw.plan; const ScanParams& sp = lw.sp;
+  const bool profile = (g_engine.flags & PG_CFG_PROFILE_WAVES) != 0;
+  ScanChoice k;
+  auto pick = [&k](ScanKernel kernel) { k.kernel = kernel; return k; };
+  // The lane-private kernel (no LDS, plain global loads) takes every query whose leaves and aggregations it implements:
+  // scan / set / bitmap leaves and raw INT ranges; COUNT, and SUM through a value plane / MIN / MAX on dictionary columns.
+  // (the per-wave phase counters of PG_CFG_PROFILE_WAVES exist in the LDS-staged kernel only)
+  bool private_leaves = true;
+  for (int l = 0; l < pl.num_leaves; ++l) private_leaves &= pl.leaves[l].kind <= kLeafBitmap || pl.leaves[l].kind == kLeafDocRange;
+  bool lane_private = g_engine.scan_private && !typed && !profile && private_leaves;
+  for (int i = 0; i < pl.num_agg_cols && hist_col >= 0; ++i) if (lw.col_of_slot[(size_t)pl.agg_cols[i].col] == hist_col * 2) k.hist_slot = i;
+  for (int i = 0; i < pl.num_agg_cols && lane_private; ++i) {
+    const DevColumn& c = pl.cols[pl.agg_cols[i].col];
+    lane_private = !c.is_raw && c.vkind == kValI32 && c.bits <= 31 && (!pl.agg_cols[i].need_sum || c.is_plane || i == k.hist_slot);
   }
-  exec_mark(1);
-  HIP_TRY(hipSetDevice(phys_device(seg->device)));
-  ExecCtx* ctx = nullptr;
-  pg_status st = acquire_ctx(seg, &ctx);
-  if (st != PG_OK) return st;
-  CtxGuard guard{seg, ctx};
-
-  const bool want_bitmap = host_bitmap != nullptr || d_out_bitmap_request != nullptr;
-  const int na = want_bitmap ? 0 : q->num_aggregations;
-  const int ng = want_bitmap ? 0 : q->num_group_by;
-  if (na < 0 || ng < 0 || (na > 0 && !q->aggregations) || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
-  if (ng > kMaxGroupCols) return fail(PG_ERR_UNSUPPORTED, "more than %d group-by columns", kMaxGroupCols);
-  const bool timed = (g_engine.flags & PG_CFG_TIME_KERNELS) != 0;
-
-  // NonScanBasedAggregationOperator (core/plan/AggregationPlanNode.java:98-115,159-190; core/operator/query/
-  // NonScanBasedAggregationOperator.java:83-105): the filter matches everything and every function is COUNT, or MIN / MAX of a
-  // dictionary column -> the answer comes from the segment metadata and the dictionary ends; nothing is scanned.
-  if (ng == 0 && !want_bitmap && out && na > 0 && allow_metadata_plan) {
-    bool match_all = q->num_filter_nodes == 0;
-    if (q->num_filter_nodes == 1 && q->filter && q->predicates && q->filter[0].op == PG_FILTER_LEAF && q->filter[0].predicate >= 0 &&
-        q->filter[0].predicate < q->num_predicates) {
-      const pg_predicate& pr = q->predicates[q->filter[0].predicate];
-      match_all = (pr.kind == PG_PRED_MATCH_ALL && !pr.exclusive) || (pr.kind == PG_PRED_MATCH_NONE && pr.exclusive);
-    }
-    bool fit = match_all;
-    for (int a = 0; a < na && fit; ++a) {
-      const pg_aggregation& ag = q->aggregations[a];
-      if (ag.function == PG_AGG_COUNT) continue;
-      fit = (ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) && ag.column >= 0 && ag.column < (int)seg->cols.size() &&
-            seg->cols[(size_t)ag.column].encoding == PG_FWD_FIXED_BIT_DICT;
-    }
-    if (fit) {
-      memset(out, 0, sizeof(*out));
-      out->num_aggregations = na;
-      out->aggregations = (pg_agg_value*)calloc((size_t)na, sizeof(pg_agg_value));
-      for (int a = 0; a < na; ++a) {
-        const pg_aggregation& ag = q->aggregations[a];
-        pg_agg_value& v = out->aggregations[a];
-        v.count = seg->num_docs;
-        v.min = std::numeric_limits<double>::infinity();
-        v.max = -std::numeric_limits<double>::infinity();
-        if (ag.function == PG_AGG_MIN) v.min = seg->cols[(size_t)ag.column].h_dict_f64.front();
-        if (ag.function == PG_AGG_MAX) v.max = seg->cols[(size_t)ag.column].h_dict_f64.back();
-      }
-      out->stats.num_docs_scanned = seg->num_docs;          // NonScanBasedAggregationOperator.getExecutionStatistics: (totalDocs, 0, 0, totalDocs)
-      out->stats.num_entries_scanned_in_filter = 0;
-      out->filter_entries_exact = 1;
-      out->stats.num_entries_scanned_post_filter = 0;
-      out->stats.num_total_docs = seg->num_docs;
-      if (out_cardinality) *out_cardinality = seg->num_docs;
-      return PG_OK;
-    }
+  const bool hist = lane_private && k.hist_slot == 0 && pl.num_agg_cols == 1;      // the histogram kernel aggregates one column
+  if (k.hist_slot >= 0 && !hist) lane_private = false;                            // (rare: the gather path of the LDS-staged kernel)
+  // Raw columns and 8-byte dictionaries: the same lane-private layout, read with 16-byte loads (scan_private_typed_kernel).
+  // PINOT_GPU_SCAN_TYPED_PRIVATE=0 keeps them in the LDS-staged kernel.
+  bool lane_typed = g_engine.scan_private && g_engine.scan_typed_private && !lane_private && pl.num_agg_cols > 0 && !profile && private_leaves;
+  for (int i = 0; i < pl.num_agg_cols && lane_typed; ++i) {
+    const DevColumn& c = pl.cols[pl.agg_cols[i].col];
+    lane_typed = c.is_raw || (c.vkind != kValI32 && c.bits <= 31);      // every slot raw, or an 8-byte dictionary
   }
-
+  k.general = k.kernel = lane_private ? ScanKernel::Private : (lane_typed ? ScanKernel::PrivateTyped : ScanKernel::Agg);
+  if (hist) {
+    k.hist_cw = hist_counter_bits(seg->cols[(size_t)hist_col]);
+    k.hist_guarded = std::max(__atomic_load_n(&seg->cols[(size_t)hist_col].hist_tier, __ATOMIC_RELAXED), g_engine.hist_guard ? 1 : 0) >= 1 && k.hist_cw < 32;
+    return pick(ScanKernel::Hist);
+  }
+  if (k.general == ScanKernel::Agg) return k;
+  // Nothing but a filter over narrow dictionary columns (COUNT(*) and / or the bitmap): scan_narrow_kernel, four tiles per wave and iteration
+  // (a leap-frogging `a AND b` is counted by eval_filter_private's hook: the narrow kernels have their own evaluator and do not carry it)
+  if (g_engine.scan_narrow && lane_private && pl.num_agg_cols == 0 && lw.tile_list == nullptr && sp.num_nodes > 0 && !(want_result && lw.stats_leap2_flagged)) {
+    bool narrow = true; int depth = 0, max_depth = 0;
+    for (int n = 0; n < sp.num_nodes && narrow; ++n) {
+      const DevNode& dn = sp.nodes[n];
+      if (dn.op == PG_FILTER_LEAF) {
+        narrow = dn.kind == kLeafMatchAll || dn.kind == kLeafMatchNone || ((dn.kind == kLeafDictRange || (dn.kind == kLeafDictSet && g_engine.set_lds)) && dn.bits >= 1 && dn.bits <= kNarrowMaxBits);      // (a set of a narrow column: eight words in LDS, pg_scan_narrow.h)
+        depth++;
+      } else if (dn.op != PG_FILTER_NOT) depth -= dn.num_children - 1;
+      max_depth = std::max(max_depth, depth);
+    }
+    if (narrow && max_depth <= kNarrowStack)
+      return pick(g_engine.scan_narrow_single && sp.num_nodes == 1 && sp.nodes[0].kind == kLeafDictRange ? ScanKernel::NarrowSingle : ScanKernel::Narrow);
+  }
+  // The whole filter is ONE bitmap that index_and_kernel made (its tiles listed), and every aggregated column is read as bit-packed
+  // fields: eight tiles per wave and iteration, only the matching docs' values are touched (scan_sparse_kernel)
+  if (g_engine.scan_sparse && lane_private && !want_bitmap && pl.num_agg_cols > 0 && lw.tile_list != nullptr && sp.num_nodes == 1 && sp.nodes[0].kind == kLeafBitmap &&
+      sp.nodes[0].exclusive == 0) return pick(ScanKernel::Sparse);
+  // the lean kernels below: at most one leaf (without the count hooks) and one aggregated column, no tile list, no statistics they do not count
+  if (want_bitmap || lw.tile_list != nullptr || sp.num_nodes > 1 || pl.num_agg_cols > 1 || (want_result && (lw.stats_leap2_flagged || lw.stats_chain_flagged))) return k;
+  const DevNode* leaf = sp.num_nodes == 1 ? &sp.nodes[0] : nullptr;
+  const bool plain_leaf = leaf == nullptr || (leaf->op == PG_FILTER_LEAF && (leaf->flags & (kNodeCountEntries | kNodeLeapfrog2)) == 0);
+  const DevAggCol* ac = pl.num_agg_cols == 1 ? &sp.agg_cols[0] : nullptr;
+  // One dictionary-range leaf (or no filter) in front of at most one aggregated packed column, both of at most kSimpleMaxBits bits:
+  // scan_simple_kernel -- the same per-tile code with none of the general machinery, at twice the waves per SIMD (pg_scan_simple.h).
+  // (the one-stream shape `SUM(v) WHERE v in range` keeps scan_private_kernel's fused decode)
+  // (a dictId SET over a column of at most 16 bits -- its words fit the LDS area -- takes scan_simple_set_kernel: round 6b)
+  const bool set = leaf != nullptr && leaf->op == PG_FILTER_LEAF && leaf->kind == kLeafDictSet && g_engine.set_lds && leaf->bits <= 16;
+  bool simple = g_engine.scan_simple && lane_private && plain_leaf &&
+                (leaf == nullptr || ((leaf->kind == kLeafDictRange || set) && leaf->bits >= 1 && leaf->bits <= kSimpleMaxBits));
+  if (simple && ac != nullptr)
+    simple = ac->bits >= 1 && ac->bits <= kSimpleMaxBits && !ac->is_raw && !(leaf != nullptr && leaf->fwd == ac->fwd && leaf->bits == ac->bits && ac->need_sum != 0 && ac->need_minmax == 0 && leaf->exclusive == 0);
+  if (simple) return pick(set ? ScanKernel::SimpleSet : ScanKernel::Simple);
+  // The same idea for raw INT columns (BASELINE.json configs[0]'s scan pair): one raw-range leaf (or no filter) in front of at most one
+  // aggregated raw INT column -- scan_raw_kernel, five waves per SIMD, coalesced reads (pg_scan_raw.h).
+  if (g_engine.scan_raw && lw.side == nullptr && sp.num_nodes + pl.num_agg_cols >= 1 && plain_leaf && (leaf == nullptr || (leaf->kind == kLeafRawRange && leaf->fwd != nullptr)) &&
+      (ac == nullptr || (ac->is_raw != 0 && ac->vkind == kValI32 && ac->is_plane == 0 && ac->bits == 32))) return pick(ScanKernel::Raw);
+  return k;
+}
+// threads: the workgroup the kernel's records are counted in (profile_waves); lds: Agg's staged layout, or Hist's histogram with the set
+// area at hist_set_off; wide: scan_simple / scan_raw launch workgroups of kWideBlockThreads (PINOT_GPU_WIDE_BLOCKS=1)
+struct ScanGrid { int blocks = 1, threads = kBlockThreads; size_t lds = 0, hist_set_off = 0; bool wide = false; };
+// A segment whose tiles all fit the chip at once (one tile per wave: a 10 M-row segment at five waves per SIMD) is latency from end
+// to end -- launch, one round of loads, the hand-off of the workgroups' records to the fold.  Ten waves per workgroup there: 2.5x
+// fewer records, and a folding workgroup of 640 threads takes them in ONE round of loads (256 threads took five for 1221 records).
+static void lean_grid(const pg_segment* seg, int wave_cap, ScanGrid* g) {
+  const long long tiles2k = doc_tiles(seg);
+  static const bool wide_ok = getenv("PINOT_GPU_WIDE_BLOCKS") && getenv("PINOT_GPU_WIDE_BLOCKS")[0] == '1';      // (measured slower at every size: off unless asked for)
+  g->wide = wide_ok && wave_cap >= 2 * (kWideBlockThreads / 64) && tiles2k > 64 && tiles2k <= (long long)seg->num_cus * wave_cap && g_engine.blocks_per_cu <= 0;
+  const int wpb = (g->wide ? kWideBlockThreads : kBlockThreads) / 64;
+  int bpc = std::max(1, wave_cap / wpb);
+  // Up to two rounds of resident waves' worth of tiles (~20 M rows), the hand-off of the workgroups' records to the fold weighs more
+  // than a second round of loads: two workgroups per CU (profiles/r4/c1_probe_blocks_per_cu.jsonl: 10 M rows, 1221 workgroups
+  // 21.4 us, 512 workgroups 17.8 us; the scan alone 12.9 us)
+  static const int small_bpc = getenv("PINOT_GPU_SMALL_BLOCKS_PER_CU") ? atoi(getenv("PINOT_GPU_SMALL_BLOCKS_PER_CU")) : 2;
+  if (!g->wide && small_bpc > 0 && tiles2k <= 2ll * seg->num_cus * wave_cap) bpc = std::min(bpc, small_bpc);
+  g->blocks = grid_blocks(seg, tiles2k, wpb, bpc);
+}
+// The chosen kernel's grid (`geo`: the layout finish_geometry made for the LDS-staged kernel).  PrivateFsm is chosen after the grid: Private's.
+static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const ScanParams& sp, const Geometry& geo, int num_agg_cols, int hist_col) {
+  ScanGrid g;
+  const long long tiles = doc_tiles(seg);
+  const int wpb = kBlockThreads / 64, hist_waves = kHistBlockThreads / 64;
+  switch (k.kernel) {
+    case ScanKernel::Hist: {
+      // one histogram per workgroup of 16 wavefronts; as many workgroups per CU as LDS and registers admit
+      const int per_word = 32 / k.hist_cw;
+      g.lds = (((size_t)(seg->cols[(size_t)hist_col].cardinality + per_word - 1) / per_word * 4) + 15) & ~(size_t)15;
+      g.lds = std::max(g.lds, sizeof(BlockPartial) * (kHistBlockThreads / 64) + 16);      // the reduction records (+ the fold flag) reuse the counters' LDS
+      // the filter's dictId sets (IN lists) behind the counters: ScanParams.set_leaves_in_lds = 1 + the area's byte offset (scan_hist_body)
+      if (g_engine.set_lds && g.lds + (size_t)kSetLdsWords * 4 <= 150 * 1024)
+        for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) g.hist_set_off = g.lds;
+      if (g.hist_set_off != 0) g.lds += (size_t)kSetLdsWords * 4;
+      g.threads = kHistBlockThreads;
+      g.blocks = grid_blocks(seg, tiles, hist_waves, std::max(1, std::min(waves_scan_hist(k.hist_cw, k.hist_guarded) / hist_waves, (int)((160 * 1024 - 2048) / (g.lds + 256)))));
+      if (g_engine.hist_blocks > 0) g.blocks = std::min(g.blocks, g_engine.hist_blocks);
+      break;
+    }
+    case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
+    case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
+    case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
+    case ScanKernel::Simple: case ScanKernel::SimpleSet: lean_grid(seg, waves_scan_simple(), &g); break;
+    case ScanKernel::Raw: lean_grid(seg, waves_scan_raw(), &g); break;
+    case ScanKernel::Private: g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, waves_scan_private(num_agg_cols) / wpb)); break;
+    case ScanKernel::PrivateTyped: g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, waves_scan_private_typed(num_agg_cols) / wpb)); break;
+    default: g.blocks = geo.blocks; g.threads = geo.threads; g.lds = geo.lds; break;      // Agg
+  }
+  return g;
+}
+// The kind of shared launch an item of the chosen kernel joins (false: none, it runs its own kernel).  Without PINOT_GPU_LEAN_BATCH the
+// simple shapes join the general kind; a raw-shaped item has no general form when its column is aggregated: it stays lean.
+static bool scan_batch_kind(const ScanChoice& k, int num_agg_cols, BatchKind* kind) {
+  const bool lean = g_engine.lean_batch;
+  switch (k.kernel) {
+    case ScanKernel::Hist: *kind = k.hist_cw == 8 ? BatchKind::Hist8 : (k.hist_cw == 16 ? BatchKind::Hist16 : BatchKind::Hist32); return !k.hist_guarded && g_engine.batch_hist;
+    case ScanKernel::Narrow: case ScanKernel::NarrowSingle: *kind = k.kernel == ScanKernel::Narrow ? BatchKind::Narrow : BatchKind::NarrowSingle; return g_engine.batch_more;
+    case ScanKernel::Simple: case ScanKernel::SimpleSet: *kind = !lean ? BatchKind::Private : (k.kernel == ScanKernel::Simple ? BatchKind::Simple : BatchKind::SimpleSet); return true;
+    case ScanKernel::Raw: *kind = !lean && k.general == ScanKernel::Private ? BatchKind::Private : BatchKind::Raw; return true;
+    case ScanKernel::PrivateFsm: case ScanKernel::Private: *kind = BatchKind::Private; return true;
+    case ScanKernel::PrivateTyped: *kind = num_agg_cols <= 1 ? BatchKind::Typed1 : (num_agg_cols == 2 ? BatchKind::Typed2 : BatchKind::TypedMax); return g_engine.batch_more;
+    default: return false;      // Sparse, Agg
+  }
+}
+static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_agg_cols, bool typed, hipStream_t stream, const ScanParams& sp) {
+  const bool one = num_agg_cols <= 1;      // the single-aggregated-column instantiation needs a third fewer registers (one more wavefront per SIMD)
+  const int lean_threads = g.wide ? kWideBlockThreads : kBlockThreads;
+  switch (k.kernel) {
+    case ScanKernel::Hist: launch_scan_hist(k.hist_cw, k.hist_guarded, g.blocks, g.lds, stream, sp); break;
+    case ScanKernel::Narrow: case ScanKernel::NarrowSingle: launch_scan_narrow(k.kernel == ScanKernel::NarrowSingle, g.blocks, stream, sp); break;
+    case ScanKernel::Sparse: launch_scan_sparse(one, g.blocks, stream, sp); break;
+    case ScanKernel::Simple: case ScanKernel::SimpleSet: launch_scan_simple(g.blocks, lean_threads, stream, sp, k.kernel == ScanKernel::SimpleSet); break;
+    case ScanKernel::Raw: launch_scan_raw(g.blocks, lean_threads, stream, sp); break;
+    case ScanKernel::PrivateFsm: launch_scan_private_fsm(num_agg_cols, g.blocks, stream, sp); break;
+    case ScanKernel::Private: launch_scan_private(num_agg_cols, g.blocks, stream, sp); break;
+    case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
+    case ScanKernel::Agg: launch_scan_agg(g_engine.use_dma, one, typed, g.blocks, g.threads, g.lds, stream, sp); break;
+  }
+}
+// What the phases of execute_impl share about one query
+struct QueryRun {
+  pg_segment* seg; const pg_query* q; pg_result* out; ExecCtx* ctx; Deferred* defer;
+  int na, ng, hist_col = -1;          // hist_col: the summed column that goes through the LDS histogram (scan_hist_kernel)
+  bool want_bitmap, timed, stats_is_final = false;
   Lowered lw;
-  memset(&lw.sp, 0, sizeof(lw.sp));
-  memset(&lw.plan, 0, sizeof(lw.plan));
-  lw.plan.lazy_node = -1;
-  const int num_cols_total = (int)seg->cols.size();
-  // Columns that are summed are read through their value plane (built on first use); decided before the filter is
-  // lowered so that a range predicate on the same column can be evaluated on the plane too.
-  lw.plane_cols.assign((size_t)std::max(num_cols_total, 1), 0);
-  PlaneHold planes(seg, {});
-  // At most one summed column goes through the LDS histogram instead (scan_hist_kernel); it needs the lane-private kernel, so the
-  // shapes that kernel does not take are ruled out here, before a plane is (not) built.
-  int hist_col = -1;
-  if (ng == 0 && !want_bitmap && g_engine.scan_private && !(g_engine.flags & PG_CFG_PROFILE_WAVES)) {
-    bool shape_ok = true;
-    int only_col = -1;                  // the histogram kernel aggregates ONE column (SUM / AVG / MIN / MAX of it, and COUNT)
-    for (int a = 0; a < na && shape_ok; ++a) {
-      const pg_aggregation& ag = q->aggregations[a];
-      if (ag.function == PG_AGG_COUNT) continue;
-      shape_ok = ag.column >= 0 && ag.column < num_cols_total && seg->cols[(size_t)ag.column].encoding == PG_FWD_FIXED_BIT_DICT &&
-                 seg->cols[(size_t)ag.column].vkind == kValI32 && (only_col < 0 || only_col == ag.column);
-      only_col = ag.column;
-    }
-    for (int i = 0; i < q->num_predicates && shape_ok && q->predicates; ++i) {
-      const pg_predicate& pr = q->predicates[i];
-      if (pr.kind == PG_PRED_RAW_RANGE) shape_ok = pr.column >= 0 && pr.column < num_cols_total && seg->cols[(size_t)pr.column].stored_type == PG_TYPE_INT;
-    }
-    for (int a = 0; a < na && shape_ok && hist_col < 0; ++a) {
-      const pg_aggregation& ag = q->aggregations[a];
-      if ((ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) && want_hist(seg->cols[(size_t)ag.column])) hist_col = ag.column;
-    }
+  PlaneHold planes;                   // the value planes the kernels read
+  std::vector<int> projected;         // distinct projected columns (ExecutionStatistics numEntriesScannedPostFilter = numDocsScanned * numProjectedColumns)
+  QueryRun(pg_segment* s, const pg_query* q_, pg_result* o, ExecCtx* c, Deferred* d, int na_, int ng_, bool want_bitmap_, bool timed_)
+      : seg(s), q(q_), out(o), ctx(c), defer(d), na(na_), ng(ng_), want_bitmap(want_bitmap_), timed(timed_), planes(s, {}) {}
+  void add_projected(int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); }
+};
+// The query becomes an item of pg_execute_batch's shared launch; the value planes its kernel reads stay held until the batch has run
+static pg_status defer_item(QueryRun& r, std::shared_ptr<LoweredItem> item) {
+  item->plane_columns = r.planes.columns;      // (none for an index-only COUNT)
+  r.defer->item = std::move(item);
+  r.defer->cacheable = !r.lw.plane_pending;
+  r.defer->planes.reset(new PlaneHold(std::move(r.planes)));
+  return kDeferred;
+}
+// an item whose whole device work is index_and_kernel publishing the query's record (BatchKind::IndexAnd)
+static std::shared_ptr<LoweredItem> index_and_item(const Lowered& lw) {
+  auto item = std::make_shared<LoweredItem>();
+  memset(&item->sp, 0, sizeof(item->sp));
+  item->sp.lean_kind = (int32_t)BatchKind::IndexAnd;
+  item->and_params = std::make_shared<IndexAndParams>(lw.and_params);
+  item->and_windows = lw.finalize_windows;
+  item->blocks = (int)std::min<long long>(((long long)lw.finalize_windows + index_and_batch_block_waves() - 1) / index_and_batch_block_waves(), (long long)lw.and_num_cus * index_and_batch_blocks_per_cu());
+  return item;
+}
+// a holder that no value reached yet; the statistics of an answer that scanned nothing
+static void empty_agg_value(pg_agg_value* v, int64_t count) { v->count = count; v->min = std::numeric_limits<double>::infinity(); v->max = -std::numeric_limits<double>::infinity(); }
+// index_and_kernel is the query: [ev[0], ev[3]] brackets the kernel and the copy of its counter lines
+static void nothing_scanned(pg_result* o, int64_t docs, int total_docs) {
+  o->stats.num_docs_scanned = docs; o->stats.num_entries_scanned_in_filter = 0; o->filter_entries_exact = 1; o->stats.num_entries_scanned_post_filter = 0; o->stats.num_total_docs = total_docs;
+}
+// a group-by result's header and its arrays for num_present groups (pg_result_free releases them)
+static void start_group_result(pg_result* out, int na, int ng, int num_present, int kernel, int upper_bound, int key_kind) {
+  out->num_aggregations = na; out->dominant_kernel = kernel; out->num_groups = num_present; out->group_id_upper_bound = upper_bound;
+  out->group_ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(num_present, 1));
+  out->group_aggregations = (pg_agg_value*)calloc((size_t)std::max(num_present, 1) * (size_t)std::max(na, 1), sizeof(pg_agg_value));
+  out->group_key_dict_ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(num_present, 1) * (size_t)ng);
+  out->group_key_kind = key_kind;
+}
+static pg_status time_index_and(const ExecCtx* ctx, pg_result* out) {
+  float ms_all = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms_all, ctx->ev[0], ctx->ev[3]));
+  out->device_ms = ms_all; out->dominant_kernel_ms = ms_all;
+  return PG_OK;
+}
+// NonScanBasedAggregationOperator (core/plan/AggregationPlanNode.java:98-115,159-190; core/operator/query/
+// NonScanBasedAggregationOperator.java:83-105): the filter matches everything and every function is COUNT, or MIN / MAX of a
+// dictionary column -> the answer comes from the segment metadata and the dictionary ends; nothing is scanned.
+static bool answer_from_metadata(const pg_segment* seg, const pg_query* q, int na, pg_result* out, int64_t* out_cardinality) {
+  bool match_all = q->num_filter_nodes == 0;
+  if (q->num_filter_nodes == 1 && q->filter && q->predicates && q->filter[0].op == PG_FILTER_LEAF && q->filter[0].predicate >= 0 &&
+      q->filter[0].predicate < q->num_predicates) {
+    const pg_predicate& pr = q->predicates[q->filter[0].predicate];
+    match_all = (pr.kind == PG_PRED_MATCH_ALL && !pr.exclusive) || (pr.kind == PG_PRED_MATCH_NONE && pr.exclusive);
   }
+  bool fit = match_all;
+  for (int a = 0; a < na && fit; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if (ag.function == PG_AGG_COUNT) continue;
+    fit = (ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) && ag.column >= 0 && ag.column < (int)seg->cols.size() &&
+          seg->cols[(size_t)ag.column].encoding == PG_FWD_FIXED_BIT_DICT;
+  }
+  if (!fit) return false;
+  memset(out, 0, sizeof(*out));
+  out->num_aggregations = na;
+  out->aggregations = (pg_agg_value*)calloc((size_t)na, sizeof(pg_agg_value));
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    if ((ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) && ag.column >= 0 && ag.column < num_cols_total && ag.column != hist_col &&
-        (want_value_plane(seg->cols[(size_t)ag.column]) || (!want_bitmap && want_wide_plane(seg, q, ag.column)))) {
-      if (lw.plane_cols[(size_t)ag.column]) continue;
-      bool ready = false;
-      st = acquire_plane(seg, ag.column, &ready);
-      if (st != PG_OK) return st;
-      if (ready) { planes.columns.push_back(ag.column); lw.plane_cols[(size_t)ag.column] = 1; }
-      else lw.plane_pending = true;
+    pg_agg_value& v = out->aggregations[a];
+    empty_agg_value(&v, seg->num_docs);
+    if (ag.function == PG_AGG_MIN) v.min = seg->cols[(size_t)ag.column].h_dict_f64.front();
+    if (ag.function == PG_AGG_MAX) v.max = seg->cols[(size_t)ag.column].h_dict_f64.back();
+  }
+  nothing_scanned(out, seg->num_docs, seg->num_docs);      // NonScanBasedAggregationOperator.getExecutionStatistics: (totalDocs, 0, 0, totalDocs)
+  if (out_cardinality) *out_cardinality = seg->num_docs;
+  return true;
+}
+// FastFilteredCountOperator (core/plan/AggregationPlanNode.java:98-115, core/operator/query/FastFilteredCountOperator.java:66-72): COUNT(*)
+// over a filter that the indexes answer alone is the cardinality of the and-ed bitmaps -- index_and_kernel counted it, nothing is scanned.
+static pg_status count_from_index(QueryRun& r, int64_t* out_cardinality) {
+  pg_segment* seg = r.seg; pg_result* out = r.out; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; const int na = r.na; const bool timed = r.timed;
+  pg_status st = PG_OK;
+  const int total_docs = seg->num_docs;
+  auto convert = [na, total_docs](const BlockPartial& fp, pg_result* o) {
+    const int64_t card = (int64_t)fp.count;
+    o->num_aggregations = na;
+    o->aggregations = (pg_agg_value*)calloc((size_t)na, sizeof(pg_agg_value));
+    for (int a = 0; a < na; ++a) empty_agg_value(&o->aggregations[a], card);
+    o->dominant_kernel = PG_KERNEL_INDEX_AND;
+    nothing_scanned(o, card, total_docs);     // bitmaps only: nothing is scanned
+  };
+  if (r.defer != nullptr && !r.defer->single && g_engine.batch_index && g_engine.direct_result && lw.and_cardinality_only && index_and_shares_a_launch(lw)) {
+    // pg_execute_batch: the item is index_and_kernel publishing the cardinality -- it shares index_and_batch_kernel's launch (BatchKind::IndexAnd)
+    auto item = index_and_item(lw);
+    item->convert = convert;
+    return defer_item(r, std::move(item));
+  }
+  st = launch_index_and(&lw, ctx, nullptr); if (st != PG_OK) return st;
+  unsigned long long* h_card = &ctx->h_partial->count;
+  if (lw.cardinality_atomic) HIP_TRY(hipMemcpyAsync(ctx->h_and_shards, ctx->d_and_counters + 2, kAndShardBytes, hipMemcpyDeviceToHost, ctx->stream));
+  else HIP_TRY(hipMemcpyAsync(h_card, lw.d_cardinality, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (timed) { HIP_TRY(mark_pre_work(ctx)); HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream)); }
+  exec_mark(3);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  exec_mark(4);
+  if (lw.cardinality_atomic) {
+    BlockPartial g;
+    st = read_index_and_shards(ctx, 0, &g); if (st != PG_OK) return st;
+    *h_card = g.count;
+  }
+  convert(*ctx->h_partial, out);      // (h_card is its count)
+  if (out_cardinality) *out_cardinality = (int64_t)*h_card;
+  return timed ? time_index_and(ctx, out) : PG_OK;
+}
+// ---------------- aggregation only ----------------
+static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_request, uint64_t* host_bitmap, int64_t host_bitmap_words, int64_t* out_cardinality) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; ScanParams& sp = lw.sp;
+  PlanParams& pl = lw.plan; const int na = r.na, num_cols_total = (int)seg->cols.size(); const bool want_bitmap = r.want_bitmap, timed = r.timed;
+  pg_status st = PG_OK;
+  std::vector<int> agg_slot_of((size_t)std::max(na, 1), -1);
+  for (int a = 0; a < na; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if (ag.function == PG_AGG_COUNT) continue;
+    if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
+    if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
+    r.add_projected(ag.column);
+    int s = slot_for(&lw, seg, ag.column, lw.plane_cols[(size_t)ag.column] != 0);
+    if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+    pl.cols[s].in_agg = 1;
+    int ac = -1;
+    for (int i = 0; i < pl.num_agg_cols; ++i) if (pl.agg_cols[i].col == s) ac = i;
+    if (ac < 0) {
+      if (pl.num_agg_cols >= kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d aggregated columns", kMaxAggCols);
+      ac = pl.num_agg_cols++;
+      pl.agg_cols[ac] = PlanAggCol{s, 0, 0, 0};
+    }
+    if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) pl.agg_cols[ac].need_sum = 1;
+    if (ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) pl.agg_cols[ac].need_minmax = 1;
+    agg_slot_of[(size_t)a] = ac;
+  }
+  bool need_queue = false, typed = false;
+  for (int i = 0; i < pl.num_agg_cols; ++i) {
+    const DevColumn& c = pl.cols[pl.agg_cols[i].col];
+    need_queue |= pl.agg_cols[i].need_sum && !c.is_raw && !c.is_plane && c.vkind == kValI32;
+    typed |= c.vkind != kValI32 && (pl.agg_cols[i].need_sum || c.is_raw);     // 8-byte / floating-point values are read
+  }
+  Geometry geo;
+  finish_geometry(seg, &lw, 0, need_queue, kBlockThreads / 64, waves_scan_agg(pl.num_agg_cols <= 1, typed), &geo);
+  ScanChoice k = choose_scan_kernel(seg, lw, r.hist_col, typed, want_bitmap, out != nullptr);
+  if (k.kernel == ScanKernel::Agg && (size_t)sp.wave_lds_bytes > kLdsBudget) return fail(PG_ERR_UNSUPPORTED, "query needs %d bytes of LDS per wavefront", sp.wave_lds_bytes);
+  const ScanGrid grid = scan_grid(seg, k, sp, geo, pl.num_agg_cols, r.hist_col);
+  const int blocks = grid.blocks;
+  if (k.kernel == ScanKernel::Hist) { sp.hist_slot = k.hist_slot; sp.hist_bins = seg->cols[(size_t)r.hist_col].cardinality; }
+  sp.speculate = 1;
+  sp.profile = (g_engine.flags & PG_CFG_PROFILE_WAVES) ? 1 : 0;
+  st = ensure_partials(ctx, blocks); if (st != PG_OK) return st;
+  sp.partials = ctx->d_partials;
+  sp.out_bitmap = nullptr;
+  if (want_bitmap) {
+    st = ensure_bitmap(seg, ctx, 0); if (st != PG_OK) return st;
+    sp.out_bitmap = ctx->d_bitmaps[0];
+  }
+  sp.sparse_windows = nullptr; sp.sparse_num_windows = 0;
+  bool defer_index_and = false;
+  const unsigned long long seq = ++ctx->seq;      // the sequence number the query's folded record is published under (a gathering index_and_kernel's, or the scan kernel's)
+  const bool lane_private = k.general != ScanKernel::Agg;      // a lane-private kernel, or one specialised from it
+  if (k.kernel == ScanKernel::Sparse) {
+    // A handful of survivors per window (the planner's estimate from the postings' sizes: independent predicates): index_and_kernel reads
+    // their values itself -- ONE launch for `SUM(v) WHERE p = 3 AND q = 5 AND r = 7` (BASELINE.json configs[4]); else scan_sparse_kernel
+    // walks the window masks behind it (no list, no index_and_finalize_kernel between the two kernels).  PINOT_GPU_INDEX_GATHER=0: never.
+    const bool gather = g_engine.index_gather && lw.and_pending && lw.index_and_is_whole_filter && out && pl.num_agg_cols <= kMaxAndGather &&
+                        lw.and_expected_docs <= 4.0 * (double)lw.finalize_windows;
+    defer_index_and = gather && r.defer != nullptr && !r.defer->single && g_engine.batch_index && g_engine.direct_result && !want_bitmap && index_and_shares_a_launch(lw);
+    if (defer_index_and) arm_index_gather(&lw, &sp);      // (launched by the batch: BatchKind::IndexAnd)
+    else st = launch_index_and(&lw, ctx, gather ? &sp : nullptr);
+    if (st != PG_OK) return st;
+    sp.tile_list = lw.tile_list; sp.tile_count = lw.tile_count;      // (not read by the kernel; "listed" is what the planner and the statistics go by)
+    sp.sparse_windows = lw.and_info; sp.sparse_num_windows = (int32_t)lw.finalize_windows;
+  } else if (!want_bitmap && lane_private) {
+    st = complete_index_list(&lw, ctx); if (st != PG_OK) return st;
+    sp.tile_list = lw.tile_list; sp.tile_count = lw.tile_count;
+  }
+  else { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
+  const bool count_leap2 = out && lw.stats_leap2_flagged && k.kernel != ScanKernel::Narrow && k.kernel != ScanKernel::NarrowSingle && lane_private;
+  const bool count_entries = (out && lw.stats_chain_flagged && lane_private) || count_leap2;
+  if (lw.side != nullptr) {
+    // the transducer pass behind this query: a kernel that evaluates the filter with eval_filter_private over every tile leaves the leaves' bitmaps behind
+    const bool wrote = kScanKernels[(int)k.kernel].writes_leaves && sp.tile_list == nullptr;
+    for (int l = 0; l < kMaxLeaves; ++l) sp.leaf_out[l] = wrote ? lw.sp_leaf_out[l] : nullptr;
+    sp.leaf_out_enabled = wrote ? 1 : 0;
+    lw.side->kernel_wrote = wrote;
+  }
+  // The transducer walked INSIDE the general lane-private kernel (scan_private_fsm_kernel): machines of at most four states over at most
+  // four inputs, every input a leaf of its own in the lowered filter.  No leaf bitmap is written or read back; the tiles' tables are
+  // joined by fsm_chain_kernel / fsm_finish_kernel behind the scan, on the query's stream.  PINOT_GPU_FSM_FUSED=0: the separate pass.
+  sp.fsm_tables = nullptr; sp.fsm_states = 0; sp.fsm_inputs = 0;
+  // (NOT in scan_narrow_kernel: measured on `COUNT(*) WHERE p = 3 AND q = 5 AND r = 7` over 4 / 6 / 8-bit columns, 1 B rows -- the walk takes the
+  //  kernel from 164 to 199 registers, three to two waves per SIMD, 0.53 -> 0.85 ms, more than the 0.24 ms pass it replaces: 0.767 -> 0.868 ms
+  //  for the query; the same query through this kernel: 1.06 ms.  profiles/r5/fsm_walk_inside_the_scan_ab.txt)
+  if (lw.side != nullptr && sp.leaf_out_enabled != 0 && g_engine.fsm_fused && g_engine.fsm_perm && k.kernel == ScanKernel::Private && out) {
+    const fstats::Fsm& f = *lw.side->fsm;
+    int max_inc = 0;
+    for (uint8_t d : f.delta) max_inc = std::max(max_inc, (int)(d >> 4));
+    bool fits = f.num_states <= 4 && f.num_inputs <= 4 && max_inc <= 7 && !f.has_episodes();      // (episodes need the second walk of the pass)
+    for (int i = 0; i < f.num_inputs && fits; ++i) fits = lw.side->mapped[i];
+    if (fits) {
+      k.kernel = ScanKernel::PrivateFsm;
+      sp.fsm_tables = lw.side->tables; sp.fsm_states = f.num_states; sp.fsm_inputs = f.num_inputs;
+      for (int l = 0; l < kMaxLeaves; ++l) {
+        sp.fsm_input_of_leaf[l] = -1;
+        for (int i = 0; i < f.num_inputs; ++i) if (sp.leaf_out[l] != nullptr && sp.leaf_out[l] == lw.side->bitmap[i]) sp.fsm_input_of_leaf[l] = (int8_t)i;
+        sp.leaf_out[l] = nullptr;
+      }
+      sp.leaf_out_enabled = 0;
+      memset(sp.fsm_delta, 0, sizeof(sp.fsm_delta));
+      for (int st8 = 0; st8 < f.num_states; ++st8)
+        for (int in = 0; in < (1 << f.num_inputs); ++in) sp.fsm_delta[(st8 << 4) | in] = f.delta[(size_t)((st8 << f.num_inputs) | in)];
+      if (!ctx->h_filter_entries) HIP_TRY(hipHostMalloc((void**)&ctx->h_filter_entries, 8, hipHostMallocDefault));
     }
   }
-  ctx->pre_enqueued = false;
-  ctx->pre_started = false;      // ev[0] is recorded by the first piece of work that precedes the scan kernel (mark_pre_work)
-  ctx->ev_last = 3;
-  if (out && !want_bitmap) lw.stats_plan = fstats::choose_plan(q, &lw.stats_scan_leaves);
-  if (lw.stats_plan == fstats::Plan::kLeap2 && (!g_engine.leap2 || (q->flags & PG_QUERY_STATS_UPPER_BOUND_OK))) lw.stats_plan = fstats::Plan::kReplay;      // (kReplay with nobody replaying: the upper bound)
-  // the caller takes the upper bound (PG_QUERY_STATS_UPPER_BOUND_OK): a leap-frogging filter has no pass behind its kernel, so in a batch it shares the launch like any other
-  const bool stats_is_final = lw.stats_plan == fstats::Plan::kZero || lw.stats_plan == fstats::Plan::kPerLeaf ||
-                              (lw.stats_plan == fstats::Plan::kReplay && (q->flags & PG_QUERY_STATS_UPPER_BOUND_OK) != 0);
-  lw.cardinality_only_hint = ng == 0 && out && !want_bitmap && na > 0;
-  for (int a = 0; a < na; ++a) lw.cardinality_only_hint = lw.cardinality_only_hint && q->aggregations[a].function == PG_AGG_COUNT;
-  lw.side = nullptr;
-  if (out && !want_bitmap && lw.stats_plan == fstats::Plan::kReplay && side != nullptr && side->fsm != nullptr) {
-    // numEntriesScannedInFilter is a statistic: a pass that cannot get its scratch leaves the query's answer standing with
-    // filter_entries_exact = 0 (pg_execute's host replay still applies at its sizes) -- it never fails the query
-    if (prepare_fsm_side(seg, ctx, *side->fsm, side) == PG_OK) lw.side = side;
-    else (void)hipGetLastError();
-  }
-  st = lower_filter(seg, ctx, q, &lw);
-  if (st != PG_OK) return st;
-  exec_mark(2);
-  ScanParams& sp = lw.sp;
-  PlanParams& pl = lw.plan;
-
-  // distinct projected columns (ExecutionStatistics numEntriesScannedPostFilter = numDocsScanned * numProjectedColumns)
-  std::vector<int> projected;
-  auto add_projected = [&](int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); };
-
-  if (out) memset(out, 0, sizeof(*out));
-
-  if (ng == 0 && out && !want_bitmap && lw.index_and_is_whole_filter && na > 0) {
-    // FastFilteredCountOperator (core/plan/AggregationPlanNode.java:98-115, core/operator/query/FastFilteredCountOperator.java:66-72): COUNT(*)
-    // over a filter that the indexes answer alone is the cardinality of the and-ed bitmaps -- index_and_kernel counted it, nothing is scanned.
-    bool only_count = true;
-    for (int a = 0; a < na; ++a) only_count &= q->aggregations[a].function == PG_AGG_COUNT;
-    if (only_count && defer != nullptr && !defer->single && g_engine.batch_index && g_engine.direct_result && lw.and_cardinality_only && index_and_shares_a_launch(lw)) {
-      // pg_execute_batch: the item is index_and_kernel publishing the cardinality -- it shares index_and_batch_kernel's launch (lean_kind 12)
-      auto item = std::make_shared<LoweredItem>();
-      memset(&item->sp, 0, sizeof(item->sp));
-      item->sp.lean_kind = 12;
-      item->and_params = std::make_shared<IndexAndParams>(lw.and_params);
-      item->and_windows = lw.finalize_windows;
-      item->blocks = (int)std::min<long long>(((long long)lw.finalize_windows + index_and_batch_block_waves() - 1) / index_and_batch_block_waves(), (long long)lw.and_num_cus * index_and_batch_blocks_per_cu());
-      const int total_docs = seg->num_docs;
-      item->convert = [na, total_docs](const BlockPartial& fp, pg_result* o) {
-        const int64_t card = (int64_t)fp.count;
-        o->num_aggregations = na;
-        o->aggregations = (pg_agg_value*)calloc((size_t)na, sizeof(pg_agg_value));
-        for (int a = 0; a < na; ++a) {
-          o->aggregations[a].count = card;
-          o->aggregations[a].min = std::numeric_limits<double>::infinity();
-          o->aggregations[a].max = -std::numeric_limits<double>::infinity();
-        }
-        o->dominant_kernel = PG_KERNEL_INDEX_AND;
-        o->stats.num_docs_scanned = card;
-        o->stats.num_entries_scanned_in_filter = 0;     // bitmaps only: nothing is scanned
-        o->filter_entries_exact = 1;
-        o->stats.num_entries_scanned_post_filter = 0;
-        o->stats.num_total_docs = total_docs;
-      };
-      defer->item = std::move(item);
-      defer->cacheable = !lw.plane_pending;
-      defer->planes.reset(new PlaneHold(std::move(planes)));
-      return kDeferred;
-    }
-    if (only_count) {
-      st = launch_index_and(&lw, ctx, nullptr);
-      if (st != PG_OK) return st;
-      unsigned long long* h_card = &ctx->h_partial->count;
-      if (lw.cardinality_atomic) HIP_TRY(hipMemcpyAsync(ctx->h_and_shards, ctx->d_and_counters + 2, kAndShardBytes, hipMemcpyDeviceToHost, ctx->stream));
-      else HIP_TRY(hipMemcpyAsync(h_card, lw.d_cardinality, 8, hipMemcpyDeviceToHost, ctx->stream));
-      if (timed) { HIP_TRY(mark_pre_work(ctx)); HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream)); }
-      exec_mark(3);
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      exec_mark(4);
-      if (lw.cardinality_atomic) {
-        BlockPartial g;
-        st = read_index_and_shards(ctx, 0, &g);
-        if (st != PG_OK) return st;
-        *h_card = g.count;
-      }
-      const int64_t card = (int64_t)*h_card;
-      out->num_aggregations = na;
-      out->aggregations = (pg_agg_value*)calloc((size_t)na, sizeof(pg_agg_value));
-      for (int a = 0; a < na; ++a) {
-        out->aggregations[a].count = card;
-        out->aggregations[a].min = std::numeric_limits<double>::infinity();
-        out->aggregations[a].max = -std::numeric_limits<double>::infinity();
-      }
-      out->dominant_kernel = PG_KERNEL_INDEX_AND;
-      out->stats.num_docs_scanned = card;
-      out->stats.num_entries_scanned_in_filter = 0;     // bitmaps only: nothing is scanned
-      out->filter_entries_exact = 1;
-      out->stats.num_entries_scanned_post_filter = 0;
-      out->stats.num_total_docs = seg->num_docs;
-      if (out_cardinality) *out_cardinality = card;
-      if (timed) {
-        float ms_all = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms_all, ctx->ev[0], ctx->ev[3]));
-        out->device_ms = ms_all;
-        out->dominant_kernel_ms = ms_all;        // the index AND is the query
-      }
-      return PG_OK;
-    }
-  }
-  if (ng == 0) {
-    // ---------------- aggregation only ----------------
-    std::vector<int> agg_slot_of((size_t)std::max(na, 1), -1);
+  sp.filter_entries = nullptr;
+  sp.leap_tables = nullptr;
+  if (count_leap2) { st = arm_leap_tables(seg, ctx, &sp.leap_tables, nullptr); if (st != PG_OK) return st; }
+  else if (lw.stats_leap2_flagged) for (int n = 0; n < sp.num_nodes; ++n) sp.nodes[n].flags &= ~kNodeLeapfrog2;      // a kernel without the count runs this query
+  sp.raw64_coalesced = g_engine.raw64_coalesced ? 1 : 0;
+  // (the entries counted by the kernel travel in its record: BlockPartial.entries -- no counter to zero, no copy command)
+  // The folded record -> the reference's holder types.  Everything is captured by value: pg_execute_batch calls it after this function
+  // has returned (the query, the segment and the context's pinned counter outlive the batch).
+  const int kernel_id = lw.gathered ? PG_KERNEL_INDEX_AND : kScanKernels[(int)k.kernel].id;
+  const HostRecord* host_record = ctx->h_record;
+  const int profile_waves = blocks * (grid.threads / 64);
+  const size_t num_projected = r.projected.size();
+  auto convert = [q, seg, na, agg_slot_of, lw, kernel_id, host_record, count_entries, count_leap2, profile_waves, num_projected](const BlockPartial& fp, pg_result* out) {
+    out->num_aggregations = na;
+    out->aggregations = (pg_agg_value*)calloc((size_t)std::max(na, 1), sizeof(pg_agg_value));
     for (int a = 0; a < na; ++a) {
       const pg_aggregation& ag = q->aggregations[a];
+      pg_agg_value& v = out->aggregations[a];
+      empty_agg_value(&v, (int64_t)fp.count);
       if (ag.function == PG_AGG_COUNT) continue;
-      if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
-      if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
-      add_projected(ag.column);
-      int s = slot_for(&lw, seg, ag.column, lw.plane_cols[(size_t)ag.column] != 0);
-      if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
-      pl.cols[s].in_agg = 1;
-      int ac = -1;
-      for (int i = 0; i < pl.num_agg_cols; ++i) if (pl.agg_cols[i].col == s) ac = i;
-      if (ac < 0) {
-        if (pl.num_agg_cols >= kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d aggregated columns", kMaxAggCols);
-        ac = pl.num_agg_cols++;
-        pl.agg_cols[ac] = PlanAggCol{s, 0, 0, 0};
-      }
-      if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) pl.agg_cols[ac].need_sum = 1;
-      if (ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) pl.agg_cols[ac].need_minmax = 1;
-      agg_slot_of[(size_t)a] = ac;
-    }
-    bool need_queue = false, typed = false;
-    for (int i = 0; i < pl.num_agg_cols; ++i) {
-      const DevColumn& c = pl.cols[pl.agg_cols[i].col];
-      need_queue |= pl.agg_cols[i].need_sum && !c.is_raw && !c.is_plane && c.vkind == kValI32;
-      typed |= c.vkind != kValI32 && (pl.agg_cols[i].need_sum || c.is_raw);     // 8-byte / floating-point values are read
-    }
-    // The lane-private kernel (no LDS, plain global loads) takes every query whose leaves and aggregations it implements:
-    // scan / set / bitmap leaves and raw INT ranges; COUNT, and SUM through a value plane / MIN / MAX on dictionary columns.
-    // (the per-wave phase counters of PG_CFG_PROFILE_WAVES exist in the LDS-staged kernel only)
-    bool use_private = g_engine.scan_private && !typed && !(g_engine.flags & PG_CFG_PROFILE_WAVES);
-    for (int l = 0; l < pl.num_leaves && use_private; ++l) use_private = pl.leaves[l].kind <= kLeafBitmap || pl.leaves[l].kind == kLeafDocRange;
-    int hist_slot = -1;
-    for (int i = 0; i < pl.num_agg_cols && hist_col >= 0; ++i) if (lw.col_of_slot[(size_t)pl.agg_cols[i].col] == hist_col * 2) hist_slot = i;
-    for (int i = 0; i < pl.num_agg_cols && use_private; ++i) {
-      const DevColumn& c = pl.cols[pl.agg_cols[i].col];
-      use_private = !c.is_raw && c.vkind == kValI32 && c.bits <= 31 && (!pl.agg_cols[i].need_sum || c.is_plane || i == hist_slot);
-    }
-    const bool use_hist = use_private && hist_slot == 0 && pl.num_agg_cols == 1;      // the histogram kernel aggregates one column
-    if (hist_slot >= 0 && !use_hist) use_private = false;                           // (rare: the gather path of the LDS-staged kernel)
-    const int hist_cw = use_hist ? hist_counter_bits(seg->cols[(size_t)hist_col]) : 0;
-    const int hist_tier = use_hist ? std::max(__atomic_load_n(&seg->cols[(size_t)hist_col].hist_tier, __ATOMIC_RELAXED), g_engine.hist_guard ? 1 : 0) : 0;
-    const bool hist_guarded = hist_tier >= 1 && hist_cw < 32;
-    // Raw columns and 8-byte dictionaries: the same lane-private layout, read with 16-byte loads (scan_private_typed_kernel).
-    // PINOT_GPU_SCAN_TYPED_PRIVATE=0 keeps them in the LDS-staged kernel.
-    bool use_private_typed = g_engine.scan_private && g_engine.scan_typed_private && !use_private && pl.num_agg_cols > 0 && !(g_engine.flags & PG_CFG_PROFILE_WAVES);
-    for (int l = 0; l < pl.num_leaves && use_private_typed; ++l) use_private_typed = pl.leaves[l].kind <= kLeafBitmap || pl.leaves[l].kind == kLeafDocRange;
-    for (int i = 0; i < pl.num_agg_cols && use_private_typed; ++i) {
-      const DevColumn& c = pl.cols[pl.agg_cols[i].col];
-      use_private_typed = c.is_raw || (c.vkind != kValI32 && c.bits <= 31);      // every slot raw, or an 8-byte dictionary
-    }
-    Geometry geo;
-    const int agg_wave_cap = waves_scan_agg(pl.num_agg_cols <= 1, typed);
-    finish_geometry(seg, &lw, 0, need_queue, kBlockThreads / 64, agg_wave_cap, &geo);
-    int blocks = geo.blocks;
-    const size_t lds = geo.lds;
-    size_t hist_lds = 0, hist_set_off = 0;
-    if (use_hist) {
-      // one histogram per workgroup of 16 wavefronts; as many workgroups per CU as LDS and registers admit
-      const int per_word = 32 / hist_cw;
-      hist_lds = (((size_t)(seg->cols[(size_t)hist_col].cardinality + per_word - 1) / per_word * 4) + 15) & ~(size_t)15;
-      hist_lds = std::max(hist_lds, sizeof(BlockPartial) * (kHistBlockThreads / 64) + 16);      // the reduction records (+ the fold flag) reuse the counters' LDS
-      // the filter's dictId sets (IN lists) behind the counters: ScanParams.set_leaves_in_lds = 1 + the area's byte offset (scan_hist_body)
-      hist_set_off = 0;
-      if (g_engine.set_lds && hist_lds + (size_t)kSetLdsWords * 4 <= 150 * 1024)
-        for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) hist_set_off = hist_lds;
-      if (hist_set_off != 0) hist_lds += (size_t)kSetLdsWords * 4;
-      const size_t per_block = hist_lds + 256;
-      int bpc = std::max(1, std::min(waves_scan_hist(hist_cw, hist_guarded) / (kHistBlockThreads / 64), (int)((160 * 1024 - 2048) / per_block)));
-      if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-      const long long tiles2k = ((long long)seg->num_docs + 2047) / 2048;
-      const int wpb = kHistBlockThreads / 64;
-      blocks = (int)std::max<long long>(1, std::min<long long>((tiles2k + wpb - 1) / wpb, (long long)seg->num_cus * bpc));
-      if (g_engine.hist_blocks > 0) blocks = std::min(blocks, g_engine.hist_blocks);
-      geo.threads = kHistBlockThreads;
-      sp.hist_slot = hist_slot;
-      sp.hist_bins = seg->cols[(size_t)hist_col].cardinality;
-    } else if (use_private || use_private_typed) {
-      const int cap = use_private_typed ? waves_scan_private_typed(pl.num_agg_cols) : waves_scan_private(pl.num_agg_cols);
-      int bpc = std::max(1, cap / (kBlockThreads / 64));
-      if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-      const long long tiles2k = ((long long)seg->num_docs + 2047) / 2048;
-      blocks = (int)std::max<long long>(1, std::min<long long>((tiles2k + 3) / 4, (long long)seg->num_cus * bpc));
-      geo.threads = kBlockThreads;
-    } else if ((size_t)sp.wave_lds_bytes > kLdsBudget) return fail(PG_ERR_UNSUPPORTED, "query needs %d bytes of LDS per wavefront", sp.wave_lds_bytes);
-    // Nothing but a filter over narrow dictionary columns (COUNT(*) and / or the bitmap): scan_narrow_kernel, four tiles per wave and iteration
-    // (a leap-frogging `a AND b` is counted by eval_filter_private's hook: the narrow kernels have their own evaluator and do not carry it)
-    bool use_narrow = g_engine.scan_narrow && use_private && !use_hist && pl.num_agg_cols == 0 && lw.tile_list == nullptr && sp.num_nodes > 0 && !(out && lw.stats_leap2_flagged);
-    if (use_narrow) {
-      int depth = 0, max_depth = 0;
-      for (int n = 0; n < sp.num_nodes && use_narrow; ++n) {
-        const DevNode& dn = sp.nodes[n];
-        if (dn.op == PG_FILTER_LEAF) {
-          use_narrow = dn.kind == kLeafMatchAll || dn.kind == kLeafMatchNone || ((dn.kind == kLeafDictRange || (dn.kind == kLeafDictSet && g_engine.set_lds)) && dn.bits >= 1 && dn.bits <= kNarrowMaxBits);      // (a set of a narrow column: eight words in LDS, pg_scan_narrow.h)
-          depth++;
-        } else if (dn.op != PG_FILTER_NOT) depth -= dn.num_children - 1;
-        max_depth = std::max(max_depth, depth);
-      }
-      use_narrow = use_narrow && max_depth <= kNarrowStack;
-    }
-    const bool narrow_single = use_narrow && g_engine.scan_narrow_single && sp.num_nodes == 1 && sp.nodes[0].kind == kLeafDictRange;
-    // The whole filter is ONE bitmap that index_and_kernel made (its tiles listed), and every aggregated column is read as bit-packed
-    // fields: eight tiles per wave and iteration, only the matching docs' values are touched (scan_sparse_kernel)
-    const bool use_sparse = g_engine.scan_sparse && use_private && !use_hist && !use_narrow && !want_bitmap && pl.num_agg_cols > 0 && lw.tile_list != nullptr &&
-                            sp.num_nodes == 1 && sp.nodes[0].kind == kLeafBitmap && sp.nodes[0].exclusive == 0 && !(g_engine.flags & PG_CFG_PROFILE_WAVES);
-    if (use_sparse) {
-      const long long tiles2k = ((long long)seg->num_docs + 2047) / 2048;
-      int bpc = std::max(1, waves_scan_sparse(pl.num_agg_cols <= 1) / (kBlockThreads / 64));
-      if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-      blocks = (int)std::max<long long>(1, std::min<long long>((tiles2k + 4 * kSparseTiles - 1) / (4 * kSparseTiles), (long long)seg->num_cus * bpc));
-    }
-    // One dictionary-range leaf (or no filter) in front of at most one aggregated packed column, both of at most kSimpleMaxBits bits:
-    // scan_simple_kernel -- the same per-tile code with none of the general machinery, at twice the waves per SIMD (pg_scan_simple.h).
-    // (the one-stream shape `SUM(v) WHERE v in range` keeps scan_private_kernel's fused decode)
-    bool use_simple = g_engine.scan_simple && use_private && !use_hist && !use_narrow && !use_sparse && !want_bitmap && lw.tile_list == nullptr && sp.num_nodes <= 1 &&
-                      pl.num_agg_cols <= 1 && !(g_engine.flags & PG_CFG_PROFILE_WAVES) && !(out && (lw.stats_leap2_flagged || lw.stats_chain_flagged));
-    bool simple_set = false;
-    if (use_simple && sp.num_nodes == 1) {
-      const DevNode& dn = sp.nodes[0];
-      // (a dictId SET over a column of at most 16 bits -- its words fit the LDS area -- takes scan_simple_set_kernel: round 6b)
-      simple_set = dn.op == PG_FILTER_LEAF && dn.kind == kLeafDictSet && g_engine.set_lds && dn.bits <= 16;
-      use_simple = dn.op == PG_FILTER_LEAF && (dn.kind == kLeafDictRange || simple_set) && dn.bits >= 1 && dn.bits <= kSimpleMaxBits && (dn.flags & (kNodeCountEntries | kNodeLeapfrog2)) == 0;
-    }
-    if (use_simple && pl.num_agg_cols == 1) {
-      const DevAggCol& ac = sp.agg_cols[0];
-      use_simple = ac.bits >= 1 && ac.bits <= kSimpleMaxBits && !ac.is_raw;
-      if (use_simple && sp.num_nodes == 1 && sp.nodes[0].fwd == ac.fwd && sp.nodes[0].bits == ac.bits && ac.need_sum != 0 && ac.need_minmax == 0 && sp.nodes[0].exclusive == 0) use_simple = false;
-    }
-    // A segment whose tiles all fit the chip at once (one tile per wave: a 10 M-row segment at five waves per SIMD) is latency from end
-    // to end -- launch, one round of loads, the hand-off of the workgroups' records to the fold.  Ten waves per workgroup there: 2.5x
-    // fewer records, and a folding workgroup of 640 threads takes them in ONE round of loads (256 threads took five for 1221 records).
-    int lean_threads = kBlockThreads;
-    auto lean_geometry = [&](int wave_cap) {
-      const long long tiles2k = ((long long)seg->num_docs + 2047) / 2048;
-      static const bool wide_ok = getenv("PINOT_GPU_WIDE_BLOCKS") && getenv("PINOT_GPU_WIDE_BLOCKS")[0] == '1';      // (measured slower at every size: off unless asked for)
-      const int wide_waves = kWideBlockThreads / 64;
-      const bool wide = wide_ok && wave_cap >= 2 * wide_waves && tiles2k > 64 && tiles2k <= (long long)seg->num_cus * wave_cap && g_engine.blocks_per_cu <= 0;
-      lean_threads = wide ? kWideBlockThreads : kBlockThreads;
-      const int wpb = lean_threads / 64;
-      int bpc = std::max(1, wave_cap / wpb);
-      // Up to two rounds of resident waves' worth of tiles (~20 M rows), the hand-off of the workgroups' records to the fold weighs more
-      // than a second round of loads: two workgroups per CU (profiles/r4/c1_probe_blocks_per_cu.jsonl: 10 M rows, 1221 workgroups
-      // 21.4 us, 512 workgroups 17.8 us; the scan alone 12.9 us)
-      static const int small_bpc = getenv("PINOT_GPU_SMALL_BLOCKS_PER_CU") ? atoi(getenv("PINOT_GPU_SMALL_BLOCKS_PER_CU")) : 2;
-      if (!wide && small_bpc > 0 && tiles2k <= 2ll * seg->num_cus * wave_cap) bpc = std::min(bpc, small_bpc);
-      if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-      blocks = (int)std::max<long long>(1, std::min<long long>((tiles2k + wpb - 1) / wpb, (long long)seg->num_cus * bpc));
-    };
-    if (use_simple) lean_geometry(waves_scan_simple());
-    // The same idea for raw INT columns (BASELINE.json configs[0]'s scan pair): one raw-range leaf (or no filter) in front of at most one
-    // aggregated raw INT column -- scan_raw_kernel, five waves per SIMD, coalesced reads (pg_scan_raw.h).
-    bool use_raw = g_engine.scan_raw && (use_private || use_private_typed) && !use_hist && !use_narrow && !use_sparse && !use_simple && !want_bitmap && lw.tile_list == nullptr &&
-                   lw.side == nullptr && sp.num_nodes <= 1 && pl.num_agg_cols <= 1 && sp.num_nodes + pl.num_agg_cols >= 1 && !(g_engine.flags & PG_CFG_PROFILE_WAVES) &&
-                   !(out && (lw.stats_leap2_flagged || lw.stats_chain_flagged));
-    if (use_raw && sp.num_nodes == 1) {
-      const DevNode& dn = sp.nodes[0];
-      use_raw = dn.op == PG_FILTER_LEAF && dn.kind == kLeafRawRange && dn.fwd != nullptr && (dn.flags & (kNodeCountEntries | kNodeLeapfrog2)) == 0;
-    }
-    if (use_raw && pl.num_agg_cols == 1) {
-      const DevAggCol& ac = sp.agg_cols[0];
-      use_raw = ac.is_raw != 0 && ac.vkind == kValI32 && ac.is_plane == 0 && ac.bits == 32;
-    }
-    if (use_raw) lean_geometry(waves_scan_raw());
-    if (use_narrow) {
-      const int per_wave = narrow_single ? kNarrowSingleTiles : kNarrowTiles;
-      const long long quads = (((long long)seg->num_docs + 2047) / 2048 + per_wave - 1) / per_wave;
-      int bpc = std::max(1, waves_scan_narrow(narrow_single) / (kBlockThreads / 64));
-      if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-      blocks = (int)std::max<long long>(1, std::min<long long>((quads + 3) / 4, (long long)seg->num_cus * bpc));
-    }
-    sp.speculate = 1;
-    sp.profile = (g_engine.flags & PG_CFG_PROFILE_WAVES) ? 1 : 0;
-    st = ensure_partials(ctx, blocks);
-    if (st != PG_OK) return st;
-    sp.partials = ctx->d_partials;
-    sp.out_bitmap = nullptr;
-    if (want_bitmap) {
-      st = ensure_bitmap(seg, ctx, 0);
-      if (st != PG_OK) return st;
-      sp.out_bitmap = ctx->d_bitmaps[0];
-    }
-    sp.sparse_windows = nullptr; sp.sparse_num_windows = 0;
-    bool defer_index_and = false;
-    const unsigned long long seq = ++ctx->seq;      // the sequence number the query's folded record is published under (a gathering index_and_kernel's, or the scan kernel's)
-    if (use_sparse) {
-      // A handful of survivors per window (the planner's estimate from the postings' sizes: independent predicates): index_and_kernel reads
-      // their values itself -- ONE launch for `SUM(v) WHERE p = 3 AND q = 5 AND r = 7` (BASELINE.json configs[4]); else scan_sparse_kernel
-      // walks the window masks behind it (no list, no index_and_finalize_kernel between the two kernels).  PINOT_GPU_INDEX_GATHER=0: never.
-      const bool gather = g_engine.index_gather && lw.and_pending && lw.index_and_is_whole_filter && out && pl.num_agg_cols <= kMaxAndGather &&
-                          lw.and_expected_docs <= 4.0 * (double)lw.finalize_windows;
-      defer_index_and = gather && defer != nullptr && !defer->single && g_engine.batch_index && g_engine.direct_result && !want_bitmap && index_and_shares_a_launch(lw);
-      if (defer_index_and) arm_index_gather(&lw, &sp);      // (launched by the batch: index_and_batch_kernel, lean_kind 12)
-      else st = launch_index_and(&lw, ctx, gather ? &sp : nullptr);
-      if (st != PG_OK) return st;
-      sp.tile_list = lw.tile_list; sp.tile_count = lw.tile_count;      // (not read by the kernel; "listed" is what the planner and the statistics go by)
-      sp.sparse_windows = lw.and_info; sp.sparse_num_windows = (int32_t)lw.finalize_windows;
-    } else if (!want_bitmap && (use_hist || use_private || use_private_typed)) {
-      st = complete_index_list(&lw, ctx); if (st != PG_OK) return st;
-      sp.tile_list = lw.tile_list; sp.tile_count = lw.tile_count;
-    }
-    else { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
-    const bool count_leap2 = out && lw.stats_leap2_flagged && !use_narrow && (use_hist || use_private || use_private_typed);
-    const bool count_entries = (out && lw.stats_chain_flagged && (use_hist || use_private || use_private_typed)) || count_leap2;
-    if (lw.side != nullptr) {
-      // the transducer pass behind this query: a kernel that evaluates the filter with eval_filter_private over every tile leaves the leaves' bitmaps behind
-      const bool wrote = !(use_narrow && narrow_single) && !use_sparse && !use_simple && !use_raw && (use_hist || use_private || use_private_typed) && sp.tile_list == nullptr;
-      for (int l = 0; l < kMaxLeaves; ++l) sp.leaf_out[l] = wrote ? lw.sp_leaf_out[l] : nullptr;
-      sp.leaf_out_enabled = wrote ? 1 : 0;
-      lw.side->kernel_wrote = wrote;
-    }
-    // The transducer walked INSIDE the general lane-private kernel (scan_private_fsm_kernel): machines of at most four states over at most
-    // four inputs, every input a leaf of its own in the lowered filter.  No leaf bitmap is written or read back; the tiles' tables are
-    // joined by fsm_chain_kernel / fsm_finish_kernel behind the scan, on the query's stream.  PINOT_GPU_FSM_FUSED=0: the separate pass.
-    bool fuse_fsm = false;
-    sp.fsm_tables = nullptr; sp.fsm_states = 0; sp.fsm_inputs = 0;
-    // (NOT in scan_narrow_kernel: measured on `COUNT(*) WHERE p = 3 AND q = 5 AND r = 7` over 4 / 6 / 8-bit columns, 1 B rows -- the walk takes the
-    //  kernel from 164 to 199 registers, three to two waves per SIMD, 0.53 -> 0.85 ms, more than the 0.24 ms pass it replaces: 0.767 -> 0.868 ms
-    //  for the query; the same query through this kernel: 1.06 ms.  profiles/r5/fsm_walk_inside_the_scan_ab.txt)
-    if (lw.side != nullptr && sp.leaf_out_enabled != 0 && g_engine.fsm_fused && g_engine.fsm_perm && use_private && !use_hist && !use_narrow && !use_sparse && !use_simple && !use_raw && out) {
-      const fstats::Fsm& f = *lw.side->fsm;
-      int max_inc = 0;
-      for (uint8_t d : f.delta) max_inc = std::max(max_inc, (int)(d >> 4));
-      bool fits = f.num_states <= 4 && f.num_inputs <= 4 && max_inc <= 7 && !f.has_episodes();      // (episodes need the second walk of the pass)
-      for (int i = 0; i < f.num_inputs && fits; ++i) fits = lw.side->mapped[i];
-      if (fits) {
-        fuse_fsm = true;
-        sp.fsm_tables = lw.side->tables; sp.fsm_states = f.num_states; sp.fsm_inputs = f.num_inputs;
-        for (int l = 0; l < kMaxLeaves; ++l) {
-          sp.fsm_input_of_leaf[l] = -1;
-          for (int i = 0; i < f.num_inputs; ++i) if (sp.leaf_out[l] != nullptr && sp.leaf_out[l] == lw.side->bitmap[i]) sp.fsm_input_of_leaf[l] = (int8_t)i;
-          sp.leaf_out[l] = nullptr;
+      const int ac = agg_slot_of[(size_t)a];
+      const ColumnDev& col = seg->cols[(size_t)ag.column];
+      const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
+      const bool raw = col.encoding == PG_FWD_RAW_FIXED_BYTE;
+      if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) {
+        if (col.vkind == kValF64 || col.vkind == kValF32) {
+          // SumAggregationFunction on FLOAT / DOUBLE: a double sum; the addition order differs from the reference's
+          // doc order, so the last bits may (tests/test_gpu_typed.py states the tolerance)
+          v.sum = fp.fsum[ac];
+          v.sum_i64 = 0;
+          v.sum_exact = 0;
+        } else if (col.vkind == kValI64) {
+          // LONG values: the int64 sum is exact unless it wrapped, which the double image of the same sum reveals (a wrap moves
+          // it by a multiple of 2^64).  Wrapped: report the double sum, like the reference's double accumulation, inexact.
+          v.sum_i64 = fp.sum[ac];
+          const bool wrapped = std::fabs(fp.fsum[ac] - (double)fp.sum[ac]) > 4.6e18;
+          v.sum_exact = wrapped ? 0 : 1;
+          v.sum = wrapped ? fp.fsum[ac] : (double)v.sum_i64;
+        } else {
+          // value plane: sum(value) = count * base + sum(value - base); offset dictionaries add count * value_base
+          set_integer_sum(&v, (__int128)fp.sum[ac] * (__int128)sum_scale(col, plane) + (__int128)fp.count * (__int128)sum_base(col, plane));
         }
-        sp.leaf_out_enabled = 0;
-        memset(sp.fsm_delta, 0, sizeof(sp.fsm_delta));
-        for (int st8 = 0; st8 < f.num_states; ++st8)
-          for (int in = 0; in < (1 << f.num_inputs); ++in) sp.fsm_delta[(st8 << 4) | in] = f.delta[(size_t)((st8 << f.num_inputs) | in)];
-        if (!ctx->h_filter_entries) HIP_TRY(hipHostMalloc((void**)&ctx->h_filter_entries, 8, hipHostMallocDefault));
-      }
-    }
-    sp.filter_entries = nullptr;
-    sp.leap_tables = nullptr;
-    if (count_leap2) { st = arm_leap_tables(seg, ctx, &sp.leap_tables, nullptr); if (st != PG_OK) return st; }
-    else if (lw.stats_leap2_flagged) for (int n = 0; n < sp.num_nodes; ++n) sp.nodes[n].flags &= ~kNodeLeapfrog2;      // a kernel without the count runs this query
-    sp.raw64_coalesced = g_engine.raw64_coalesced ? 1 : 0;
-    // (the entries counted by the kernel travel in its record: BlockPartial.entries -- no counter to zero, no copy command)
-    // The folded record -> the reference's holder types.  Everything is captured by value: pg_execute_batch calls it after this function
-    // has returned (the query, the segment and the context's pinned counter outlive the batch).
-    const int kernel_id = lw.gathered ? PG_KERNEL_INDEX_AND : use_hist ? PG_KERNEL_SCAN_HIST : use_narrow ? PG_KERNEL_SCAN_NARROW : use_sparse ? PG_KERNEL_SCAN_SPARSE : use_simple ? PG_KERNEL_SCAN_SIMPLE : use_raw ? PG_KERNEL_SCAN_RAW : use_private ? PG_KERNEL_SCAN_PRIVATE : (use_private_typed ? PG_KERNEL_SCAN_PRIVATE_TYPED : PG_KERNEL_SCAN_AGG);
-    const HostRecord* host_record = ctx->h_record;
-    const int profile_waves = blocks * (geo.threads / 64);
-    const size_t num_projected = projected.size();
-    auto convert = [q, seg, na, agg_slot_of, lw, kernel_id, host_record, count_entries, count_leap2, profile_waves, num_projected](const BlockPartial& fp, pg_result* out) {
-      out->num_aggregations = na;
-      out->aggregations = (pg_agg_value*)calloc((size_t)std::max(na, 1), sizeof(pg_agg_value));
-      for (int a = 0; a < na; ++a) {
-        const pg_aggregation& ag = q->aggregations[a];
-        pg_agg_value& v = out->aggregations[a];
-        v.count = (int64_t)fp.count;
-        v.min = std::numeric_limits<double>::infinity();
-        v.max = -std::numeric_limits<double>::infinity();
-        if (ag.function == PG_AGG_COUNT) continue;
-        const int ac = agg_slot_of[(size_t)a];
-        const ColumnDev& col = seg->cols[(size_t)ag.column];
-        const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
-        const bool raw = col.encoding == PG_FWD_RAW_FIXED_BYTE;
-        if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) {
-          if (col.vkind == kValF64 || col.vkind == kValF32) {
-            // SumAggregationFunction on FLOAT / DOUBLE: a double sum; the addition order differs from the reference's
-            // doc order, so the last bits may (tests/test_gpu_typed.py states the tolerance)
-            v.sum = fp.fsum[ac];
-            v.sum_i64 = 0;
-            v.sum_exact = 0;
-          } else if (col.vkind == kValI64) {
-            // LONG values: the int64 sum is exact unless it wrapped, which the double image of the same sum reveals (a wrap moves
-            // it by a multiple of 2^64).  Wrapped: report the double sum, like the reference's double accumulation, inexact.
-            v.sum_i64 = fp.sum[ac];
-            const bool wrapped = std::fabs(fp.fsum[ac] - (double)fp.sum[ac]) > 4.6e18;
-            v.sum_exact = wrapped ? 0 : 1;
-            v.sum = wrapped ? fp.fsum[ac] : (double)v.sum_i64;
-          } else {
-            // value plane: sum(value) = count * base + sum(value - base); offset dictionaries add count * value_base
-            set_integer_sum(&v, (__int128)fp.sum[ac] * (__int128)sum_scale(col, plane) + (__int128)fp.count * (__int128)sum_base(col, plane));
-          }
-        } else if (fp.count > 0) {
-          if (raw && col.vkind != kValI32) {
-            double mn = key64_to_double(col, fp.kmin64[ac]), mx = key64_to_double(col, fp.kmax64[ac]);
-            if (mx != mx) mn = mx;      // Math.min / Math.max propagate NaN
-            if (ag.function == PG_AGG_MIN) v.min = mn;
-            if (ag.function == PG_AGG_MAX) v.max = mx;
-          } else {
-            if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, fp.kmin[ac], plane);
-            if (ag.function == PG_AGG_MAX) v.max = agg_value_double(col, fp.kmax[ac], plane);
-          }
+      } else if (fp.count > 0) {
+        if (raw && col.vkind != kValI32) {
+          double mn = key64_to_double(col, fp.kmin64[ac]), mx = key64_to_double(col, fp.kmax64[ac]);
+          if (mx != mx) mn = mx;      // Math.min / Math.max propagate NaN
+          if (ag.function == PG_AGG_MIN) v.min = mn;
+          if (ag.function == PG_AGG_MAX) v.max = mx;
+        } else {
+          if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, fp.kmin[ac], plane);
+          if (ag.function == PG_AGG_MAX) v.max = agg_value_double(col, fp.kmax[ac], plane);
         }
       }
-      out->dominant_kernel = kernel_id;
-      for (int c = 0; c < 4; ++c) out->profile_cycles[c] = fp.cyc[c];
-      out->profile_waves = profile_waves;
-      out->stats.num_docs_scanned = (int64_t)fp.count;
-      // (the scan kernels count into their records; a leap-frogging a AND b adds what leapfrog2_chain_kernel left in the pinned record)
-      finish_filter_stats(lw, seg, (int64_t)fp.entries + (count_leap2 ? host_record->leap_correction : 0), count_entries, out);
-      out->stats.num_entries_scanned_post_filter = (int64_t)fp.count * (int64_t)num_projected;
-      out->stats.num_total_docs = seg->num_docs;
-    };
-    // The workgroups' records are folded by the scan kernel's last workgroup, straight into the pinned host record.
-    // Measured (profiles/r3, tools/ab_r3.py): the fold costs the kernel 5.5 us of tail on a 1024-workgroup grid where the finalize launch
-    // costs 8.8 us (boundary + a one-workgroup kernel) -- 13 % of a 10 M-row query's device time.  Round 4: at EVERY size (1 B-row scans
-    // were left with the separate launch so that the scan kernel's profiler duration was "the scan and nothing else"; the query paid
-    // ~15 us for that, and its roofline fraction is a statement about the query, not about its largest kernel).
-    const bool folded = g_engine.fold_finalize >= 0 ? g_engine.fold_finalize != 0 : true;
-    sp.done_counter = folded ? ctx->d_done : nullptr;
-    sp.host_out = g_engine.direct_result ? ctx->h_record_dev : nullptr;
-    sp.host_seq = seq;
-    // fields a fold reduces: the aggregation slots in use (the histogram kernel keeps its checksum in slot 1), typed extras only for the typed kernels
-    sp.fold_slots = use_hist ? 2 : pl.num_agg_cols;
-    sp.fold_typed = (!use_raw && (use_private_typed || (!use_hist && !use_narrow && !use_private && typed))) ? 1 : 0;
-    sp.lane_skip = g_engine.lane_skip ? 1 : 0;
-    sp.set_leaves_in_lds = 0;
-    if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
-    if (use_hist) sp.set_leaves_in_lds = hist_set_off != 0 ? 1 + (int32_t)hist_set_off : 0;      // (the histogram kernel keeps the area in its dynamic LDS, behind the counters)
-    sp.sparse_lanes = g_engine.sparse_lanes;
-    sp.fold_one_counter = g_engine.fold_one_counter;
-    if (defer_index_and) {
-      auto item = std::make_shared<LoweredItem>();
-      memset(&item->sp, 0, sizeof(item->sp));
-      item->sp.lean_kind = 12;
-      item->and_params = std::make_shared<IndexAndParams>(lw.and_params);
-      item->and_windows = lw.finalize_windows;
-      item->blocks = (int)std::min<long long>(((long long)lw.finalize_windows + index_and_batch_block_waves() - 1) / index_and_batch_block_waves(), (long long)lw.and_num_cus * index_and_batch_blocks_per_cu());
-      item->one_slot = pl.num_agg_cols <= 1;
-      item->convert = convert;
-      item->plane_columns = planes.columns;
-      defer->item = std::move(item);
-      defer->cacheable = !lw.plane_pending;
-      defer->planes.reset(new PlaneHold(std::move(planes)));
-      return kDeferred;
     }
-    if (defer != nullptr) {
-      // (the shared launch is for the many small segments of a server: a segment that fills the chip on its own -- more tiles than a few
-      //  rounds of resident waves -- runs the kernel the planner picked for it, concurrently with the others, on a worker thread's stream:
-      //  eight 1 B-row items 4.72 ms in one launch, 4.45 ms as eight overlapping launches)
-      // kinds of shared launch (ScanParams.lean_kind; pg_execute_batch groups a batch's deferred items by device and kind, one launch each):
-      //   0 scan_private_batch_kernel (the general body)   1 / 2 scan_lean_batch_kernel (scan_simple / scan_raw shape)
-      //   3 / 4 / 5 scan_hist_batch_kernel<8 | 16 | 32> (SUM through the LDS histogram: dictionaries without structure, plain counters)
-      //   6 group_lds_batch_kernel (group-bys of the LDS-table form: lowered in the group-by branch below)
-      //   7 / 8 scan_narrow_batch_kernel<general | single leaf> (COUNT under filters over columns of at most 8 bits)
-      //   9 / 10 / 11 scan_typed_batch_kernel<1 | 2 | kMaxAggCols> (raw and 8-byte aggregated columns)
-      const bool hist_item = use_hist && !hist_guarded && g_engine.batch_hist;
-      const bool narrow_item = use_narrow && g_engine.batch_more;
-      const bool typed_item = use_private_typed && !use_raw && !use_sparse && g_engine.batch_more;
-      if (!defer->single && ((use_private && !use_hist && !use_narrow) || use_raw || hist_item || narrow_item || typed_item) && !use_sparse && !want_bitmap && out && sp.tile_list == nullptr && !count_entries && !ctx->pre_enqueued && g_engine.direct_result &&
-          lw.side == nullptr && ((long long)seg->num_docs + 2047) / 2048 <= kBatchMaxTiles &&
-          stats_is_final) {
-        // items of scan_simple_kernel's / scan_raw_kernel's shape share a launch of their own kind (scan_lean_batch_kernel), the rest the general one
-        const bool lean_batch = g_engine.lean_batch;
-        sp.lean_kind = hist_item ? (hist_cw == 8 ? 3 : (hist_cw == 16 ? 4 : 5)) : narrow_item ? (narrow_single ? 8 : 7) : typed_item ? (pl.num_agg_cols <= 1 ? 9 : (pl.num_agg_cols == 2 ? 10 : 11))
-                       : use_simple ? (simple_set ? 13 : 1) : (use_raw ? 2 : 0);      // (13: scan_lean_batch_kernel<13>, the simple body with its one set leaf in LDS)
-        if (!lean_batch && (sp.lean_kind == 1 || sp.lean_kind == 13)) sp.lean_kind = 0;      // (a raw-shaped item has no general form when its column is aggregated: it stays lean)
-        if (sp.lean_kind == 2 && !lean_batch && use_private) sp.lean_kind = 0;
-        auto item = std::make_shared<LoweredItem>();
-        item->sp = sp;
-        item->blocks = blocks;
-        item->one_slot = pl.num_agg_cols <= 1;
-        item->convert = convert;
-        item->plane_columns = planes.columns;
-        item->sets = lw.set_leaves;
-        if (hist_item) { item->hist_lds = hist_lds; item->hist_cw = hist_cw; item->hist_col = hist_col; }
-        defer->item = std::move(item);
-        defer->cacheable = !lw.plane_pending;
-        defer->planes.reset(new PlaneHold(std::move(planes)));
-        return kDeferred;
-      }
-    }
-    // HIP events (PG_CFG_TIME_KERNELS): [ev_first, ev_last] brackets the query's device work, [ev[1], ev[2]] the scan kernel.  Each
-    // record is a packet of its own on the queue, so a query that runs nothing but the scan kernel records just the two.
-    // (the chain kernel / copy commands behind the scan kernel; a kernel that leaves leaf bitmaps behind for the transducer pass must have
-    //  RETIRED before that pass reads them -- its plain stores are only ordered by the end of the kernel, not by the pinned record's seq)
-    if (lw.gathered) {
-      // index_and_kernel did the aggregation: its counter lines are the query's record
-      // (timed runs: ev[0] in front of the kernel and ev[3] behind the copy, like the COUNT(*) path -- two more records between the
-      //  kernel and its copy were two more packets on the queue, ~5 us that only a timed run paid)
-      HIP_TRY(hipMemcpyAsync(ctx->h_and_shards, ctx->d_and_counters + 2, kAndShardBytes, hipMemcpyDeviceToHost, ctx->stream));
-      if (timed) HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-      ctx->ev_last = 3;
-      exec_mark(3);
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      exec_mark(4);
-      BlockPartial g;
-      st = read_index_and_shards(ctx, pl.num_agg_cols, &g);
-      if (st != PG_OK) return st;
-      *ctx->h_partial = g;
-    } else {
-    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || fuse_fsm;
+    out->dominant_kernel = kernel_id;
+    for (int c = 0; c < 4; ++c) out->profile_cycles[c] = fp.cyc[c];
+    out->profile_waves = profile_waves;
+    out->stats.num_docs_scanned = (int64_t)fp.count;
+    // (the scan kernels count into their records; a leap-frogging a AND b adds what leapfrog2_chain_kernel left in the pinned record)
+    finish_filter_stats(lw, seg, (int64_t)fp.entries + (count_leap2 ? host_record->leap_correction : 0), count_entries, out);
+    out->stats.num_entries_scanned_post_filter = (int64_t)fp.count * (int64_t)num_projected;
+    out->stats.num_total_docs = seg->num_docs;
+  };
+  // The workgroups' records are folded by the scan kernel's last workgroup, straight into the pinned host record.
+  // Measured (profiles/r3, tools/ab_r3.py): the fold costs the kernel 5.5 us of tail on a 1024-workgroup grid where the finalize launch
+  // costs 8.8 us (boundary + a one-workgroup kernel) -- 13 % of a 10 M-row query's device time.  Round 4: at EVERY size (1 B-row scans
+  // were left with the separate launch so that the scan kernel's profiler duration was "the scan and nothing else"; the query paid
+  // ~15 us for that, and its roofline fraction is a statement about the query, not about its largest kernel).
+  const bool folded = g_engine.fold_finalize >= 0 ? g_engine.fold_finalize != 0 : true;
+  sp.done_counter = folded ? ctx->d_done : nullptr;
+  sp.host_out = g_engine.direct_result ? ctx->h_record_dev : nullptr;
+  sp.host_seq = seq;
+  // fields a fold reduces: the aggregation slots in use (the histogram kernel keeps its checksum in slot 1), typed extras only for the typed kernels
+  sp.fold_slots = k.kernel == ScanKernel::Hist ? 2 : pl.num_agg_cols;
+  sp.fold_typed = (k.kernel == ScanKernel::PrivateTyped || (k.kernel == ScanKernel::Agg && typed)) ? 1 : 0;
+  sp.lane_skip = g_engine.lane_skip ? 1 : 0;
+  sp.set_leaves_in_lds = 0;
+  if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
+  if (k.kernel == ScanKernel::Hist) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram kernel keeps the area in its dynamic LDS, behind the counters)
+  sp.sparse_lanes = g_engine.sparse_lanes;
+  sp.fold_one_counter = g_engine.fold_one_counter;
+  if (defer_index_and) {
+    auto item = index_and_item(lw);
+    item->one_slot = pl.num_agg_cols <= 1;
+    item->convert = convert;
+    return defer_item(r, std::move(item));
+  }
+  // (the shared launch is for the many small segments of a server: a segment that fills the chip on its own -- more tiles than a few
+  //  rounds of resident waves -- runs the kernel the planner picked for it, concurrently with the others, on a worker thread's stream:
+  //  eight 1 B-row items 4.72 ms in one launch, 4.45 ms as eight overlapping launches)
+  BatchKind kind = BatchKind::Private;
+  if (r.defer != nullptr && !r.defer->single && scan_batch_kind(k, pl.num_agg_cols, &kind) && !want_bitmap && out && sp.tile_list == nullptr && !count_entries &&
+      !ctx->pre_enqueued && g_engine.direct_result && lw.side == nullptr && doc_tiles(seg) <= kBatchMaxTiles && r.stats_is_final) {
+    sp.lean_kind = (int32_t)kind;
+    auto item = std::make_shared<LoweredItem>();
+    item->sp = sp;
+    item->blocks = blocks;
+    item->one_slot = pl.num_agg_cols <= 1;
+    item->convert = convert;
+    item->sets = lw.set_leaves;
+    if (k.kernel == ScanKernel::Hist) { item->hist_lds = grid.lds; item->hist_cw = k.hist_cw; item->hist_col = r.hist_col; }
+    return defer_item(r, std::move(item));
+  }
+  // HIP events (PG_CFG_TIME_KERNELS): [ev_first, ev_last] brackets the query's device work, [ev[1], ev[2]] the scan kernel.  Each
+  // record is a packet of its own on the queue, so a query that runs nothing but the scan kernel records just the two.
+  // (the chain kernel / copy commands behind the scan kernel; a kernel that leaves leaf bitmaps behind for the transducer pass must have
+  //  RETIRED before that pass reads them -- its plain stores are only ordered by the end of the kernel, not by the pinned record's seq)
+  if (lw.gathered) {
+    // index_and_kernel did the aggregation: its counter lines are the query's record
+    // (timed runs: ev[0] in front of the kernel and ev[3] behind the copy, like the COUNT(*) path -- two more records between the
+    //  kernel and its copy were two more packets on the queue, ~5 us that only a timed run paid)
+    HIP_TRY(hipMemcpyAsync(ctx->h_and_shards, ctx->d_and_counters + 2, kAndShardBytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (timed) HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->ev_last = 3;
+    exec_mark(3);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    exec_mark(4);
+    BlockPartial g;
+    st = read_index_and_shards(ctx, pl.num_agg_cols, &g); if (st != PG_OK) return st;
+    *ctx->h_partial = g;
+  } else {
+    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm;
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    // the single-aggregated-column instantiation needs a third fewer registers (one more wavefront per SIMD)
-    const bool one = pl.num_agg_cols <= 1;
-    if (use_hist) launch_scan_hist(hist_cw, hist_guarded, blocks, hist_lds, ctx->stream, sp);
-    else if (use_narrow) launch_scan_narrow(narrow_single, blocks, ctx->stream, sp);
-    else if (use_sparse) launch_scan_sparse(one, blocks, ctx->stream, sp);
-    else if (use_simple) launch_scan_simple(blocks, lean_threads, ctx->stream, sp, simple_set && use_simple);
-    else if (use_raw) launch_scan_raw(blocks, lean_threads, ctx->stream, sp);
-    else if (use_private && fuse_fsm) launch_scan_private_fsm(pl.num_agg_cols, blocks, ctx->stream, sp);
-    else if (use_private) launch_scan_private(pl.num_agg_cols, blocks, ctx->stream, sp);
-    else if (use_private_typed) launch_scan_private_typed(pl.num_agg_cols, blocks, ctx->stream, sp);
-    else launch_scan_agg(g_engine.use_dma, one, typed, blocks, geo.threads, lds, ctx->stream, sp);
+    launch_scan_kernel(k, grid, pl.num_agg_cols, typed, ctx->stream, sp);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
     if (!folded) {
@@ -3301,7 +3237,7 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
     }
     if (!g_engine.direct_result) HIP_TRY(hipMemcpyAsync(ctx->h_partial, ctx->d_partials + blocks, sizeof(BlockPartial), hipMemcpyDeviceToHost, ctx->stream));
     if (count_leap2) { st = launch_leap_chain(seg, ctx, seq); if (st != PG_OK) return st; }
-    if (fuse_fsm) {
+    if (k.kernel == ScanKernel::PrivateFsm) {
       // the tiles' tables -> the count (the same two kernels that end the separate pass), then eight bytes to the context's pinned counter
       const FsmSide& fs = *lw.side;
       fsm_chain_kernel<<<dim3((unsigned)fs.num_chunks), dim3(1024), 0, ctx->stream>>>(fs.tables, fs.num_tiles, sp.fsm_states, fs.chunks);
@@ -3325,8 +3261,7 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
     if (g_engine.poll_result && !post_work && !timed) {
       // nothing follows the kernel on the stream: the record's sequence number is the completion signal
       volatile unsigned long long* flag = &ctx->h_record->seq;
-      st = wait_polled(ctx->stream, (long long)seg->num_docs, [&] { return *flag == seq; });
-      if (st != PG_OK) return st;
+      st = wait_polled(ctx->stream, (long long)seg->num_docs, [&] { return *flag == seq; }); if (st != PG_OK) return st;
       if (*flag != seq) return fail(PG_ERR_INTERNAL, "the scan kernel finished without publishing its record");
     } else {
       HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -3334,747 +3269,729 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
     exec_mark(4);
     if (count_leap2 && ctx->h_record->leap_seq != seq) return fail(PG_ERR_INTERNAL, "the leap-frog chain kernel did not publish its result");
     if (g_engine.direct_result && ctx->h_record->seq != seq) return fail(PG_ERR_INTERNAL, "the scan kernel's record carries sequence %llu, expected %llu", ctx->h_record->seq, seq);
-    }
-    const BlockPartial& fp = *ctx->h_partial;
-    // (the in-kernel fold orders the workgroups' records against their arrival counter through write-through stores, not through a
-    //  release / acquire pair: every record carries its launch's stamp and a foreign one is an error, never an answer)
-    if (fp.flags & kPartialStale) return fail(PG_ERR_INTERNAL, "the scan kernel's fold read a record that was not written by this launch (sequence %llu)", seq);
-    // plain narrow counters: the counters must add up to the matches (a wrapped counter always leaves the total short)
-    const bool hist_wrapped = use_hist && !hist_guarded && hist_cw < 32 && (unsigned long long)fp.sum[1] != fp.count;
-    if (use_hist && (hist_wrapped || (fp.flags & kPartialHistAlarm))) {
-      // Skewed dictIds: the histogram's sum is not used.  From now on the column runs in the next tier -- guarded counters, which count
-      // hot dictIds exactly through guard-bit claims, then the value plane / gather path -- and this query is answered again.
-      __atomic_store_n(&seg->cols[(size_t)hist_col].hist_tier, hist_wrapped ? 1 : 2, __ATOMIC_RELAXED);
-      seg->plane_epoch.fetch_add(1, std::memory_order_acq_rel);      // (what the plan cache holds for this segment was lowered for the plain tier)
-      release_ctx(seg, ctx);
-      guard.ctx = nullptr;
-      return execute_impl(seg, q, out, d_out_bitmap_request, host_bitmap, host_bitmap_words, out_cardinality, allow_metadata_plan, nullptr, side);
-    }
-    if (out_cardinality) *out_cardinality = (int64_t)fp.count;
-    if (out) convert(fp, out);
-    if (out && fuse_fsm) {
-      // (the stream was synchronised: the walk's count is in the pinned counter)
-      out->stats.num_entries_scanned_in_filter = (int64_t)*ctx->h_filter_entries;
-      out->filter_entries_exact = 1;
-      lw.side->fused = true;
-    }
-  } else {
-    // ---------------- group-by (ArrayBasedHolder) ----------------
-    GroupParams gp;
-    memset(&gp, 0, sizeof(gp));
-    int group_slot[kMaxGroupCols] = {}, group_mult[kMaxGroupCols] = {};
-    PlanGroupAgg plan_aggs[kMaxGroupAggs];
-    long long product = 1;
-    std::vector<int> cards;
-    bool no_dict_keys = false;            // a key is a raw column read through its key image, or the null-key image of one
-    for (int g = 0; g < ng; ++g) {
-      int c = q->group_by_columns[g];
-      if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
-      add_projected(seg->cols[(size_t)c].key_image_of >= 0 ? seg->cols[(size_t)c].key_image_of : c);      // numEntriesScannedPostFilter counts the caller's column
-      if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
-        // NoDictionarySingle/MultiColumnGroupKeyGenerator: the raw INT / LONG column through its key image (value - min as the dictId)
-        st = ensure_key_image(seg, c, &c);
-        if (st != PG_OK) return st;
-      }
-      const ColumnDev& col = seg->cols[(size_t)c];
-      no_dict_keys |= col.key_image_of >= 0;
-      int s = slot_for(&lw, seg, c);
-      if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
-      pl.cols[s].in_agg = 1;
-      group_slot[g] = s;
-      cards.push_back(col.cardinality);
-    }
-    // DictionaryBasedGroupKeyGenerator.java:164-184: up to arrayBasedThreshold (10 000) the raw key IS the group id (ArrayBasedHolder);
-    // above it the reference hashes raw keys (IntMapBasedHolder) -- here the table stays direct-indexed, in HBM, one slot per raw
-    // key, and only the groups that exist come back.  2^24 slots keep the 24-bit key multiplies exact and the table <= 1.2 GB.
-    // Beyond an int (Long / ArrayMap holders) the table is hashed: `product` is then its number of slots (plan_hash_holder).
-    HashPlan hash_plan;
-    st = plan_hash_holder(seg, cards, &hash_plan);
-    if (st != PG_OK) return st;
-    if (hash_plan.kind == 0) {
-      for (int g = 0; g < ng; ++g) { group_mult[g] = (int32_t)product; product *= cards[(size_t)g]; }
-    } else {
-      product = hash_plan.slots;
-      if (q->flags & kQueryHashHolder) return fail(PG_ERR_UNSUPPORTED, "group-by with raw keys beyond an int under null handling (plan-time fallback)");
-    }
-    // (kQueryHashHolder: the no-dictionary key generators of null handling hand out group ids by first appearance up to numGroupsLimit
-    //  whatever the key space: the compaction path below is the one that honours the limit)
-    // A raw key column always runs the no-dictionary generators (DefaultGroupByExecutor.java:106-121): _globalGroupIdUpperBound =
-    // numGroupsLimit whatever the key space (NoDictionarySingleColumnGroupKeyGenerator.java:73-79), ids by first appearance.
-    const bool first_appearance = (q->flags & kQueryHashHolder) != 0 || (no_dict_keys && hash_plan.kind == 0 && (long long)(q->num_groups_limit > 0 ? q->num_groups_limit : 100000) < product);
-    const bool map_based = product > 10000 || first_appearance || hash_plan.kind != 0;
-    bool typed_direct = false;            // an aggregation input is a raw LONG / FLOAT / DOUBLE column: group_typed_direct_kernel
-    gp.num_group_cols = ng;
-    gp.num_groups = (int32_t)product;
-    gp.dense_ok = 1;
-    std::vector<int> dev_agg_of((size_t)std::max(na, 1), -1);
-    for (int a = 0; a < na; ++a) {
-      const pg_aggregation& ag = q->aggregations[a];
-      if (ag.function == PG_AGG_COUNT) continue;
-      if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
-      if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
-      add_projected(ag.column);
-      int s = slot_for(&lw, seg, ag.column, lw.plane_cols[(size_t)ag.column] != 0);
-      if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
-      pl.cols[s].in_agg = 1;
-      const int kind = (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) ? kGroupSum : (ag.function == PG_AGG_MIN ? kGroupMin : kGroupMax);
-      int da = -1;
-      for (int i = 0; i < gp.num_group_aggs; ++i) if (plan_aggs[i].col == s && plan_aggs[i].kind == kind) da = i;
-      if (da < 0) {
-        if (gp.num_group_aggs >= kMaxGroupAggs) return fail(PG_ERR_UNSUPPORTED, "more than %d distinct group-by aggregations", kMaxGroupAggs);
-        da = gp.num_group_aggs++;
-        plan_aggs[da] = PlanGroupAgg{s, kind};
-      }
-      dev_agg_of[(size_t)a] = da;
-    }
-    gp.wide_keys = product > (1ll << 24) ? 1 : 0;
-    // (hashed holders: one more word per slot for its key, and the first table of an ArrayMap-range key)
-    const size_t table_words = (size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs + (hash_plan.kind ? 1 : 0)) + (size_t)hash_plan.level_slots();
-    if ((unsigned long long)table_words * 8ull > g_engine.group_table_bytes)
-      return fail(PG_ERR_UNSUPPORTED, "group-by table of %lld slots x %d words exceeds the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", product, 1 + gp.num_group_aggs,
-                  (unsigned long long)g_engine.group_table_bytes);
-    st = ensure_table(ctx, table_words, map_based ? 0 : table_words);
-    if (st != PG_OK) return st;
-    struct TableTrim {            // a table of the upper IntMapBasedHolder range goes back to the allocator with the query
-      ExecCtx* c;
-      ~TableTrim() {
-        if (c->table_capacity * 8 > kGroupTableKeepBytes) { (void)hipFree(c->d_table); c->d_table = nullptr; c->table_capacity = 0; }
-      }
-    } table_trim{ctx};
-    gp.table_count = ctx->d_table;
-    gp.table_acc = reinterpret_cast<long long*>(ctx->d_table + gp.num_groups);
-    gp.hash_kind = hash_plan.kind;
-    gp.hash_levels = hash_plan.levels;
-    if (hash_plan.kind != 0) {
-      gp.hash_mask = (unsigned long long)gp.num_groups - 1ull;
-      gp.hash_keys = ctx->d_table + (size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs);
-      unsigned long long* next_table = gp.hash_keys + gp.num_groups;
-      for (int l = 0; l < hash_plan.levels; ++l) {
-        gp.hash_split[l] = hash_plan.split[l];
-        gp.hash_mask_lvl[l] = (unsigned long long)hash_plan.slots_lvl[l] - 1ull;
-        gp.hash_keys_lvl[l] = next_table;
-        next_table += hash_plan.slots_lvl[l];
-      }
-      for (int g = 0; g < ng; ++g) gp.key_mult[g] = hash_plan.mult[g];
-    }
-    const size_t table_bytes = table_words * 8;
-    Geometry geo;
-    const int group_wave_cap = waves_scan_group();
-    finish_geometry(seg, &lw, table_bytes, false, g_engine.group_waves > 0 ? std::min(g_engine.group_waves, kGroupBlockThreads / 64) : kGroupBlockThreads / 64, group_wave_cap, &geo);
-    if ((size_t)sp.wave_lds_bytes > kLdsBudget) return fail(PG_ERR_UNSUPPORTED, "query needs %d bytes of LDS per wavefront", sp.wave_lds_bytes);
-    gp.use_lds_table = geo.table_in_lds ? 1 : 0;
-    const int blocks = geo.blocks;
-    const size_t lds = geo.lds;
-    sp.speculate = 1;
-    for (int g = 0; g < ng; ++g) {
-      const DevColumn& c = pl.cols[group_slot[g]];
-      gp.group_keys[g] = DevGroupKey{c.bits, c.slot_off, group_mult[g], 0, c.fwd};
-    }
-    for (int a = 0; a < gp.num_group_aggs; ++a) {
-      const DevColumn& c = pl.cols[plan_aggs[a].col];
-      DevGroupAgg& ga = gp.group_aggs[a];
-      ga.kind = plan_aggs[a].kind; ga.bits = c.bits; ga.slot_off = c.slot_off; ga.is_raw = c.is_raw; ga.is_plane = c.is_plane;
-      ga.dict_bytes = c.dict_bytes; ga.fwd = c.fwd; ga.dict = c.dict;
-      // MIN / MAX run on dictIds whatever the value type; only a SUM reads 8-byte / floating-point dictionary entries
-      ga.vkind = (ga.kind == kGroupSum) ? c.vkind : kValI32;
-      if (c.is_raw && c.vkind != kValI32) { typed_direct = true; ga.vkind = c.vkind; }      // group_typed_direct_kernel: the value type decides the accumulator
-      // (the SUM of a dictionary column with 8-byte values under a Long / ArrayMap holder: the staged kernel that gathers such values has no
-      //  hashed table, group_typed_direct_kernel<.., kHash> gathers them too)
-      if (hash_plan.kind != 0 && ga.vkind != kValI32) typed_direct = true;
-      if (ga.vkind != kValI32) gp.dense_ok = 0;
-      if (ga.vkind == kValI64 && !c.is_raw) {
-        // the table slot is one wrapping int64: refuse (plan-time fallback) when numDocs * max|value| could overflow it
-        const ColumnDev& sc = seg->cols[(size_t)(lw.col_of_slot[(size_t)plan_aggs[a].col] / 2)];
-        const double max_abs = std::max(std::fabs((double)sc.h_dict_i64.front()), std::fabs((double)sc.h_dict_i64.back()));
-        if ((double)seg->num_docs * max_abs >= 9.2e18) return fail(PG_ERR_UNSUPPORTED, "group-by SUM of LONG column %s could overflow int64", sc.name.c_str());
-      }
-    }
-    // Without a filter every tile is aggregated in full: the lane-private kernel decodes straight from HBM and needs LDS only
-    // for the table (group_private_kernel).
-    // every leaf kind the lane-private filter implements (scan / set / bitmap / docId-range leaves, raw INT ranges)
-    bool private_leaves = true;
-    for (int l = 0; l < pl.num_leaves; ++l) private_leaves &= pl.leaves[l].kind <= kLeafBitmap || pl.leaves[l].kind == kLeafDocRange;
-    if (typed_direct && !private_leaves) return fail(PG_ERR_UNSUPPORTED, "group-by aggregation of a raw 8-byte column under a raw 8-byte range predicate (plan-time fallback)");
-    const bool use_private = (g_engine.group_private || hash_plan.kind != 0) && private_leaves && gp.dense_ok && !want_bitmap && !typed_direct;
-    if (hash_plan.kind != 0 && !use_private && !typed_direct) return fail(PG_ERR_UNSUPPORTED, "group-by with raw keys beyond an int: only 32-bit-domain or raw 8-byte aggregations under lane-private filter leaves");
-    int pblocks = blocks, pthreads = geo.threads;
-    size_t plds = lds;
-    if (use_private) {
-      const int private_wave_cap = waves_group_private();
-      const bool in_lds = table_bytes <= 96 * 1024;
-      gp.use_lds_table = in_lds ? 1 : 0;
-      int waves = in_lds ? kGroupBlockThreads / 64 : kBlockThreads / 64;
-      if (g_engine.group_waves > 0) waves = std::min(waves, g_engine.group_waves);
-      while (waves > private_wave_cap) waves >>= 1;
-      pthreads = waves * 64;
-      plds = in_lds ? table_bytes : 0;
-      int bpc = std::max(1, private_wave_cap / waves);
-      if (in_lds) bpc = std::max(1, std::min(bpc, (int)(kLdsBudget / std::max<size_t>(plds, 1))));
-      if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-      const long long tiles2k = ((long long)seg->num_docs + 2047) / 2048;
-      pblocks = (int)std::max<long long>(1, std::min<long long>((tiles2k + waves - 1) / waves, (long long)seg->num_cus * bpc));
-    }
-    // Count packing: when the first summed value plane is narrow enough, its 64-bit LDS slot carries (count << shift) | sum
-    // and the separate count atomic disappears.  Safe while a workgroup sees fewer than 2^cbits docs:
-    // sum < 2^cbits * 2^w = 2^shift and count < 2^cbits, so cbits + shift <= 64 never carries into or out of the count.
-    gp.packed_agg = -1;
-    gp.packed_shift = 0;
-    if (gp.use_lds_table && g_engine.group_pack) {
-      const long long waves_total = use_private ? (long long)pblocks * (pthreads / 64) : (long long)blocks * (geo.threads / 64);
-      const long long tiles_total = use_private ? ((long long)seg->num_docs + 2047) / 2048 : (long long)sp.num_tiles;
-      const long long tiles_per_wave = (tiles_total + waves_total - 1) / waves_total;
-      const long long docs_per_block = use_private ? tiles_per_wave * (pthreads / 64) * 2048 : tiles_per_wave * (geo.threads / 64) * 64 * sp.tile_steps;
-      int cbits = 1;
-      while ((1ll << cbits) <= docs_per_block) ++cbits;
-      for (int a = 0; a < gp.num_group_aggs; ++a) {
-        const DevGroupAgg& ga = gp.group_aggs[a];
-        if (ga.kind == kGroupSum && ga.is_plane && !ga.is_raw && 2 * cbits + ga.bits <= 64) { gp.packed_agg = a; gp.packed_shift = std::max(32, cbits + ga.bits); break; }
-      }
-    }
-    // group_private_kernel's LDS table in as many bank-interleaved copies as the workgroup's share of the CU's LDS holds (pg_kernels.h,
-    // lds_group_table_bytes): C3's 1000 groups x (SUM + MAX) are 12 KB a copy, eight copies for the one 16-wave workgroup of a CU.
-    gp.lds_log_replicas = 0;
-    // (a filter with dictId-set leaves: kSetLdsWords words of the workgroup's LDS hold the sets, behind the table -- pg_kernels.h stage_filter_sets)
-    sp.set_leaves_in_lds = 0;
-    if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
-    const size_t set_area = (use_private && sp.set_leaves_in_lds != 0) ? (size_t)kSetLdsWords * 4 : 0;
-    if (use_private && gp.use_lds_table) {
-      const int resident = std::max(1, std::min(waves_group_private() / std::max(1, pthreads / 64), g_engine.blocks_per_cu > 0 ? g_engine.blocks_per_cu : 1 << 30));
-      const size_t budget = kLdsBudget / (size_t)resident - set_area;
-      int log_r = 0;
-      while (log_r < g_engine.group_log_replicas && (size_t)lds_group_table_bytes(gp, log_r + 1) <= budget) ++log_r;
-      gp.lds_log_replicas = log_r;
-      plds = lds_group_table_bytes(gp, log_r);
-    }
-    gp.set_lds_off = -1;
-    if (set_area != 0 && plds + set_area <= kLdsBudget) { gp.set_lds_off = (int32_t)((plds + 15) & ~(size_t)15); plds = (size_t)gp.set_lds_off + set_area; }
-    gp.scan = sp;
-    gp.scan.partials = nullptr;
-    gp.scan.out_bitmap = nullptr;
-    if (lw.tile_list != nullptr) { st = complete_index_list(&lw, ctx); if (st != PG_OK) return st; }
-    gp.scan.tile_list = lw.tile_list;            // read by group_private_kernel only
-    gp.scan.tile_count = lw.tile_count;
-    gp.scan.filter_entries = nullptr;
-    // pg_execute_batch: a group-by of the LDS-table form over a small segment shares ONE launch with the batch's other such items
-    // (group_lds_batch_kernel; ScanParams.lean_kind 6) -- no table init, no compaction launches: the item's slice of the batch's table is
-    // all-zero before the launch (zero-identity keys), comes back whole in the batch's one copy, and the host keeps the slots whose
-    // count is not zero.  What GroupByCombineOperator.java:102-165 gets from one task per segment.
-    if (defer != nullptr && g_engine.batch_group && use_private && gp.use_lds_table && hash_plan.kind == 0 && !first_appearance && !typed_direct && !want_bitmap && out &&
-        lw.tile_list == nullptr && lw.side == nullptr && !lw.stats_leap2_flagged && !lw.stats_chain_flagged && !ctx->pre_enqueued &&
-        stats_is_final &&
-        (long long)(q->num_groups_limit > 0 ? q->num_groups_limit : 100000) >= product && (defer->single || ((long long)seg->num_docs + 2047) / 2048 <= kBatchMaxTiles)) {
-      auto item = std::make_shared<LoweredItem>();
-      item->gp = std::make_shared<GroupParams>(gp);
-      item->gp->zero_identity = 1;
-      item->gp->scan.lean_kind = 6;
-      item->sp.lean_kind = 6;
-      item->blocks = pblocks;
-      item->group_threads = pthreads;
-      item->group_lds = plds;
-      item->group_table_words = ((size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs) + 31) & ~(size_t)31;      // (slices start on 256-byte boundaries)
-      item->plane_columns = planes.columns;
-      item->sets = lw.set_leaves;
-      const int G = gp.num_groups, NA = gp.num_group_aggs;
-      int agg_kind[kMaxGroupAggs] = {};
-      for (int a = 0; a < NA; ++a) agg_kind[a] = gp.group_aggs[a].kind;
-      std::array<int, kMaxGroupAggs> kinds{};
-      for (int a = 0; a < NA; ++a) kinds[(size_t)a] = agg_kind[a];
-      const size_t num_projected = projected.size();
-      // (captured by value and kept with the cached item: what the conversion needs of the lowering -- the planes its aggregations read through
-      //  and the statistics plan -- not the whole Lowered with its index-AND parameter block: advisor, round 5)
-      const std::vector<char> plane_cols = lw.plane_cols;
-      const fstats::Plan stats_plan = lw.stats_plan;
-      const int stats_scan_leaves = lw.stats_scan_leaves;
-      item->convert_group = [q, seg, na, ng, cards, dev_agg_of, plane_cols, stats_plan, stats_scan_leaves, G, kinds, num_projected, no_dict_keys](const unsigned long long* table, pg_result* out) {
-        int num_present = 0;
-        for (int g = 0; g < G; ++g) num_present += table[g] != 0ull ? 1 : 0;
-        out->num_aggregations = na;
-        out->dominant_kernel = PG_KERNEL_GROUP_PRIVATE;
-        out->num_groups = num_present;
-        out->group_id_upper_bound = no_dict_keys ? (q->num_groups_limit > 0 ? q->num_groups_limit : 100000) : G;
-        out->group_ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(num_present, 1));
-        out->group_aggregations = (pg_agg_value*)calloc((size_t)std::max(num_present, 1) * (size_t)std::max(na, 1), sizeof(pg_agg_value));
-        out->group_key_dict_ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(num_present, 1) * (size_t)ng);
-        out->group_key_kind = 0;
-        long long docs = 0;
-        int k = 0;
-        for (int g = 0; g < G; ++g) {
-          const unsigned long long group_docs = table[g];
-          if (group_docs == 0ull) continue;
-          docs += (long long)group_docs;
-          out->group_ids[k] = g;
-          long long raw = g;
-          for (int c = 0; c < ng; ++c) { out->group_key_dict_ids[(size_t)k * (size_t)ng + (size_t)c] = (int32_t)(raw % cards[(size_t)c]); raw /= cards[(size_t)c]; }
-          for (int a = 0; a < na; ++a) {
-            const pg_aggregation& ag = q->aggregations[a];
-            pg_agg_value& v = out->group_aggregations[(size_t)k * (size_t)na + (size_t)a];
-            v.count = (int64_t)group_docs;
-            v.min = std::numeric_limits<double>::infinity();
-            v.max = -std::numeric_limits<double>::infinity();
-            if (ag.function == PG_AGG_COUNT) continue;
-            const int da = dev_agg_of[(size_t)a];
-            long long acc = (long long)table[(size_t)G * (size_t)(1 + da) + (size_t)g];
-            // zero-identity keys of the shared launch (group_private_body's flush): MIN travelled as 2^31 - v, MAX as v + 2^31 + 1
-            if (kinds[(size_t)da] == kGroupMin) acc = 0x80000000ll - acc;
-            else if (kinds[(size_t)da] == kGroupMax) acc = acc - 0x80000001ll;
-            const ColumnDev& col = seg->cols[(size_t)ag.column];
-            const bool plane = plane_cols[(size_t)ag.column] != 0;
-            if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) set_integer_sum(&v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
-            else if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, (int32_t)acc, plane);
-            else v.max = agg_value_double(col, (int32_t)acc, plane);
-          }
-          ++k;
-        }
-        out->stats.num_docs_scanned = docs;
-        finish_filter_stats(stats_plan, stats_scan_leaves, seg, 0, false, out);
-        out->stats.num_entries_scanned_post_filter = docs * (int64_t)num_projected;
-        out->stats.num_total_docs = seg->num_docs;
-      };
-      defer->item = std::move(item);
-      defer->cacheable = !lw.plane_pending;
-      defer->planes.reset(new PlaneHold(std::move(planes)));
-      return kDeferred;
-    }
-    HIP_TRY(mark_pre_work(ctx));
-    init_group_table_kernel<<<dim3((unsigned)std::max<long long>(64, std::min<long long>(product >> 12, (long long)seg->num_cus * 16))), dim3(256), 0, ctx->stream>>>(gp);
-    HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    // Key spaces above the LDS table: partition the docs by key range first, then aggregate every partition in LDS
-    // (pg_group_partition.h) instead of one global atomic per doc and aggregation.
-    const int partition_entry_bytes = 4 + 8 * gp.num_group_aggs;
-    const int partition_shift = partition_entry_bytes <= 20 ? 12 : 11;
-    const long long fine_partitions = (product + (1ll << partition_shift) - 1) >> partition_shift;
-    // More fine partitions than one scatter pass can address (key spaces of 2 M .. 2^31 raw keys): two levels -- pass A scatters by
-    // coarse partition (2^k fine ones each), group_repartition_*_kernel scatter every coarse partition's records by fine partition
-    // (pg_group_partition.h).  PINOT_GPU_PARTITION_TWO_LEVEL=0: such key spaces keep the direct HBM atomics.
-    const bool two_level_on = g_engine.partition_two_level;
-    int log2_fine_per_coarse = 0;
-    while (((fine_partitions + (1ll << log2_fine_per_coarse) - 1) >> log2_fine_per_coarse) > kMaxPartitions) ++log2_fine_per_coarse;
-    const bool two_level = log2_fine_per_coarse > 0;
-    const long long num_partitions = (fine_partitions + (1ll << log2_fine_per_coarse) - 1) >> log2_fine_per_coarse;       // what pass A scatters into
-    const int scatter_shift = partition_shift + log2_fine_per_coarse;
-    const bool use_partition = hash_plan.kind == 0 && !typed_direct && map_based && g_engine.group_partition && g_engine.group_private && private_leaves && gp.dense_ok && !want_bitmap &&
-                               gp.num_group_aggs <= kMaxPartitionAggs && (!two_level || (two_level_on && (1 << log2_fine_per_coarse) <= kMaxFinePerCoarse)) &&
-                               (long long)seg->num_docs >= g_engine.partition_min_docs;
-    static const bool partition_trace = getenv("PINOT_GPU_PARTITION_TRACE") != nullptr;
-    if (partition_trace)
-      fprintf(stderr, "group-by plan: product %lld, fine partitions %lld (shift %d), 2^%d per coarse -> %lld scatter partitions; partition %d (hash %d typed_direct %d map_based %d "
-                      "private_leaves %d dense_ok %d aggs %d docs %d)\n", product, fine_partitions, partition_shift, log2_fine_per_coarse, num_partitions, (int)use_partition,
-              hash_plan.kind, (int)typed_direct, (int)map_based, (int)private_leaves, gp.dense_ok, gp.num_group_aggs, seg->num_docs);
-    if (use_partition || !(use_private || typed_direct)) { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
-    if (lw.side != nullptr) {
-      const bool wrote = ((use_private && !use_partition) || typed_direct) && gp.scan.tile_list == nullptr;
-      for (int l = 0; l < kMaxLeaves; ++l) gp.scan.leaf_out[l] = wrote ? lw.sp_leaf_out[l] : nullptr;
-      gp.scan.leaf_out_enabled = wrote ? 1 : 0;
-      lw.side->kernel_wrote = wrote;
-    }
-    const bool count_leap2 = out && lw.stats_leap2_flagged && ((use_private && !use_partition) || typed_direct);
-    const bool count_entries = (out && lw.stats_chain_flagged && ((use_private && !use_partition) || typed_direct)) || count_leap2;
-    gp.scan.leap_tables = nullptr;
-    if (count_leap2) { st = arm_leap_tables(seg, ctx, &gp.scan.leap_tables, &gp.scan.filter_entries); if (st != PG_OK) return st; }
-    else if (lw.stats_leap2_flagged) for (int n = 0; n < gp.scan.num_nodes; ++n) gp.scan.nodes[n].flags &= ~kNodeLeapfrog2;
-    if (count_entries && !count_leap2) { st = arm_filter_entries(ctx, &gp.scan.filter_entries); if (st != PG_OK) return st; }
-    if (use_partition) {
-      const int P = (int)num_partitions;
-      const size_t N = (size_t)std::max(seg->num_tiles, 1) * 2048;
-      const size_t max_work = N / (1u << 16) + (size_t)P + 1;
-      auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-      const size_t off_upper = 0, off_cursor = align(off_upper + (size_t)P * 4), off_offsets = align(off_cursor + (size_t)P * 4);
-      const size_t off_work = align(off_offsets + (size_t)(P + 1) * 4), off_key = align(off_work + max_work * sizeof(PartitionWork));
-      // one packed dword per doc when the only aggregation input is an unsigned field that fits beside the slot (pg_group_partition.h)
-      int packed_bits = 0;
-      if (g_engine.partition_packed) {
-        if (gp.num_group_aggs == 0) packed_bits = 1;
-        else if (gp.num_group_aggs == 1) {
-          const DevGroupAgg& ga = gp.group_aggs[0];
-          const bool unsigned_field = !ga.is_raw && ga.vkind == kValI32 && (ga.kind != kGroupSum || ga.is_plane);
-          if (unsigned_field && ga.bits + scatter_shift <= 32) packed_bits = ga.bits;
-        }
-      }
-      const size_t off_val = align(off_key + N * 4), level1_bytes = off_val + (packed_bits > 0 ? 0 : (size_t)gp.num_group_aggs * align(N * 4));
-      // two levels: the second record buffer(s), the fine partitions' count / offset / cursor arrays, pass B's device-built work list and its
-      // length, and the re-scatter's own chunk list
-      const int num_vals = packed_bits > 0 ? 0 : gp.num_group_aggs;
-      const size_t fine_slots = (size_t)P << log2_fine_per_coarse;
-      const size_t max_work2 = N / (1u << 16) + fine_slots + 1, max_chunks = N / kRepartitionChunk + (size_t)P + 1;
-      const size_t off_key2 = align(level1_bytes), off_val2 = align(off_key2 + N * 4);
-      const size_t off_fine = align(off_val2 + (size_t)num_vals * align(N * 4));                       // count | cursor | work_count (zeroed together), then offsets
-      const size_t off_fine_offsets = align(off_fine + 2 * fine_slots * 4 + 64);
-      const size_t off_work2 = align(off_fine_offsets + fine_slots * 4), off_chunks = align(off_work2 + max_work2 * sizeof(PartitionWork));
-      const size_t bytes = two_level ? align(off_chunks + max_chunks * sizeof(PartitionWork)) : level1_bytes;
-      if (ctx->partition_capacity < bytes) {
-        if (ctx->d_partition) (void)hipFree(ctx->d_partition);
-        ctx->d_partition = nullptr; ctx->partition_capacity = 0;
-        if (hipMalloc((void**)&ctx->d_partition, bytes) != hipSuccess) return fail(PG_ERR_OUT_OF_MEMORY, "partitioned group-by needs %zu bytes of record buffers", bytes);
-        ctx->partition_capacity = bytes;
-      }
-      PartitionParams pp;
-      memset(&pp, 0, sizeof(pp));
-      pp.gp = gp;
-      pp.shift = scatter_shift;                     // (two levels: pass 0 and pass A work on coarse partitions)
-      pp.num_partitions = P;
-      pp.packed_bits = packed_bits;
-      pp.upper = reinterpret_cast<uint32_t*>(ctx->d_partition + off_upper);
-      pp.cursor = reinterpret_cast<uint32_t*>(ctx->d_partition + off_cursor);
-      pp.offsets = reinterpret_cast<const uint32_t*>(ctx->d_partition + off_offsets);
-      pp.work = reinterpret_cast<const PartitionWork*>(ctx->d_partition + off_work);
-      pp.part_key = reinterpret_cast<uint32_t*>(ctx->d_partition + off_key);
-      for (int a = 0; a < gp.num_group_aggs; ++a) pp.part_val[a] = reinterpret_cast<uint32_t*>(ctx->d_partition + off_val + (size_t)a * align(N * 4));
-      HIP_TRY(hipMemsetAsync(ctx->d_partition, 0, off_offsets, ctx->stream));          // upper and cursor
-      const long long tiles2k = ((long long)seg->num_docs + 2047) / 2048;
-      const int hist_blocks = (int)std::max<long long>(1, std::min<long long>((tiles2k + 3) / 4, (long long)seg->num_cus * 6));
-      std::vector<int> stats_key{scatter_shift};
-      for (int g = 0; g < ng; ++g) stats_key.push_back(q->group_by_columns[g]);
-      std::vector<uint32_t> upper;
-      if (g_engine.partition_stats_cache) {
-        std::lock_guard<std::mutex> lk(seg->partition_stats_mu);
-        for (const auto& e : seg->partition_stats) if (e.first == stats_key) upper = e.second;
-      }
-      if ((int)upper.size() != P) {
-        upper.assign((size_t)P, 0u);
-        launch_group_partition_histogram(hist_blocks, ctx->stream, pp);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(upper.data(), pp.upper, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (g_engine.partition_stats_cache) {
-          std::lock_guard<std::mutex> lk(seg->partition_stats_mu);
-          if (seg->partition_stats.size() < 64) seg->partition_stats.emplace_back(stats_key, upper);
-        }
-      }
-      std::vector<uint32_t> offsets((size_t)P + 1, 0u);
-      std::vector<PartitionWork> work;
-      // chunk size: about two rounds of resident pass-B workgroups over the whole input, so that the flush of the touched slots
-      // (one global atomic per slot, accumulator and chunk) stays small next to the records a chunk aggregates
-      unsigned long long total_upper = 0;
-      for (int p = 0; p < P; ++p) total_upper += upper[(size_t)p];
-      const unsigned long long want_chunk = (total_upper + (unsigned long long)seg->num_cus * 6 - 1) / ((unsigned long long)seg->num_cus * 6);
-      const uint32_t chunk = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>((want_chunk + 1023) & ~1023ull, 1u << 16), (unsigned long long)kPartitionChunk);
-      for (int p = 0; p < P; ++p) {
-        offsets[(size_t)p + 1] = offsets[(size_t)p] + upper[(size_t)p];
-        for (uint32_t s0 = 0; s0 < upper[(size_t)p]; s0 += chunk) work.push_back(PartitionWork{p, s0, std::min<uint32_t>(chunk, upper[(size_t)p] - s0), 0u});
-      }
-      HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_offsets, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-      if (!work.empty()) HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_work, work.data(), work.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
-      const int scatter_bpc = packed_bits > 0 ? blocks_per_cu_group_partition_scatter_packed(P) : std::max(1, waves_group_partition_scatter() / 4);
-      const int scatter_blocks = (int)std::max<long long>(1, std::min<long long>((tiles2k + 3) / 4, (long long)seg->num_cus * scatter_bpc));
-      launch_group_partition_scatter(scatter_blocks, ctx->stream, pp);
-      HIP_TRY(hipGetLastError());
-      std::vector<PartitionWork> chunks;
-      if (two_level && !work.empty()) {
-        RepartitionParams rp;
-        memset(&rp, 0, sizeof(rp));
-        rp.src_key = pp.part_key;
-        rp.dst_key = reinterpret_cast<uint32_t*>(ctx->d_partition + off_key2);
-        for (int a = 0; a < num_vals; ++a) { rp.src_val[a] = pp.part_val[a]; rp.dst_val[a] = reinterpret_cast<uint32_t*>(ctx->d_partition + off_val2 + (size_t)a * align(N * 4)); }
-        rp.coarse_offsets = pp.offsets; rp.coarse_cursor = pp.cursor;
-        rp.fine_count = reinterpret_cast<uint32_t*>(ctx->d_partition + off_fine);
-        rp.fine_cursor = rp.fine_count + fine_slots;
-        rp.work_count = rp.fine_cursor + fine_slots;
-        rp.fine_offsets = reinterpret_cast<uint32_t*>(ctx->d_partition + off_fine_offsets);
-        rp.work = reinterpret_cast<PartitionWork*>(ctx->d_partition + off_work2);
-        rp.chunks = reinterpret_cast<const PartitionWork*>(ctx->d_partition + off_chunks);
-        rp.num_coarse = P; rp.log2_fine_per_coarse = log2_fine_per_coarse; rp.fine_shift = partition_shift; rp.packed_bits = packed_bits; rp.num_vals = num_vals;
-        rp.aggregate_chunk = chunk;
-        for (int p = 0; p < P; ++p)
-          for (uint32_t s0 = 0; s0 < upper[(size_t)p]; s0 += kRepartitionChunk) chunks.push_back(PartitionWork{p, s0, std::min<uint32_t>(kRepartitionChunk, upper[(size_t)p] - s0), 0u});
-        HIP_TRY(hipMemsetAsync(ctx->d_partition + off_fine, 0, 2 * fine_slots * 4 + 64, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_chunks, chunks.data(), chunks.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
-        launch_group_repartition((int)chunks.size(), ctx->stream, rp);
-        HIP_TRY(hipGetLastError());
-        // pass B over the fine partitions: the second buffer, the device-built work list (as many workgroups as it can have entries)
-        PartitionParams fine = pp;
-        fine.shift = partition_shift;
-        fine.num_partitions = (int32_t)fine_slots;
-        fine.cursor = rp.fine_cursor; fine.offsets = rp.fine_offsets;
-        fine.work = rp.work; fine.work_count = rp.work_count;
-        fine.part_key = rp.dst_key;
-        for (int a = 0; a < num_vals; ++a) fine.part_val[a] = rp.dst_val[a];
-        launch_group_partition_aggregate((int)max_work2, ((size_t)partition_entry_bytes) << partition_shift, ctx->stream, fine);
-      } else if (!work.empty()) {
-        launch_group_partition_aggregate((int)work.size(), ((size_t)partition_entry_bytes) << partition_shift, ctx->stream, pp);
-      }
-      HIP_TRY(hipStreamSynchronize(ctx->stream));      // `offsets` / `work` / `chunks` are pageable host vectors: keep them alive until the copies ran
-    }
-    else if (typed_direct) {
-      const long long tiles2k = ((long long)seg->num_docs + 2047) / 2048;
-      launch_group_typed_direct((int)std::max<long long>(1, std::min<long long>((tiles2k + 3) / 4, (long long)seg->num_cus * 8)), ctx->stream, gp);
-    }
-    else if (use_private) launch_group_private(gp.use_lds_table != 0, pblocks, pthreads, plds, ctx->stream, gp);
-    else launch_scan_group(g_engine.use_dma, gp.use_lds_table != 0, blocks, geo.threads, lds, ctx->stream, gp);
-    HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    if (count_leap2) { st = launch_leap_chain(seg, ctx, 0); if (st != PG_OK) return st; }
-    if (count_entries) HIP_TRY(hipMemcpyAsync(ctx->h_filter_entries, ctx->d_filter_entries, 8, hipMemcpyDeviceToHost, ctx->stream));
-    // The groups that exist, in ascending raw-key order: (raw key, doc count, accumulators[a * num_present + k]).
-    std::vector<unsigned long long> hash_keys;                    // hashed holders: the keys of the present slots ...
-    std::vector<std::vector<unsigned long long>> hash_keys_lvl;    // ... and, per chained first table, the key behind the slot number a later key starts with
-    std::vector<int32_t> present_ids;
-    std::vector<unsigned long long> present_counts;
-    std::vector<long long> present_acc;
-    const int32_t* ids_of = nullptr;                 // [num_present] where the conversion below reads: the vectors, or pinned staging
-    const unsigned long long* counts_of = nullptr;
-    const long long* acc_of = nullptr;
+  }
+  const BlockPartial& fp = *ctx->h_partial;
+  // (the in-kernel fold orders the workgroups' records against their arrival counter through write-through stores, not through a
+  //  release / acquire pair: every record carries its launch's stamp and a foreign one is an error, never an answer)
+  if (fp.flags & kPartialStale) return fail(PG_ERR_INTERNAL, "the scan kernel's fold read a record that was not written by this launch (sequence %llu)", seq);
+  // plain narrow counters: the counters must add up to the matches (a wrapped counter always leaves the total short)
+  const bool hist_wrapped = k.kernel == ScanKernel::Hist && !k.hist_guarded && k.hist_cw < 32 && (unsigned long long)fp.sum[1] != fp.count;
+  if (k.kernel == ScanKernel::Hist && (hist_wrapped || (fp.flags & kPartialHistAlarm))) {
+    // Skewed dictIds: the histogram's sum is not used.  From now on the column runs in the next tier -- guarded counters, which count
+    // hot dictIds exactly through guard-bit claims, then the value plane / gather path -- and execute_impl answers this query again.
+    __atomic_store_n(&seg->cols[(size_t)r.hist_col].hist_tier, hist_wrapped ? 1 : 2, __ATOMIC_RELAXED);
+    seg->plane_epoch.fetch_add(1, std::memory_order_acq_rel);      // (what the plan cache holds for this segment was lowered for the plain tier)
+    return kHistRetry;
+  }
+  if (out_cardinality) *out_cardinality = (int64_t)fp.count;
+  if (out) convert(fp, out);
+  if (out && k.kernel == ScanKernel::PrivateFsm) {
+    // (the stream was synchronised: the walk's count is in the pinned counter)
+    out->stats.num_entries_scanned_in_filter = (int64_t)*ctx->h_filter_entries;
+    out->filter_entries_exact = 1;
+    lw.side->fused = true;
+  }
+  return PG_OK;
+}
+// pg_execute_batch: a group-by of the LDS-table form over a small segment shares ONE launch with the batch's other such items
+// (group_lds_batch_kernel; BatchKind::GroupLds) -- no table init, no compaction launches: the item's slice of the batch's table is
+// all-zero before the launch (zero-identity keys), comes back whole in the batch's one copy, and the host keeps the slots whose
+// count is not zero.  What GroupByCombineOperator.java:102-165 gets from one task per segment.
+static pg_status defer_group_item(QueryRun& r, const GroupParams& gp, int pblocks, int pthreads, size_t plds, const std::vector<int>& cards,
+                                  const std::vector<int>& dev_agg_of, bool no_dict_keys) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; const Lowered& lw = r.lw; const int na = r.na, ng = r.ng;
+  auto item = std::make_shared<LoweredItem>();
+  item->gp = std::make_shared<GroupParams>(gp);
+  item->gp->zero_identity = 1;
+  item->gp->scan.lean_kind = (int32_t)BatchKind::GroupLds;
+  item->sp.lean_kind = (int32_t)BatchKind::GroupLds;
+  item->blocks = pblocks;
+  item->group_threads = pthreads;
+  item->group_lds = plds;
+  item->group_table_words = ((size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs) + 31) & ~(size_t)31;      // (slices start on 256-byte boundaries)
+  item->sets = lw.set_leaves;
+  const int G = gp.num_groups, NA = gp.num_group_aggs;
+  std::array<int, kMaxGroupAggs> kinds{};
+  for (int a = 0; a < NA; ++a) kinds[(size_t)a] = gp.group_aggs[a].kind;
+  const size_t num_projected = r.projected.size();
+  // (captured by value and kept with the cached item: what the conversion needs of the lowering -- the planes its aggregations read through
+  //  and the statistics plan -- not the whole Lowered with its index-AND parameter block: advisor, round 5)
+  const std::vector<char> plane_cols = lw.plane_cols;
+  const fstats::Plan stats_plan = lw.stats_plan;
+  const int stats_scan_leaves = lw.stats_scan_leaves;
+  item->convert_group = [q, seg, na, ng, cards, dev_agg_of, plane_cols, stats_plan, stats_scan_leaves, G, kinds, num_projected, no_dict_keys](const unsigned long long* table, pg_result* out) {
     int num_present = 0;
+    for (int g = 0; g < G; ++g) num_present += table[g] != 0ull ? 1 : 0;
+    start_group_result(out, na, ng, num_present, PG_KERNEL_GROUP_PRIVATE, no_dict_keys ? (q->num_groups_limit > 0 ? q->num_groups_limit : 100000) : G, 0);
     long long docs = 0;
-    if (!map_based) {
-      HIP_TRY(hipMemcpyAsync(ctx->h_table, ctx->d_table, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
-      if (timed) HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      const unsigned long long* hc = ctx->h_table;
-      const long long* ha = reinterpret_cast<const long long*>(ctx->h_table + gp.num_groups);
-      for (int g = 0; g < gp.num_groups; ++g) if (hc[g]) { num_present++; docs += (long long)hc[g]; }
-      present_ids.reserve((size_t)num_present); present_counts.reserve((size_t)num_present);
-      present_acc.resize((size_t)num_present * (size_t)gp.num_group_aggs);
-      int k = 0;
-      for (int g = 0; g < gp.num_groups; ++g) {
-        if (!hc[g]) continue;
-        present_ids.push_back(g); present_counts.push_back(hc[g]);
-        for (int a = 0; a < gp.num_group_aggs; ++a) present_acc[(size_t)a * (size_t)num_present + (size_t)k] = ha[(size_t)a * (size_t)gp.num_groups + (size_t)g];
-        k++;
-      }
-    } else {
-      // IntMapBasedHolder range: compact the HBM table on the device; honour numGroupsLimit the way the reference does
-      // (_globalGroupIdUpperBound = min(product, numGroupsLimit), DictionaryBasedGroupKeyGenerator.java:176).
-      const int limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
-      const long long bound = hash_plan.kind != 0 ? (long long)limit : std::min<long long>(product, limit);      // LongMap / ArrayMap holders: _globalGroupIdUpperBound = numGroupsLimit (:150-163)
-      const int num_chunks = (int)(((long long)gp.num_groups + kGroupChunk - 1) / kGroupChunk);
-      DeviceScratch scratch(ctx);
-      uint32_t* d_chunk_counts = (uint32_t*)scratch.alloc((size_t)num_chunks * 4);
-      uint32_t* d_chunk_offsets = (uint32_t*)scratch.alloc((size_t)(num_chunks + 1) * 4);
-      unsigned long long* d_total_docs = (unsigned long long*)scratch.alloc(8);
-      if (!d_chunk_counts || !d_chunk_offsets || !d_total_docs) return fail(PG_ERR_OUT_OF_MEMORY, "group-by compaction scratch");
-      uint32_t* d_first_doc = nullptr;
-      uint32_t max_first_doc = 0xFFFFFFFFu;
-      auto count_groups = [&](bool with_docs, uint32_t* total) -> pg_status {
-        if (with_docs) HIP_TRY(hipMemsetAsync(d_total_docs, 0, 8, ctx->stream));
-        group_chunk_count_kernel<<<dim3((unsigned)num_chunks), dim3(256), 0, ctx->stream>>>(gp.table_count, d_first_doc, max_first_doc, gp.num_groups, d_chunk_counts,
-                                                                                             with_docs ? d_total_docs : nullptr);
-        group_chunk_scan_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(d_chunk_counts, num_chunks, d_chunk_offsets);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(total, d_chunk_offsets + num_chunks, 4, hipMemcpyDeviceToHost, ctx->stream));
-        return PG_OK;
-      };
-      uint32_t total = 0;
-      unsigned long long total_docs = 0;
-      st = count_groups(true, &total);
-      if (st != PG_OK) return st;
-      HIP_TRY(hipMemcpyAsync(&total_docs, d_total_docs, 8, hipMemcpyDeviceToHost, ctx->stream));
-      if (timed) HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      docs = (long long)total_docs;
-      out->num_groups_limit_reached = (long long)total >= (long long)limit ? 1 : 0;      // GroupByOperator.java:114-115
-      if ((long long)total > bound) {
-        // More groups than the reference would have created: it hands out group ids in order of first appearance (docId order)
-        // and drops the docs of later keys, so the survivors are the `bound` groups whose first doc comes earliest.
-        unsigned long long* d_filter = nullptr;
-        if (q->num_filter_nodes > 0 && hash_plan.kind == 0) {
-          d_filter = (unsigned long long*)scratch.alloc((((size_t)seg->num_docs + 63) / 64 + 1) * 8);
-          if (!d_filter) return fail(PG_ERR_OUT_OF_MEMORY, "group-by first-doc pass: filter bitmap");
-          pg_query fq = *q;
-          fq.num_aggregations = 0; fq.num_group_by = 0;
-          st = execute_impl(seg, &fq, nullptr, d_filter, nullptr, 0, nullptr);      // stays on the device
-          if (st != PG_OK) return st;
-        }
-        d_first_doc = (uint32_t*)scratch.alloc((size_t)gp.num_groups * 4);
-        if (!d_first_doc) return fail(PG_ERR_OUT_OF_MEMORY, "group-by first-doc pass: %d slots", gp.num_groups);
-        HIP_TRY(hipMemsetAsync(d_first_doc, 0xFF, (size_t)gp.num_groups * 4, ctx->stream));
-        // The survivors are the distinct keys of a PREFIX of the matching docs -- the reference stops admitting keys at the doc
-        // where the bound-th one appears.  With far more groups than the limit that prefix is short, so the docs are visited in
-        // growing prefixes until `bound` keys have a first doc, not all of them.
-        uint32_t seen = 0;
-        long long done_docs = 0;
-        long long step_docs = std::max<long long>(1 << 16, 4 * bound);
-        if (hash_plan.kind != 0) {
-          // hashed holders: the group-by kernel once more, in its first-doc mode (same filter, same keys, every key already has its slot)
-          GroupParams fg = gp;
-          fg.first_doc = d_first_doc;
-          fg.scan.filter_entries = nullptr; fg.scan.leap_tables = nullptr;
-          for (int n = 0; n < fg.scan.num_nodes; ++n) fg.scan.nodes[n].flags &= ~(kNodeLeapfrog2 | kNodeCountEntries);
-          // (plds: the set area, when the filter has dictId sets.  A query whose aggregation runs in group_typed_direct_kernel never sized a
-          //  group_private_kernel launch: the pass takes that kernel's own geometry then)
-          const long long fd_tiles = ((long long)seg->num_docs + 2047) / 2048;
-          const int fd_threads = use_private ? pthreads : kBlockThreads;
-          const int fd_blocks = use_private ? pblocks : (int)std::max<long long>(1, std::min<long long>((fd_tiles + 3) / 4, (long long)seg->num_cus * 8));
-          if (!use_private) fg.set_lds_off = -1;
-          launch_group_private(false, fd_blocks, fd_threads, use_private ? plds : 0, ctx->stream, fg);
-          HIP_TRY(hipGetLastError());
-          done_docs = seg->num_docs;
-          max_first_doc = 0xFFFFFFFEu;
-          st = count_groups(false, &seen);
-          if (st != PG_OK) return st;
-          HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        while (done_docs < (long long)seg->num_docs && (long long)seen < bound) {
-          const long long hi = std::min<long long>((long long)seg->num_docs, done_docs + step_docs);
-          const long long span = hi - done_docs;
-          group_first_doc_kernel<<<dim3((unsigned)std::min<long long>((span + 255) / 256, (long long)seg->num_cus * 16)), dim3(256), 0, ctx->stream>>>(gp, d_filter, d_first_doc, done_docs, hi);
-          HIP_TRY(hipGetLastError());
-          done_docs = hi;
-          step_docs *= 2;
-          max_first_doc = 0xFFFFFFFEu;            // "has a first doc"
-          st = count_groups(false, &seen);
-          if (st != PG_OK) return st;
-          HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        uint32_t* d_present_first = (uint32_t*)scratch.alloc((size_t)std::max<uint32_t>(seen, 1) * 4);
-        if (!d_present_first) return fail(PG_ERR_OUT_OF_MEMORY, "group-by first-doc pass: %u groups", seen);
-        group_compact_kernel<<<dim3((unsigned)num_chunks), dim3(256), 0, ctx->stream>>>(gp.table_count, gp.table_acc, 0, gp.num_groups, d_first_doc, 0xFFFFFFFEu, d_chunk_offsets, seen,
-                                                                                         nullptr, nullptr, nullptr, d_present_first);
-        HIP_TRY(hipGetLastError());
-        std::vector<uint32_t> firsts((size_t)seen);
-        HIP_TRY(hipMemcpyAsync(firsts.data(), d_present_first, (size_t)seen * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        std::nth_element(firsts.begin(), firsts.begin() + (bound - 1), firsts.end());
-        max_first_doc = firsts[(size_t)bound - 1];      // first docs are distinct (a doc has one key): exactly `bound` groups pass
-        st = count_groups(false, &total);
-        if (st != PG_OK) return st;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-      }
-      num_present = (int)total;
-      if (num_present > 0) {
-        const size_t ids_bytes = ((size_t)num_present * 4 + 255) & ~(size_t)255, counts_bytes = (size_t)num_present * 8;
-        const size_t acc_bytes = (size_t)num_present * (size_t)gp.num_group_aggs * 8;
-        st = ensure_host_groups(ctx, ids_bytes + counts_bytes + acc_bytes + 256);
-        if (st != PG_OK) return st;
-        int32_t* h_ids = reinterpret_cast<int32_t*>(ctx->h_groups);
-        unsigned long long* h_counts = reinterpret_cast<unsigned long long*>(ctx->h_groups + ids_bytes);
-        long long* h_acc = reinterpret_cast<long long*>(ctx->h_groups + ids_bytes + counts_bytes);
-        ids_of = h_ids; counts_of = h_counts; acc_of = h_acc;
-        int32_t* d_ids = (int32_t*)scratch.alloc((size_t)num_present * 4);
-        unsigned long long* d_counts = (unsigned long long*)scratch.alloc((size_t)num_present * 8);
-        long long* d_acc = (long long*)scratch.alloc(std::max<size_t>((size_t)num_present * (size_t)gp.num_group_aggs * 8, 8));
-        if (!d_ids || !d_counts || !d_acc) return fail(PG_ERR_OUT_OF_MEMORY, "group-by result of %d groups", num_present);
-        group_compact_kernel<<<dim3((unsigned)num_chunks), dim3(256), 0, ctx->stream>>>(gp.table_count, gp.table_acc, gp.num_group_aggs, gp.num_groups, d_first_doc, max_first_doc,
-                                                                                         d_chunk_offsets, total, d_ids, d_counts, d_acc, nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_ids, d_ids, (size_t)num_present * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(h_counts, d_counts, counts_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (gp.num_group_aggs > 0) HIP_TRY(hipMemcpyAsync(h_acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (hash_plan.kind != 0) {
-          // the slots that hold a group -> their 64-bit keys (and, for a key beyond a long, the first table's key behind its slot number)
-          unsigned long long* d_keys = (unsigned long long*)scratch.alloc((size_t)num_present * 8 * (size_t)(1 + hash_plan.levels));
-          if (!d_keys) return fail(PG_ERR_OUT_OF_MEMORY, "group-by keys of %d groups", num_present);
-          hash_keys.resize((size_t)num_present);
-          const unsigned gblocks = (unsigned)std::min<long long>(((long long)num_present + 255) / 256, (long long)seg->num_cus * 8);
-          gather_u64_kernel<<<dim3(gblocks), dim3(256), 0, ctx->stream>>>(gp.hash_keys, d_ids, num_present, gp.hash_mask, d_keys);
-          HIP_TRY(hipGetLastError());
-          HIP_TRY(hipMemcpyAsync(hash_keys.data(), d_keys, (size_t)num_present * 8, hipMemcpyDeviceToHost, ctx->stream));
-          // chained first tables, last one first: the low part of a key is the slot number of the table before it
-          hash_keys_lvl.resize((size_t)hash_plan.levels);
-          for (int l = hash_plan.levels - 1; l >= 0; --l) {
-            unsigned long long* src = d_keys + (size_t)(hash_plan.levels - 1 - l) * (size_t)num_present;
-            hash_keys_lvl[(size_t)l].resize((size_t)num_present);
-            gather_u64_by_key_kernel<<<dim3(gblocks), dim3(256), 0, ctx->stream>>>(gp.hash_keys_lvl[l], src, num_present, gp.hash_mask_lvl[l], src + num_present);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(hash_keys_lvl[(size_t)l].data(), src + num_present, (size_t)num_present * 8, hipMemcpyDeviceToHost, ctx->stream));
-          }
-        }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-      }
-    }
-    if (!ids_of) { ids_of = present_ids.data(); counts_of = present_counts.data(); acc_of = present_acc.data(); }
-    out->num_aggregations = na;
-    out->dominant_kernel = use_partition ? PG_KERNEL_GROUP_PARTITION : (use_private ? PG_KERNEL_GROUP_PRIVATE : PG_KERNEL_SCAN_GROUP);
-    out->num_groups = num_present;
-    out->group_id_upper_bound = (hash_plan.kind != 0 || no_dict_keys) ? (q->num_groups_limit > 0 ? q->num_groups_limit : 100000) : gp.num_groups;      // hashed holders / no-dictionary generators: numGroupsLimit, like the reference (:150-163)
-    out->group_ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(num_present, 1));
-    out->group_aggregations = (pg_agg_value*)calloc((size_t)std::max(num_present, 1) * (size_t)std::max(na, 1), sizeof(pg_agg_value));
-    // The keys as dictId tuples, for every kind of holder (what GroupKeyGenerator.getGroupKeys turns into values); rows in ascending
-    // raw-key order.  Hashed holders come out of the table in slot order: `perm` sorts them.
-    out->group_key_dict_ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(num_present, 1) * (size_t)ng);
-    out->group_key_kind = hash_plan.kind;
-    std::vector<int> perm;
-    if (hash_plan.kind == 0) {
-      for (int k = 0; k < num_present; ++k) {
-        long long raw = ids_of[(size_t)k];
-        for (int g = 0; g < ng; ++g) { out->group_key_dict_ids[(size_t)k * (size_t)ng + (size_t)g] = (int32_t)(raw % cards[(size_t)g]); raw /= cards[(size_t)g]; }
-      }
-    } else {
-      std::vector<int32_t> tuples((size_t)num_present * (size_t)ng);
-      for (int k = 0; k < num_present; ++k) {
-        // key l covers the columns [segment_begin(l), segment_end(l)); above its lowest digit -- the slot number of table l - 1 -- it is
-        // a mixed-radix number of those columns' dictIds
-        for (int l = 0; l <= hash_plan.levels; ++l) {
-          unsigned long long key = l == hash_plan.levels ? hash_keys[(size_t)k] : hash_keys_lvl[(size_t)l][(size_t)k];
-          if (l > 0) key /= (unsigned long long)hash_plan.slots_lvl[l - 1];
-          for (int g = hash_plan.segment_begin(l); g < hash_plan.segment_end(l, ng); ++g) {
-            tuples[(size_t)k * (size_t)ng + (size_t)g] = (int32_t)(key % (unsigned long long)cards[(size_t)g]); key /= (unsigned long long)cards[(size_t)g];
-          }
-        }
-      }
-      perm.resize((size_t)num_present);
-      for (int k = 0; k < num_present; ++k) perm[(size_t)k] = k;
-      std::sort(perm.begin(), perm.end(), [&](int a, int b) {
-        for (int g = ng - 1; g >= 0; --g) {      // the last column is the most significant digit of the raw key
-          const int32_t x = tuples[(size_t)a * (size_t)ng + (size_t)g], y = tuples[(size_t)b * (size_t)ng + (size_t)g];
-          if (x != y) return x < y;
-        }
-        return false;
-      });
-      if (hash_plan.kind == 1) out->group_ids64 = (int64_t*)malloc(sizeof(int64_t) * (size_t)std::max(num_present, 1));
-      for (int k = 0; k < num_present; ++k) {
-        const int src = perm[(size_t)k];
-        memcpy(out->group_key_dict_ids + (size_t)k * (size_t)ng, tuples.data() + (size_t)src * (size_t)ng, sizeof(int32_t) * (size_t)ng);
-        if (hash_plan.kind == 1) out->group_ids64[k] = (int64_t)hash_keys[(size_t)src];
-      }
-    }
-    // Turning accumulators into the reference's holder values is independent per group: large results (the IntMapBasedHolder range
-    // returns up to numGroupsLimit rows) are converted by a few host threads, each touching its own pages of the result.
-    auto convert_groups = [&](int k_begin, int k_end) {
-    for (int k = k_begin; k < k_end; ++k) {
-      const int src = perm.empty() ? k : perm[(size_t)k];       // the row of the compacted table behind result row k
-      const unsigned long long group_docs = counts_of[(size_t)src];
-      out->group_ids[k] = perm.empty() ? ids_of[(size_t)src] : k;      // (hashed holders: a row number; the key is in group_ids64 / group_key_dict_ids)
+    int k = 0;
+    for (int g = 0; g < G; ++g) {
+      const unsigned long long group_docs = table[g];
+      if (group_docs == 0ull) continue;
+      docs += (long long)group_docs;
+      out->group_ids[k] = g;
+      long long raw = g;
+      for (int c = 0; c < ng; ++c) { out->group_key_dict_ids[(size_t)k * (size_t)ng + (size_t)c] = (int32_t)(raw % cards[(size_t)c]); raw /= cards[(size_t)c]; }
       for (int a = 0; a < na; ++a) {
         const pg_aggregation& ag = q->aggregations[a];
         pg_agg_value& v = out->group_aggregations[(size_t)k * (size_t)na + (size_t)a];
-        v.count = (int64_t)group_docs;
-        v.min = std::numeric_limits<double>::infinity();
-        v.max = -std::numeric_limits<double>::infinity();
+        empty_agg_value(&v, (int64_t)group_docs);
         if (ag.function == PG_AGG_COUNT) continue;
-        const long long acc = acc_of[(size_t)dev_agg_of[(size_t)a] * (size_t)num_present + (size_t)src];
+        const int da = dev_agg_of[(size_t)a];
+        long long acc = (long long)table[(size_t)G * (size_t)(1 + da) + (size_t)g];
+        // zero-identity keys of the shared launch (group_private_body's flush): MIN travelled as 2^31 - v, MAX as v + 2^31 + 1
+        if (kinds[(size_t)da] == kGroupMin) acc = 0x80000000ll - acc;
+        else if (kinds[(size_t)da] == kGroupMax) acc = acc - 0x80000001ll;
         const ColumnDev& col = seg->cols[(size_t)ag.column];
-        const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
-        if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) {
-          if (col.vkind == kValF64 || col.vkind == kValF32) {
-            memcpy(&v.sum, &acc, 8);          // the slot accumulated doubles (ds_add_f64 / global_atomic_add_f64)
-            v.sum_i64 = 0;
-            v.sum_exact = 0;
-          } else {
-            set_integer_sum(&v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
-          }
-        }
-        else if (col.encoding == PG_FWD_RAW_FIXED_BYTE && col.vkind != kValI32) {      // raw LONG value, or the order key of a raw FLOAT / DOUBLE value
-          if (ag.function == PG_AGG_MIN) v.min = key64_to_double(col, acc); else v.max = key64_to_double(col, acc);
-        }
+        const bool plane = plane_cols[(size_t)ag.column] != 0;
+        if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) set_integer_sum(&v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
         else if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, (int32_t)acc, plane);
         else v.max = agg_value_double(col, (int32_t)acc, plane);
       }
-    }
-    };
-    const int convert_threads = num_present >= (1 << 16) ? (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency())) : 1;
-    if (convert_threads <= 1) {
-      convert_groups(0, num_present);
-    } else {
-      std::vector<std::thread> workers;
-      for (int t = 0; t < convert_threads; ++t) {
-        const int k0 = (int)((long long)num_present * t / convert_threads), k1 = (int)((long long)num_present * (t + 1) / convert_threads);
-        workers.emplace_back(convert_groups, k0, k1);
-      }
-      for (auto& w : workers) w.join();
+      ++k;
     }
     out->stats.num_docs_scanned = docs;
-    finish_filter_stats(lw, seg, count_entries ? (int64_t)*ctx->h_filter_entries : 0, count_entries, out);
-    out->stats.num_entries_scanned_post_filter = docs * (int64_t)projected.size();
+    finish_filter_stats(stats_plan, stats_scan_leaves, seg, 0, false, out);
+    out->stats.num_entries_scanned_post_filter = docs * (int64_t)num_projected;
     out->stats.num_total_docs = seg->num_docs;
+  };
+  return defer_item(r, std::move(item));
+}
+// Key spaces above the LDS table: the docs are partitioned by key range first, then every partition is aggregated in LDS
+// (pg_group_partition.h) instead of one global atomic per doc and aggregation.  P partitions of 2^partition_shift keys each; two
+// levels when log2_fine_per_coarse > 0 (pass A scatters by coarse partition, group_repartition_*_kernel by fine partition).
+static pg_status run_partitioned_group_by(QueryRun& r, const GroupParams& gp, int P, int partition_shift, int log2_fine_per_coarse) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; ExecCtx* ctx = r.ctx; const int ng = r.ng;
+  const bool two_level = log2_fine_per_coarse > 0;
+  const int scatter_shift = partition_shift + log2_fine_per_coarse;
+  const int partition_entry_bytes = 4 + 8 * gp.num_group_aggs;
+  const size_t N = (size_t)std::max(seg->num_tiles, 1) * 2048;
+  const size_t max_work = N / (1u << 16) + (size_t)P + 1;
+  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t off_upper = 0, off_cursor = align(off_upper + (size_t)P * 4), off_offsets = align(off_cursor + (size_t)P * 4);
+  const size_t off_work = align(off_offsets + (size_t)(P + 1) * 4), off_key = align(off_work + max_work * sizeof(PartitionWork));
+  // one packed dword per doc when the only aggregation input is an unsigned field that fits beside the slot (pg_group_partition.h)
+  int packed_bits = 0;
+  if (g_engine.partition_packed) {
+    if (gp.num_group_aggs == 0) packed_bits = 1;
+    else if (gp.num_group_aggs == 1) {
+      const DevGroupAgg& ga = gp.group_aggs[0];
+      const bool unsigned_field = !ga.is_raw && ga.vkind == kValI32 && (ga.kind != kGroupSum || ga.is_plane);
+      if (unsigned_field && ga.bits + scatter_shift <= 32) packed_bits = ga.bits;
+    }
   }
-  if (timed && out && lw.gathered) {
-    // index_and_kernel is the query: [ev[0], ev[3]] brackets the kernel and the copy of its counter lines
-    float ms_all = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_all, ctx->ev[0], ctx->ev[3]));
-    out->device_ms = ms_all;
-    out->dominant_kernel_ms = ms_all;
-  } else if (timed && out) {
+  const size_t off_val = align(off_key + N * 4), level1_bytes = off_val + (packed_bits > 0 ? 0 : (size_t)gp.num_group_aggs * align(N * 4));
+  // two levels: the second record buffer(s), the fine partitions' count / offset / cursor arrays, pass B's device-built work list and its
+  // length, and the re-scatter's own chunk list
+  const int num_vals = packed_bits > 0 ? 0 : gp.num_group_aggs;
+  const size_t fine_slots = (size_t)P << log2_fine_per_coarse;
+  const size_t max_work2 = N / (1u << 16) + fine_slots + 1, max_chunks = N / kRepartitionChunk + (size_t)P + 1;
+  const size_t off_key2 = align(level1_bytes), off_val2 = align(off_key2 + N * 4);
+  const size_t off_fine = align(off_val2 + (size_t)num_vals * align(N * 4));                       // count | cursor | work_count (zeroed together), then offsets
+  const size_t off_fine_offsets = align(off_fine + 2 * fine_slots * 4 + 64);
+  const size_t off_work2 = align(off_fine_offsets + fine_slots * 4), off_chunks = align(off_work2 + max_work2 * sizeof(PartitionWork));
+  const size_t bytes = two_level ? align(off_chunks + max_chunks * sizeof(PartitionWork)) : level1_bytes;
+  if (ctx->partition_capacity < bytes) {
+    if (ctx->d_partition) (void)hipFree(ctx->d_partition);
+    ctx->d_partition = nullptr; ctx->partition_capacity = 0;
+    if (hipMalloc((void**)&ctx->d_partition, bytes) != hipSuccess) return fail(PG_ERR_OUT_OF_MEMORY, "partitioned group-by needs %zu bytes of record buffers", bytes);
+    ctx->partition_capacity = bytes;
+  }
+  PartitionParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.gp = gp;
+  pp.shift = scatter_shift;                     // (two levels: pass 0 and pass A work on coarse partitions)
+  pp.num_partitions = P;
+  pp.packed_bits = packed_bits;
+  pp.upper = reinterpret_cast<uint32_t*>(ctx->d_partition + off_upper);
+  pp.cursor = reinterpret_cast<uint32_t*>(ctx->d_partition + off_cursor);
+  pp.offsets = reinterpret_cast<const uint32_t*>(ctx->d_partition + off_offsets);
+  pp.work = reinterpret_cast<const PartitionWork*>(ctx->d_partition + off_work);
+  pp.part_key = reinterpret_cast<uint32_t*>(ctx->d_partition + off_key);
+  for (int a = 0; a < gp.num_group_aggs; ++a) pp.part_val[a] = reinterpret_cast<uint32_t*>(ctx->d_partition + off_val + (size_t)a * align(N * 4));
+  HIP_TRY(hipMemsetAsync(ctx->d_partition, 0, off_offsets, ctx->stream));          // upper and cursor
+  const long long tiles2k = doc_tiles(seg);
+  const int hist_blocks = grid_blocks(seg, tiles2k, 4, 6, false);
+  std::vector<int> stats_key{scatter_shift};
+  for (int g = 0; g < ng; ++g) stats_key.push_back(q->group_by_columns[g]);
+  std::vector<uint32_t> upper;
+  if (g_engine.partition_stats_cache) {
+    std::lock_guard<std::mutex> lk(seg->partition_stats_mu);
+    for (const auto& e : seg->partition_stats) if (e.first == stats_key) upper = e.second;
+  }
+  if ((int)upper.size() != P) {
+    upper.assign((size_t)P, 0u);
+    launch_group_partition_histogram(hist_blocks, ctx->stream, pp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(upper.data(), pp.upper, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (g_engine.partition_stats_cache) {
+      std::lock_guard<std::mutex> lk(seg->partition_stats_mu);
+      if (seg->partition_stats.size() < 64) seg->partition_stats.emplace_back(stats_key, upper);
+    }
+  }
+  std::vector<uint32_t> offsets((size_t)P + 1, 0u);
+  std::vector<PartitionWork> work;
+  // chunk size: about two rounds of resident pass-B workgroups over the whole input, so that the flush of the touched slots
+  // (one global atomic per slot, accumulator and chunk) stays small next to the records a chunk aggregates
+  unsigned long long total_upper = 0;
+  for (int p = 0; p < P; ++p) total_upper += upper[(size_t)p];
+  const unsigned long long want_chunk = (total_upper + (unsigned long long)seg->num_cus * 6 - 1) / ((unsigned long long)seg->num_cus * 6);
+  const uint32_t chunk = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>((want_chunk + 1023) & ~1023ull, 1u << 16), (unsigned long long)kPartitionChunk);
+  for (int p = 0; p < P; ++p) {
+    offsets[(size_t)p + 1] = offsets[(size_t)p] + upper[(size_t)p];
+    for (uint32_t s0 = 0; s0 < upper[(size_t)p]; s0 += chunk) work.push_back(PartitionWork{p, s0, std::min<uint32_t>(chunk, upper[(size_t)p] - s0), 0u});
+  }
+  HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_offsets, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (!work.empty()) HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_work, work.data(), work.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
+  const int scatter_bpc = packed_bits > 0 ? blocks_per_cu_group_partition_scatter_packed(P) : std::max(1, waves_group_partition_scatter() / 4);
+  const int scatter_blocks = grid_blocks(seg, tiles2k, 4, scatter_bpc, false);
+  launch_group_partition_scatter(scatter_blocks, ctx->stream, pp);
+  HIP_TRY(hipGetLastError());
+  std::vector<PartitionWork> chunks;
+  if (two_level && !work.empty()) {
+    RepartitionParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.src_key = pp.part_key;
+    rp.dst_key = reinterpret_cast<uint32_t*>(ctx->d_partition + off_key2);
+    for (int a = 0; a < num_vals; ++a) { rp.src_val[a] = pp.part_val[a]; rp.dst_val[a] = reinterpret_cast<uint32_t*>(ctx->d_partition + off_val2 + (size_t)a * align(N * 4)); }
+    rp.coarse_offsets = pp.offsets; rp.coarse_cursor = pp.cursor;
+    rp.fine_count = reinterpret_cast<uint32_t*>(ctx->d_partition + off_fine);
+    rp.fine_cursor = rp.fine_count + fine_slots;
+    rp.work_count = rp.fine_cursor + fine_slots;
+    rp.fine_offsets = reinterpret_cast<uint32_t*>(ctx->d_partition + off_fine_offsets);
+    rp.work = reinterpret_cast<PartitionWork*>(ctx->d_partition + off_work2);
+    rp.chunks = reinterpret_cast<const PartitionWork*>(ctx->d_partition + off_chunks);
+    rp.num_coarse = P; rp.log2_fine_per_coarse = log2_fine_per_coarse; rp.fine_shift = partition_shift; rp.packed_bits = packed_bits; rp.num_vals = num_vals;
+    rp.aggregate_chunk = chunk;
+    for (int p = 0; p < P; ++p)
+      for (uint32_t s0 = 0; s0 < upper[(size_t)p]; s0 += kRepartitionChunk) chunks.push_back(PartitionWork{p, s0, std::min<uint32_t>(kRepartitionChunk, upper[(size_t)p] - s0), 0u});
+    HIP_TRY(hipMemsetAsync(ctx->d_partition + off_fine, 0, 2 * fine_slots * 4 + 64, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_chunks, chunks.data(), chunks.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
+    launch_group_repartition((int)chunks.size(), ctx->stream, rp);
+    HIP_TRY(hipGetLastError());
+    // pass B over the fine partitions: the second buffer, the device-built work list (as many workgroups as it can have entries)
+    PartitionParams fine = pp;
+    fine.shift = partition_shift;
+    fine.num_partitions = (int32_t)fine_slots;
+    fine.cursor = rp.fine_cursor; fine.offsets = rp.fine_offsets;
+    fine.work = rp.work; fine.work_count = rp.work_count;
+    fine.part_key = rp.dst_key;
+    for (int a = 0; a < num_vals; ++a) fine.part_val[a] = rp.dst_val[a];
+    launch_group_partition_aggregate((int)max_work2, ((size_t)partition_entry_bytes) << partition_shift, ctx->stream, fine);
+  } else if (!work.empty()) {
+    launch_group_partition_aggregate((int)work.size(), ((size_t)partition_entry_bytes) << partition_shift, ctx->stream, pp);
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));      // `offsets` / `work` / `chunks` are pageable host vectors: keep them alive until the copies ran
+  return PG_OK;
+}
+// The groups that exist, in ascending raw-key order: (raw key, doc count, accumulators[a * num_present + k]), read through ids_of /
+// counts_of / acc_of -- the vectors below, or the context's pinned staging.
+struct PresentGroups {
+  std::vector<unsigned long long> hash_keys;                    // hashed holders: the keys of the present slots ...
+  std::vector<std::vector<unsigned long long>> hash_keys_lvl;    // ... and, per chained first table, the key behind the slot number a later key starts with
+  std::vector<int32_t> ids; std::vector<unsigned long long> counts; std::vector<long long> acc;
+  const int32_t* ids_of = nullptr; const unsigned long long* counts_of = nullptr; const long long* acc_of = nullptr;
+  int num_present = 0; long long docs = 0;
+};
+
+// IntMapBasedHolder range: compact the HBM table on the device; honour numGroupsLimit the way the reference does
+// (_globalGroupIdUpperBound = min(product, numGroupsLimit), DictionaryBasedGroupKeyGenerator.java:176).
+static pg_status compact_map_groups(QueryRun& r, const GroupParams& gp, const HashPlan& hash_plan, long long product, bool use_private, int pblocks, int pthreads,
+                                    size_t plds, PresentGroups* found) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; const bool timed = r.timed;
+  pg_status st = PG_OK;
+  const int limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
+  const long long bound = hash_plan.kind != 0 ? (long long)limit : std::min<long long>(product, limit);      // LongMap / ArrayMap holders: _globalGroupIdUpperBound = numGroupsLimit (:150-163)
+  const int num_chunks = (int)(((long long)gp.num_groups + kGroupChunk - 1) / kGroupChunk);
+  DeviceScratch scratch(ctx);
+  uint32_t* d_chunk_counts = (uint32_t*)scratch.alloc((size_t)num_chunks * 4);
+  uint32_t* d_chunk_offsets = (uint32_t*)scratch.alloc((size_t)(num_chunks + 1) * 4);
+  unsigned long long* d_total_docs = (unsigned long long*)scratch.alloc(8);
+  if (!d_chunk_counts || !d_chunk_offsets || !d_total_docs) return fail(PG_ERR_OUT_OF_MEMORY, "group-by compaction scratch");
+  uint32_t* d_first_doc = nullptr;
+  uint32_t max_first_doc = 0xFFFFFFFFu;
+  auto count_groups = [&](bool with_docs, uint32_t* total) -> pg_status {
+    if (with_docs) HIP_TRY(hipMemsetAsync(d_total_docs, 0, 8, ctx->stream));
+    group_chunk_count_kernel<<<dim3((unsigned)num_chunks), dim3(256), 0, ctx->stream>>>(gp.table_count, d_first_doc, max_first_doc, gp.num_groups, d_chunk_counts,
+                                                                                         with_docs ? d_total_docs : nullptr);
+    group_chunk_scan_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(d_chunk_counts, num_chunks, d_chunk_offsets);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(total, d_chunk_offsets + num_chunks, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (!with_docs) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the first pass waits behind its doc total)
+    return PG_OK;
+  };
+  uint32_t total = 0;
+  unsigned long long total_docs = 0;
+  st = count_groups(true, &total); if (st != PG_OK) return st;
+  HIP_TRY(hipMemcpyAsync(&total_docs, d_total_docs, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (timed) HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  found->docs = (long long)total_docs;
+  out->num_groups_limit_reached = (long long)total >= (long long)limit ? 1 : 0;      // GroupByOperator.java:114-115
+  if ((long long)total > bound) {
+    // More groups than the reference would have created: it hands out group ids in order of first appearance (docId order)
+    // and drops the docs of later keys, so the survivors are the `bound` groups whose first doc comes earliest.
+    unsigned long long* d_filter = nullptr;
+    if (q->num_filter_nodes > 0 && hash_plan.kind == 0) {
+      d_filter = (unsigned long long*)scratch.alloc((((size_t)seg->num_docs + 63) / 64 + 1) * 8);
+      if (!d_filter) return fail(PG_ERR_OUT_OF_MEMORY, "group-by first-doc pass: filter bitmap");
+      pg_query fq = *q;
+      fq.num_aggregations = 0; fq.num_group_by = 0;
+      st = execute_impl(seg, &fq, nullptr, d_filter, nullptr, 0, nullptr);      // stays on the device
+      if (st != PG_OK) return st;
+    }
+    d_first_doc = (uint32_t*)scratch.alloc((size_t)gp.num_groups * 4);
+    if (!d_first_doc) return fail(PG_ERR_OUT_OF_MEMORY, "group-by first-doc pass: %d slots", gp.num_groups);
+    HIP_TRY(hipMemsetAsync(d_first_doc, 0xFF, (size_t)gp.num_groups * 4, ctx->stream));
+    // The survivors are the distinct keys of a PREFIX of the matching docs -- the reference stops admitting keys at the doc
+    // where the bound-th one appears.  With far more groups than the limit that prefix is short, so the docs are visited in
+    // growing prefixes until `bound` keys have a first doc, not all of them.
+    uint32_t seen = 0;
+    long long done_docs = 0;
+    long long step_docs = std::max<long long>(1 << 16, 4 * bound);
+    if (hash_plan.kind != 0) {
+      // hashed holders: the group-by kernel once more, in its first-doc mode (same filter, same keys, every key already has its slot)
+      GroupParams fg = gp;
+      fg.first_doc = d_first_doc;
+      fg.scan.filter_entries = nullptr; fg.scan.leap_tables = nullptr;
+      for (int n = 0; n < fg.scan.num_nodes; ++n) fg.scan.nodes[n].flags &= ~(kNodeLeapfrog2 | kNodeCountEntries);
+      // (plds: the set area, when the filter has dictId sets.  A query whose aggregation runs in group_typed_direct_kernel never sized a
+      //  group_private_kernel launch: the pass takes that kernel's own geometry then)
+      const int fd_threads = use_private ? pthreads : kBlockThreads;
+      const int fd_blocks = use_private ? pblocks : grid_blocks(seg, doc_tiles(seg), 4, 8, false);
+      if (!use_private) fg.set_lds_off = -1;
+      launch_group_private(false, fd_blocks, fd_threads, use_private ? plds : 0, ctx->stream, fg);
+      HIP_TRY(hipGetLastError());
+      done_docs = seg->num_docs;
+      max_first_doc = 0xFFFFFFFEu;
+      st = count_groups(false, &seen); if (st != PG_OK) return st;
+    }
+    while (done_docs < (long long)seg->num_docs && (long long)seen < bound) {
+      const long long hi = std::min<long long>((long long)seg->num_docs, done_docs + step_docs);
+      const long long span = hi - done_docs;
+      group_first_doc_kernel<<<dim3((unsigned)std::min<long long>((span + 255) / 256, (long long)seg->num_cus * 16)), dim3(256), 0, ctx->stream>>>(gp, d_filter, d_first_doc, done_docs, hi);
+      HIP_TRY(hipGetLastError());
+      done_docs = hi;
+      step_docs *= 2;
+      max_first_doc = 0xFFFFFFFEu;            // "has a first doc"
+      st = count_groups(false, &seen); if (st != PG_OK) return st;
+    }
+    uint32_t* d_present_first = (uint32_t*)scratch.alloc((size_t)std::max<uint32_t>(seen, 1) * 4);
+    if (!d_present_first) return fail(PG_ERR_OUT_OF_MEMORY, "group-by first-doc pass: %u groups", seen);
+    group_compact_kernel<<<dim3((unsigned)num_chunks), dim3(256), 0, ctx->stream>>>(gp.table_count, gp.table_acc, 0, gp.num_groups, d_first_doc, 0xFFFFFFFEu, d_chunk_offsets, seen,
+                                                                                     nullptr, nullptr, nullptr, d_present_first);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> firsts((size_t)seen);
+    HIP_TRY(hipMemcpyAsync(firsts.data(), d_present_first, (size_t)seen * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::nth_element(firsts.begin(), firsts.begin() + (bound - 1), firsts.end());
+    max_first_doc = firsts[(size_t)bound - 1];      // first docs are distinct (a doc has one key): exactly `bound` groups pass
+    st = count_groups(false, &total); if (st != PG_OK) return st;
+  }
+  found->num_present = (int)total;
+  if (found->num_present > 0) {
+    const size_t ids_bytes = ((size_t)found->num_present * 4 + 255) & ~(size_t)255, counts_bytes = (size_t)found->num_present * 8;
+    const size_t acc_bytes = (size_t)found->num_present * (size_t)gp.num_group_aggs * 8;
+    st = ensure_host_groups(ctx, ids_bytes + counts_bytes + acc_bytes + 256); if (st != PG_OK) return st;
+    int32_t* h_ids = reinterpret_cast<int32_t*>(ctx->h_groups);
+    unsigned long long* h_counts = reinterpret_cast<unsigned long long*>(ctx->h_groups + ids_bytes);
+    long long* h_acc = reinterpret_cast<long long*>(ctx->h_groups + ids_bytes + counts_bytes);
+    found->ids_of = h_ids; found->counts_of = h_counts; found->acc_of = h_acc;
+    int32_t* d_ids = (int32_t*)scratch.alloc((size_t)found->num_present * 4);
+    unsigned long long* d_counts = (unsigned long long*)scratch.alloc((size_t)found->num_present * 8);
+    long long* d_acc = (long long*)scratch.alloc(std::max<size_t>((size_t)found->num_present * (size_t)gp.num_group_aggs * 8, 8));
+    if (!d_ids || !d_counts || !d_acc) return fail(PG_ERR_OUT_OF_MEMORY, "group-by result of %d groups", found->num_present);
+    group_compact_kernel<<<dim3((unsigned)num_chunks), dim3(256), 0, ctx->stream>>>(gp.table_count, gp.table_acc, gp.num_group_aggs, gp.num_groups, d_first_doc, max_first_doc,
+                                                                                     d_chunk_offsets, total, d_ids, d_counts, d_acc, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_ids, d_ids, (size_t)found->num_present * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_counts, d_counts, counts_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (gp.num_group_aggs > 0) HIP_TRY(hipMemcpyAsync(h_acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (hash_plan.kind != 0) {
+      // the slots that hold a group -> their 64-bit keys (and, for a key beyond a long, the first table's key behind its slot number)
+      unsigned long long* d_keys = (unsigned long long*)scratch.alloc((size_t)found->num_present * 8 * (size_t)(1 + hash_plan.levels));
+      if (!d_keys) return fail(PG_ERR_OUT_OF_MEMORY, "group-by keys of %d groups", found->num_present);
+      found->hash_keys.resize((size_t)found->num_present);
+      const unsigned gblocks = (unsigned)std::min<long long>(((long long)found->num_present + 255) / 256, (long long)seg->num_cus * 8);
+      gather_u64_kernel<<<dim3(gblocks), dim3(256), 0, ctx->stream>>>(gp.hash_keys, d_ids, found->num_present, gp.hash_mask, d_keys);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(found->hash_keys.data(), d_keys, (size_t)found->num_present * 8, hipMemcpyDeviceToHost, ctx->stream));
+      // chained first tables, last one first: the low part of a key is the slot number of the table before it
+      found->hash_keys_lvl.resize((size_t)hash_plan.levels);
+      for (int l = hash_plan.levels - 1; l >= 0; --l) {
+        unsigned long long* src = d_keys + (size_t)(hash_plan.levels - 1 - l) * (size_t)found->num_present;
+        found->hash_keys_lvl[(size_t)l].resize((size_t)found->num_present);
+        gather_u64_by_key_kernel<<<dim3(gblocks), dim3(256), 0, ctx->stream>>>(gp.hash_keys_lvl[l], src, found->num_present, gp.hash_mask_lvl[l], src + found->num_present);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(found->hash_keys_lvl[(size_t)l].data(), src + found->num_present, (size_t)found->num_present * 8, hipMemcpyDeviceToHost, ctx->stream));
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  return PG_OK;
+}
+// ---------------- group-by (ArrayBasedHolder) ----------------
+static pg_status run_group_by(QueryRun& r) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; ScanParams& sp = lw.sp;
+  PlanParams& pl = lw.plan; const int na = r.na, ng = r.ng, num_cols_total = (int)seg->cols.size();
+  const bool want_bitmap = r.want_bitmap, timed = r.timed;
+  pg_status st = PG_OK;
+  GroupParams gp;
+  memset(&gp, 0, sizeof(gp));
+  int group_slot[kMaxGroupCols] = {}, group_mult[kMaxGroupCols] = {};
+  PlanGroupAgg plan_aggs[kMaxGroupAggs];
+  long long product = 1;
+  std::vector<int> cards;
+  bool no_dict_keys = false;            // a key is a raw column read through its key image, or the null-key image of one
+  for (int g = 0; g < ng; ++g) {
+    int c = q->group_by_columns[g];
+    if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
+    r.add_projected(seg->cols[(size_t)c].key_image_of >= 0 ? seg->cols[(size_t)c].key_image_of : c);      // numEntriesScannedPostFilter counts the caller's column
+    if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
+      // NoDictionarySingle/MultiColumnGroupKeyGenerator: the raw INT / LONG column through its key image (value - min as the dictId)
+      st = ensure_key_image(seg, c, &c); if (st != PG_OK) return st;
+    }
+    const ColumnDev& col = seg->cols[(size_t)c];
+    no_dict_keys |= col.key_image_of >= 0;
+    int s = slot_for(&lw, seg, c);
+    if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+    pl.cols[s].in_agg = 1;
+    group_slot[g] = s;
+    cards.push_back(col.cardinality);
+  }
+  // DictionaryBasedGroupKeyGenerator.java:164-184: up to arrayBasedThreshold (10 000) the raw key IS the group id (ArrayBasedHolder);
+  // above it the reference hashes raw keys (IntMapBasedHolder) -- here the table stays direct-indexed, in HBM, one slot per raw
+  // key, and only the groups that exist come back.  2^24 slots keep the 24-bit key multiplies exact and the table <= 1.2 GB.
+  // Beyond an int (Long / ArrayMap holders) the table is hashed: `product` is then its number of slots (plan_hash_holder).
+  HashPlan hash_plan;
+  st = plan_hash_holder(seg, cards, &hash_plan); if (st != PG_OK) return st;
+  if (hash_plan.kind == 0) {
+    for (int g = 0; g < ng; ++g) { group_mult[g] = (int32_t)product; product *= cards[(size_t)g]; }
+  } else {
+    product = hash_plan.slots;
+    if (q->flags & kQueryHashHolder) return fail(PG_ERR_UNSUPPORTED, "group-by with raw keys beyond an int under null handling (plan-time fallback)");
+  }
+  // (kQueryHashHolder: the no-dictionary key generators of null handling hand out group ids by first appearance up to numGroupsLimit
+  //  whatever the key space: the compaction path below is the one that honours the limit)
+  // A raw key column always runs the no-dictionary generators (DefaultGroupByExecutor.java:106-121): _globalGroupIdUpperBound =
+  // numGroupsLimit whatever the key space (NoDictionarySingleColumnGroupKeyGenerator.java:73-79), ids by first appearance.
+  const bool first_appearance = (q->flags & kQueryHashHolder) != 0 || (no_dict_keys && hash_plan.kind == 0 && (long long)(q->num_groups_limit > 0 ? q->num_groups_limit : 100000) < product);
+  const bool map_based = product > 10000 || first_appearance || hash_plan.kind != 0;
+  bool typed_direct = false;            // an aggregation input is a raw LONG / FLOAT / DOUBLE column: group_typed_direct_kernel
+  gp.num_group_cols = ng;
+  gp.num_groups = (int32_t)product;
+  gp.dense_ok = 1;
+  std::vector<int> dev_agg_of((size_t)std::max(na, 1), -1);
+  for (int a = 0; a < na; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if (ag.function == PG_AGG_COUNT) continue;
+    if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
+    if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
+    r.add_projected(ag.column);
+    int s = slot_for(&lw, seg, ag.column, lw.plane_cols[(size_t)ag.column] != 0);
+    if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+    pl.cols[s].in_agg = 1;
+    const int kind = (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) ? kGroupSum : (ag.function == PG_AGG_MIN ? kGroupMin : kGroupMax);
+    int da = -1;
+    for (int i = 0; i < gp.num_group_aggs; ++i) if (plan_aggs[i].col == s && plan_aggs[i].kind == kind) da = i;
+    if (da < 0) {
+      if (gp.num_group_aggs >= kMaxGroupAggs) return fail(PG_ERR_UNSUPPORTED, "more than %d distinct group-by aggregations", kMaxGroupAggs);
+      da = gp.num_group_aggs++;
+      plan_aggs[da] = PlanGroupAgg{s, kind};
+    }
+    dev_agg_of[(size_t)a] = da;
+  }
+  gp.wide_keys = product > (1ll << 24) ? 1 : 0;
+  // (hashed holders: one more word per slot for its key, and the first table of an ArrayMap-range key)
+  const size_t table_words = (size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs + (hash_plan.kind ? 1 : 0)) + (size_t)hash_plan.level_slots();
+  if ((unsigned long long)table_words * 8ull > g_engine.group_table_bytes)
+    return fail(PG_ERR_UNSUPPORTED, "group-by table of %lld slots x %d words exceeds the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", product, 1 + gp.num_group_aggs,
+                (unsigned long long)g_engine.group_table_bytes);
+  st = ensure_table(ctx, table_words, map_based ? 0 : table_words); if (st != PG_OK) return st;
+  struct TableTrim {            // a table of the upper IntMapBasedHolder range goes back to the allocator with the query
+    ExecCtx* c;
+    ~TableTrim() {
+      if (c->table_capacity * 8 > kGroupTableKeepBytes) { (void)hipFree(c->d_table); c->d_table = nullptr; c->table_capacity = 0; }
+    }
+  } table_trim{ctx};
+  gp.table_count = ctx->d_table;
+  gp.table_acc = reinterpret_cast<long long*>(ctx->d_table + gp.num_groups);
+  gp.hash_kind = hash_plan.kind;
+  gp.hash_levels = hash_plan.levels;
+  if (hash_plan.kind != 0) {
+    gp.hash_mask = (unsigned long long)gp.num_groups - 1ull;
+    gp.hash_keys = ctx->d_table + (size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs);
+    unsigned long long* next_table = gp.hash_keys + gp.num_groups;
+    for (int l = 0; l < hash_plan.levels; ++l) {
+      gp.hash_split[l] = hash_plan.split[l];
+      gp.hash_mask_lvl[l] = (unsigned long long)hash_plan.slots_lvl[l] - 1ull;
+      gp.hash_keys_lvl[l] = next_table;
+      next_table += hash_plan.slots_lvl[l];
+    }
+    for (int g = 0; g < ng; ++g) gp.key_mult[g] = hash_plan.mult[g];
+  }
+  const size_t table_bytes = table_words * 8;
+  Geometry geo;
+  const int group_wave_cap = waves_scan_group();
+  finish_geometry(seg, &lw, table_bytes, false, g_engine.group_waves > 0 ? std::min(g_engine.group_waves, kGroupBlockThreads / 64) : kGroupBlockThreads / 64, group_wave_cap, &geo);
+  if ((size_t)sp.wave_lds_bytes > kLdsBudget) return fail(PG_ERR_UNSUPPORTED, "query needs %d bytes of LDS per wavefront", sp.wave_lds_bytes);
+  gp.use_lds_table = geo.table_in_lds ? 1 : 0;
+  const int blocks = geo.blocks;
+  const size_t lds = geo.lds;
+  sp.speculate = 1;
+  for (int g = 0; g < ng; ++g) {
+    const DevColumn& c = pl.cols[group_slot[g]];
+    gp.group_keys[g] = DevGroupKey{c.bits, c.slot_off, group_mult[g], 0, c.fwd};
+  }
+  for (int a = 0; a < gp.num_group_aggs; ++a) {
+    const DevColumn& c = pl.cols[plan_aggs[a].col];
+    DevGroupAgg& ga = gp.group_aggs[a];
+    ga.kind = plan_aggs[a].kind; ga.bits = c.bits; ga.slot_off = c.slot_off; ga.is_raw = c.is_raw; ga.is_plane = c.is_plane;
+    ga.dict_bytes = c.dict_bytes; ga.fwd = c.fwd; ga.dict = c.dict;
+    // MIN / MAX run on dictIds whatever the value type; only a SUM reads 8-byte / floating-point dictionary entries
+    ga.vkind = (ga.kind == kGroupSum) ? c.vkind : kValI32;
+    if (c.is_raw && c.vkind != kValI32) { typed_direct = true; ga.vkind = c.vkind; }      // group_typed_direct_kernel: the value type decides the accumulator
+    // (the SUM of a dictionary column with 8-byte values under a Long / ArrayMap holder: the staged kernel that gathers such values has no
+    //  hashed table, group_typed_direct_kernel<.., kHash> gathers them too)
+    if (hash_plan.kind != 0 && ga.vkind != kValI32) typed_direct = true;
+    if (ga.vkind != kValI32) gp.dense_ok = 0;
+    if (ga.vkind == kValI64 && !c.is_raw) {
+      // the table slot is one wrapping int64: refuse (plan-time fallback) when numDocs * max|value| could overflow it
+      const ColumnDev& sc = seg->cols[(size_t)(lw.col_of_slot[(size_t)plan_aggs[a].col] / 2)];
+      const double max_abs = std::max(std::fabs((double)sc.h_dict_i64.front()), std::fabs((double)sc.h_dict_i64.back()));
+      if ((double)seg->num_docs * max_abs >= 9.2e18) return fail(PG_ERR_UNSUPPORTED, "group-by SUM of LONG column %s could overflow int64", sc.name.c_str());
+    }
+  }
+  // Without a filter every tile is aggregated in full: the lane-private kernel decodes straight from HBM and needs LDS only
+  // for the table (group_private_kernel).
+  // every leaf kind the lane-private filter implements (scan / set / bitmap / docId-range leaves, raw INT ranges)
+  bool private_leaves = true;
+  for (int l = 0; l < pl.num_leaves; ++l) private_leaves &= pl.leaves[l].kind <= kLeafBitmap || pl.leaves[l].kind == kLeafDocRange;
+  if (typed_direct && !private_leaves) return fail(PG_ERR_UNSUPPORTED, "group-by aggregation of a raw 8-byte column under a raw 8-byte range predicate (plan-time fallback)");
+  const bool use_private = (g_engine.group_private || hash_plan.kind != 0) && private_leaves && gp.dense_ok && !want_bitmap && !typed_direct;
+  if (hash_plan.kind != 0 && !use_private && !typed_direct) return fail(PG_ERR_UNSUPPORTED, "group-by with raw keys beyond an int: only 32-bit-domain or raw 8-byte aggregations under lane-private filter leaves");
+  int pblocks = blocks, pthreads = geo.threads;
+  size_t plds = lds;
+  if (use_private) {
+    const int private_wave_cap = waves_group_private();
+    const bool in_lds = table_bytes <= 96 * 1024;
+    gp.use_lds_table = in_lds ? 1 : 0;
+    int waves = in_lds ? kGroupBlockThreads / 64 : kBlockThreads / 64;
+    if (g_engine.group_waves > 0) waves = std::min(waves, g_engine.group_waves);
+    while (waves > private_wave_cap) waves >>= 1;
+    pthreads = waves * 64;
+    plds = in_lds ? table_bytes : 0;
+    int bpc = std::max(1, private_wave_cap / waves);
+    if (in_lds) bpc = std::max(1, std::min(bpc, (int)(kLdsBudget / std::max<size_t>(plds, 1))));
+    pblocks = grid_blocks(seg, doc_tiles(seg), waves, bpc);
+  }
+  // Count packing: when the first summed value plane is narrow enough, its 64-bit LDS slot carries (count << shift) | sum
+  // and the separate count atomic disappears.  Safe while a workgroup sees fewer than 2^cbits docs:
+  // sum < 2^cbits * 2^w = 2^shift and count < 2^cbits, so cbits + shift <= 64 never carries into or out of the count.
+  gp.packed_agg = -1;
+  gp.packed_shift = 0;
+  if (gp.use_lds_table && g_engine.group_pack) {
+    const long long waves_total = use_private ? (long long)pblocks * (pthreads / 64) : (long long)blocks * (geo.threads / 64);
+    const long long tiles_total = use_private ? doc_tiles(seg) : (long long)sp.num_tiles;
+    const long long tiles_per_wave = (tiles_total + waves_total - 1) / waves_total;
+    const long long docs_per_block = use_private ? tiles_per_wave * (pthreads / 64) * 2048 : tiles_per_wave * (geo.threads / 64) * 64 * sp.tile_steps;
+    int cbits = 1;
+    while ((1ll << cbits) <= docs_per_block) ++cbits;
+    for (int a = 0; a < gp.num_group_aggs; ++a) {
+      const DevGroupAgg& ga = gp.group_aggs[a];
+      if (ga.kind == kGroupSum && ga.is_plane && !ga.is_raw && 2 * cbits + ga.bits <= 64) { gp.packed_agg = a; gp.packed_shift = std::max(32, cbits + ga.bits); break; }
+    }
+  }
+  // group_private_kernel's LDS table in as many bank-interleaved copies as the workgroup's share of the CU's LDS holds (pg_kernels.h,
+  // lds_group_table_bytes): C3's 1000 groups x (SUM + MAX) are 12 KB a copy, eight copies for the one 16-wave workgroup of a CU.
+  gp.lds_log_replicas = 0;
+  // (a filter with dictId-set leaves: kSetLdsWords words of the workgroup's LDS hold the sets, behind the table -- pg_kernels.h stage_filter_sets)
+  sp.set_leaves_in_lds = 0;
+  if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
+  const size_t set_area = (use_private && sp.set_leaves_in_lds != 0) ? (size_t)kSetLdsWords * 4 : 0;
+  if (use_private && gp.use_lds_table) {
+    const int resident = std::max(1, std::min(waves_group_private() / std::max(1, pthreads / 64), g_engine.blocks_per_cu > 0 ? g_engine.blocks_per_cu : 1 << 30));
+    const size_t budget = kLdsBudget / (size_t)resident - set_area;
+    int log_r = 0;
+    while (log_r < g_engine.group_log_replicas && (size_t)lds_group_table_bytes(gp, log_r + 1) <= budget) ++log_r;
+    gp.lds_log_replicas = log_r;
+    plds = lds_group_table_bytes(gp, log_r);
+  }
+  gp.set_lds_off = -1;
+  if (set_area != 0 && plds + set_area <= kLdsBudget) { gp.set_lds_off = (int32_t)((plds + 15) & ~(size_t)15); plds = (size_t)gp.set_lds_off + set_area; }
+  gp.scan = sp;
+  gp.scan.partials = nullptr;
+  gp.scan.out_bitmap = nullptr;
+  if (lw.tile_list != nullptr) { st = complete_index_list(&lw, ctx); if (st != PG_OK) return st; }
+  gp.scan.tile_list = lw.tile_list;            // read by group_private_kernel only
+  gp.scan.tile_count = lw.tile_count;
+  gp.scan.filter_entries = nullptr;
+  if (r.defer != nullptr && g_engine.batch_group && use_private && gp.use_lds_table && hash_plan.kind == 0 && !first_appearance && !typed_direct && !want_bitmap && out &&
+      lw.tile_list == nullptr && lw.side == nullptr && !lw.stats_leap2_flagged && !lw.stats_chain_flagged && !ctx->pre_enqueued && r.stats_is_final &&
+      (long long)(q->num_groups_limit > 0 ? q->num_groups_limit : 100000) >= product && (r.defer->single || doc_tiles(seg) <= kBatchMaxTiles))
+    return defer_group_item(r, gp, pblocks, pthreads, plds, cards, dev_agg_of, no_dict_keys);
+  HIP_TRY(mark_pre_work(ctx));
+  init_group_table_kernel<<<dim3((unsigned)std::max<long long>(64, std::min<long long>(product >> 12, (long long)seg->num_cus * 16))), dim3(256), 0, ctx->stream>>>(gp);
+  HIP_TRY(hipGetLastError());
+  if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+  // Key spaces above the LDS table: partition the docs by key range first, then aggregate every partition in LDS
+  // (pg_group_partition.h) instead of one global atomic per doc and aggregation.
+  const int partition_entry_bytes = 4 + 8 * gp.num_group_aggs;
+  const int partition_shift = partition_entry_bytes <= 20 ? 12 : 11;
+  const long long fine_partitions = (product + (1ll << partition_shift) - 1) >> partition_shift;
+  // More fine partitions than one scatter pass can address (key spaces of 2 M .. 2^31 raw keys): two levels -- pass A scatters by
+  // coarse partition (2^k fine ones each), group_repartition_*_kernel scatter every coarse partition's records by fine partition
+  // (pg_group_partition.h).  PINOT_GPU_PARTITION_TWO_LEVEL=0: such key spaces keep the direct HBM atomics.
+  const bool two_level_on = g_engine.partition_two_level;
+  int log2_fine_per_coarse = 0;
+  while (((fine_partitions + (1ll << log2_fine_per_coarse) - 1) >> log2_fine_per_coarse) > kMaxPartitions) ++log2_fine_per_coarse;
+  const bool two_level = log2_fine_per_coarse > 0;
+  const long long num_partitions = (fine_partitions + (1ll << log2_fine_per_coarse) - 1) >> log2_fine_per_coarse;       // what pass A scatters into
+  const bool use_partition = hash_plan.kind == 0 && !typed_direct && map_based && g_engine.group_partition && g_engine.group_private && private_leaves && gp.dense_ok && !want_bitmap &&
+                             gp.num_group_aggs <= kMaxPartitionAggs && (!two_level || (two_level_on && (1 << log2_fine_per_coarse) <= kMaxFinePerCoarse)) &&
+                             (long long)seg->num_docs >= g_engine.partition_min_docs;
+  static const bool partition_trace = getenv("PINOT_GPU_PARTITION_TRACE") != nullptr;
+  if (partition_trace)
+    fprintf(stderr, "group-by plan: product %lld, fine partitions %lld (shift %d), 2^%d per coarse -> %lld scatter partitions; partition %d (hash %d typed_direct %d map_based %d "
+                    "private_leaves %d dense_ok %d aggs %d docs %d)\n", product, fine_partitions, partition_shift, log2_fine_per_coarse, num_partitions, (int)use_partition,
+            hash_plan.kind, (int)typed_direct, (int)map_based, (int)private_leaves, gp.dense_ok, gp.num_group_aggs, seg->num_docs);
+  if (use_partition || !(use_private || typed_direct)) { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
+  if (lw.side != nullptr) {
+    const bool wrote = ((use_private && !use_partition) || typed_direct) && gp.scan.tile_list == nullptr;
+    for (int l = 0; l < kMaxLeaves; ++l) gp.scan.leaf_out[l] = wrote ? lw.sp_leaf_out[l] : nullptr;
+    gp.scan.leaf_out_enabled = wrote ? 1 : 0;
+    lw.side->kernel_wrote = wrote;
+  }
+  const bool count_leap2 = out && lw.stats_leap2_flagged && ((use_private && !use_partition) || typed_direct);
+  const bool count_entries = (out && lw.stats_chain_flagged && ((use_private && !use_partition) || typed_direct)) || count_leap2;
+  gp.scan.leap_tables = nullptr;
+  if (count_leap2) { st = arm_leap_tables(seg, ctx, &gp.scan.leap_tables, &gp.scan.filter_entries); if (st != PG_OK) return st; }
+  else if (lw.stats_leap2_flagged) for (int n = 0; n < gp.scan.num_nodes; ++n) gp.scan.nodes[n].flags &= ~kNodeLeapfrog2;
+  if (count_entries && !count_leap2) { st = arm_filter_entries(ctx, &gp.scan.filter_entries); if (st != PG_OK) return st; }
+  if (use_partition) { st = run_partitioned_group_by(r, gp, (int)num_partitions, partition_shift, log2_fine_per_coarse); if (st != PG_OK) return st; }
+  else if (typed_direct) launch_group_typed_direct(grid_blocks(seg, doc_tiles(seg), 4, 8, false), ctx->stream, gp);
+  else if (use_private) launch_group_private(gp.use_lds_table != 0, pblocks, pthreads, plds, ctx->stream, gp);
+  else launch_scan_group(g_engine.use_dma, gp.use_lds_table != 0, blocks, geo.threads, lds, ctx->stream, gp);
+  HIP_TRY(hipGetLastError());
+  if (timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+  if (count_leap2) { st = launch_leap_chain(seg, ctx, 0); if (st != PG_OK) return st; }
+  if (count_entries) HIP_TRY(hipMemcpyAsync(ctx->h_filter_entries, ctx->d_filter_entries, 8, hipMemcpyDeviceToHost, ctx->stream));
+  // The groups that exist, in ascending raw-key order
+  PresentGroups found;
+  if (!map_based) {
+    HIP_TRY(hipMemcpyAsync(ctx->h_table, ctx->d_table, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (timed) HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const unsigned long long* hc = ctx->h_table;
+    const long long* ha = reinterpret_cast<const long long*>(ctx->h_table + gp.num_groups);
+    for (int g = 0; g < gp.num_groups; ++g) if (hc[g]) { found.num_present++; found.docs += (long long)hc[g]; }
+    found.ids.reserve((size_t)found.num_present); found.counts.reserve((size_t)found.num_present);
+    found.acc.resize((size_t)found.num_present * (size_t)gp.num_group_aggs);
+    int k = 0;
+    for (int g = 0; g < gp.num_groups; ++g) {
+      if (!hc[g]) continue;
+      found.ids.push_back(g); found.counts.push_back(hc[g]);
+      for (int a = 0; a < gp.num_group_aggs; ++a) found.acc[(size_t)a * (size_t)found.num_present + (size_t)k] = ha[(size_t)a * (size_t)gp.num_groups + (size_t)g];
+      k++;
+    }
+  } else {
+    st = compact_map_groups(r, gp, hash_plan, product, use_private, pblocks, pthreads, plds, &found); if (st != PG_OK) return st;
+  }
+  if (!found.ids_of) { found.ids_of = found.ids.data(); found.counts_of = found.counts.data(); found.acc_of = found.acc.data(); }
+  // hashed holders / no-dictionary generators: group_id_upper_bound = numGroupsLimit, like the reference (:150-163).  The keys come as dictId
+  // tuples for every kind of holder (what GroupKeyGenerator.getGroupKeys turns into values); rows in ascending raw-key order.  Hashed holders
+  // come out of the table in slot order: `perm` sorts them.
+  start_group_result(out, na, ng, found.num_present, use_partition ? PG_KERNEL_GROUP_PARTITION : (use_private ? PG_KERNEL_GROUP_PRIVATE : PG_KERNEL_SCAN_GROUP),
+                     (hash_plan.kind != 0 || no_dict_keys) ? (q->num_groups_limit > 0 ? q->num_groups_limit : 100000) : gp.num_groups, hash_plan.kind);
+  std::vector<int> perm;
+  if (hash_plan.kind == 0) {
+    for (int k = 0; k < found.num_present; ++k) {
+      long long raw = found.ids_of[(size_t)k];
+      for (int g = 0; g < ng; ++g) { out->group_key_dict_ids[(size_t)k * (size_t)ng + (size_t)g] = (int32_t)(raw % cards[(size_t)g]); raw /= cards[(size_t)g]; }
+    }
+  } else {
+    std::vector<int32_t> tuples((size_t)found.num_present * (size_t)ng);
+    for (int k = 0; k < found.num_present; ++k) {
+      // key l covers the columns [segment_begin(l), segment_end(l)); above its lowest digit -- the slot number of table l - 1 -- it is
+      // a mixed-radix number of those columns' dictIds
+      for (int l = 0; l <= hash_plan.levels; ++l) {
+        unsigned long long key = l == hash_plan.levels ? found.hash_keys[(size_t)k] : found.hash_keys_lvl[(size_t)l][(size_t)k];
+        if (l > 0) key /= (unsigned long long)hash_plan.slots_lvl[l - 1];
+        for (int g = hash_plan.segment_begin(l); g < hash_plan.segment_end(l, ng); ++g) {
+          tuples[(size_t)k * (size_t)ng + (size_t)g] = (int32_t)(key % (unsigned long long)cards[(size_t)g]); key /= (unsigned long long)cards[(size_t)g];
+        }
+      }
+    }
+    perm.resize((size_t)found.num_present);
+    for (int k = 0; k < found.num_present; ++k) perm[(size_t)k] = k;
+    std::sort(perm.begin(), perm.end(), [&](int a, int b) {
+      for (int g = ng - 1; g >= 0; --g) {      // the last column is the most significant digit of the raw key
+        const int32_t x = tuples[(size_t)a * (size_t)ng + (size_t)g], y = tuples[(size_t)b * (size_t)ng + (size_t)g];
+        if (x != y) return x < y;
+      }
+      return false;
+    });
+    if (hash_plan.kind == 1) out->group_ids64 = (int64_t*)malloc(sizeof(int64_t) * (size_t)std::max(found.num_present, 1));
+    for (int k = 0; k < found.num_present; ++k) {
+      const int src = perm[(size_t)k];
+      memcpy(out->group_key_dict_ids + (size_t)k * (size_t)ng, tuples.data() + (size_t)src * (size_t)ng, sizeof(int32_t) * (size_t)ng);
+      if (hash_plan.kind == 1) out->group_ids64[k] = (int64_t)found.hash_keys[(size_t)src];
+    }
+  }
+  // Turning accumulators into the reference's holder values is independent per group: large results (the IntMapBasedHolder range
+  // returns up to numGroupsLimit rows) are converted by a few host threads, each touching its own pages of the result.
+  auto convert_groups = [&](int k_begin, int k_end) {
+  for (int k = k_begin; k < k_end; ++k) {
+    const int src = perm.empty() ? k : perm[(size_t)k];       // the row of the compacted table behind result row k
+    const unsigned long long group_docs = found.counts_of[(size_t)src];
+    out->group_ids[k] = perm.empty() ? found.ids_of[(size_t)src] : k;      // (hashed holders: a row number; the key is in group_ids64 / group_key_dict_ids)
+    for (int a = 0; a < na; ++a) {
+      const pg_aggregation& ag = q->aggregations[a];
+      pg_agg_value& v = out->group_aggregations[(size_t)k * (size_t)na + (size_t)a];
+      empty_agg_value(&v, (int64_t)group_docs);
+      if (ag.function == PG_AGG_COUNT) continue;
+      const long long acc = found.acc_of[(size_t)dev_agg_of[(size_t)a] * (size_t)found.num_present + (size_t)src];
+      const ColumnDev& col = seg->cols[(size_t)ag.column];
+      const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
+      if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) {
+        if (col.vkind == kValF64 || col.vkind == kValF32) {
+          memcpy(&v.sum, &acc, 8);          // the slot accumulated doubles (ds_add_f64 / global_atomic_add_f64)
+          v.sum_i64 = 0;
+          v.sum_exact = 0;
+        } else {
+          set_integer_sum(&v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
+        }
+      }
+      else if (col.encoding == PG_FWD_RAW_FIXED_BYTE && col.vkind != kValI32) {      // raw LONG value, or the order key of a raw FLOAT / DOUBLE value
+        if (ag.function == PG_AGG_MIN) v.min = key64_to_double(col, acc); else v.max = key64_to_double(col, acc);
+      }
+      else if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, (int32_t)acc, plane);
+      else v.max = agg_value_double(col, (int32_t)acc, plane);
+    }
+  }
+  };
+  const int convert_threads = found.num_present >= (1 << 16) ? (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency())) : 1;
+  if (convert_threads <= 1) convert_groups(0, found.num_present);
+  else {
+    std::vector<std::thread> workers;
+    for (int t = 0; t < convert_threads; ++t) {
+      const int k0 = (int)((long long)found.num_present * t / convert_threads), k1 = (int)((long long)found.num_present * (t + 1) / convert_threads);
+      workers.emplace_back(convert_groups, k0, k1);
+    }
+    for (auto& w : workers) w.join();
+  }
+  out->stats.num_docs_scanned = found.docs;
+  finish_filter_stats(lw, seg, count_entries ? (int64_t)*ctx->h_filter_entries : 0, count_entries, out);
+  out->stats.num_entries_scanned_post_filter = found.docs * (int64_t)r.projected.size();
+  out->stats.num_total_docs = seg->num_docs;
+  return PG_OK;
+}
+// The query's device time (PG_CFG_TIME_KERNELS) and the transducer pass behind its kernels
+static pg_status finish_query(QueryRun& r) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; const Lowered& lw = r.lw; const bool timed = r.timed;
+  if (timed && out && lw.gathered) { const pg_status st = time_index_and(ctx, out); if (st != PG_OK) return st; }
+  else if (timed && out) {
     float ms_all = 0.f, ms_scan = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms_scan, ctx->ev[1], ctx->ev[2]));
     if (!ctx->pre_started && ctx->ev_last == 2) ms_all = ms_scan;
@@ -4094,6 +4011,105 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
     if (device_fsm_filter_stats(seg, ctx, q, *lw.side, out) != PG_OK) { (void)hipGetLastError(); out->filter_entries_exact = 0; }
   }
   return PG_OK;
+}
+static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out, unsigned long long* d_out_bitmap_request,
+                              uint64_t* host_bitmap, int64_t host_bitmap_words, int64_t* out_cardinality, bool allow_metadata_plan,
+                              Deferred* defer, FsmSide* side) {
+  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
+  if (!seg || !q) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  // d_out_bitmap_request: like host_bitmap, but the filter's doc-order bitmap is copied device to device into the caller's
+  // buffer ((num_docs + 63) / 64 words, any stream-ordered device memory) and never visits the host.
+  {
+    pg_query shape = *q;                      // pg_filter_bitmap evaluates the filter only
+    if (host_bitmap != nullptr || d_out_bitmap_request != nullptr) { shape.num_aggregations = 0; shape.num_group_by = 0; }
+    const pg_status eligible = check_query_plan(seg, &shape, 0);
+    if (eligible != PG_OK) return eligible;
+  }
+  exec_mark(1);
+  HIP_TRY(hipSetDevice(phys_device(seg->device)));
+  ExecCtx* ctx = nullptr;
+  pg_status st = acquire_ctx(seg, &ctx); if (st != PG_OK) return st;
+  CtxGuard guard{seg, ctx};
+
+  const bool want_bitmap = host_bitmap != nullptr || d_out_bitmap_request != nullptr;
+  const int na = want_bitmap ? 0 : q->num_aggregations;
+  const int ng = want_bitmap ? 0 : q->num_group_by;
+  if (na < 0 || ng < 0 || (na > 0 && !q->aggregations) || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
+  if (ng > kMaxGroupCols) return fail(PG_ERR_UNSUPPORTED, "more than %d group-by columns", kMaxGroupCols);
+  const bool timed = (g_engine.flags & PG_CFG_TIME_KERNELS) != 0;
+  if (ng == 0 && !want_bitmap && out && na > 0 && allow_metadata_plan && answer_from_metadata(seg, q, na, out, out_cardinality)) return PG_OK;
+
+  QueryRun r(seg, q, out, ctx, defer, na, ng, want_bitmap, timed);
+  Lowered& lw = r.lw;
+  memset(&lw.sp, 0, sizeof(lw.sp));
+  memset(&lw.plan, 0, sizeof(lw.plan));
+  lw.plan.lazy_node = -1;
+  const int num_cols_total = (int)seg->cols.size();
+  // Columns that are summed are read through their value plane (built on first use); decided before the filter is
+  // lowered so that a range predicate on the same column can be evaluated on the plane too.
+  lw.plane_cols.assign((size_t)std::max(num_cols_total, 1), 0);
+  // At most one summed column goes through the LDS histogram instead (scan_hist_kernel); it needs the lane-private kernel, so the
+  // shapes that kernel does not take are ruled out here, before a plane is (not) built.
+  if (ng == 0 && !want_bitmap && g_engine.scan_private && !(g_engine.flags & PG_CFG_PROFILE_WAVES)) {
+    bool shape_ok = true;
+    int only_col = -1;                  // the histogram kernel aggregates ONE column (SUM / AVG / MIN / MAX of it, and COUNT)
+    for (int a = 0; a < na && shape_ok; ++a) {
+      const pg_aggregation& ag = q->aggregations[a];
+      if (ag.function == PG_AGG_COUNT) continue;
+      shape_ok = ag.column >= 0 && ag.column < num_cols_total && seg->cols[(size_t)ag.column].encoding == PG_FWD_FIXED_BIT_DICT &&
+                 seg->cols[(size_t)ag.column].vkind == kValI32 && (only_col < 0 || only_col == ag.column);
+      only_col = ag.column;
+    }
+    for (int i = 0; i < q->num_predicates && shape_ok && q->predicates; ++i) {
+      const pg_predicate& pr = q->predicates[i];
+      if (pr.kind == PG_PRED_RAW_RANGE) shape_ok = pr.column >= 0 && pr.column < num_cols_total && seg->cols[(size_t)pr.column].stored_type == PG_TYPE_INT;
+    }
+    for (int a = 0; a < na && shape_ok && r.hist_col < 0; ++a) {
+      const pg_aggregation& ag = q->aggregations[a];
+      if ((ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) && want_hist(seg->cols[(size_t)ag.column])) r.hist_col = ag.column;
+    }
+  }
+  for (int a = 0; a < na; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if ((ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) && ag.column >= 0 && ag.column < num_cols_total && ag.column != r.hist_col &&
+        (want_value_plane(seg->cols[(size_t)ag.column]) || (!want_bitmap && want_wide_plane(seg, q, ag.column)))) {
+      if (lw.plane_cols[(size_t)ag.column]) continue;
+      bool ready = false;
+      st = acquire_plane(seg, ag.column, &ready); if (st != PG_OK) return st;
+      if (ready) { r.planes.columns.push_back(ag.column); lw.plane_cols[(size_t)ag.column] = 1; }
+      else lw.plane_pending = true;
+    }
+  }
+  ctx->pre_enqueued = false;
+  ctx->pre_started = false;      // ev[0] is recorded by the first piece of work that precedes the scan kernel (mark_pre_work)
+  ctx->ev_last = 3;
+  if (out && !want_bitmap) lw.stats_plan = fstats::choose_plan(q, &lw.stats_scan_leaves);
+  if (lw.stats_plan == fstats::Plan::kLeap2 && (!g_engine.leap2 || (q->flags & PG_QUERY_STATS_UPPER_BOUND_OK))) lw.stats_plan = fstats::Plan::kReplay;      // (kReplay with nobody replaying: the upper bound)
+  // the caller takes the upper bound (PG_QUERY_STATS_UPPER_BOUND_OK): a leap-frogging filter has no pass behind its kernel, so in a batch it shares the launch like any other
+  r.stats_is_final = lw.stats_plan == fstats::Plan::kZero || lw.stats_plan == fstats::Plan::kPerLeaf ||
+                              (lw.stats_plan == fstats::Plan::kReplay && (q->flags & PG_QUERY_STATS_UPPER_BOUND_OK) != 0);
+  lw.cardinality_only_hint = ng == 0 && out && !want_bitmap && na > 0;
+  for (int a = 0; a < na; ++a) lw.cardinality_only_hint = lw.cardinality_only_hint && q->aggregations[a].function == PG_AGG_COUNT;
+  lw.side = nullptr;
+  if (out && !want_bitmap && lw.stats_plan == fstats::Plan::kReplay && side != nullptr && side->fsm != nullptr) {
+    // numEntriesScannedInFilter is a statistic: a pass that cannot get its scratch leaves the query's answer standing with
+    // filter_entries_exact = 0 (pg_execute's host replay still applies at its sizes) -- it never fails the query
+    if (prepare_fsm_side(seg, ctx, *side->fsm, side) == PG_OK) lw.side = side;
+    else (void)hipGetLastError();
+  }
+  st = lower_filter(seg, ctx, q, &lw); if (st != PG_OK) return st;
+  exec_mark(2);
+  if (out) memset(out, 0, sizeof(*out));
+  if (lw.cardinality_only_hint && lw.index_and_is_whole_filter) return count_from_index(r, out_cardinality);
+  st = ng == 0 ? run_aggregation(r, d_out_bitmap_request, host_bitmap, host_bitmap_words, out_cardinality) : run_group_by(r);
+  if (st == kHistRetry) {
+    // (the histogram's next tier: the context goes back before the query is answered again)
+    release_ctx(seg, ctx);
+    guard.ctx = nullptr;
+    return execute_impl(seg, q, out, d_out_bitmap_request, host_bitmap, host_bitmap_words, out_cardinality, allow_metadata_plan, nullptr, side);
+  }
+  if (st != PG_OK) return st;
+  return finish_query(r);
 }
 
 // ---- PG_QUERY_NULL_HANDLING (query option enableNullHandling=true) ----
@@ -4414,7 +4430,7 @@ struct FsmScratch {
   size_t front_bytes = 0;            // machines with episodes: fsm_tile_fns_kernel's lane fronts (4 / 8 / 16 bytes a lane for <= 4 / 8 / 16 states), behind the last opens
   long long tiles = 0, chunks = 0;
   FsmScratch(const pg_segment* seg, const fstats::Fsm& fsm) {
-    tiles = std::max<long long>(1, ((long long)seg->num_docs + 2047) / 2048);
+    tiles = std::max<long long>(1, doc_tiles(seg));
     chunks = (tiles + kFsmChunk - 1) / kFsmChunk;
     bitmap_bytes = (size_t)tiles * 256;
     delta_bytes = (((size_t)fsm.num_states << fsm.num_inputs) + 255) & ~(size_t)255;
@@ -4924,9 +4940,10 @@ void remember_item(pg_segment* seg, std::string&& key, const std::shared_ptr<con
 
 struct DeferredLaunch {
   BatchCtx* b = nullptr;
-  int device = -1, n = 0, lean_kind = 0;       // lean_kind: ScanParams.lean_kind of every item (0: scan_private_batch_kernel, 1 / 2: scan_lean_batch_kernel)
+  int device = -1, n = 0;
+  BatchKind kind = BatchKind::Private;     // ScanParams.lean_kind of every item
   std::vector<int> items, blocks;
-  std::vector<size_t> table_offsets;       // lean_kind 6: where every item's slice starts in the context's table (words)
+  std::vector<size_t> table_offsets;       // GroupLds: where every item's slice starts in the context's table (words)
   long long total_blocks = 0, docs = 0;
   size_t lds = 0;
   unsigned long long seq = 0;
@@ -4935,7 +4952,20 @@ struct DeferredLaunch {
   ~DeferredLaunch() { if (b) { std::lock_guard<std::mutex> lk(g_batch_mu); g_batch_free.push_back(b); } }
 };
 
-// The group-by items of one device (lean_kind 6): one launch of group_lds_batch_kernel over the items' GroupParams, each with a slice of the
+// Workgroups per item of a shared launch in proportion to its tiles (`budget` workgroups for the launch's `total_tiles`), never more than
+// the item would get on its own nor one per `per_block` tiles (L->blocks; returns their sum, L->total_blocks)
+static long long share_blocks(DeferredLaunch* L, const std::vector<Deferred>& defs, pg_segment* const* segments, long long total_tiles, long long budget, long long per_block) {
+  L->blocks.assign((size_t)L->n, 0);
+  L->total_blocks = 0;
+  for (int k = 0; k < L->n; ++k) {
+    const int i = L->items[(size_t)k];
+    const long long tiles = doc_tiles(segments[i]), share = total_tiles > 0 ? (tiles * budget + total_tiles - 1) / total_tiles : 1;
+    L->blocks[(size_t)k] = (int)std::max<long long>(1, std::min<long long>({(long long)defs[(size_t)i].item->blocks, share, (tiles + per_block - 1) / per_block}));
+    L->total_blocks += L->blocks[(size_t)k];
+  }
+  return L->total_blocks;
+}
+// The group-by items of one device (BatchKind::GroupLds): one launch of group_lds_batch_kernel over the items' GroupParams, each with a slice of the
 // context's table; then ONE copy of all slices to the pinned host image and a memset that leaves the table all-zero for the next launch.
 // The dictId sets (IN lists) of a deferred item ride in the batch's blob: copied behind the item slots, the item's leaves pointed at the copy
 // (they were lowered against the words of a context the item is no longer tied to).  *set_off: bytes of the set area used so far.
@@ -4961,7 +4991,7 @@ pg_status enqueue_group_launch(DeferredLaunch* L, BatchCtx* b, std::vector<Defer
   int threads = 64;
   for (int i : items) {
     const LoweredItem& d = *defs[(size_t)i].item;
-    total_tiles += ((long long)segments[i]->num_docs + 2047) / 2048;
+    total_tiles += doc_tiles(segments[i]);
     L->docs += (long long)segments[i]->num_docs;
     launch_lds = std::max(launch_lds, d.group_lds);
     threads = std::max(threads, d.group_threads);
@@ -4971,18 +5001,8 @@ pg_status enqueue_group_launch(DeferredLaunch* L, BatchCtx* b, std::vector<Defer
   const int wpb = threads / 64;
   int bpc = std::max(1, std::min(waves_group_lds_batch() / wpb, (int)(kLdsBudget / std::max<size_t>(launch_lds, 1))));
   if (g_engine.blocks_per_cu > 0) bpc = g_engine.blocks_per_cu;
-  const long long budget = (long long)segments[items[0]]->num_cus * bpc;
-  std::vector<int>& blocks = L->blocks;
-  blocks.assign((size_t)n, 0);
-  long long total_blocks = 0;
-  for (int k = 0; k < n; ++k) {
-    const LoweredItem& d = *defs[(size_t)items[(size_t)k]].item;
-    const long long tiles = ((long long)segments[items[(size_t)k]]->num_docs + 2047) / 2048;
-    const long long share = total_tiles > 0 ? (tiles * budget + total_tiles - 1) / total_tiles : 1;
-    blocks[(size_t)k] = (int)std::max<long long>(1, std::min<long long>({(long long)d.blocks, share, (tiles + wpb - 1) / wpb}));
-    total_blocks += blocks[(size_t)k];
-  }
-  L->total_blocks = total_blocks;
+  const std::vector<int>& blocks = L->blocks;
+  share_blocks(L, defs, segments, total_tiles, (long long)segments[items[0]]->num_cus * bpc, wpb);
   size_t set_bytes = 0, set_off = 0;
   for (int i : items) set_bytes += item_set_bytes(*defs[(size_t)i].item);
   pg_status st = ensure_batch_ctx(b, n, 0, set_bytes);
@@ -5039,7 +5059,7 @@ pg_status enqueue_group_launch(DeferredLaunch* L, BatchCtx* b, std::vector<Defer
   if (set_off) HIP_TRY(hipMemcpyAsync(b->d_blob + b->sets_offset, b->h_blob + b->sets_offset, set_off, hipMemcpyHostToDevice, b->stream));
   if (L->timed) HIP_TRY(hipEventRecord(b->ev[0], b->stream));
   b->gtable_dirty = true;
-  launch_group_lds_batch((int)total_blocks, threads, launch_lds, b->stream, d_items, b->d_first, n);
+  launch_group_lds_batch((int)L->total_blocks, threads, launch_lds, b->stream, d_items, b->d_first, n);
   HIP_TRY(hipGetLastError());
   if (L->timed) HIP_TRY(hipEventRecord(b->ev[1], b->stream));
   if (publish) b->gtable_dirty = false;          // (the launch leaves table and counters as it found them; finish_group_launch says otherwise when an item stays silent)
@@ -5119,7 +5139,7 @@ pg_status finish_group_launch(DeferredLaunch* L, std::vector<Deferred>& defs, pg
   return PG_OK;
 }
 
-// The index-led items of one device (lean_kind 12): one launch of index_and_batch_kernel -- the items' workgroups
+// The index-led items of one device (BatchKind::IndexAnd): one launch of index_and_batch_kernel -- the items' workgroups
 // in proportion to their windows, about what is resident in total -- every item with its own records, arrival counters and pinned host record.
 static_assert(sizeof(IndexAndParams) <= kBatchItemSlot, "an index-AND item takes a slot of the batch's parameter blob");
 pg_status enqueue_index_and_launch(DeferredLaunch* L, BatchCtx* b, std::vector<Deferred>& defs, pg_segment* const* segments) {
@@ -5194,44 +5214,28 @@ pg_status enqueue_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_se
   if (!b) { b = new BatchCtx(); b->device = device; }
   L->b = b;
   const int n = L->n = (int)items.size();
-  if (L->lean_kind == 6) return enqueue_group_launch(L, b, defs, segments);
-  if (L->lean_kind == 12) return enqueue_index_and_launch(L, b, defs, segments);
+  if (L->kind == BatchKind::GroupLds) return enqueue_group_launch(L, b, defs, segments);
+  if (L->kind == BatchKind::IndexAnd) return enqueue_index_and_launch(L, b, defs, segments);
   // Workgroups per item in proportion to its tiles, about sixteen per CU in total (four waves each: ~4x what is resident, so that
   // the items' tails overlap other items' scans); never more than the item would get on its own.
   long long total_tiles = 0;
-  for (int i : items) { total_tiles += ((long long)segments[i]->num_docs + 2047) / 2048; L->docs += (long long)segments[i]->num_docs; }
+  for (int i : items) { total_tiles += doc_tiles(segments[i]); L->docs += (long long)segments[i]->num_docs; }
   // (the lean kernels hold five -- raw: four -- waves per SIMD: a workgroup per CU more than the general body's four)
-  const bool hist_kind = L->lean_kind >= 3 && L->lean_kind <= 5;
-  const int hist_cw = L->lean_kind == 3 ? 8 : (L->lean_kind == 4 ? 16 : 32);
-  const int wpb = hist_kind ? kHistBlockThreads / 64 : kBlockThreads / 64;      // wavefronts of a workgroup
-  const bool narrow_kind = L->lean_kind == 7 || L->lean_kind == 8, typed_kind = L->lean_kind >= 9 && L->lean_kind <= 11;
-  const int typed_slots = L->lean_kind == 9 ? 1 : (L->lean_kind == 10 ? 2 : kMaxAggCols);
-  // tiles a wave takes per iteration (the narrow kernels walk four / eight tiles at a time)
-  const int tiles_per_wave = L->lean_kind == 7 ? kNarrowTiles : (L->lean_kind == 8 ? kNarrowSingleTiles : 1);
+  const BatchKindInfo info = batch_kind_info(L->kind);
+  const int wpb = info.block_waves, tiles_per_wave = info.tiles_per_wave;
   size_t launch_lds = 0;
   for (int i : items) launch_lds = std::max(launch_lds, defs[(size_t)i].item->hist_lds);
   L->lds = launch_lds;
-  const int lean_bpc = hist_kind ? std::max(1, std::min(waves_scan_hist_batch(hist_cw) / wpb, (int)((160 * 1024 - 2048) / (launch_lds + 256))))
-                       : narrow_kind ? std::max(1, waves_scan_narrow_batch(L->lean_kind == 8) / wpb)
-                       : typed_kind ? std::max(1, waves_scan_typed_batch(typed_slots) / wpb)
-                       : (L->lean_kind != 0 ? std::max(1, waves_scan_lean_batch(L->lean_kind) / wpb) : 0);
+  int lean_bpc = std::max(1, info.wave_cap / wpb);
+  if (info.hist_bits) lean_bpc = std::max(1, std::min(info.wave_cap / wpb, (int)((160 * 1024 - 2048) / (launch_lds + 256))));
   const bool bpc_forced = g_engine.batch_blocks_per_cu_forced;      // (read once per pg_init: bench sweeps re-initialise the engine with it)
-  const long long budget = (long long)segments[items[0]]->num_cus * ((L->lean_kind != 0 && (!bpc_forced || hist_kind)) ? lean_bpc : g_engine.batch_blocks_per_cu);
-  std::vector<int>& blocks = L->blocks;
-  blocks.assign((size_t)n, 0);
+  const bool lean = L->kind != BatchKind::Private && (!bpc_forced || info.hist_bits != 0);
+  const long long budget = (long long)segments[items[0]]->num_cus * (lean ? lean_bpc : g_engine.batch_blocks_per_cu);
+  const std::vector<int>& blocks = L->blocks;
+  const long long total_blocks = share_blocks(L, defs, segments, total_tiles, budget, (long long)wpb * tiles_per_wave);
   size_t partials = 0;
-  long long total_blocks = 0;
   bool one_slot = true;
-  for (int k = 0; k < n; ++k) {
-    const LoweredItem& d = *defs[(size_t)items[(size_t)k]].item;
-    const long long tiles = ((long long)segments[items[(size_t)k]]->num_docs + 2047) / 2048;
-    const long long share = total_tiles > 0 ? (tiles * budget + total_tiles - 1) / total_tiles : 1;
-    blocks[(size_t)k] = (int)std::max<long long>(1, std::min<long long>({(long long)d.blocks, share, (tiles + (long long)wpb * tiles_per_wave - 1) / ((long long)wpb * tiles_per_wave)}));
-    partials += (size_t)blocks[(size_t)k] + (size_t)kFoldExtraRecords;
-    total_blocks += blocks[(size_t)k];
-    one_slot = one_slot && d.one_slot;
-  }
-  L->total_blocks = total_blocks;
+  for (int k = 0; k < n; ++k) { partials += (size_t)blocks[(size_t)k] + (size_t)kFoldExtraRecords; one_slot = one_slot && defs[(size_t)items[(size_t)k]].item->one_slot; }
   size_t set_bytes = 0;
   for (int i : items) set_bytes += item_set_bytes(*defs[(size_t)i].item);
   pg_status st = ensure_batch_ctx(b, n, partials, set_bytes);
@@ -5257,11 +5261,7 @@ pg_status enqueue_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_se
   HIP_TRY(hipMemcpyAsync(b->d_blob, b->h_blob, b->items_offset + sizeof(ScanParams) * (size_t)n, hipMemcpyHostToDevice, b->stream));
   if (set_off) HIP_TRY(hipMemcpyAsync(b->d_blob + b->sets_offset, b->h_blob + b->sets_offset, set_off, hipMemcpyHostToDevice, b->stream));
   if (L->timed) HIP_TRY(hipEventRecord(b->ev[0], b->stream));
-  if (hist_kind) launch_scan_hist_batch(hist_cw, (int)total_blocks, launch_lds, b->stream, b->d_items, b->d_first, n);
-  else if (narrow_kind) launch_scan_narrow_batch(L->lean_kind == 8, (int)total_blocks, b->stream, b->d_items, b->d_first, n);
-  else if (typed_kind) launch_scan_typed_batch(typed_slots, (int)total_blocks, b->stream, b->d_items, b->d_first, n);
-  else if (L->lean_kind != 0) launch_scan_lean_batch(L->lean_kind, (int)total_blocks, b->stream, b->d_items, b->d_first, n);
-  else launch_scan_private_batch(one_slot, (int)total_blocks, b->stream, b->d_items, b->d_first, n);
+  launch_batch_kind(L->kind, info, one_slot, (int)total_blocks, launch_lds, b->stream, b->d_items, b->d_first, n);
   HIP_TRY(hipGetLastError());
   if (L->timed) HIP_TRY(hipEventRecord(b->ev[1], b->stream));
   L->t1 = std::chrono::steady_clock::now();
@@ -5270,7 +5270,7 @@ pg_status enqueue_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_se
 }
 
 pg_status finish_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_result* results, pg_status* statuses) {
-  if (L->lean_kind == 6) return finish_group_launch(L, defs, results, statuses);
+  if (L->kind == BatchKind::GroupLds) return finish_group_launch(L, defs, results, statuses);
   BatchCtx* b = L->b;
   const int n = L->n;
   const unsigned long long seq = L->seq;
@@ -5353,7 +5353,7 @@ pg_status pg_execute(pg_segment* segment, const pg_query* query, pg_result* out_
     if (st != kDeferred) return st;                     // ran the usual way (or failed): nothing was deferred
   }
   DeferredLaunch L;
-  L.device = segment->device; L.lean_kind = 6; L.items.push_back(0);
+  L.device = segment->device; L.kind = BatchKind::GroupLds; L.items.push_back(0);
   pg_segment* const segs[1] = {segment};
   pg_status item_status = PG_ERR_INTERNAL;
   st = enqueue_deferred(&L, defs, segs);
@@ -5389,7 +5389,7 @@ pg_status pg_execute_batch(pg_segment* const* segments, const pg_query* const* q
   // is claimed alone)
   // (an item too large for the shared launch runs its whole kernel inside its claim: such batches are claimed one item at a time)
   bool all_small = g_engine.batch_launch;
-  for (int i : todo) all_small = all_small && segments[i] != nullptr && ((long long)segments[i]->num_docs + 2047) / 2048 <= kBatchMaxTiles;
+  for (int i : todo) all_small = all_small && segments[i] != nullptr && doc_tiles(segments[i]) <= kBatchMaxTiles;
   const int todo_count = (int)todo.size();
   if (todo_count > 0) run_items(todo_count, all_small ? threads : std::min(threads, todo_count), all_small ? 8 : 1, !all_small, [&](int t) {
     const int i = todo[(size_t)t];
@@ -5411,9 +5411,9 @@ pg_status pg_execute_batch(pg_segment* const* segments, const pg_query* const* q
   for (int i = 0; i < count; ++i) {
     if (statuses[i] != kDeferred) continue;
     DeferredLaunch* L = nullptr;
-    const int kind = defs[(size_t)i].item->sp.lean_kind;
-    for (auto& l : launches) if (l->device == segments[i]->device && l->lean_kind == kind) L = l.get();
-    if (!L) { launches.emplace_back(new DeferredLaunch()); L = launches.back().get(); L->device = segments[i]->device; L->lean_kind = kind; }
+    const BatchKind kind = static_cast<BatchKind>(defs[(size_t)i].item->sp.lean_kind);
+    for (auto& l : launches) if (l->device == segments[i]->device && l->kind == kind) L = l.get();
+    if (!L) { launches.emplace_back(new DeferredLaunch()); L = launches.back().get(); L->device = segments[i]->device; L->kind = kind; }
     L->items.push_back(i);
   }
   auto fail_items = [&](DeferredLaunch* L, pg_status st) {
