@@ -48,8 +48,9 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 3   /* 2: pg_result.filter_entries_exact, pg_query_check, pg_config.plane_budget_bytes;
-                            * 3: pg_execute_batch, pg_result.group_key_kind / group_ids64 / group_key_dict_ids (Long / ArrayMap holders) */
+#define PG_ABI_VERSION 4   /* 2: pg_result.filter_entries_exact, pg_query_check, pg_config.plane_budget_bytes;
+                            * 3: pg_execute_batch, pg_result.group_key_kind / group_ids64 / group_key_dict_ids (Long / ArrayMap holders);
+                            * 4: PG_PRED_RAW_SET (IN / NOT IN on raw INT / LONG / FLOAT / DOUBLE columns); no struct layout changed */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -132,9 +133,27 @@ typedef enum pg_predicate_kind {
                                 * range [lo, hi] (both inclusive) that SortedIndexReader.getDocIds gives for the predicate's dictIds on a sorted
                                 * column; `exclusive` inverts it over [0, numDocs).  No column is read.  `column` is ignored unless the query
                                 * runs with PG_QUERY_NULL_HANDLING, where it names the sorted column (its null docs are excluded) or is -1. */
-  PG_PRED_IS_NULL = 6          /* FilterPlanNode.java:294-307: BitmapBasedFilterOperator over the column's null bitmap; `exclusive` = IS NOT NULL.
+  PG_PRED_IS_NULL = 6,         /* FilterPlanNode.java:294-307: BitmapBasedFilterOperator over the column's null bitmap; `exclusive` = IS NOT NULL.
                                 * A column without a null vector matches nothing (IS NULL) / everything (IS NOT NULL).  No entries are scanned. */
+  PG_PRED_RAW_SET = 7          /* Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator.applySV (InPredicateEvaluatorFactory.java:74-107,
+                                * :215-380): value is a member of the literal set; `exclusive` = NOT_IN (NotInPredicateEvaluatorFactory).  A raw
+                                * (no-dictionary) INT / LONG / FLOAT / DOUBLE column, `eval` = PG_EVAL_SCAN (a ScanBasedFilterOperator).  The
+                                * values travel in set_words, TWO 32-bit words per value, low word first: INT / LONG columns the value as int64,
+                                * FLOAT / DOUBLE columns the IEEE-754 bits of the value as a double (FLOAT literals widened exactly, as RAW_RANGE
+                                * does for lo / hi).  Any order, duplicates allowed; the engine sorts and de-duplicates.  lo / hi are unused.
+                                *  - an empty list matches nothing (NOT_IN: everything);
+                                *  - INT column: a value outside int32 can never match and is dropped; FLOAT column: a value that is not
+                                *    exactly a float is dropped;
+                                *  - FLOAT / DOUBLE: members are compared by bit pattern.  A list that holds +0.0, -0.0 or a NaN is declined
+                                *    (PG_ERR_UNSUPPORTED): whether the reference's hash set separates the zeros and unifies the NaNs is not
+                                *    known here, and for every other value bit equality and == agree;
+                                *  - more than PG_RAW_SET_MAX_VALUES distinct values: PG_ERR_UNSUPPORTED;
+                                *  - an odd num_set_words, a null set_words with a non-zero count, PG_EVAL_INVERTED or a dictionary column:
+                                *    PG_ERR_INVALID_ARGUMENT. */
 } pg_predicate_kind;
+
+#define PG_RAW_SET_MAX_VALUES 1024   /* PG_PRED_RAW_SET: distinct values after de-duplication */
+#define PG_RAW_SET_WORDS_PER_VALUE 2  /* PG_PRED_RAW_SET: 32-bit set words per value, low word first */
 
 typedef enum pg_leaf_eval {
   PG_EVAL_SCAN = 0,            /* ScanBasedFilterOperator */
@@ -151,7 +170,7 @@ typedef struct pg_predicate {
                                 * RAW_RANGE on a raw FLOAT / DOUBLE column: lo / hi carry the IEEE-754 bit pattern of the inclusive
                                 * bounds as doubles (Float / DoubleRawValueBasedRangePredicateEvaluator after Math.nextUp / nextDown
                                 * made exclusive bounds inclusive; FLOAT bounds widened exactly). */
-  const uint32_t* set_words;   /* DICT_SET: bitset over dictIds, bit d = (set_words[d >> 5] >> (d & 31)) & 1 */
+  const uint32_t* set_words;   /* DICT_SET: bitset over dictIds, bit d = (set_words[d >> 5] >> (d & 31)) & 1 ; RAW_SET: two words per value */
   int32_t num_set_words;
   int32_t reserved;
 } pg_predicate;
@@ -258,6 +277,7 @@ typedef enum pg_kernel_id {
                                     * index-led aggregation whose index phase (index_and_kernel + its tile-list pass) outlasts the scan of the listed tiles */
   PG_KERNEL_SCAN_NARROW = 8,       /* scan_narrow_kernel: COUNT(*) / bitmap of a filter over dictionary columns of at most 8 bits, four tiles per wave */
   PG_KERNEL_SCAN_SPARSE = 9,       /* scan_sparse_kernel: aggregation of the docs a sparse docId bitmap names (index-led filters), eight tiles per wave */
+  PG_KERNEL_SCAN_RAW_SET = 12,     /* scan_raw_set_kernel: one PG_PRED_RAW_SET leaf (its hash table in LDS) + at most one aggregated raw INT column, coalesced reads */
   PG_KERNEL_SCAN_RAW = 11,         /* scan_raw_kernel: one raw INT range leaf + at most one aggregated raw INT column, five waves per SIMD, coalesced reads */
   PG_KERNEL_SCAN_SIMPLE = 10,      /* scan_simple_kernel: one dictionary-range leaf + at most one aggregated packed column, twice the waves per SIMD */
   PG_KERNEL_SCAN_HIST = 6          /* scan_hist_kernel: lane-private scan, SUM = sum_d matches[d] * dictionary[d] through an LDS histogram */

@@ -51,6 +51,9 @@ char* ph_explain_filter(void* segment, const char* sql, int32_t* status);
 char* ph_lower_range_predicate(const void* dict, int32_t cardinality, const char* lower, int32_t lower_inclusive, const char* upper, int32_t upper_inclusive, int32_t* status);
 /* the raw-value range evaluator of an INT (0) / LONG (1) column: inclusive [rawLower, rawUpper] */
 char* ph_lower_raw_range_predicate(int32_t data_type, const char* lower, int32_t lower_inclusive, const char* upper, int32_t upper_inclusive, int32_t* status);
+/* the LDS membership table of a PG_PRED_RAW_SET leaf, built from `members` (distinct 4- / 8-byte bit patterns) and probed as the kernels probe it:
+ * out_hits[i] = probes[i] found; returns the bucket count (0: no table) */
+int32_t ph_raw_set_table_probe(int32_t key_bytes, const uint64_t* members, int32_t num_members, const uint64_t* probes, int64_t num_probes, uint8_t* out_hits);
 char* ph_execute_sql(void** segments, int32_t num_segments, const char* sql, int32_t max_execution_threads, int32_t* status);
 
 /* ---- DataTable V4 (DataTableImplV4.toBytes of the intermediate results: what the server sends the broker; host/datatable_v4.cpp) ---- */

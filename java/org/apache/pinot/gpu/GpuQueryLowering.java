@@ -21,6 +21,7 @@ import java.util.Map;
 import javax.annotation.Nullable;
 import org.apache.pinot.common.request.context.ExpressionContext;
 import org.apache.pinot.common.request.context.FilterContext;
+import org.apache.pinot.common.request.context.predicate.BaseInPredicate;
 import org.apache.pinot.common.request.context.predicate.EqPredicate;
 import org.apache.pinot.common.request.context.predicate.NotEqPredicate;
 import org.apache.pinot.common.request.context.predicate.Predicate;
@@ -46,6 +47,7 @@ final class GpuQueryLowering {
   static final int PRED_DICT_RANGE = PinotGpuNative.PG_PRED_DICT_RANGE;
   static final int PRED_DICT_SET = PinotGpuNative.PG_PRED_DICT_SET;
   static final int PRED_RAW_RANGE = PinotGpuNative.PG_PRED_RAW_RANGE;
+  static final int PRED_RAW_SET = PinotGpuNative.PG_PRED_RAW_SET;
   static final int PRED_DOC_RANGE = PinotGpuNative.PG_PRED_DOC_RANGE;
   static final int PRED_IS_NULL = PinotGpuNative.PG_PRED_IS_NULL;
   static final int EVAL_SCAN = PinotGpuNative.PG_EVAL_SCAN;
@@ -515,8 +517,11 @@ final class GpuQueryLowering {
         upper = lower;
         exclusive = true;
         break;
+      case IN:
+      case NOT_IN:
+        return lowerRawSetPredicate((BaseInPredicate) predicate, column, storedType);
       default:
-        throw new NotOffloadable("IN / NOT_IN on a raw column");
+        throw new NotOffloadable("predicate type " + predicate.getType() + " on a raw column");
     }
     boolean lowerUnbounded = RangePredicate.UNBOUNDED.equals(lower);
     boolean upperUnbounded = RangePredicate.UNBOUNDED.equals(upper);
@@ -613,6 +618,62 @@ final class GpuQueryLowering {
         throw new NotOffloadable("predicate on a raw " + storedType + " column");
     }
     return leaf(PRED_RAW_RANGE, column, EVAL_SCAN, exclusive, lo, hi, null, SCAN_PRIORITY);
+  }
+
+  /**
+   * Raw (no-dictionary) INT / LONG / FLOAT / DOUBLE column, IN / NOT_IN: Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator
+   * (InPredicateEvaluatorFactory.java:74-107, :215-380; NotInPredicateEvaluatorFactory negates) -- the literals parsed with the column type's
+   * parser into a hash set, applySV = set.contains(value).  PG_PRED_RAW_SET: the distinct values, ascending, two set words each (low word
+   * first): the value as a long, or the bits of the value as a double (a FLOAT literal is rounded once, by Float.parseFloat, then widened).
+   * A scan leaf.  Kept on the CPU plan: a FLOAT / DOUBLE list with a zero or a NaN (how the reference's hash set treats +0.0 / -0.0 and the
+   * NaNs is not settled on the device side; for every other value bit equality and == agree), and more than PG_RAW_SET_MAX_VALUES distinct values.
+   */
+  private Node lowerRawSetPredicate(BaseInPredicate predicate, int column, DataType storedType) {
+    boolean exclusive = predicate.getType() == Predicate.Type.NOT_IN;
+    List<String> literals = predicate.getValues();
+    long[] values = new long[literals.size()];
+    int n = 0;
+    for (String literal : literals) {
+      switch (storedType) {
+        case INT:
+          values[n++] = Integer.parseInt(literal);
+          break;
+        case LONG:
+          values[n++] = Long.parseLong(literal);
+          break;
+        case FLOAT:
+        case DOUBLE: {
+          double v = storedType == DataType.FLOAT ? (double) Float.parseFloat(literal) : Double.parseDouble(literal);
+          if (v != v || v == 0.0) {
+            throw new NotOffloadable("IN / NOT_IN list with a zero or a NaN on a raw " + storedType + " column");
+          }
+          values[n++] = Double.doubleToRawLongBits(v);
+          break;
+        }
+        default:
+          throw new NotOffloadable("predicate on a raw " + storedType + " column");
+      }
+    }
+    Arrays.sort(values);
+    int distinct = 0;
+    for (int i = 0; i < n; i++) {
+      if (i == 0 || values[i] != values[i - 1]) {
+        values[distinct++] = values[i];
+      }
+    }
+    if (distinct > PinotGpuNative.PG_RAW_SET_MAX_VALUES) {
+      throw new NotOffloadable("IN / NOT_IN list of " + distinct + " distinct values on a raw column");
+    }
+    if (distinct == 0) {
+      return constant(exclusive);
+    }
+    int[] words = new int[PinotGpuNative.PG_RAW_SET_WORDS_PER_VALUE * distinct];
+    int w = 0;
+    for (int i = 0; i < distinct; i++) {
+      words[w++] = (int) values[i];
+      words[w++] = (int) (values[i] >>> 32);
+    }
+    return leaf(PRED_RAW_SET, column, EVAL_SCAN, exclusive, 0, 0, words, SCAN_PRIORITY);
   }
 
   private static boolean hasNulls(DataSource dataSource) {

@@ -24,7 +24,7 @@ public final class PinotGpuNative {
   // may spell one of these numbers as a literal.
 
   /** PG_ABI_VERSION (include/pinot_gpu.h): checked against pg_version() in GpuPlanMaker.init. */
-  public static final int PG_ABI_VERSION = 3;
+  public static final int PG_ABI_VERSION = 4;
 
   /** pg_status */
   public static final int PG_OK = 0;
@@ -53,6 +53,12 @@ public final class PinotGpuNative {
   public static final int PG_PRED_RAW_RANGE = 4;
   public static final int PG_PRED_DOC_RANGE = 5;
   public static final int PG_PRED_IS_NULL = 6;
+  /** IN / NOT_IN on a raw INT / LONG / FLOAT / DOUBLE column: two set words per value (low word first), see include/pinot_gpu.h. */
+  public static final int PG_PRED_RAW_SET = 7;
+  /** PG_RAW_SET_MAX_VALUES: distinct values of one PG_PRED_RAW_SET list. */
+  public static final int PG_RAW_SET_MAX_VALUES = 1024;
+  /** PG_RAW_SET_WORDS_PER_VALUE: set words one value of a PG_PRED_RAW_SET list takes (low word first). */
+  public static final int PG_RAW_SET_WORDS_PER_VALUE = 2;
 
   /** pg_leaf_eval */
   public static final int PG_EVAL_SCAN = 0;

@@ -48,7 +48,7 @@ pgm_query* pgm_query_build(const int32_t* filter_nodes, int32_t num_nodes, const
   if ((num_nodes && !filter_nodes) || (num_preds && (!pred_ints || !pred_longs || !set_offsets)) || (num_set_words && !set_words) ||
       (num_aggs && !aggregations) || (num_group_by && !group_by)) { set_error("null array"); return NULL; }
   for (int32_t p = 0; p < num_preds; p++) {
-    if (set_offsets[p] < 0 || set_offsets[p + 1] < set_offsets[p] || set_offsets[p + 1] > num_set_words) { set_error("dictId-set offsets of predicate %d leave the word array", p); return NULL; }
+    if (set_offsets[p] < 0 || set_offsets[p + 1] < set_offsets[p] || set_offsets[p + 1] > num_set_words) { set_error("set-word offsets of predicate %d leave the word array", p); return NULL; }
   }
   pgm_query* q = (pgm_query*)calloc(1, sizeof(pgm_query));
   if (!q) { set_error("out of memory"); return NULL; }

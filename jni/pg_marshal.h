@@ -9,7 +9,7 @@
  *   filter_nodes   int32[3 * num_nodes]     {op, predicate, num_children} per pg_filter_node, postfix order
  *   pred_ints      int32[4 * num_preds]     {kind, column, eval, exclusive} per pg_predicate
  *   pred_longs     int64[2 * num_preds]     {lo, hi}
- *   set_offsets    int32[num_preds + 1]     predicate p owns set_words[set_offsets[p] .. set_offsets[p + 1]) (DICT_SET; empty otherwise)
+ *   set_offsets    int32[num_preds + 1]     predicate p owns set_words[set_offsets[p] .. set_offsets[p + 1]) (DICT_SET: the dictId bitset; RAW_SET: two words per value, low word first; empty otherwise)
  *   set_words      uint32[]                 bit d of a predicate's words = dictId d matches
  *   aggregations   int32[2 * num_aggs]      {function, column}
  *   group_by       int32[num_group_by]

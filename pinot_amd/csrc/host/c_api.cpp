@@ -8,6 +8,7 @@
 #include <sstream>
 
 #include "pinot_host.h"
+#include "../pg_raw_set_table.h"
 
 using namespace pinot;
 
@@ -498,6 +499,17 @@ char* ph_lower_raw_range_predicate(int32_t data_type, const char* lower, int32_t
     out = o.str();
   });
   return *status == 0 ? strdup(out.c_str()) : nullptr;
+}
+
+// The membership table of a PG_PRED_RAW_SET leaf (../pg_raw_set_table.h: what the engine builds and the kernels probe in LDS), built from
+// `members` (bit patterns of 4- or 8-byte keys, distinct) and probed with the kernels' own lookup: out_hits[i] = 1 when probes[i] is found.
+// Returns the table's bucket count, 0 when no table could be built.
+int32_t ph_raw_set_table_probe(int32_t key_bytes, const uint64_t* members, int32_t num_members, const uint64_t* probes, int64_t num_probes, uint8_t* out_hits) {
+  std::vector<uint64_t> keys(members, members + std::max(num_members, 0));
+  pg::RawSetTable t;
+  if (!pg::build_raw_set_table(keys, key_bytes, &t)) return 0;
+  for (int64_t i = 0; i < num_probes; ++i) out_hits[i] = pg::raw_set_table_contains(t, probes[i]) ? 1 : 0;
+  return (int32_t)t.buckets;
 }
 
 // getOperator(sql).nextBlock() per segment + the combined block: {"segments": [...], "combined": {...}}

@@ -258,6 +258,10 @@ struct PredicateEvaluator {                          // operator/filter/predicat
   std::vector<int> matchingDictIds;                  // sorted (IN / NOT_IN inner set)
   bool rawRange = false; int64_t rawLower = 0, rawUpper = 0;   // raw INT / LONG columns: inclusive bounds
   bool rawFloating = false;                          // raw FLOAT / DOUBLE: rawLower / rawUpper hold the bit patterns of inclusive double bounds
+  // raw INT / LONG / FLOAT / DOUBLE columns, IN / NOT_IN (Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator): the distinct members as
+  // PG_PRED_RAW_SET carries them -- the int64 value, or the bit pattern of the value as a double (FLOAT literals rounded once to float, then
+  // widened) -- ascending as int64; `exclusive` = NOT_IN
+  bool rawSet = false; std::vector<int64_t> rawSetValues;
   int getNumMatchingItems() const;
 };
 // PredicateEvaluatorProvider.getPredicateEvaluator (operator/filter/predicate/PredicateEvaluatorProvider.java)

@@ -294,6 +294,16 @@ PhysNode lowerFilter(const FilterContext& f, const ImmutableSegment& seg, bool n
         p.kind = PG_PRED_RAW_RANGE; p.lo = ev.rawLower; p.hi = ev.rawUpper; p.exclusive = ev.exclusive;
         return physLeaf(out, p, kScanPriority);
       }
+      if (ev.rawSet) {
+        // a ScanBasedFilterOperator like the raw range; the values live in the lowered query (two words each, low word first)
+        p.kind = PG_PRED_RAW_SET; p.eval = PG_EVAL_SCAN; p.exclusive = ev.exclusive;
+        std::vector<uint32_t> words;
+        for (int64_t v : ev.rawSetValues) { words.push_back((uint32_t)(uint64_t)v); words.push_back((uint32_t)((uint64_t)v >> 32)); }
+        out->setWords.push_back(std::move(words));
+        p.set_words = out->setWords.back().data();
+        p.num_set_words = (int32_t)out->setWords.back().size();
+        return physLeaf(out, p, kScanPriority);
+      }
       if (ds.isSorted && ev.isRange && (int)ds.sortedDocIdRanges.size() == 2 * ds.cardinality && ev.endDictId > ev.startDictId) {
         // SortedIndexBasedFilterOperator (priority 0, FilterOperatorUtils.java:96-104): RANGE / EQ / NOT_EQ on a sorted column are the docId
         // range [start of startDictId, end of endDictId - 1] (SortedIndexBasedFilterOperator.java:60-85); nothing is scanned
@@ -377,6 +387,12 @@ std::string explainPhysical(const PhysNode& n, const LoweredQuery& lq, const Imm
     case PG_PRED_DOC_RANGE: return "SORTED(" + col + neg + " docs " + std::to_string(p.lo) + ".." + std::to_string(p.hi) + ")";
     case PG_PRED_IS_NULL: return "BITMAP(" + col + " IS" + neg + " NULL)";
     case PG_PRED_RAW_RANGE: return "SCAN(" + col + neg + " raw " + std::to_string(p.lo) + ".." + std::to_string(p.hi) + ")";
+    case PG_PRED_RAW_SET: {
+      std::string s = "SCAN(" + col + neg + " raw IN ";
+      for (int w = 0; w + 1 < p.num_set_words; w += 2)
+        s += (w ? "," : "") + std::to_string((int64_t)((uint64_t)p.set_words[w] | ((uint64_t)p.set_words[w + 1] << 32)));
+      return s + ")";
+    }
     case PG_PRED_DICT_RANGE:
       return std::string(p.eval == PG_EVAL_INVERTED ? "INVERTED(" : "SCAN(") + col + neg + " dictIds " + std::to_string(p.lo) + ".." + std::to_string(p.hi - 1) + ")";
     default: {

@@ -525,6 +525,15 @@ int PredicateEvaluator::getNumMatchingItems() const {
   return (int)matchingDictIds.size();
 }
 
+// a raw IN / NOT_IN list: distinct, ascending; more than the ABI's cap keeps the CPU plan; an empty one is constant
+static void finishRawSet(PredicateEvaluator* ev) {
+  std::sort(ev->rawSetValues.begin(), ev->rawSetValues.end());
+  ev->rawSetValues.erase(std::unique(ev->rawSetValues.begin(), ev->rawSetValues.end()), ev->rawSetValues.end());
+  if (ev->rawSetValues.size() > (size_t)PG_RAW_SET_MAX_VALUES)
+    throw UnsupportedOperationException("IN / NOT IN list of " + std::to_string(ev->rawSetValues.size()) + " distinct values on a raw column (max " + std::to_string(PG_RAW_SET_MAX_VALUES) + ") is not offloaded");
+  if (ev->rawSetValues.empty()) { if (ev->exclusive) ev->alwaysTrue = true; else ev->alwaysFalse = true; }
+}
+
 PredicateEvaluator getPredicateEvaluator(const Predicate& predicate, const DataSource& ds) {
   PredicateEvaluator ev;
   ev.predicateType = predicate.type;
@@ -563,7 +572,22 @@ PredicateEvaluator getPredicateEvaluator(const Predicate& predicate, const DataS
       lo = hi = toFp(predicate.values.at(0));
       ev.exclusive = predicate.type == Predicate::Type::NOT_EQ;
     } else {
-      throw UnsupportedOperationException("IN / NOT IN on a raw column is not offloaded");
+      // Float / DoubleRawValueBasedInPredicateEvaluator (InPredicateEvaluatorFactory.java:74-107, :294-380): the literals parsed with
+      // Float.parseFloat / Double.parseDouble into a fastutil hash set, applySV = set.contains(value); NOT_IN negates.  Members are compared
+      // by bit pattern on the device.  A zero or a NaN in the list keeps the CPU plan: whether the reference's set separates +0.0 / -0.0
+      // and unifies the NaNs is not settled here, and for every other value bit equality and == agree.
+      ev.rawRange = ev.rawFloating = false;
+      ev.rawSet = true;
+      ev.exclusive = predicate.type == Predicate::Type::NOT_IN;
+      for (const std::string& s : predicate.values) {
+        const double v = toFp(s);
+        if (v != v || v == 0.0) throw UnsupportedOperationException("IN / NOT IN list with a zero or a NaN on a raw FLOAT / DOUBLE column is not offloaded");
+        int64_t bits;
+        memcpy(&bits, &v, 8);
+        ev.rawSetValues.push_back(bits);
+      }
+      finishRawSet(&ev);
+      return ev;
     }
     memcpy(&ev.rawLower, &lo, 8);
     memcpy(&ev.rawUpper, &hi, 8);
@@ -595,7 +619,14 @@ PredicateEvaluator getPredicateEvaluator(const Predicate& predicate, const DataS
       ev.rawLower = ev.rawUpper = toInt(predicate.values.at(0));
       ev.exclusive = predicate.type == Predicate::Type::NOT_EQ;
     } else {
-      throw UnsupportedOperationException("IN / NOT IN on a raw column is not offloaded");
+      // Int / LongRawValueBasedInPredicateEvaluator (InPredicateEvaluatorFactory.java:74-107, :215-293): Integer.parseInt / Long.parseLong of
+      // every literal into a fastutil hash set, applySV = set.contains(value); NOT_IN negates
+      ev.rawRange = false;
+      ev.rawSet = true;
+      ev.exclusive = predicate.type == Predicate::Type::NOT_IN;
+      for (const std::string& s : predicate.values) ev.rawSetValues.push_back(toInt(s));
+      finishRawSet(&ev);
+      return ev;
     }
     if (ev.rawLower > ev.rawUpper) { if (ev.exclusive) ev.alwaysTrue = true; else ev.alwaysFalse = true; }
     return ev;

@@ -40,7 +40,8 @@ enum LeafKind : int32_t {
   kLeafRawRange64 = 6,  // raw LONG column: (uint64)(value - lo64) <= span64
   kLeafRawRangeF64 = 7, // raw DOUBLE column: the same compare on the order-preserving integer image of the value
   kLeafRawRangeF32 = 8, // raw FLOAT column (widened to double first)
-  kLeafDocRange = 9     // (uint32)(docId - lo) <= span: sorted-column predicates resolved to a docId range, no column read
+  kLeafDocRange = 9,    // (uint32)(docId - lo) <= span: sorted-column predicates resolved to a docId range, no column read
+  kLeafRawSet = 10      // raw column IN (...): the leaf of scan_raw_set_kernel ONLY (set_words = its LDS table, lo = hash multiplier, span = shift); every other kernel sees such a leaf as a kLeafBitmap
 };
 
 // How an aggregated column's VALUES are represented on the device.
@@ -231,6 +232,15 @@ struct ScanParams {
   uint8_t fsm_delta[64];                     // [state << 4 | input]: next state | entries << 4 (pg_filter_fsm.h's delta, four input bits wide)
   int32_t lean_kind;               // pg_execute_batch: the item's kind of shared launch, a value of pg_engine.hip's BatchKind (Private 0, Simple 1, Raw 2,
                                    // SimpleSet 13: scan_lean_batch_kernel runs those three at five waves per SIMD)
+};
+
+// raw_set_bitmap_kernel (pg_scan_raw_set.h): the match bitmap of one PG_PRED_RAW_SET leaf
+struct RawSetBitmapParams {
+  const uint8_t* fwd;                   // the raw column's first value byte (padded to whole 2048-doc tiles)
+  const uint32_t* table;                // RawSetTable.words on the device
+  uint32_t table_bytes, mult, shift;
+  int32_t num_docs;
+  uint32_t* out;                        // [tiles * 64] dword tile * 64 + lane: docs tile * 2048 + 32 lane .. + 31
 };
 
 // What a query's scan brings back to the host: the folded record, then a sequence number written after it.

@@ -29,6 +29,7 @@
 #include "pg_kernels.h"
 #include "pg_launch.h"
 #include "pg_rank_image.h"
+#include "pg_raw_set_table.h"
 
 namespace {
 
@@ -81,6 +82,7 @@ struct Engine {
   bool batch_blocks_per_cu_forced = false;
   int batch_blocks_per_cu = 4;    // PINOT_GPU_BATCH_BLOCKS_PER_CU: workgroups per CU a batch launch is cut into (all items together)
   bool scan_raw = true;      // PINOT_GPU_SCAN_RAW=0: raw INT scans stay in scan_private_kernel / scan_private_typed_kernel (four waves per SIMD)
+  bool scan_raw_set = true;  // PINOT_GPU_SCAN_RAW_SET=0: a lone IN / NOT IN leaf on a raw column takes the membership pre-pass + the general kernels, like every other shape (pg_scan_raw_set.h)
   bool scan_simple = true;   // PINOT_GPU_SCAN_SIMPLE=0: one-leaf / one-column queries stay in scan_private_kernel (half the waves per SIMD)
   bool scan_sparse = true;   // PINOT_GPU_SCAN_SPARSE=0: index-led aggregations scan their listed tiles in scan_private_kernel (one tile per wave and iteration)
   // (read at every pg_init like the rest: they were function-local statics, fixed at their first use in the process, until the kernel
@@ -968,6 +970,10 @@ struct Lowered {
   IndexAndParams and_params;
   double and_expected_docs = 0;                // the planner's estimate of the AND's cardinality (independent postings)
   FsmSide* side = nullptr;                     // in: the transducer pass wants the leaves' bitmaps (ScanParams.leaf_out)
+  // PG_PRED_RAW_SET leaves.  in: the query has the shape of scan_raw_set_kernel (raw_set_lean_shape), so its one leaf stays a kLeafRawSet; every
+  // other query gets the leaf's match bitmap from raw_set_bitmap_kernel ahead of its kernel.  The host tables live as long as the lowering.
+  bool raw_set_lean_hint = false;
+  std::vector<std::shared_ptr<RawSetTable>> raw_set_tables;
   uint32_t* sp_leaf_out[kMaxLeaves] = {};      // out: ScanParams.leaf_out, by LEAF node ordinal
 };
 
@@ -1237,6 +1243,41 @@ pg_status complete_index_and_bitmap(Lowered* lw, ExecCtx* ctx) {
   HIP_TRY(hipGetLastError());
   lw->and_bitmap = nullptr;
   return PG_OK;
+}
+
+// PG_PRED_RAW_SET (include/pinot_gpu.h): the argument checks and the declines, the same for pg_query_check and pg_execute.  *keys: the
+// distinct members as bit patterns of the column's own type (empty: the leaf matches nothing).
+static pg_status check_raw_set(const pg_segment* seg, const pg_predicate& pr, std::vector<uint64_t>* keys) {
+  if (pr.column < 0 || pr.column >= (int)seg->cols.size()) return fail(PG_ERR_INVALID_ARGUMENT, "predicate column %d out of range", pr.column);
+  const ColumnDev& col = seg->cols[(size_t)pr.column];
+  if (col.encoding == PG_FWD_FIXED_BIT_DICT) return fail(PG_ERR_INVALID_ARGUMENT, "raw predicate on dictionary column %s", col.name.c_str());
+  if (pr.eval != PG_EVAL_SCAN) return fail(PG_ERR_INVALID_ARGUMENT, "a raw value set on column %s is a scan leaf (eval %d)", col.name.c_str(), pr.eval);
+  if (pr.num_set_words < 0 || (pr.num_set_words & 1) || (pr.num_set_words > 0 && !pr.set_words))
+    return fail(PG_ERR_INVALID_ARGUMENT, "bad raw value set on column %s: %d words (two per value)", col.name.c_str(), pr.num_set_words);
+  const int rc = decode_raw_set_words(col.stored_type, pr.set_words, pr.num_set_words, keys);
+  if (rc == 1) return fail(PG_ERR_UNSUPPORTED, "IN list on raw column %s holds a zero or a NaN: how the reference's hash set treats them is not settled -- CPU plan", col.name.c_str());
+  if (rc == 2) return fail(PG_ERR_UNSUPPORTED, "IN list on raw column %s has %zu distinct values (max %d)", col.name.c_str(), keys->size(), kRawSetMaxValues);
+  return PG_OK;
+}
+static int raw_set_key_bytes(const ColumnDev& col) { return (col.stored_type == PG_TYPE_INT || col.stored_type == PG_TYPE_FLOAT) ? 4 : 8; }
+
+// The shape scan_raw_set_kernel takes (the test choose_scan_kernel applies for scan_raw_kernel, on the query itself: the leaf's device form
+// is decided while the filter is lowered): the whole filter is ONE raw-set leaf, no group-by, no bitmap wanted, and at most one aggregated
+// column, a raw INT one.
+static bool raw_set_lean_shape(const pg_segment* seg, const pg_query* q, int na, int ng, bool want_bitmap, bool want_result) {
+  if (!g_engine.scan_raw_set || ng != 0 || want_bitmap || !want_result || (g_engine.flags & PG_CFG_PROFILE_WAVES)) return false;
+  if (q->num_filter_nodes != 1 || q->filter[0].op != PG_FILTER_LEAF || q->filter[0].predicate < 0 || q->filter[0].predicate >= q->num_predicates) return false;
+  if (q->predicates[q->filter[0].predicate].kind != PG_PRED_RAW_SET) return false;
+  int only = -1;
+  for (int a = 0; a < na; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if (ag.function == PG_AGG_COUNT) continue;
+    if (ag.column < 0 || ag.column >= (int)seg->cols.size() || (only >= 0 && only != ag.column)) return false;
+    const ColumnDev& c = seg->cols[(size_t)ag.column];
+    if (c.encoding != PG_FWD_RAW_FIXED_BYTE || c.stored_type != PG_TYPE_INT || c.vkind != kValI32) return false;
+    only = ag.column;
+  }
+  return true;
 }
 
 pg_status lower_filter(pg_segment* seg, ExecCtx* ctx, const pg_query* q, Lowered* lw) {
@@ -1530,6 +1571,53 @@ pg_status lower_filter(pg_segment* seg, ExecCtx* ctx, const pg_query* q, Lowered
           L.kind = kLeafDictSet; L.col = s; L.set_words = ctx->d_sets[set_idx]; L.set_bytes = (int32_t)bytes;
           set_idx++;
           lw->num_scan_leaves++;
+        } else if (pr.kind == PG_PRED_RAW_SET) {
+          // Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator: set.contains(value).  A ScanBasedFilterOperator for the plan (child order,
+          // count hooks, statistics all go by the PREDICATE's kind); on the device the leaf is a hash table in LDS -- probed by scan_raw_set_kernel
+          // itself when the query has its shape, else by raw_set_bitmap_kernel ahead of the query's kernel, which then reads a kLeafBitmap.
+          std::vector<uint64_t> keys;
+          pg_status st = check_raw_set(seg, pr, &keys);
+          if (st != PG_OK) return st;
+          if (keys.empty()) { L.kind = kLeafMatchNone; }
+          else {
+            const int key_bytes = raw_set_key_bytes(col);
+            auto table = std::make_shared<RawSetTable>();
+            if (!build_raw_set_table(keys, key_bytes, table.get())) return fail(PG_ERR_UNSUPPORTED, "IN list on raw column %s: no table of %d bytes places its %zu values", col.name.c_str(), kRawSetMaxTableBytes, keys.size());
+            lw->raw_set_tables.push_back(table);
+            st = ensure_set(ctx, set_idx, table->bytes());
+            if (st != PG_OK) return st;
+            HIP_TRY(mark_pre_work(ctx));      // (the table is the context's: in pg_execute_batch such a query runs by itself)
+            HIP_TRY(hipMemcpyAsync(ctx->d_sets[set_idx], table->words.data(), table->bytes(), hipMemcpyHostToDevice, ctx->stream));
+            const uint32_t* d_table = ctx->d_sets[set_idx++];
+            if (lw->raw_set_lean_hint) {
+              int s = slot_for(lw, seg, pr.column);
+              if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+              sp.cols[s].in_filter = 1;
+              L.kind = kLeafRawSet; L.col = s; L.set_words = d_table; L.set_bytes = (int32_t)table->bytes(); L.span_hi = (uint32_t)table->bytes();
+              L.lo = (int32_t)table->mult; L.span = table->shift; L.lo_hi = key_bytes;
+              lw->num_scan_leaves++;
+            } else {
+              const size_t had = ctx->d_bitmaps.size();
+              st = ensure_bitmap(seg, ctx, bitmap_idx);
+              if (st != PG_OK) return st;
+              // (the context keeps the buffer for its later queries, like its other scratch: part of what pg_segment_device_bytes reports)
+              seg->device_bytes += (uint64_t)(ctx->d_bitmaps.size() - had) * (uint64_t)std::max(seg->num_tiles, 1) * kMaxTileSteps * 8;
+              unsigned long long* bm = ctx->d_bitmaps[bitmap_idx++];
+              RawSetBitmapParams bp;
+              memset(&bp, 0, sizeof(bp));
+              bp.fwd = col.d_fwd; bp.table = d_table; bp.table_bytes = (uint32_t)table->bytes(); bp.mult = table->mult; bp.shift = table->shift;
+              bp.num_docs = seg->num_docs; bp.out = reinterpret_cast<uint32_t*>(bm);
+              const int wpb = kBlockThreads / 64;
+              // a persistent grid: as many workgroups per CU as registers and the tables (of the 160 KiB of LDS) admit, a tile per wave and round
+              const int bpc = std::max(1, std::min(waves_raw_set_bitmap(key_bytes) / wpb, (int)((size_t)(156 * 1024) / (table->bytes() + 256))));
+              const long long tiles = ((long long)seg->num_docs + 2047) / 2048;
+              launch_raw_set_bitmap(key_bytes, (int)std::max<long long>(1, std::min<long long>((tiles + wpb - 1) / wpb, (long long)seg->num_cus * bpc)), ctx->stream, bp);
+              HIP_TRY(hipGetLastError());
+              L.kind = kLeafBitmap;
+              L.bitmap = bm;
+              sp.num_bitmap_leaves++;
+            }
+          }
         } else if (pr.kind == PG_PRED_RAW_RANGE && col.stored_type == PG_TYPE_LONG) {
           // LongRawValueBasedRangePredicateEvaluator (RangePredicateEvaluatorFactory.java:411-446): inclusive int64 bounds
           if (pr.lo > pr.hi) { L.kind = kLeafMatchNone; }
@@ -1829,6 +1917,8 @@ pg_status pg_init(const pg_config* config) {
   g_engine.scan_simple = !(ssm && ssm[0] == '0');
   const char* srw = getenv("PINOT_GPU_SCAN_RAW");
   g_engine.scan_raw = !(srw && srw[0] == '0');
+  const char* srs = getenv("PINOT_GPU_SCAN_RAW_SET");
+  g_engine.scan_raw_set = !(srs && srs[0] == '0');
   const char* bla = getenv("PINOT_GPU_BATCH_LAUNCH");
   g_engine.batch_launch = !(bla && bla[0] == '0');
   auto env_on = [](const char* name) { const char* v = getenv(name); return !(v && v[0] == '0'); };
@@ -2436,6 +2526,11 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
       max_depth = std::max(max_depth, depth);
       if (sn.op == PG_FILTER_LEAF && sn.src >= 0) {
         const pg_predicate& pr = q->predicates[q->filter[sn.src].predicate];
+        if (pr.kind == PG_PRED_RAW_SET) {
+          std::vector<uint64_t> keys;
+          const pg_status rst = check_raw_set(seg, pr, &keys);
+          if (rst != PG_OK) return rst;
+        }
         const bool stages = pr.kind == PG_PRED_RAW_RANGE || ((pr.kind == PG_PRED_DICT_RANGE || pr.kind == PG_PRED_DICT_SET) && pr.eval != PG_EVAL_INVERTED);
         if (stages) {
           if (pr.column < 0 || pr.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "predicate column %d out of range", pr.column);
@@ -2713,12 +2808,12 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
 // ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
 // preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
-enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, Raw, PrivateFsm, Private, PrivateTyped, Agg };
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Agg };
 // per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
 // leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
 static const struct { int id; bool writes_leaves; } kScanKernels[] = {
   {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
-  {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
+  {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
   {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_AGG, false}};
 static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
 // general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
@@ -2733,6 +2828,9 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
   const bool profile = (g_engine.flags & PG_CFG_PROFILE_WAVES) != 0;
   ScanChoice k;
   auto pick = [&k](ScanKernel kernel) { k.kernel = kernel; return k; };
+  // A kLeafRawSet leaf exists only in a query lowered for scan_raw_set_kernel (raw_set_lean_shape: the shape test below for scan_raw_kernel,
+  // applied to the query before its filter was lowered); no other kernel evaluates that kind.
+  if (sp.num_nodes == 1 && sp.nodes[0].op == PG_FILTER_LEAF && sp.nodes[0].kind == kLeafRawSet) { k.general = ScanKernel::Private; return pick(ScanKernel::RawSet); }
   // The lane-private kernel (no LDS, plain global loads) takes every query whose leaves and aggregations it implements:
   // scan / set / bitmap leaves and raw INT ranges; COUNT, and SUM through a value plane / MIN / MAX on dictionary columns.
   // (the per-wave phase counters of PG_CFG_PROFILE_WAVES exist in the LDS-staged kernel only)
@@ -2844,6 +2942,14 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Scan
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
     case ScanKernel::Simple: case ScanKernel::SimpleSet: lean_grid(seg, waves_scan_simple(), &g); break;
     case ScanKernel::Raw: lean_grid(seg, waves_scan_raw(), &g); break;
+    case ScanKernel::RawSet: {
+      // every workgroup keeps the leaf's table in dynamic LDS: as many workgroups per CU as registers AND the tables admit; small grids two, as lean_grid
+      g.lds = (size_t)sp.nodes[0].set_bytes;
+      int bpc = std::max(1, std::min(waves_scan_raw_set(sp.nodes[0].lo_hi) / wpb, (int)(kLdsBudget / (g.lds + 1024))));
+      if (tiles <= 2ll * seg->num_cus * bpc * wpb) bpc = std::min(bpc, 2);
+      g.blocks = grid_blocks(seg, tiles, wpb, bpc);
+      break;
+    }
     case ScanKernel::Private: g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, waves_scan_private(num_agg_cols) / wpb)); break;
     case ScanKernel::PrivateTyped: g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, waves_scan_private_typed(num_agg_cols) / wpb)); break;
     default: g.blocks = geo.blocks; g.threads = geo.threads; g.lds = geo.lds; break;      // Agg
@@ -2859,6 +2965,7 @@ static bool scan_batch_kind(const ScanChoice& k, int num_agg_cols, BatchKind* ki
     case ScanKernel::Narrow: case ScanKernel::NarrowSingle: *kind = k.kernel == ScanKernel::Narrow ? BatchKind::Narrow : BatchKind::NarrowSingle; return g_engine.batch_more;
     case ScanKernel::Simple: case ScanKernel::SimpleSet: *kind = !lean ? BatchKind::Private : (k.kernel == ScanKernel::Simple ? BatchKind::Simple : BatchKind::SimpleSet); return true;
     case ScanKernel::Raw: *kind = !lean && k.general == ScanKernel::Private ? BatchKind::Private : BatchKind::Raw; return true;
+    case ScanKernel::RawSet: return false;      // (no shared-launch form: the table belongs to the context)
     case ScanKernel::PrivateFsm: case ScanKernel::Private: *kind = BatchKind::Private; return true;
     case ScanKernel::PrivateTyped: *kind = num_agg_cols <= 1 ? BatchKind::Typed1 : (num_agg_cols == 2 ? BatchKind::Typed2 : BatchKind::TypedMax); return g_engine.batch_more;
     default: return false;      // Sparse, Agg
@@ -2873,6 +2980,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Sparse: launch_scan_sparse(one, g.blocks, stream, sp); break;
     case ScanKernel::Simple: case ScanKernel::SimpleSet: launch_scan_simple(g.blocks, lean_threads, stream, sp, k.kernel == ScanKernel::SimpleSet); break;
     case ScanKernel::Raw: launch_scan_raw(g.blocks, lean_threads, stream, sp); break;
+    case ScanKernel::RawSet: launch_scan_raw_set(sp.nodes[0].lo_hi, g.blocks, g.lds, stream, sp); break;
     case ScanKernel::PrivateFsm: launch_scan_private_fsm(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::Private: launch_scan_private(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
@@ -4097,6 +4205,7 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
     if (prepare_fsm_side(seg, ctx, *side->fsm, side) == PG_OK) lw.side = side;
     else (void)hipGetLastError();
   }
+  lw.raw_set_lean_hint = lw.side == nullptr && raw_set_lean_shape(seg, q, na, ng, want_bitmap, out != nullptr);
   st = lower_filter(seg, ctx, q, &lw); if (st != PG_OK) return st;
   exec_mark(2);
   if (out) memset(out, 0, sizeof(*out));
@@ -4128,7 +4237,7 @@ struct NullRewriter {
   const pg_segment* seg;
   bool has_nulls(int column) const { return column >= 0 && column < (int)seg->cols.size() && seg->cols[(size_t)column].d_null_bitmap != nullptr; }
   static bool column_leaf(const pg_predicate& p) {
-    return p.kind == PG_PRED_DICT_RANGE || p.kind == PG_PRED_DICT_SET || p.kind == PG_PRED_RAW_RANGE || p.kind == PG_PRED_DOC_RANGE;
+    return p.kind == PG_PRED_DICT_RANGE || p.kind == PG_PRED_DICT_SET || p.kind == PG_PRED_RAW_RANGE || p.kind == PG_PRED_RAW_SET || p.kind == PG_PRED_DOC_RANGE;
   }
   static FilterExpr leaf(const pg_predicate& p) { FilterExpr e; e.pred = p; return e; }
   static FilterExpr null_leaf(int column, bool is_not_null) {

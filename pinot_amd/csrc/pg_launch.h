@@ -52,6 +52,12 @@ int waves_scan_simple();
 // scan_raw_kernel: one raw INT range leaf (or no filter) + at most one aggregated raw INT column, five waves per SIMD, coalesced reads (pg_scan_raw.h)
 void launch_scan_raw(int blocks, int threads, hipStream_t stream, const ScanParams& p);
 int waves_scan_raw();
+// scan_raw_set_kernel<4 | 8>: one PG_PRED_RAW_SET leaf (its hash table in `table_bytes` of dynamic LDS) + at most one aggregated raw INT column (pg_scan_raw_set.h)
+void launch_scan_raw_set(int key_bytes, int blocks, size_t table_bytes, hipStream_t stream, const ScanParams& p);
+int waves_scan_raw_set(int key_bytes);
+// raw_set_bitmap_kernel<4 | 8>: the doc-order match bitmap of such a leaf, for every other query shape
+void launch_raw_set_bitmap(int key_bytes, int blocks, hipStream_t stream, const RawSetBitmapParams& p);
+int waves_raw_set_bitmap(int key_bytes);
 // scan_lean_batch_kernel: the shared launch of pg_execute_batch for items of those two shapes (ScanParams.lean_kind), five waves per SIMD
 void launch_scan_lean_batch(int kind, int total_blocks, hipStream_t stream, const ScanParams* items, const uint32_t* block_first, int num_items);      // kind: 1 simple, 2 raw (every item)
 int waves_scan_lean_batch(int kind);

@@ -172,6 +172,20 @@ def explain_filter(segment, sql):
         lib.ph_free(ptr)
 
 
+def raw_set_table_probe(key_bytes, members, probes):
+    """Builds the LDS membership table of a PG_PRED_RAW_SET leaf from `members` (distinct bit patterns, uint64) and looks `probes` up the
+    way the kernels do.  Returns (bucket count, bool array of hits); bucket count 0: no table could be built."""
+    import numpy as np
+    lib = _lib()
+    members = np.ascontiguousarray(members, dtype=np.uint64)
+    probes = np.ascontiguousarray(probes, dtype=np.uint64)
+    hits = np.zeros(len(probes), dtype=np.uint8)
+    lib.ph_raw_set_table_probe.restype = C.c_int32
+    lib.ph_raw_set_table_probe.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    buckets = lib.ph_raw_set_table_probe(int(key_bytes), members.ctypes.data, len(members), probes.ctypes.data, len(probes), hits.ctypes.data)
+    return int(buckets), hits.astype(bool)
+
+
 def execute_sql(segments, sql, max_execution_threads=0):
     """Returns {"segments": [per-segment block...], "combined": block}."""
     lib = _lib()

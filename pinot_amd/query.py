@@ -64,6 +64,21 @@ class Pred:
         """lo <= value <= hi on a raw FLOAT / DOUBLE column (Float / DoubleRawValueBasedRangePredicateEvaluator)."""
         return Pred(_abi.PG_PRED_RAW_RANGE, column, f64_bits(lo), f64_bits(hi), exclusive=exclusive)
 
+    @staticmethod
+    def raw_set(column, values, exclusive=False):
+        """value IN (values) on a raw INT / LONG column (Int / LongRawValueBasedInPredicateEvaluator); exclusive=True: NOT IN.
+        PG_PRED_RAW_SET: two 32-bit words per value, low word first, the value as int64; any order, duplicates allowed."""
+        p = Pred(_abi.PG_PRED_RAW_SET, column, exclusive=exclusive)
+        p.set_words = np.array([int(v) for v in values], dtype=np.int64).view(np.uint32).copy()
+        return p
+
+    @staticmethod
+    def raw_set_f64(column, values, exclusive=False):
+        """The same on a raw FLOAT / DOUBLE column: every value travels as the bit pattern of a double (FLOAT literals widened exactly)."""
+        p = Pred(_abi.PG_PRED_RAW_SET, column, exclusive=exclusive)
+        p.set_words = np.array([float(v) for v in values], dtype=np.float64).view(np.uint32).copy()
+        return p
+
 
 def f64_bits(x):
     """IEEE-754 bit pattern of a double as a signed 64-bit integer (how RAW_RANGE bounds of FLOAT / DOUBLE columns travel)."""

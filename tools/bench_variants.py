@@ -211,6 +211,52 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                        % tuple(c.bits for c in cols), n_c5, sum(B(c) for c in cols), g, seg5, ispec)
         del seg5, cols
 
+    # ---- C1 with IN lists on the raw column (PG_PRED_RAW_SET: scan_raw_set_kernel; raw_set_bitmap_kernel ahead of the general kernels) next to
+    # their range twins (scan_raw_kernel), at 10 M rows and at 400 M (C1L-*).  The lists are runs of consecutive values, so the range twin
+    # selects the same docs and is what the oracle checks (it has no raw-set kind).  *-in-cap: a list of PG_RAW_SET_MAX_VALUES values.
+    raw_in_ids = ("count-range-100", "sum-range", "count-in-list", "sum-in-list", "count-in-cap", "sum-in-cap", "long-count-in-list", "dict-sum-in-list-and-range", "dict-sum-range-and-range")
+    for prefix, rows_in in (("C1", 10_000_000), ("C1L", 400_000_000)):
+        ids_in = [prefix + "-" + x for x in raw_in_ids]      # (count-range-100: C1-count-range of the block below is BETWEEN 1 AND 10 on a segment of its own)
+        if not any(want(x) for x in ids_in):
+            continue
+        raw = S.Column.raw("raw_i32", S.synthetic_dict_ids(42, 0, rows_in, 1_000_000))
+        fcol = S.Column.synthetic_uniform("f", rows_in, np.arange(1000, dtype=np.int32), seed=43)
+        vcol = S.Column.synthetic_uniform("v", rows_in, (np.arange(100000, dtype=np.int64) * 7 + 3).astype(np.int32), seed=44)
+        long_rows = rows_in // 2                                                                              # (the 8-byte column: the same bytes as raw_i32 at half the rows, a segment of its own)
+        segi = S.SegmentData("c1in", rows_in, [raw, fcol, vcol])
+        cfg = "BASELINE.json configs[0], scan-forcing companion, IN list on the raw column"
+        size = "%d M rows, raw" % (rows_in // 1_000_000)
+        f100 = Q.leaf(Q.Pred.dict_range(1, 0, 100))
+        with engine.open(segi) as g:
+            for tag, hi in (("list", 100), ("cap", _abi.PG_RAW_SET_MAX_VALUES)):
+                members = list(range(1, hi + 1))
+                rng_leaf, set_leaf = Q.leaf(Q.Pred.raw_range(0, 1, hi)), Q.leaf(Q.Pred.raw_set(0, members))
+                for agg, aggs in (("count", [(Q.COUNT, -1)]), ("sum", [(Q.SUM, 0)])):
+                    if want("%s-%s-in-%s" % (prefix, agg, tag)):
+                        report("%s-%s-in-%s" % (prefix, agg, tag), cfg, "SELECT %s WHERE raw_i32 IN (1 .. %d: %d values) (%s)" % ("COUNT(*)" if agg == "count" else "SUM(raw_i32)", hi, hi, size),
+                               rows_in, 4 * rows_in, g, segi, Q.QuerySpec(aggs, filter=set_leaf), oracle_spec=Q.QuerySpec(aggs, filter=rng_leaf))
+                    twin = "%s-%s-range%s" % (prefix, agg, "-100" if agg == "count" else "")
+                    if tag == "list" and want(twin):
+                        report(twin, cfg.replace(", IN list on the raw column", ""), "SELECT %s WHERE raw_i32 BETWEEN 1 AND %d (%s)" % ("COUNT(*)" if agg == "count" else "SUM(raw_i32)", hi, size),
+                               rows_in, 4 * rows_in, g, segi, Q.QuerySpec(aggs, filter=rng_leaf))
+            # the other tier: the membership pre-pass writes the leaf's bitmap, scan_private_kernel reads it next to f and v
+            for vid in ("dict-sum-in-list-and-range", "dict-sum-range-and-range"):
+                if not want(prefix + "-" + vid):
+                    continue
+                leaf0 = Q.leaf(Q.Pred.raw_set(0, list(range(1, 1001)))) if vid.startswith("dict-sum-in") else Q.leaf(Q.Pred.raw_range(0, 1, 1000))
+                report(prefix + "-" + vid, cfg, "SELECT SUM(v) WHERE raw_i32 %s AND f < 100 (%s + two dictionary columns)" % ("IN (1 .. 1000)" if vid.startswith("dict-sum-in") else "BETWEEN 1 AND 1000", size),
+                       rows_in, 4 * rows_in + B(fcol) + B(vcol), g, segi, Q.QuerySpec([(Q.SUM, 2)], filter=Q.and_(leaf0, f100)),
+                       oracle_spec=Q.QuerySpec([(Q.SUM, 2)], filter=Q.and_(Q.leaf(Q.Pred.raw_range(0, 1, 1000)), f100)))
+        del segi, raw, fcol, vcol
+        if want(prefix + "-long-count-in-list"):
+            rawl = S.Column.raw_typed("raw_i64", S.synthetic_dict_ids(45, 0, long_rows, 1_000_000).astype(np.int64) * 4_294_967_311)
+            segl = S.SegmentData("c1in64", long_rows, [rawl])
+            with engine.open(segl) as g:
+                report(prefix + "-long-count-in-list", cfg, "SELECT COUNT(*) WHERE raw_i64 IN (100 values) (%d M rows, raw LONG: the bytes of %s)" % (long_rows // 1_000_000, size), long_rows, 8 * long_rows, g, segl,
+                       Q.QuerySpec([(Q.COUNT, -1)], filter=Q.leaf(Q.Pred.raw_set(0, [m * 4_294_967_311 for m in range(1, 101)]))),
+                       oracle_spec=Q.QuerySpec([(Q.COUNT, -1)], filter=Q.leaf(Q.Pred.raw_range(0, 4_294_967_311, 100 * 4_294_967_311))))
+            del segl, rawl
+
     # ---- C1: 10 M rows, raw int32 forward index (BASELINE.json configs[0] is the reference's CPU case; COUNT(*) itself is O(1)) ----
     if any(want(x) for x in ("C1-count-range", "C1-sum", "C1-count", "C1-group-by", "C1-group-by-raw-double")):
         n1 = 10_000_000

@@ -86,6 +86,20 @@ def table(Q, n):
     add("simple-set", {}, "scan_simple_kernel", Q.QuerySpec([(Q.SUM, V), (Q.COUNT, -1)], filter=L(Q.Pred.dict_set(F, list(range(0, 300, 3)), 1000))))      # scan_simple_set_kernel: the one leaf an IN list, its words in LDS
     add("raw", {}, "scan_raw_kernel", Q.QuerySpec([(Q.COUNT, -1)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))
     add("raw-sum", {}, "scan_raw_kernel", Q.QuerySpec([(Q.SUM, RI), (Q.MAX, RI)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))
+    # IN lists on raw columns (PG_PRED_RAW_SET).  The oracle has no such kind: each list is a run of consecutive column values, so the same docs and
+    # the same statistics (one scan leaf) come from the raw RANGE leaf the entry carries as `oracle_spec`.
+    rl_step = (1 << 20) + 3
+    def raw_in(aggs, column, members, lo, hi, exclusive=False, also=None, **kw):
+        both = lambda leaf: leaf if also is None else Q.and_(leaf, also)
+        spec = Q.QuerySpec(aggs, filter=both(L(Q.Pred.raw_set(column, members, exclusive=exclusive))), **kw)
+        spec.oracle_spec = Q.QuerySpec(aggs, filter=both(L(Q.Pred.raw_range(column, lo, hi, exclusive=exclusive))), **kw)
+        return spec
+    ri_list, rl_list = list(range(1000, 1900)), [m * rl_step for m in range(-300, 500)]
+    add("raw-set-4", {}, "scan_raw_set_kernel", raw_in([(Q.COUNT, -1), (Q.SUM, RI), (Q.MAX, RI)], RI, ri_list, 1000, 1899))                    # scan_raw_set_kernel<4>
+    add("raw-set-8", {}, "scan_raw_set_kernel", raw_in([(Q.SUM, RI), (Q.MIN, RI)], RL, rl_list, -300 * rl_step, 499 * rl_step, exclusive=True))   # scan_raw_set_kernel<8>
+    add("raw-set-bitmap-4", {}, None, raw_in([(Q.SUM, V), (Q.COUNT, -1)], RI, ri_list, 1000, 1899, also=f_lt(500)))                             # raw_set_bitmap_kernel<4> + the general kernels
+    add("raw-set-bitmap-8", {}, None, raw_in([(Q.SUM, RL), (Q.COUNT, -1)], RL, rl_list, -300 * rl_step, 499 * rl_step))                         # raw_set_bitmap_kernel<8>
+    add("raw-set-bitmap-group", {}, None, raw_in([(Q.SUM, V)], RI, ri_list, 1000, 1899, exclusive=True, group_by=[K]))
     add("private-1", {}, "scan_private_kernel", Q.QuerySpec([(Q.SUM, V), (Q.COUNT, -1)], filter=Q.and_(f_lt(300), L(Q.Pred.dict_range(K, 100, 900)))))
     add("private-4", {}, "scan_private_kernel", Q.QuerySpec([(Q.SUM, V), (Q.MAX, F), (Q.MIN, K)], filter=Q.or_(f_lt(100), L(Q.Pred.dict_set(K, [1, 5, 77, 500, 999], 1000)))))
     add("typed-1", {}, "scan_private_typed_kernel", Q.QuerySpec([(Q.SUM, RL), (Q.MIN, RL)], filter=Q.and_(f_lt(400), a_lt(150))))
@@ -267,7 +281,7 @@ def main():
 
     def want_of(key, spec):
         if key not in wants:
-            wants[key] = oracle.execute(seg, spec)
+            wants[key] = oracle.execute(seg, getattr(spec, "oracle_spec", spec))      # (raw IN lists: the equivalent range, see table())
         return wants[key]
 
     def check(eid, got, want, family):
