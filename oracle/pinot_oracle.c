@@ -611,6 +611,21 @@ static inline int pred_apply(const pg_predicate* p, int64_t v) {
   return p->exclusive ? !m : m;
 }
 
+/* PG_PRED_RAW_SET: Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator.applySV (InPredicateEvaluatorFactory.java:215-300):
+ * _matchingValues.contains(value) on the column's own type.  On the ABI (include/pinot_gpu.h) the list travels as 64-bit patterns, two
+ * set words per value, low word first: the long for INT / LONG columns (an int widened), the bits of the double for FLOAT / DOUBLE
+ * columns (a float widened exactly) -- so one 64-bit compare restates all four evaluators: a long outside int32 never equals a widened
+ * int, a double that is not a float never equals a widened float.  The fastutil float / double sets compare floatToIntBits /
+ * doubleToLongBits; for everything but the zeros and NaN that is ==, and lists holding those are not offloaded (they never get here
+ * from the tests that compare with the device).  Any order, duplicates allowed; an empty list matches nothing. */
+static inline int raw_set_contains(const pg_predicate* p, uint64_t bits) {
+  const int32_t nv = p->num_set_words / PG_RAW_SET_WORDS_PER_VALUE;
+  for (int32_t i = 0; i < nv; i++) {
+    if (((uint64_t)p->set_words[2 * i] | ((uint64_t)p->set_words[2 * i + 1] << 32)) == bits) return 1;
+  }
+  return 0;
+}
+
 /* SVScanDocIdIterator (core/operator/dociditerators/SVScanDocIdIterator.java:76-98, 213-243):
  * fills 256 sequential docIds, reads their dictIds / values, compacts the matches in place. */
 typedef struct po_scan_iter {
@@ -634,6 +649,20 @@ static int32_t scan_match_values(po_scan_iter* it, int32_t limit, int32_t* doc_i
   const pg_column_desc* d = it->col->desc;
   if (d->fwd_encoding == PG_FWD_FIXED_BIT_DICT) {
     po_fixedbit_read_dict_ids((const uint8_t*)d->fwd_data, d->bits_per_value, it->num_docs, doc_ids, limit, it->buffer);
+  } else if (it->pred->kind == PG_PRED_RAW_SET) {
+    int32_t matches = 0;
+    for (int32_t i = 0; i < limit; i++) {
+      uint64_t bits;
+      if (d->stored_type == PG_TYPE_INT) bits = (uint64_t)(int64_t)raw_get_int(&it->col->raw, doc_ids[i]);
+      else if (d->stored_type == PG_TYPE_LONG) bits = (uint64_t)raw_get_long(&it->col->raw, doc_ids[i]);
+      else {
+        const double v = d->stored_type == PG_TYPE_FLOAT ? (double)raw_get_float(&it->col->raw, doc_ids[i]) : raw_get_double(&it->col->raw, doc_ids[i]);
+        memcpy(&bits, &v, 8);
+      }
+      const int m = raw_set_contains(it->pred, bits);
+      if (it->pred->exclusive ? !m : m) doc_ids[matches++] = doc_ids[i];
+    }
+    return matches;
   } else if (d->stored_type == PG_TYPE_FLOAT || d->stored_type == PG_TYPE_DOUBLE) {
     /* Float / DoubleRawValueBasedRangePredicateEvaluator.applySV, RangePredicateEvaluatorFactory.java:448-560:
      * value >= inclusiveLowerBound && value <= inclusiveUpperBound on primitives (NaN never matches, -0.0 == 0.0) */
@@ -781,7 +810,7 @@ static int filter_to_bitmap_nulls(const po_column* cols, const pg_segment_desc* 
       const pg_predicate* p = &q->predicates[node->predicate];
       po_tnf e; e.t = (uint64_t*)malloc(bytes); e.n = (uint64_t*)calloc(1, bytes); e.f = (uint64_t*)malloc(bytes);
       rc = leaf_to_bitmap(cols, seg, p, e.t, entries_scanned);
-      const int column_leaf = p->kind == PG_PRED_DICT_RANGE || p->kind == PG_PRED_DICT_SET || p->kind == PG_PRED_RAW_RANGE || p->kind == PG_PRED_DOC_RANGE;
+      const int column_leaf = p->kind == PG_PRED_DICT_RANGE || p->kind == PG_PRED_DICT_SET || p->kind == PG_PRED_RAW_RANGE || p->kind == PG_PRED_RAW_SET || p->kind == PG_PRED_DOC_RANGE;
       uint64_t* nulls = (!rc && column_leaf) ? column_null_words(seg, p->column) : NULL;
       if (nulls) { for (int64_t i = 0; i < nw; i++) { e.n[i] = nulls[i]; e.t[i] &= ~nulls[i]; } free(nulls); }
       for (int64_t i = 0; i < nw; i++) e.f[i] = ~(e.t[i] | e.n[i]);
@@ -1533,8 +1562,8 @@ int po_execute(const pg_segment_desc* seg, const pg_query* q, pg_result* res) {
     it->kind = 0;
   } else if (!null_handling && q->num_filter_nodes == 1 && q->filter[0].op == PG_FILTER_LEAF &&
              q->predicates[q->filter[0].predicate].eval == PG_EVAL_SCAN &&
-             q->predicates[q->filter[0].predicate].kind >= PG_PRED_DICT_RANGE &&
-             q->predicates[q->filter[0].predicate].kind <= PG_PRED_RAW_RANGE) {
+             ((q->predicates[q->filter[0].predicate].kind >= PG_PRED_DICT_RANGE &&
+               q->predicates[q->filter[0].predicate].kind <= PG_PRED_RAW_RANGE) || q->predicates[q->filter[0].predicate].kind == PG_PRED_RAW_SET)) {
     it->kind = 1;
     const pg_predicate* p = &q->predicates[q->filter[0].predicate];
     scan_iter_init(&it->scan, &cols[p->column], p, num_docs);

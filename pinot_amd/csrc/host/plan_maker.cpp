@@ -149,19 +149,6 @@ IntermediateResult AggregationFunction::fromDevice(const pg_agg_value& v) const 
   return 0.0;
 }
 
-// java.lang.Math.min / max on doubles (MinAggregationFunction.merge / MaxAggregationFunction.merge): a NaN operand gives NaN, and
-// the zeros are ordered -0.0 < +0.0 -- std::fmin / fmax drop NaNs and leave the zeros' order unspecified.
-static double javaMin(double a, double b) {
-  if (a != a || b != b) return std::numeric_limits<double>::quiet_NaN();
-  if (a == 0.0 && b == 0.0) return std::signbit(a) ? a : b;
-  return a < b ? a : b;
-}
-static double javaMax(double a, double b) {
-  if (a != a || b != b) return std::numeric_limits<double>::quiet_NaN();
-  if (a == 0.0 && b == 0.0) return std::signbit(a) ? b : a;
-  return a > b ? a : b;
-}
-
 IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const IntermediateResult& b) const {
   // SumAggregationFunction.merge :223-233 and friends under null handling: a null side yields the other side
   if (isNullResult(a)) return b;
@@ -169,8 +156,11 @@ IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const
   switch (_type) {
     case AggregationFunctionType::COUNT: return std::get<int64_t>(a) + std::get<int64_t>(b);   // CountAggregationFunction.merge
     case AggregationFunctionType::SUM: return std::get<double>(a) + std::get<double>(b);        // SumAggregationFunction.merge :223-233
-    case AggregationFunctionType::MIN: return javaMin(std::get<double>(a), std::get<double>(b));      // Math.min: NaN wins, -0.0 < +0.0
-    case AggregationFunctionType::MAX: return javaMax(std::get<double>(a), std::get<double>(b));
+    // Min / MaxAggregationFunction.merge (:237-251): `if (r1 < r2) return r1; return r2;` / `if (r1 > r2) ...` -- a primitive compare, not
+    // Math.min / max (that is the aggregation-only fold): a NaN on the left is dropped, a NaN on the right is returned, and of two
+    // equal zeros the right one is.
+    case AggregationFunctionType::MIN: { const double x = std::get<double>(a), y = std::get<double>(b); return x < y ? x : y; }
+    case AggregationFunctionType::MAX: { const double x = std::get<double>(a), y = std::get<double>(b); return x > y ? x : y; }
     case AggregationFunctionType::AVG: {                                                       // AvgAggregationFunction.merge -> AvgPair.apply
       AvgPair r = std::get<AvgPair>(a);
       const AvgPair& o = std::get<AvgPair>(b);

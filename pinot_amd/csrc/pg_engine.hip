@@ -1820,6 +1820,19 @@ double agg_value_double(const ColumnDev& col, int32_t key, bool plane) {
   if (plane) return (double)(col.value_base + col.plane_base + col.plane_scale * (int64_t)key);   // 32-bit planes: base 0, scale 1, key = value
   return col.h_dict_f64[(size_t)key];
 }
+// Group-by MAX over a FLOAT / DOUBLE dictionary that holds NaN keeps the CPU plan: the group kernels fold dictIds, the NaN entry is the
+// largest one, and MaxAggregationFunction.aggregateGroupBySV's `value > holder` never takes a NaN -- the answer is the largest OTHER dictId
+// of the group, which a maximum of dictIds has lost once the NaN entry is in.  (Said by pg_query_check and pg_execute alike.)
+pg_status fail_group_max_over_nan_dictionary(const char* name) {
+  return fail(PG_ERR_UNSUPPORTED, "group-by MAX of dictionary column %s whose dictionary holds NaN (plan-time fallback)", name);
+}
+// The same for a group's MIN: the smallest dictId of a FLOAT / DOUBLE dictionary is its NaN entry (the last one) only when every value of
+// the group is NaN, and `value < holder` never let one in: the holder still has its default.  (MAX over such a dictionary is declined at
+// plan time, group_max_over_nan_dictionary: once the NaN dictId has won the fold the group's finite maximum is gone.)
+double group_dict_min_double(const ColumnDev& col, int32_t key, bool plane) {
+  const double v = agg_value_double(col, key, plane);
+  return v != v ? std::numeric_limits<double>::infinity() : v;
+}
 // An integer sum known exactly (128 bits): sum_i64 is it modulo 2^64, `sum` its correctly rounded double; exact while it
 // fits int64 (the reference's double accumulation agrees bit for bit below 2^53 and to rounding above).
 void set_integer_sum(pg_agg_value* v, __int128 t) {
@@ -1837,6 +1850,20 @@ double key64_to_double(const ColumnDev& col, long long key) {
   double v;
   memcpy(&v, &b, 8);
   return v;
+}
+
+// A FLOAT / DOUBLE dictionary is sorted in Double.compare order: a NaN, if the column holds one, is its LAST entry.  MIN / MAX of
+// dictionary columns run on dictIds, so both of the reference's NaN rules need this: Math.min / max of the aggregation-only path make
+// BOTH extremes NaN once a matching doc has that dictId; the group-by path's `value < holder` / `value > holder` never lets it in.
+bool dict_ends_in_nan(const ColumnDev& col) {
+  return col.encoding == PG_FWD_FIXED_BIT_DICT && (col.vkind == kValF64 || col.vkind == kValF32) && !col.h_dict_f64.empty() && std::isnan(col.h_dict_f64.back());
+}
+// MIN / MAX accumulator of a group over a raw FLOAT / DOUBLE column: the order key of the extreme among the group's non-NaN values, or the
+// slot's identity when every value was NaN -- the reference's holder then still has its default (Min / MaxAggregationFunction.java:180-186).
+double group_key64_to_double(const ColumnDev& col, long long key, bool is_min) {
+  if (col.vkind != kValI64 && key == (is_min ? 0x7FFFFFFFFFFFFFFFll : (long long)0x8000000000000000ull))
+    return is_min ? std::numeric_limits<double>::infinity() : -std::numeric_limits<double>::infinity();
+  return key64_to_double(col, key);
 }
 
 inline void cpu_relax() {
@@ -2438,6 +2465,10 @@ void pg_result_free(pg_result* r) {
 }
 
 constexpr int32_t kQueryHashHolder = 1 << 30;      // internal pg_query.flags bit (execute_null_handling -> execute_impl)
+// internal pg_query.flags bit (execute_null_handling -> execute_impl): COUNT(column) keeps its input expression under enableNullHandling whether
+// or not the column has null docs (CountAggregationFunction.getInputExpressions :69-71), so the column is projected and counts in
+// numEntriesScannedPostFilter; without the option COUNT(column) is COUNT(*) and reads nothing
+constexpr int32_t kQueryCountReadsColumn = 1 << 29;
 
 // ---- plan-time eligibility (pg_query_check) ----
 // Every reason pg_execute can answer PG_ERR_UNSUPPORTED for, decided from the query and the segment's metadata alone: no context, no
@@ -2596,6 +2627,7 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
       const ColumnDev& col = seg->cols[(size_t)ag.column];
       const int kind = (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) ? 0 : (ag.function == PG_AGG_MIN ? 1 : 2);
       if (std::find(group_aggs.begin(), group_aggs.end(), std::make_pair(ag.column, kind)) == group_aggs.end()) group_aggs.emplace_back(ag.column, kind);
+      if (kind == 2 && dict_ends_in_nan(col)) return fail_group_max_over_nan_dictionary(col.name.c_str());
       if (col.encoding == PG_FWD_RAW_FIXED_BYTE && col.vkind != kValI32) {
         // group_typed_direct_kernel takes it, with the lane-private filter: a range leaf on a raw 8-byte column is not in that filter
         for (int n = 0; n < q->num_filter_nodes; ++n) {
@@ -3114,7 +3146,10 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   std::vector<int> agg_slot_of((size_t)std::max(na, 1), -1);
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    if (ag.function == PG_AGG_COUNT) continue;
+    if (ag.function == PG_AGG_COUNT) {
+      if ((q->flags & kQueryCountReadsColumn) && ag.column >= 0 && ag.column < num_cols_total) r.add_projected(ag.column);
+      continue;
+    }
     if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
     r.add_projected(ag.column);
@@ -3263,6 +3298,11 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
         } else {
           if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, fp.kmin[ac], plane);
           if (ag.function == PG_AGG_MAX) v.max = agg_value_double(col, fp.kmax[ac], plane);
+          // Math.min / Math.max propagate NaN: the largest dictId seen (every scan kernel folds it next to the smallest, whichever
+          // the query asks for) tells a MIN that a doc with the NaN entry matched
+          if (dict_ends_in_nan(col) && fp.kmax[ac] == col.cardinality - 1) {
+            if (ag.function == PG_AGG_MIN) v.min = col.h_dict_f64.back();
+          }
         }
       }
     }
@@ -3453,7 +3493,7 @@ static pg_status defer_group_item(QueryRun& r, const GroupParams& gp, int pblock
         const ColumnDev& col = seg->cols[(size_t)ag.column];
         const bool plane = plane_cols[(size_t)ag.column] != 0;
         if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) set_integer_sum(&v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
-        else if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, (int32_t)acc, plane);
+        else if (ag.function == PG_AGG_MIN) v.min = group_dict_min_double(col, (int32_t)acc, plane);
         else v.max = agg_value_double(col, (int32_t)acc, plane);
       }
       ++k;
@@ -3793,10 +3833,14 @@ static pg_status run_group_by(QueryRun& r) {
   std::vector<int> dev_agg_of((size_t)std::max(na, 1), -1);
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    if (ag.function == PG_AGG_COUNT) continue;
+    if (ag.function == PG_AGG_COUNT) {
+      if ((q->flags & kQueryCountReadsColumn) && ag.column >= 0 && ag.column < num_cols_total) r.add_projected(ag.column);
+      continue;
+    }
     if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
     r.add_projected(ag.column);
+    if (ag.function == PG_AGG_MAX && dict_ends_in_nan(seg->cols[(size_t)ag.column])) return fail_group_max_over_nan_dictionary(seg->cols[(size_t)ag.column].name.c_str());
     int s = slot_for(&lw, seg, ag.column, lw.plane_cols[(size_t)ag.column] != 0);
     if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
     pl.cols[s].in_agg = 1;
@@ -4072,9 +4116,9 @@ static pg_status run_group_by(QueryRun& r) {
         }
       }
       else if (col.encoding == PG_FWD_RAW_FIXED_BYTE && col.vkind != kValI32) {      // raw LONG value, or the order key of a raw FLOAT / DOUBLE value
-        if (ag.function == PG_AGG_MIN) v.min = key64_to_double(col, acc); else v.max = key64_to_double(col, acc);
+        if (ag.function == PG_AGG_MIN) v.min = group_key64_to_double(col, acc, true); else v.max = group_key64_to_double(col, acc, false);
       }
-      else if (ag.function == PG_AGG_MIN) v.min = agg_value_double(col, (int32_t)acc, plane);
+      else if (ag.function == PG_AGG_MIN) v.min = group_dict_min_double(col, (int32_t)acc, plane);
       else v.max = agg_value_double(col, (int32_t)acc, plane);
     }
   }
@@ -4294,7 +4338,7 @@ struct FlatQuery {
   }
   void finish(const pg_query& base) {
     q = base;
-    q.flags = base.flags & ~PG_QUERY_NULL_HANDLING;
+    q.flags = (base.flags & ~PG_QUERY_NULL_HANDLING) | ((base.flags & PG_QUERY_NULL_HANDLING) ? kQueryCountReadsColumn : 0);
     q.filter = nodes.empty() ? nullptr : nodes.data(); q.num_filter_nodes = (int32_t)nodes.size();
     q.predicates = preds.empty() ? nullptr : preds.data(); q.num_predicates = (int32_t)preds.size();
   }
@@ -4414,7 +4458,7 @@ static pg_status execute_null_handling(pg_segment* seg, const pg_query* q, pg_re
     for (int g = 0; g < ng; ++g) if (std::find(projected.begin(), projected.end(), q->group_by_columns[g]) == projected.end()) projected.push_back(q->group_by_columns[g]);
     for (int a = 0; a < na; ++a) {
       const pg_aggregation& ag = q->aggregations[a];
-      const bool reads = ag.function != PG_AGG_COUNT || rw.has_nulls(ag.column);
+      const bool reads = ag.function != PG_AGG_COUNT || ag.column >= 0;      // COUNT(col) keeps its input expression under null handling, nulls or not
       if (reads && ag.column >= 0 && std::find(projected.begin(), projected.end(), ag.column) == projected.end()) projected.push_back(ag.column);
     }
     out->stats.num_entries_scanned_post_filter = out->stats.num_docs_scanned * (int64_t)projected.size();
@@ -4471,7 +4515,7 @@ static pg_status execute_null_handling(pg_segment* seg, const pg_query* q, pg_re
   std::vector<int> projected;
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    const bool reads = ag.function != PG_AGG_COUNT || rw.has_nulls(ag.column);   // COUNT(col) keeps its input expression under null handling
+    const bool reads = ag.function != PG_AGG_COUNT || ag.column >= 0;   // COUNT(col) keeps its input expression under null handling, nulls or not
     if (reads && ag.column >= 0 && std::find(projected.begin(), projected.end(), ag.column) == projected.end()) projected.push_back(ag.column);
   }
   out->stats.num_entries_scanned_post_filter = out->stats.num_docs_scanned * (int64_t)projected.size();

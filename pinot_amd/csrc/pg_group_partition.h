@@ -484,7 +484,7 @@ static __global__ __launch_bounds__(256) void group_repartition_scatter_kernel(c
 // of the general case; the reference runs it at ~25 M rows/s per core).  Every other input kind rides along (dictIds, plane fields,
 // gathered dictionary values of either width), so the query runs in one pass.
 // Table slots: SUM of LONG / INT: int64 add; SUM of FLOAT / DOUBLE: the slot holds a double (global_atomic_add_f64); MIN / MAX of raw LONG:
-// the value; of raw FLOAT / DOUBLE: its order-preserving 64-bit key (f64_order_key); of dictionary columns: the dictId.
+// the value; of raw FLOAT / DOUBLE: its order-preserving 64-bit key (f64_order_key), NaN values left out; of dictionary columns: the dictId.
 // ------------------------------------------------------------------------------------------------
 // kHash (round 6b): the keys are beyond an int -- the slots come from the hashed table (hashed_group_slots, pg_kernels.h: the Long / ArrayMap
 // holders of DictionaryBasedGroupKeyGenerator.java:628-806), everything behind the slot number is the same.
@@ -536,6 +536,10 @@ static __global__ __launch_bounds__(256) void group_typed_direct_kernel(const Gr
           else __hip_atomic_fetch_add(slot, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
           const bool float_key = ga.is_raw && (ga.vkind == kValF64 || ga.vkind == kValF32);
+          // Min / MaxAggregationFunction.aggregateGroupBySV (:180-186): `if (value < holder)` / `if (value > holder)` -- a NaN never
+          // enters a group's holder (unlike Math.min / max of the aggregation-only path).  It stays out of the fold: an all-NaN
+          // group keeps the slot's identity, which the host reports as +Infinity / -Infinity.
+          if (float_key && __longlong_as_double(bits) != __longlong_as_double(bits)) continue;
           const long long key = float_key ? f64_order_key(__longlong_as_double(bits)) : bits;
           if (ga.kind == kGroupMin) __hip_atomic_fetch_min(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           else __hip_atomic_fetch_max(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -2,9 +2,11 @@
 reference's Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator, InPredicateEvaluatorFactory.java:74-107, under a
 ScanBasedFilterOperator).
 
-The oracle has no raw-set kind.  A scan leaf's result does not depend on how its column is encoded, so every case has a TWIN segment in
-which the filtered columns are dictionary-encoded and the predicate is a scan PG_PRED_DICT_SET over the dictIds of the listed values;
-everything else is identical.  The device runs the raw segment with PG_PRED_RAW_SET, the oracle the twin."""
+A scan leaf's result does not depend on how its column is encoded, so every case has a TWIN segment in which the filtered columns are
+dictionary-encoded and the predicate is a scan PG_PRED_DICT_SET over the dictIds of the listed values; everything else is identical.
+The device runs the raw segment with PG_PRED_RAW_SET, the oracle the twin.  (The oracle has a PG_PRED_RAW_SET leaf of its own as well --
+the typed fuzz, tests/fuzz_cases.py, needs the reference side to answer every generated query -- and tests/test_oracle_raw_in.py pins
+it to numpy and to this twin yardstick.)"""
 import numpy as np
 
 from pinot_amd import _abi

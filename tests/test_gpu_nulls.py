@@ -183,3 +183,26 @@ def test_sql_null_handling_through_the_host_mirror(tmp_path):
             assert b["intermediate"] == [int((~(values["c2"] < 5)).sum()), float(-2 ** 31)]
         finally:
             seg.destroy()
+
+
+def test_count_of_a_column_is_projected_under_null_handling_whether_or_not_it_has_nulls(engine):
+    """CountAggregationFunction.getInputExpressions (:69-71): with enableNullHandling COUNT(column) keeps its input expression, so the column is
+    projected and counts in numEntriesScannedPostFilter -- also when it has no null docs (found by tests/test_gpu_fuzz_typed.py: the device
+    counted it only for columns with a null vector).  Without the option COUNT(column) is COUNT(*): nothing is projected."""
+    rng = np.random.default_rng(7)
+    n = 4097
+    nulls = rng.random(n) < 0.3
+    plain = S.Column.dict_encoded_typed("plain", rng.integers(-2 ** 40, 2 ** 40, n).astype(np.int64))
+    nullable = S.Column.dict_encoded("nullable", rng.integers(0, 50, n).astype(np.int32)).with_nulls(nulls)
+    f = S.Column.dict_encoded("f", rng.integers(0, 20, n).astype(np.int32))
+    k = S.Column.dict_encoded("k", rng.integers(0, 5, n).astype(np.int32))
+    seg = S.SegmentData("countcol", n, [plain, nullable, f, k])
+    flt = Q.leaf(Q.Pred.dict_range(2, 3, 15))
+    with engine.open(seg) as g:
+        for aggs, columns in (([(Q.COUNT, -1), (Q.COUNT, 0)], 1), ([(Q.COUNT, 0)], 1), ([(Q.COUNT, 0), (Q.COUNT, 1)], 2), ([(Q.COUNT, 0), (Q.SUM, 0), (Q.COUNT, 1)], 2),
+                              ([(Q.COUNT, -1)], 0)):
+            for group_by in ([], [3]):
+                spec = Q.QuerySpec(aggs, filter=flt, group_by=group_by, null_handling=True)
+                got = g.execute(spec)
+                H.assert_results_equal(got, oracle.execute(seg, spec))
+                assert got.stats[2] == got.stats[0] * (columns + len(group_by)) and got.stats[0] > 0, (aggs, group_by, got.stats)

@@ -78,8 +78,11 @@ def test_raw_typed_range_filters_and_fallbacks(engine):
     dv[::101] = np.nan
     dv[1::101] = -0.0
     dv[2::101] = 0.0
+    dv[lv % 7 == 6] = np.nan              # a group (k = 6) whose DOUBLE values are all NaN
+    fv = (lv % 1000).astype(np.float32)
+    fv[3::53] = np.nan
     seg = S.SegmentData("rawlong", n, [S.Column.raw_typed("l", lv), S.Column.raw_typed("d", dv),
-                                        S.Column.raw_typed("f", (lv % 1000).astype(np.float32)), S.Column.dict_encoded("k", (lv % 7).astype(np.int32))])
+                                        S.Column.raw_typed("f", fv), S.Column.dict_encoded("k", (lv % 7).astype(np.int32))])
     with engine.open(seg) as g:
         for lo, hi in ((-2 ** 44, 2 ** 43), (0, 0), (int(lv.min()), int(lv.max())), (5, 4), (-2 ** 63, 2 ** 63 - 1)):
             spec = Q.QuerySpec([(Q.COUNT, -1), (Q.SUM, 0), (Q.SUM, 1), (Q.MAX, 2), (Q.MIN, 1)], filter=Q.leaf(Q.Pred.raw_range(0, lo, hi)))
@@ -91,15 +94,26 @@ def test_raw_typed_range_filters_and_fallbacks(engine):
                     spec = Q.QuerySpec([(Q.COUNT, -1), (Q.SUM, 0), (Q.MIN, col)], filter=Q.leaf(Q.Pred.raw_range_f64(col, dlo, dhi, exclusive=excl)))
                     H.assert_results_equal(g.execute(spec), oracle.execute(seg, spec))
         # group-by aggregation of raw LONG / FLOAT / DOUBLE columns (group_typed_direct_kernel: straight into the HBM table), alone, next to
-        # dictionary inputs, under dictionary and index filters; NaN-free columns for MIN / MAX (Math.min / max propagate NaN per group)
+        # dictionary inputs, under dictionary and index filters.  The FLOAT / DOUBLE columns hold NaN: a group's MIN / MAX is
+        # Min / MaxAggregationFunction.aggregateGroupBySV's `value < holder` / `value > holder` (:180-186), which no NaN passes -- every group
+        # reports the extremes of its other values, and the group whose values are all NaN keeps the holders' +Infinity / -Infinity
+        # (not Math.min / max, which propagate NaN: that is the aggregation-only rule)
         flt = Q.leaf(Q.Pred.dict_range(3, 1, 5))
         for aggs in ([(Q.SUM, 0)], [(Q.SUM, 0), (Q.MIN, 0), (Q.MAX, 0), (Q.AVG, 0), (Q.COUNT, -1)], [(Q.SUM, 1), (Q.SUM, 2), (Q.MIN, 2), (Q.MAX, 2)],
-                     [(Q.SUM, 0), (Q.MAX, 3), (Q.SUM, 3), (Q.AVG, 2)]):
+                     [(Q.SUM, 0), (Q.MAX, 3), (Q.SUM, 3), (Q.AVG, 2)], [(Q.MIN, 1), (Q.MAX, 1), (Q.COUNT, -1)]):
             for f in (None, flt):
                 spec = Q.QuerySpec(aggs, filter=f, group_by=[3])
                 got = g.execute(spec)
                 assert got.dominant_kernel == "scan_group_kernel", (aggs, f is not None)
                 H.assert_results_equal(got, oracle.execute(seg, spec))
+        got = g.execute(Q.QuerySpec([(Q.MIN, 1), (Q.MAX, 1), (Q.MIN, 2), (Q.MAX, 2)], group_by=[3]))
+        k = lv % 7
+        for key in range(7):
+            mn, mx, fmn, fmx = got.groups[key]
+            finite = dv[(k == key) & ~np.isnan(dv)]
+            assert (mn.min, mx.max) == ((finite.min(), finite.max()) if key != 6 else (np.inf, -np.inf)), key
+            ff = fv[(k == key) & ~np.isnan(fv)]
+            assert np.isnan(fv[k == key]).any() and (fmn.min, fmx.max) == (float(ff.min()), float(ff.max())), key
         # still a plan-time fallback: the same under a range predicate on a raw 8-byte column (that leaf lives in the LDS-staged filter only)
         with pytest.raises(_abi.PinotGpuError) as ei:
             g.execute(Q.QuerySpec([(Q.SUM, 1)], filter=Q.leaf(Q.Pred.raw_range(0, -5, 5)), group_by=[3]))
@@ -132,11 +146,28 @@ def test_long_sum_that_overflows_int64(engine):
 
 
 def test_nan_and_signed_zero_min_max(engine):
-    """java.lang.Math.min / max: NaN wins, -0.0 < +0.0."""
+    """java.lang.Math.min / max: NaN wins, -0.0 < +0.0 -- on raw columns and on their dictionary-encoded twins, whose MIN / MAX run on
+    dictIds (NaN is the last entry of a Double.compare-ordered dictionary: the smallest dictId alone does not see it)."""
     v = np.array([1.5, -0.0, 0.0, 7.25, -3.0], dtype=np.float64)
     w = np.array([1.5, np.nan, 0.0, 7.25, -3.0], dtype=np.float64)
-    seg = S.SegmentData("nan", 5, [S.Column.raw_typed("v", v), S.Column.raw_typed("w", w), S.Column.dict_encoded("k", np.arange(5, dtype=np.int32))])
+    seg = S.SegmentData("nan", 5, [S.Column.raw_typed("v", v), S.Column.raw_typed("w", w), S.Column.dict_encoded("k", np.arange(5, dtype=np.int32)),
+                                   S.Column.dict_encoded_typed("dw", w), S.Column.dict_encoded_typed("fw", w.astype(np.float32))])
     with engine.open(seg) as g:
+        # the dictionary twins behind a filter that keeps every doc / drops the NaN doc (no filter at all is answered from the dictionary's
+        # first and last entry, NonScanBasedAggregationOperator: MIN -3.0, MAX NaN on both sides)
+        for col in (3, 4):
+            for aggs in ([(Q.MIN, col), (Q.MAX, col)], [(Q.MIN, col)], [(Q.MAX, col)], [(Q.COUNT, -1), (Q.SUM, col), (Q.MIN, col)]):
+                for lo, hi, nan in ((0, 5, True), (1, 5, True), (2, 5, False), (0, 1, False)):
+                    spec = Q.QuerySpec(aggs, filter=Q.leaf(Q.Pred.dict_range(2, lo, hi)))
+                    r = g.execute(spec)
+                    H.assert_results_equal(r, oracle.execute(seg, spec))
+                    for (f, _), a in zip(aggs, r.aggregations):
+                        if f in (Q.MIN, Q.MAX):
+                            assert np.isnan(a.min if f == Q.MIN else a.max) == nan, (col, aggs, lo, hi)
+            spec = Q.QuerySpec([(Q.MIN, col), (Q.MAX, col)])
+            r = g.execute(spec)
+            H.assert_results_equal(r, oracle.execute(seg, spec))
+            assert r.aggregations[0].min == -3.0 and np.isnan(r.aggregations[1].max)
         r = g.execute(Q.QuerySpec([(Q.MIN, 0), (Q.MAX, 0), (Q.MIN, 1), (Q.MAX, 1)]))
         o = oracle.execute(seg, Q.QuerySpec([(Q.MIN, 0), (Q.MAX, 0), (Q.MIN, 1), (Q.MAX, 1)]))
         H.assert_results_equal(r, o)

@@ -304,3 +304,16 @@ def test_group_by_trim_cases_of_the_reference_test(limit, min_segment, min_serve
     want = [(10.0 + 11 * i, 11.0 + 11 * i) for i in range(9999, 9999 - kept, -1)]
     assert got == want
     assert out["resultTable"]["columns"] == ["metric_0", "max(metric_1)"] and out["resultTable"]["rows"] == [list(r) for r in want[:limit]]
+
+
+def test_min_max_merge_is_the_references_compare_not_math_min():
+    """Min / MaxAggregationFunction.merge (MinAggregationFunction.java:237-251, MaxAggregationFunction.java:237-251): `if (r1 < r2) return r1;
+    return r2;` -- a NaN already in the table is dropped by the next record, a NaN that arrives second is kept (Math.min / max, the
+    aggregation-only fold, would keep it both times)."""
+    nan = math.nan
+    rec = lambda key, v: ((key,), [cell(mn=v), cell(mx=v)])
+    ups = [rec("a", 1.0), rec("a", nan), rec("b", nan), rec("b", 1.0), rec("c", 2.0), rec("c", 1.0), rec("c", 3.0), rec("d", nan), rec("d", 5.0), rec("d", nan)]
+    out = host.group_by_combine("SELECT MIN(m1), MAX(m2) FROM testTable GROUP BY d1 LIMIT 10", [ups], [S])
+    got = {g["key"][0]: [float(x) for x in g["intermediate"]] for g in out["combined"]["groups"]}      # (the JSON spells a NaN "NaN")
+    assert math.isnan(got["a"][0]) and math.isnan(got["a"][1]) and math.isnan(got["d"][0]) and math.isnan(got["d"][1])
+    assert got["b"] == [1.0, 1.0] and got["c"] == [1.0, 3.0]
