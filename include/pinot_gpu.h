@@ -48,9 +48,10 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 4   /* 2: pg_result.filter_entries_exact, pg_query_check, pg_config.plane_budget_bytes;
+#define PG_ABI_VERSION 5   /* 2: pg_result.filter_entries_exact, pg_query_check, pg_config.plane_budget_bytes;
                             * 3: pg_execute_batch, pg_result.group_key_kind / group_ids64 / group_key_dict_ids (Long / ArrayMap holders);
-                            * 4: PG_PRED_RAW_SET (IN / NOT IN on raw INT / LONG / FLOAT / DOUBLE columns); no struct layout changed */
+                            * 4: PG_PRED_RAW_SET (IN / NOT IN on raw INT / LONG / FLOAT / DOUBLE columns); no struct layout changed;
+                            * 5: pg_doc_set_create / release / cardinality, PG_PRED_DOC_SET (upsert / dedup valid-doc sets); no struct layout changed */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -135,7 +136,7 @@ typedef enum pg_predicate_kind {
                                 * runs with PG_QUERY_NULL_HANDLING, where it names the sorted column (its null docs are excluded) or is -1. */
   PG_PRED_IS_NULL = 6,         /* FilterPlanNode.java:294-307: BitmapBasedFilterOperator over the column's null bitmap; `exclusive` = IS NOT NULL.
                                 * A column without a null vector matches nothing (IS NULL) / everything (IS NOT NULL).  No entries are scanned. */
-  PG_PRED_RAW_SET = 7          /* Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator.applySV (InPredicateEvaluatorFactory.java:74-107,
+  PG_PRED_RAW_SET = 7,         /* Int / Long / Float / DoubleRawValueBasedInPredicateEvaluator.applySV (InPredicateEvaluatorFactory.java:74-107,
                                 * :215-380): value is a member of the literal set; `exclusive` = NOT_IN (NotInPredicateEvaluatorFactory).  A raw
                                 * (no-dictionary) INT / LONG / FLOAT / DOUBLE column, `eval` = PG_EVAL_SCAN (a ScanBasedFilterOperator).  The
                                 * values travel in set_words, TWO 32-bit words per value, low word first: INT / LONG columns the value as int64,
@@ -150,6 +151,14 @@ typedef enum pg_predicate_kind {
                                 *  - more than PG_RAW_SET_MAX_VALUES distinct values: PG_ERR_UNSUPPORTED;
                                 *  - an odd num_set_words, a null set_words with a non-zero count, PG_EVAL_INVERTED or a dictionary column:
                                 *    PG_ERR_INVALID_ARGUMENT. */
+  PG_PRED_DOC_SET = 8          /* FilterPlanNode.java:88-106: BitmapBasedFilterOperator(queryableDocIdsSnapshot, false, numDocs) -- the valid docs of an
+                                * upsert / dedup segment.  `lo` = the id pg_doc_set_create returned for THIS segment; `exclusive` = the flipped set
+                                * over [0, numDocs); `column` and `eval` are ignored.  A leaf like any other: anywhere in the tree, under GROUP BY
+                                * and PG_QUERY_NULL_HANDLING (no NULL set of its own, like PG_PRED_IS_NULL).  No entries are scanned; bitmap
+                                * priority (FilterOperatorUtils.java:222-224).  COUNT(*) whose whole filter is this leaf is its cardinality
+                                * (FastFilteredCountOperator; nothing is launched); MIN / MAX of a dictionary column under it are scanned, never
+                                * answered from the dictionary, even when the set holds every doc.  An unknown or released id:
+                                * PG_ERR_INVALID_ARGUMENT, from pg_query_check too. */
 } pg_predicate_kind;
 
 #define PG_RAW_SET_MAX_VALUES 1024   /* PG_PRED_RAW_SET: distinct values after de-duplication */
@@ -165,7 +174,7 @@ typedef struct pg_predicate {
   int32_t column;              /* index into pg_segment_desc.columns */
   int32_t eval;                /* pg_leaf_eval */
   int32_t exclusive;           /* 1 = NOT_EQ / NOT_IN: matches when the inner predicate does not */
-  int64_t lo;                  /* DICT_RANGE: startDictId ; RAW_RANGE: inclusive lower bound */
+  int64_t lo;                  /* DICT_RANGE: startDictId ; RAW_RANGE: inclusive lower bound ; DOC_SET: the doc set's id */
   int64_t hi;                  /* DICT_RANGE: endDictId (exclusive) ; RAW_RANGE: inclusive upper bound.
                                 * RAW_RANGE on a raw FLOAT / DOUBLE column: lo / hi carry the IEEE-754 bit pattern of the inclusive
                                 * bounds as doubles (Float / DoubleRawValueBasedRangePredicateEvaluator after Math.nextUp / nextDown
@@ -279,6 +288,7 @@ typedef enum pg_kernel_id {
   PG_KERNEL_SCAN_SPARSE = 9,       /* scan_sparse_kernel: aggregation of the docs a sparse docId bitmap names (index-led filters), eight tiles per wave */
   PG_KERNEL_SCAN_RAW_SET = 12,     /* scan_raw_set_kernel: one PG_PRED_RAW_SET leaf (its hash table in LDS) + at most one aggregated raw INT column, coalesced reads */
   PG_KERNEL_SCAN_RAW = 11,         /* scan_raw_kernel: one raw INT range leaf + at most one aggregated raw INT column, five waves per SIMD, coalesced reads */
+  PG_KERNEL_SCAN_SIMPLE_VALID = 13,/* scan_simple_valid_kernel: scan_simple_kernel's shape behind one PG_PRED_DOC_SET leaf (a dword of the doc set per lane and tile) */
   PG_KERNEL_SCAN_SIMPLE = 10,      /* scan_simple_kernel: one dictionary-range leaf + at most one aggregated packed column, twice the waves per SIMD */
   PG_KERNEL_SCAN_HIST = 6          /* scan_hist_kernel: lane-private scan, SUM = sum_d matches[d] * dictionary[d] through an LDS histogram */
 } pg_kernel_id;
@@ -350,6 +360,19 @@ pg_status pg_segment_device_bytes(const pg_segment* segment, uint64_t* out_bytes
  * path, same result) and never fails for lack of one.  pg_set_plane_budget changes the process-wide budget at run time. */
 pg_status pg_segment_plane_bytes(const pg_segment* segment, uint64_t* out_bytes);
 pg_status pg_set_plane_budget(uint64_t budget_bytes, uint64_t* out_previous);
+
+/* Doc sets: docId bitmaps that belong to the query's segment context, not to a column -- the queryable (valid) docIds of an upsert /
+ * dedup segment (SegmentContext.getQueryableDocIdsSnapshot, FilterPlanNode.java:88-106).  A doc set is a dense doc-order bitmap in HBM,
+ * padded to whole 2048-doc tiles; a PG_PRED_DOC_SET leaf names it by id.  A RoaringBitmap is expanded on the device; the cardinality
+ * is computed once, here.  A docId >= num_docs (either format) or a `size` that does not fit the format: PG_ERR_INVALID_ARGUMENT.
+ * Ids are unique for the life of the process and never reused.  pg_doc_set_release drops the caller's reference: a query in flight
+ * keeps the bitmap until it has finished, later queries that name the id are refused.  pg_segment_close frees the rest.  The bytes
+ * count in pg_segment_device_bytes until the release.  A snapshot that changes is a new doc set (no update in place). */
+#define PG_DOC_SET_ROARING 0   /* one serialized RoaringBitmap, the format null_data already uses */
+#define PG_DOC_SET_WORDS   1   /* dense: bit (d & 63) of word d >> 6; size = 8 * ceil(num_docs / 64) */
+pg_status pg_doc_set_create(pg_segment* segment, int32_t format, const void* data, uint64_t size, int64_t* out_id);
+pg_status pg_doc_set_release(pg_segment* segment, int64_t id);
+pg_status pg_doc_set_cardinality(const pg_segment* segment, int64_t id, int64_t* out_cardinality);
 
 /* Plan-time eligibility: PG_OK when pg_execute would run this query on this segment, PG_ERR_UNSUPPORTED (pg_last_error says why) when
  * it would decline it -- more filter leaves / nodes / column streams / aggregations than the kernels take, key spaces beyond the

@@ -47,6 +47,12 @@ char* ph_lower_predicate(const char* sql_predicate, const void* dict, int32_t ca
 /* the physical filter operator tree of the WHERE clause (FilterPlanNode + FilterOperatorUtils: leaf operator per predicate, MatchAll / Empty folding,
  * AND children by priority) as text; the segment need not be loaded on a device */
 char* ph_explain_filter(void* segment, const char* sql, int32_t* status);
+/* The queryable (valid) docIds of an upsert / dedup table's segment -- SegmentContext.getQueryableDocIdsSnapshot(), one serialized
+ * RoaringBitmap, copied; NULL clears the set.  From then on every filter over the segment is FilterPlanNode.run()'s (:88-106)
+ * AND(user filter, BITMAP(queryableDocIds)), the leaf alone for a query without a filter: ph_explain_filter shows it, ph_execute_sql runs it
+ * (on a loaded segment the bitmap is a doc set of the device copy, include/pinot_gpu.h pg_doc_set_create; a segment that is not loaded on
+ * a device is declined as before: the mirror has no CPU evaluation path).  A docId >= numDocs is refused when the bitmap reaches the device. */
+int32_t ph_segment_set_queryable_doc_ids(void* segment, const void* roaring_bytes, uint64_t size);
 /* RangePredicateEvaluatorFactory.newDictionaryBasedEvaluator over an INT dictionary; bounds as strings, "*" = unbounded */
 char* ph_lower_range_predicate(const void* dict, int32_t cardinality, const char* lower, int32_t lower_inclusive, const char* upper, int32_t upper_inclusive, int32_t* status);
 /* the raw-value range evaluator of an INT (0) / LONG (1) column: inclusive [rawLower, rawUpper] */

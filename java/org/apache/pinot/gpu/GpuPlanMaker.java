@@ -147,7 +147,6 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
     GpuSegmentCache segments = _segments;
     IndexSegment indexSegment = segmentContext.getIndexSegment();
     if (segments == null || !QueryContextUtils.isAggregationQuery(queryContext)
-        || segmentContext.getQueryableDocIdsSnapshot() != null                       // upsert / dedup: FilterPlanNode.java:89-102
         || (_skipStarTreeSegments && indexSegment.getStarTrees() != null && !indexSegment.getStarTrees().isEmpty())) {
       return cpuPlan;
     }
@@ -156,9 +155,27 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
     if (segment == null || functions == null) {
       return cpuPlan;
     }
+    // upsert / dedup tables (FilterPlanNode.java:88-106): the queryable docIds are a doc set of the device copy, and-ed to the query's
+    // filter as one more leaf.  FILTER (WHERE ...) clauses over such a segment keep the CPU plan: the reference does not fold a match-all
+    // clause into the unfiltered lane there (every clause's operator carries the valid-doc bitmap), and the lanes below do.
+    long docSetId = 0;
+    if (segmentContext.getQueryableDocIdsSnapshot() != null) {
+      if (queryContext.hasFilteredAggregations()) {
+        return cpuPlan;
+      }
+      try {
+        docSetId = segments.docSet(segment, segmentContext.getQueryableDocIdsSnapshot());
+      } catch (RuntimeException e) {
+        LOGGER.debug("Segment {} keeps the CPU plan: its queryable docIds did not reach the device: {}", segment.getSegmentName(), e.toString());
+        return cpuPlan;
+      }
+      if (docSetId == 0) {
+        return cpuPlan;
+      }
+    }
     List<GpuAggregationOperator.Lane> lanes = queryContext.hasFilteredAggregations()
         ? filteredLanes(segment, indexSegment, queryContext, functions)
-        : unfilteredLane(segment, indexSegment, queryContext, functions);
+        : unfilteredLane(segment, indexSegment, queryContext, functions, docSetId);
     if (lanes == null) {
       return cpuPlan;
     }
@@ -205,8 +222,8 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
   }
 
   private static List<GpuAggregationOperator.Lane> unfilteredLane(GpuSegment segment, IndexSegment indexSegment, QueryContext queryContext,
-      AggregationFunction[] functions) {
-    GpuQueryLowering.Lowered lowered = GpuQueryLowering.lower(segment, indexSegment, queryContext, functions, queryContext.getFilter());
+      AggregationFunction[] functions, long docSetId) {
+    GpuQueryLowering.Lowered lowered = GpuQueryLowering.lowerWithDocSet(segment, indexSegment, queryContext, functions, queryContext.getFilter(), docSetId);
     if (lowered == null) {
       return null;
     }

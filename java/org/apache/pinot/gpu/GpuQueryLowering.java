@@ -50,6 +50,7 @@ final class GpuQueryLowering {
   static final int PRED_RAW_SET = PinotGpuNative.PG_PRED_RAW_SET;
   static final int PRED_DOC_RANGE = PinotGpuNative.PG_PRED_DOC_RANGE;
   static final int PRED_IS_NULL = PinotGpuNative.PG_PRED_IS_NULL;
+  static final int PRED_DOC_SET = PinotGpuNative.PG_PRED_DOC_SET;
   static final int EVAL_SCAN = PinotGpuNative.PG_EVAL_SCAN;
   static final int EVAL_INVERTED = PinotGpuNative.PG_EVAL_INVERTED;
   static final int OP_LEAF = PinotGpuNative.PG_FILTER_LEAF;
@@ -109,6 +110,7 @@ final class GpuQueryLowering {
   private final List<int[]> _predInts = new ArrayList<>();
   private final List<long[]> _predLongs = new ArrayList<>();
   private final List<int[]> _predSets = new ArrayList<>();
+  private long _docSetId;                    // the doc set of the segment's queryable docIds (upsert / dedup tables), or 0
 
   // gpu.exact.filter.stats of the plan maker's configuration (GpuPlanMaker.init); a query turns it off for itself with the option gpuExactFilterStats=false
   private static volatile boolean _exactFilterStats = true;
@@ -139,6 +141,22 @@ final class GpuQueryLowering {
       @Nullable FilterContext filter) {
     try {
       return new GpuQueryLowering(segment, indexSegment, queryContext).run(functions, filter);
+    } catch (NotOffloadable e) {
+      return null;
+    }
+  }
+
+  /**
+   * The same for a segment of an upsert / dedup table: {@code docSetId} names the doc set of its queryable docIds, and the filter becomes
+   * FilterPlanNode.run()'s (:88-106) AND(user filter, valid docs) -- the leaf alone without a user filter.
+   */
+  @Nullable
+  static Lowered lowerWithDocSet(GpuSegment segment, IndexSegment indexSegment, QueryContext queryContext, AggregationFunction[] functions,
+      @Nullable FilterContext filter, long docSetId) {
+    try {
+      GpuQueryLowering lowering = new GpuQueryLowering(segment, indexSegment, queryContext);
+      lowering._docSetId = docSetId;
+      return lowering.run(functions, filter);
     } catch (NotOffloadable e) {
       return null;
     }
@@ -231,7 +249,16 @@ final class GpuQueryLowering {
     }
     // ---- filter ----
     List<int[]> nodes = new ArrayList<>();
-    if (filter != null) {
+    if (_docSetId != 0) {
+      // FilterPlanNode.java:92-103: getAndFilterOperator(Arrays.asList(filterOperator, validDocFilter)) -- in that child order, re-ordered
+      // by priority like every AND (the bitmap leaf has priority 100); without a filter the BitmapBasedFilterOperator is the whole filter
+      Node valid = leaf(PRED_DOC_SET, -1, EVAL_SCAN, false, _docSetId, 0, null, BITMAP_PRIORITY);
+      Node root = filter != null ? and(new ArrayList<>(Arrays.asList(lowerFilter(filter), valid))) : valid;
+      if (root._kind == Kind.EMPTY) {              // the user filter matches nothing on this segment: EmptyFilterOperator
+        root = leaf(PRED_MATCH_NONE, -1, EVAL_SCAN, false, 0, 0, null, UNKNOWN_PRIORITY);
+      }
+      flatten(root, nodes);
+    } else if (filter != null) {
       Node root = lowerFilter(filter);
       if (root._kind != Kind.MATCH_ALL) {          // a filter that matches everything is no filter (MatchAllFilterOperator)
         flatten(root, nodes);

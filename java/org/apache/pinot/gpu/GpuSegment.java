@@ -66,6 +66,10 @@ final class GpuSegment implements Closeable {
   private volatile long _lastUsedNanos = System.nanoTime();
   private volatile long _deviceBytes;
   private volatile GpuSegmentCache.Account _account;
+  // The doc set of the queryable-docIds snapshot the last query over this copy brought (upsert / dedup tables): one per (copy, snapshot
+  // object); the snapshot is held weakly -- the table's metadata manager owns it (guarded by `this`)
+  private java.lang.ref.WeakReference<Object> _docSetSnapshot;
+  private long _docSetId;
 
   /** The native handle and its one-time close. */
   static final class HandleBox {
@@ -98,6 +102,33 @@ final class GpuSegment implements Closeable {
 
   HandleBox box() {
     return _box;
+  }
+
+  /**
+   * The id of the doc set that holds {@code snapshot} (SegmentContext.getQueryableDocIdsSnapshot), created on the device the first time a
+   * query brings this snapshot object: the bitmap is serialized into a direct buffer, uploaded and expanded there (PinotGpuNative.docSetCreate).
+   * A new snapshot object replaces the set: the old id is released -- queries in flight that named it finish on their own reference.
+   * The caller holds a pin (tryPin), so the handle cannot close underneath.
+   */
+  synchronized long docSetFor(org.roaringbitmap.buffer.MutableRoaringBitmap snapshot) {
+    if (_docSetId != 0 && _docSetSnapshot != null && _docSetSnapshot.get() == snapshot) {
+      return _docSetId;
+    }
+    long handle = _box.get();
+    if (handle == 0) {
+      return 0;
+    }
+    int size = snapshot.serializedSizeInBytes();
+    java.nio.ByteBuffer buffer = java.nio.ByteBuffer.allocateDirect(Math.max(size, 1)).order(java.nio.ByteOrder.LITTLE_ENDIAN);
+    snapshot.serialize(buffer);
+    long created = PinotGpuNative.docSetCreate(handle, PinotGpuNative.PG_DOC_SET_ROARING, buffer, size);
+    if (_docSetId != 0) {
+      PinotGpuNative.docSetRelease(handle, _docSetId);
+    }
+    _docSetId = created;
+    _docSetSnapshot = new java.lang.ref.WeakReference<>(snapshot);
+    _deviceBytes = PinotGpuNative.segmentDeviceBytes(handle);
+    return created;
   }
 
   int device() {

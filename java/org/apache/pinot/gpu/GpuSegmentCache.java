@@ -90,6 +90,28 @@ final class GpuSegmentCache {
   }
 
   /**
+   * Upsert / dedup tables: the doc set of the segment's queryable docIds, one per (device copy, snapshot object) -- created when a query
+   * first brings the snapshot, replaced (and the old one released) when the table's metadata manager has published a new snapshot
+   * object.  The creation cost -- serialize, upload, expand on the device -- is paid once per snapshot, not per query.  Returns 0 when the
+   * copy was closed in the meantime (the query keeps the CPU plan).  A copy that is evicted or closed takes its doc set with it.
+   */
+  long docSet(GpuSegment segment, org.roaringbitmap.buffer.MutableRoaringBitmap snapshot) {
+    if (!segment.tryPin()) {
+      return 0;
+    }
+    try {
+      long id = segment.docSetFor(snapshot);
+      GpuSegmentCache.Account account = segment.account();
+      if (account != null) {
+        account.update(segment.deviceBytes());
+      }
+      return id;
+    } finally {
+      segment.unpin();
+    }
+  }
+
+  /**
    * The segment is going away (IndexSegment.destroy(): the server dropped, replaced or reloaded it; no query holds it any more --
    * SegmentDataManager's reference count guarantees that before destroy() runs): its HBM is given back now.
    */

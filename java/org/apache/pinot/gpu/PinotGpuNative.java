@@ -24,7 +24,7 @@ public final class PinotGpuNative {
   // may spell one of these numbers as a literal.
 
   /** PG_ABI_VERSION (include/pinot_gpu.h): checked against pg_version() in GpuPlanMaker.init. */
-  public static final int PG_ABI_VERSION = 4;
+  public static final int PG_ABI_VERSION = 5;
 
   /** pg_status */
   public static final int PG_OK = 0;
@@ -55,6 +55,11 @@ public final class PinotGpuNative {
   public static final int PG_PRED_IS_NULL = 6;
   /** IN / NOT_IN on a raw INT / LONG / FLOAT / DOUBLE column: two set words per value (low word first), see include/pinot_gpu.h. */
   public static final int PG_PRED_RAW_SET = 7;
+  /** The queryable docIds of an upsert / dedup segment (FilterPlanNode.java:88-106): lo = the id docSetCreate returned for the segment. */
+  public static final int PG_PRED_DOC_SET = 8;
+  /** pg_doc_set_create formats: one serialized RoaringBitmap / dense 64-bit words. */
+  public static final int PG_DOC_SET_ROARING = 0;
+  public static final int PG_DOC_SET_WORDS = 1;
   /** PG_RAW_SET_MAX_VALUES: distinct values of one PG_PRED_RAW_SET list. */
   public static final int PG_RAW_SET_MAX_VALUES = 1024;
   /** PG_RAW_SET_WORDS_PER_VALUE: set words one value of a PG_PRED_RAW_SET list takes (low word first). */
@@ -154,6 +159,19 @@ public final class PinotGpuNative {
 
   /** pg_segment_device_bytes */
   static native long segmentDeviceBytes(long handle);
+
+  /**
+   * pg_doc_set_create: a doc set of the segment from {@code size} bytes at the start of a DIRECT buffer -- format PG_DOC_SET_ROARING: one
+   * RoaringBitmap in the portable serialization (ImmutableRoaringBitmap.serialize); PG_DOC_SET_WORDS: dense little-endian 64-bit words.
+   * Returns its id (PG_PRED_DOC_SET.lo); ids are never reused.  The buffer is read during the call only.
+   */
+  static native long docSetCreate(long handle, int format, ByteBuffer data, long size);
+
+  /** pg_doc_set_release: drops the caller's reference; queries in flight keep the bitmap until they finish, later ones are refused. */
+  static native void docSetRelease(long handle, long docSetId);
+
+  /** pg_doc_set_cardinality */
+  static native long docSetCardinality(long handle, long docSetId);
 
   /**
    * pg_group_key_info: {base, isOffset, nullEntry} of a group-by column -- a dictionary column's key entries are dictIds (isOffset 0); a raw

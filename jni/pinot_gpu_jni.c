@@ -123,6 +123,33 @@ JNIEXPORT jlong JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_segmentDeviceBy
   return (jlong)bytes;
 }
 
+/* pg_doc_set_create over the first `size` bytes of a direct ByteBuffer (GpuSegment.docSetFor serializes the queryable-docIds snapshot into
+ * one); the buffer is read during the call only. */
+JNIEXPORT jlong JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_docSetCreate(JNIEnv* env, jclass cls, jlong handle, jint format, jobject data,
+    jlong size) {
+  (void)cls;
+  void* address = data != NULL ? (*env)->GetDirectBufferAddress(env, data) : NULL;
+  if (address == NULL || size < 0) { throw_new(env, "java/lang/IllegalArgumentException", "docSetCreate: not a direct ByteBuffer, or a negative size"); return 0; }
+  int64_t id = 0;
+  const pg_status status = pg_doc_set_create((pg_segment*)(intptr_t)handle, (int32_t)format, address, (uint64_t)size, &id);
+  if (status != PG_OK) { throw_status(env, status); return 0; }
+  return (jlong)id;
+}
+
+JNIEXPORT void JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_docSetRelease(JNIEnv* env, jclass cls, jlong handle, jlong docSetId) {
+  (void)cls;
+  const pg_status status = pg_doc_set_release((pg_segment*)(intptr_t)handle, (int64_t)docSetId);
+  if (status != PG_OK) throw_status(env, status);
+}
+
+JNIEXPORT jlong JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_docSetCardinality(JNIEnv* env, jclass cls, jlong handle, jlong docSetId) {
+  (void)cls;
+  int64_t cardinality = 0;
+  const pg_status status = pg_doc_set_cardinality((const pg_segment*)(intptr_t)handle, (int64_t)docSetId, &cardinality);
+  if (status != PG_OK) { throw_status(env, status); return 0; }
+  return (jlong)cardinality;
+}
+
 JNIEXPORT jlongArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_groupKeyInfo(JNIEnv* env, jclass cls, jlong handle, jint column) {
   (void)cls;
   int64_t base = 0;

@@ -7,18 +7,20 @@ C ABI into the HIP kernels, and loading fails loudly when the library has not be
 import ctypes as C
 import os
 
-PG_ABI_VERSION = 4
+PG_ABI_VERSION = 5
 
 # pg_status
 PG_OK, PG_ERR_INVALID_ARGUMENT, PG_ERR_UNSUPPORTED, PG_ERR_DEVICE, PG_ERR_OUT_OF_MEMORY, PG_ERR_NOT_INITIALIZED, PG_ERR_INTERNAL = range(7)
 # pg_data_type / pg_fwd_encoding
 KERNEL_NAMES = {0: "scan_agg_kernel", 1: "scan_private_kernel", 2: "scan_group_kernel", 3: "group_private_kernel",
-                4: "group_partition_scatter_kernel", 5: "scan_private_typed_kernel", 6: "scan_hist_kernel", 7: "index_and_kernel", 8: "scan_narrow_kernel", 9: "scan_sparse_kernel", 10: "scan_simple_kernel", 11: "scan_raw_kernel", 12: "scan_raw_set_kernel"}
+                4: "group_partition_scatter_kernel", 5: "scan_private_typed_kernel", 6: "scan_hist_kernel", 7: "index_and_kernel", 8: "scan_narrow_kernel", 9: "scan_sparse_kernel", 10: "scan_simple_kernel", 11: "scan_raw_kernel", 12: "scan_raw_set_kernel", 13: "scan_simple_valid_kernel"}
 PG_TYPE_INT, PG_TYPE_LONG, PG_TYPE_FLOAT, PG_TYPE_DOUBLE = range(4)
 PG_FWD_FIXED_BIT_DICT, PG_FWD_RAW_FIXED_BYTE = 0, 1
 # pg_predicate_kind / pg_leaf_eval
-PG_PRED_MATCH_ALL, PG_PRED_MATCH_NONE, PG_PRED_DICT_RANGE, PG_PRED_DICT_SET, PG_PRED_RAW_RANGE, PG_PRED_DOC_RANGE, PG_PRED_IS_NULL, PG_PRED_RAW_SET = range(8)
+PG_PRED_MATCH_ALL, PG_PRED_MATCH_NONE, PG_PRED_DICT_RANGE, PG_PRED_DICT_SET, PG_PRED_RAW_RANGE, PG_PRED_DOC_RANGE, PG_PRED_IS_NULL, PG_PRED_RAW_SET, PG_PRED_DOC_SET = range(9)
 PG_RAW_SET_MAX_VALUES, PG_RAW_SET_WORDS_PER_VALUE = 1024, 2
+# pg_doc_set_create formats
+PG_DOC_SET_ROARING, PG_DOC_SET_WORDS = 0, 1
 PG_QUERY_DEFAULT, PG_QUERY_NULL_HANDLING, PG_QUERY_STATS_UPPER_BOUND_OK = 0, 1, 2
 PG_EVAL_SCAN, PG_EVAL_INVERTED = 0, 1
 # pg_filter_op
@@ -105,6 +107,9 @@ ABI_SYMBOLS = [
     ("pg_segment_device_bytes", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("pg_segment_plane_bytes", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("pg_set_plane_budget", C.c_int, [C.c_uint64, _P(C.c_uint64)]),
+    ("pg_doc_set_create", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, _P(C.c_int64)]),
+    ("pg_doc_set_release", C.c_int, [C.c_void_p, C.c_int64]),
+    ("pg_doc_set_cardinality", C.c_int, [C.c_void_p, C.c_int64, _P(C.c_int64)]),
     ("pg_query_check", C.c_int, [C.c_void_p, _P(pg_query)]),
     ("pg_execute", C.c_int, [C.c_void_p, _P(pg_query), _P(pg_result)]),
     ("pg_result_free", None, [_P(pg_result)]),

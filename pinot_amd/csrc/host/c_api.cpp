@@ -207,6 +207,12 @@ int32_t ph_segment_set_null_vector(void* seg, const char* column, const void* da
   });
 }
 
+// SegmentContext.getQueryableDocIdsSnapshot() of an upsert / dedup table's segment: one serialized RoaringBitmap of the valid docIds (copied);
+// NULL clears it.  Every query over the segment then runs behind it (FilterPlanNode.java:88-106).
+int32_t ph_segment_set_queryable_doc_ids(void* seg, const void* roaring_bytes, uint64_t size) {
+  return guarded([&] { static_cast<ImmutableSegment*>(seg)->setQueryableDocIds(roaring_bytes, size); });
+}
+
 // Segments assembled column by column have no metadata.properties: isSorted is derived from the data the way the segment creator's
 // column statistics do (a dictionary column whose dictIds never decrease in docId order, AbstractColumnStatisticsCollector), together
 // with the [start, end] docId pair of every dictId that SortedIndexReaderImpl would hold.  Unsorted columns leave at the first descent.

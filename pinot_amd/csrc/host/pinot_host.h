@@ -163,6 +163,12 @@ class ImmutableSegment {
   pg_segment* handle() const { return _handle; }
   int deviceId() const { return _deviceId; }
   void keepAlive(std::shared_ptr<std::vector<uint8_t>> buffer) { _owned.push_back(std::move(buffer)); }   // loader-owned index buffers
+  // SegmentContext.getQueryableDocIdsSnapshot() of an upsert / dedup table's segment: one serialized RoaringBitmap (copied), or nullptr to
+  // clear.  On a loaded segment the bitmap becomes a doc set of the device copy at once (pg_doc_set_create; the old one is released);
+  // otherwise load() creates it.  FilterPlanNode.run() (:88-106) and-s it to every filter: lowerQuery / explainFilter.
+  void setQueryableDocIds(const void* roaringBytes, uint64_t size);
+  bool hasQueryableDocIds() const { return _hasQueryableDocIds; }
+  int64_t queryableDocSetId() const { return _docSetId; }      // 0: none on the device
   std::vector<std::string> notOffloaded;      // "<column>: <reason>" for columns of a loaded directory that stay on the CPU plan
  private:
   std::string _name;
@@ -171,6 +177,10 @@ class ImmutableSegment {
   std::vector<std::shared_ptr<std::vector<uint8_t>>> _owned;
   pg_segment* _handle = nullptr;
   int _deviceId = -1;
+  bool _hasQueryableDocIds = false;
+  std::vector<uint8_t> _queryableDocIds;
+  int64_t _docSetId = 0;
+  void createDocSet();
 };
 
 // ImmutableSegmentLoader.load(indexDir, ReadMode) for the single-value numeric / string columns of a v1 or v3 segment directory
@@ -485,6 +495,8 @@ struct GpuAbi {
   decltype(&pg_filter_bitmap) filter_bitmap;
   decltype(&pg_group_key_info) group_key_info;
   decltype(&pg_group_key_values) group_key_values;
+  decltype(&pg_doc_set_create) doc_set_create;
+  decltype(&pg_doc_set_release) doc_set_release;
 };
 const GpuAbi& gpuAbi();   // throws std::runtime_error when libpinot_gpu.so cannot be loaded (no fallback)
 

@@ -50,6 +50,8 @@ const GpuAbi& gpuAbi() {
     abi.filter_bitmap = (decltype(abi.filter_bitmap))sym("pg_filter_bitmap");
     abi.group_key_info = (decltype(abi.group_key_info))sym("pg_group_key_info");
     abi.group_key_values = (decltype(abi.group_key_values))sym("pg_group_key_values");
+    abi.doc_set_create = (decltype(abi.doc_set_create))sym("pg_doc_set_create");
+    abi.doc_set_release = (decltype(abi.doc_set_release))sym("pg_doc_set_release");
   });
   if (!error.empty()) throw std::runtime_error("pinot GPU engine unavailable (no CPU fallback in this library): " + error);
   return abi;
@@ -121,10 +123,38 @@ void ImmutableSegment::load(int deviceId) {
   sd.device_id = deviceId;
   checkStatus(gpuAbi().segment_open(&sd, &_handle), ("loading segment " + _name).c_str());
   _deviceId = deviceId;
+  if (_hasQueryableDocIds) createDocSet();
 }
 
 void ImmutableSegment::destroy() {
   if (_handle) { gpuAbi().segment_close(_handle); _handle = nullptr; }
+  _docSetId = 0;                    // (pg_segment_close freed the device copy's doc sets)
+}
+
+void ImmutableSegment::createDocSet() {
+  int64_t id = 0;
+  checkStatus(gpuAbi().doc_set_create(_handle, PG_DOC_SET_ROARING, _queryableDocIds.data(), _queryableDocIds.size(), &id),
+              ("uploading the queryable docIds of segment " + _name).c_str());
+  if (_docSetId != 0) gpuAbi().doc_set_release(_handle, _docSetId);      // the snapshot was replaced: queries in flight keep their reference
+  _docSetId = id;
+}
+
+void ImmutableSegment::setQueryableDocIds(const void* roaringBytes, uint64_t size) {
+  if (roaringBytes == nullptr) {
+    if (_handle && _docSetId != 0) gpuAbi().doc_set_release(_handle, _docSetId);
+    _docSetId = 0;
+    _hasQueryableDocIds = false;
+    _queryableDocIds.clear();
+    return;
+  }
+  std::vector<uint8_t> bytes((const uint8_t*)roaringBytes, (const uint8_t*)roaringBytes + size);
+  if (_handle) {
+    std::swap(bytes, _queryableDocIds);
+    try { createDocSet(); } catch (...) { std::swap(bytes, _queryableDocIds); throw; }      // (a bitmap the device refuses leaves the segment as it was)
+  } else {
+    _queryableDocIds = std::move(bytes);
+  }
+  _hasQueryableDocIds = true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -376,6 +406,7 @@ std::string explainPhysical(const PhysNode& n, const LoweredQuery& lq, const Imm
   switch (p.kind) {
     case PG_PRED_DOC_RANGE: return "SORTED(" + col + neg + " docs " + std::to_string(p.lo) + ".." + std::to_string(p.hi) + ")";
     case PG_PRED_IS_NULL: return "BITMAP(" + col + " IS" + neg + " NULL)";
+    case PG_PRED_DOC_SET: return std::string("BITMAP(") + (p.exclusive ? "NOT " : "") + "queryableDocIds)";
     case PG_PRED_RAW_RANGE: return "SCAN(" + col + neg + " raw " + std::to_string(p.lo) + ".." + std::to_string(p.hi) + ")";
     case PG_PRED_RAW_SET: {
       std::string s = "SCAN(" + col + neg + " raw IN ";
@@ -391,6 +422,24 @@ std::string explainPhysical(const PhysNode& n, const LoweredQuery& lq, const Imm
       return std::string(p.eval == PG_EVAL_INVERTED ? "INVERTED(" : "SCAN(") + col + neg + " in " + std::to_string(count) + " dictIds)";
     }
   }
+}
+
+// FilterPlanNode.run() (:88-106) on a segment with queryable docIds: BitmapBasedFilterOperator(snapshot, false, numDocs) and-ed to the
+// user's filter through getAndFilterOperator(Arrays.asList(filterOperator, validDocFilter)) -- in that child order, before the re-ordering
+// by priority --, or the whole filter when the query has none.  The leaf names the device copy's doc set (0 while the segment is not loaded:
+// enough for explainFilter).
+PhysNode withQueryableDocIds(const PhysNode* userRoot, const ImmutableSegment& seg, LoweredQuery* out) {
+  pg_predicate p;
+  memset(&p, 0, sizeof(p));
+  p.kind = PG_PRED_DOC_SET;
+  p.column = -1;
+  p.lo = seg.queryableDocSetId();
+  PhysNode valid = physLeaf(out, p, kBitmapPriority);
+  if (userRoot == nullptr) return valid;
+  std::vector<PhysNode> both;
+  both.push_back(*userRoot);
+  both.push_back(std::move(valid));
+  return physAnd(std::move(both));
 }
 
 void flattenFilter(const PhysNode& n, LoweredQuery* out) {
@@ -418,7 +467,15 @@ std::unique_ptr<LoweredQuery> lowerQuery(const ImmutableSegment& seg, const Quer
   // reserve so that set_words pointers taken during lowering stay valid
   lq->setWords.reserve(64);
   lq->predicates.reserve(256);
-  if (qc.hasFilter) {
+  if (seg.hasQueryableDocIds()) {
+    // upsert / dedup: the valid docs are one more leaf of every filter (and the whole filter of a query without one)
+    if (qc.hasFilter) {
+      const PhysNode user = lowerFilter(qc.filter, seg, qc.nullHandlingEnabled, lq.get());
+      flattenFilter(withQueryableDocIds(&user, seg, lq.get()), lq.get());
+    } else {
+      flattenFilter(withQueryableDocIds(nullptr, seg, lq.get()), lq.get());
+    }
+  } else if (qc.hasFilter) {
     const PhysNode root = lowerFilter(qc.filter, seg, qc.nullHandlingEnabled, lq.get());
     if (root.kind != PhysNode::MATCH_ALL) flattenFilter(root, lq.get());      // a filter that matches everything is no filter (MatchAllFilterOperator)
   }
@@ -662,10 +719,15 @@ class GpuAggregationPlanNode : public PlanNode {
 
 // FilterPlanNode.run() of the query's WHERE clause over this segment, as text (no device involved)
 std::string explainFilter(const ImmutableSegment& seg, const QueryContext& qc) {
-  if (!qc.hasFilter) return "MATCH_ALL";
   LoweredQuery lq;
   lq.setWords.reserve(64);
   lq.predicates.reserve(256);
+  if (seg.hasQueryableDocIds()) {
+    if (!qc.hasFilter) return explainPhysical(withQueryableDocIds(nullptr, seg, &lq), lq, seg);
+    const PhysNode user = lowerFilter(qc.filter, seg, qc.nullHandlingEnabled, &lq);
+    return explainPhysical(withQueryableDocIds(&user, seg, &lq), lq, seg);
+  }
+  if (!qc.hasFilter) return "MATCH_ALL";
   const PhysNode root = lowerFilter(qc.filter, seg, qc.nullHandlingEnabled, &lq);
   return explainPhysical(root, lq, seg);
 }

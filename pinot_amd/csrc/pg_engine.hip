@@ -83,6 +83,8 @@ struct Engine {
   int batch_blocks_per_cu = 4;    // PINOT_GPU_BATCH_BLOCKS_PER_CU: workgroups per CU a batch launch is cut into (all items together)
   bool scan_raw = true;      // PINOT_GPU_SCAN_RAW=0: raw INT scans stay in scan_private_kernel / scan_private_typed_kernel (four waves per SIMD)
   bool scan_raw_set = true;  // PINOT_GPU_SCAN_RAW_SET=0: a lone IN / NOT IN leaf on a raw column takes the membership pre-pass + the general kernels, like every other shape (pg_scan_raw_set.h)
+  int scan_simple_valid = 1;  // PINOT_GPU_SCAN_SIMPLE_VALID=0: `range leaf AND doc set` / the doc set alone stays in the general lane-private kernel; 2: the form of
+                             // scan_simple_valid_kernel whose tiles without a valid doc skip the filter column too (pg_scan_simple.h)
   bool scan_simple = true;   // PINOT_GPU_SCAN_SIMPLE=0: one-leaf / one-column queries stay in scan_private_kernel (half the waves per SIMD)
   bool scan_sparse = true;   // PINOT_GPU_SCAN_SPARSE=0: index-led aggregations scan their listed tiles in scan_private_kernel (one tile per wave and iteration)
   // (read at every pg_init like the rest: they were function-local statics, fixed at their first use in the process, until the kernel
@@ -263,6 +265,17 @@ struct ExecCtx {
 
 }  // namespace
 
+// A doc set (pg_doc_set_create): the queryable docIds of an upsert / dedup segment as a dense doc-order bitmap, padded to whole
+// 2048-doc tiles like a null bitmap.  The segment's table holds the caller's reference; every lowering that reads the words holds one
+// more (Lowered.doc_sets, LoweredItem.doc_sets), so a release never frees a bitmap under a query in flight.
+struct DocSet {
+  int64_t id = 0;
+  unsigned long long* d_words = nullptr;
+  uint64_t bytes = 0;
+  int64_t cardinality = 0;
+  ~DocSet() { if (d_words) (void)hipFree(d_words); }
+};
+
 struct pg_segment {
   int device = 0;
   int num_docs = 0;
@@ -290,6 +303,8 @@ struct pg_segment {
   std::atomic<uint64_t> plane_epoch{0};
   std::mutex plan_cache_mu;
   std::vector<std::shared_ptr<const struct LoweredItem>> plan_cache;
+  mutable std::mutex doc_sets_mu;
+  std::vector<std::shared_ptr<DocSet>> doc_sets;      // the caller's references (pg_doc_set_create .. pg_doc_set_release)
 };
 
 // What a query's scan kernel leaves behind for the transducer pass: the bitmap of every input leaf it evaluated itself.
@@ -603,6 +618,8 @@ void drop_planes_of(pg_segment* seg);
 
 void free_segment(pg_segment* seg) {
   if (!seg) return;
+  { std::lock_guard<std::mutex> lk(seg->plan_cache_mu); seg->plan_cache.clear(); }
+  { std::lock_guard<std::mutex> lk(seg->doc_sets_mu); seg->doc_sets.clear(); }
   drop_planes_of(seg);
   if (seg->plane_stream) (void)hipStreamDestroy(seg->plane_stream);
   for (auto* c : seg->all_ctx) destroy_ctx(c);
@@ -974,6 +991,11 @@ struct Lowered {
   // other query gets the leaf's match bitmap from raw_set_bitmap_kernel ahead of its kernel.  The host tables live as long as the lowering.
   bool raw_set_lean_hint = false;
   std::vector<std::shared_ptr<RawSetTable>> raw_set_tables;
+  // PG_PRED_DOC_SET leaves: the sets whose words the lowered filter reads, held for as long as the lowering lives.  valid_leaf: the index
+  // (PlanParams.leaves) of a NON-exclusive doc-set leaf, the one scan_simple_valid_kernel may take; -1: none.
+  std::vector<std::shared_ptr<DocSet>> doc_sets;
+  int valid_leaf = -1;
+  int64_t stats_closed_entries = -1;           // >= 0: numEntriesScannedInFilter as a closed form (scan_simple_valid_kernel: the doc set's cardinality)
   uint32_t* sp_leaf_out[kMaxLeaves] = {};      // out: ScanParams.leaf_out, by LEAF node ordinal
 };
 
@@ -1072,7 +1094,8 @@ void build_sequence(const pg_query* q, std::vector<SeqNode>* seq, int* lazy_node
     if (pi < 0 || pi >= q->num_predicates) return false;
     const pg_predicate& pr = q->predicates[pi];
     // index-driven leaves go first, like the reference's priorities (sorted 0 < bitmap 100 < scan 500, FilterOperatorUtils.java:205-251)
-    return pr.kind == PG_PRED_DOC_RANGE || pr.kind == PG_PRED_IS_NULL || (pr.eval == PG_EVAL_INVERTED && (pr.kind == PG_PRED_DICT_RANGE || pr.kind == PG_PRED_DICT_SET));
+    return pr.kind == PG_PRED_DOC_RANGE || pr.kind == PG_PRED_IS_NULL || pr.kind == PG_PRED_DOC_SET ||
+           (pr.eval == PG_EVAL_INVERTED && (pr.kind == PG_PRED_DICT_RANGE || pr.kind == PG_PRED_DICT_SET));
   };
   std::stable_partition(children.begin(), children.end(), is_bitmap_leaf);
   // The inverted-index children are and-ed by ONE kernel, container by container (AndDocIdSet.java:127-165 and-s the index-based
@@ -1243,6 +1266,12 @@ pg_status complete_index_and_bitmap(Lowered* lw, ExecCtx* ctx) {
   HIP_TRY(hipGetLastError());
   lw->and_bitmap = nullptr;
   return PG_OK;
+}
+
+static std::shared_ptr<DocSet> find_doc_set(const pg_segment* seg, int64_t id) {
+  std::lock_guard<std::mutex> lk(seg->doc_sets_mu);
+  for (const auto& ds : seg->doc_sets) if (ds->id == id) return ds;
+  return nullptr;
 }
 
 // PG_PRED_RAW_SET (include/pinot_gpu.h): the argument checks and the declines, the same for pg_query_check and pg_execute.  *keys: the
@@ -1502,6 +1531,14 @@ pg_status lower_filter(pg_segment* seg, ExecCtx* ctx, const pg_query* q, Lowered
         const ColumnDev& col = seg->cols[pr.column];
         if (!col.d_null_bitmap) { L.kind = kLeafMatchNone; }
         else { L.kind = kLeafBitmap; L.bitmap = col.d_null_bitmap; sp.num_bitmap_leaves++; }
+      }
+      else if (pr.kind == PG_PRED_DOC_SET) {
+        // FilterPlanNode.java:88-106: the queryable docIds as a BitmapBasedFilterOperator -- a kLeafBitmap over the doc set's words
+        std::shared_ptr<DocSet> ds = find_doc_set(seg, pr.lo);
+        if (!ds) return fail(PG_ERR_INVALID_ARGUMENT, "doc set %lld is unknown to segment %s (never created, or released)", (long long)pr.lo, seg->name.c_str());
+        L.kind = kLeafBitmap; L.bitmap = ds->d_words; sp.num_bitmap_leaves++;
+        if (!pr.exclusive && lw->valid_leaf < 0) lw->valid_leaf = dn.leaf;
+        lw->doc_sets.push_back(std::move(ds));
       }
       else if (pr.kind == PG_PRED_DOC_RANGE) {
         // SortedIndexBasedFilterOperator: one inclusive docId range; nothing is scanned
@@ -1942,6 +1979,8 @@ pg_status pg_init(const pg_config* config) {
   g_engine.scan_sparse = !(ssp && ssp[0] == '0');
   const char* ssm = getenv("PINOT_GPU_SCAN_SIMPLE");
   g_engine.scan_simple = !(ssm && ssm[0] == '0');
+  const char* ssv = getenv("PINOT_GPU_SCAN_SIMPLE_VALID");
+  g_engine.scan_simple_valid = ssv ? (ssv[0] == '0' ? 0 : (ssv[0] == '2' ? 2 : 1)) : 1;
   const char* srw = getenv("PINOT_GPU_SCAN_RAW");
   g_engine.scan_raw = !(srw && srw[0] == '0');
   const char* srs = getenv("PINOT_GPU_SCAN_RAW_SET");
@@ -2562,6 +2601,8 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
           const pg_status rst = check_raw_set(seg, pr, &keys);
           if (rst != PG_OK) return rst;
         }
+        if (pr.kind == PG_PRED_DOC_SET && !find_doc_set(seg, pr.lo))
+          return fail(PG_ERR_INVALID_ARGUMENT, "doc set %lld is unknown to segment %s (never created, or released)", (long long)pr.lo, seg->name.c_str());
         const bool stages = pr.kind == PG_PRED_RAW_RANGE || ((pr.kind == PG_PRED_DICT_RANGE || pr.kind == PG_PRED_DICT_SET) && pr.eval != PG_EVAL_INVERTED);
         if (stages) {
           if (pr.column < 0 || pr.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "predicate column %d out of range", pr.column);
@@ -2697,6 +2738,7 @@ static void finish_filter_stats(fstats::Plan stats_plan, int stats_scan_leaves, 
 }
 
 static void finish_filter_stats(const Lowered& lw, const pg_segment* seg, int64_t counted_entries, bool counted, pg_result* out) {
+  if (lw.stats_closed_entries >= 0) { out->stats.num_entries_scanned_in_filter = lw.stats_closed_entries; out->filter_entries_exact = 1; return; }
   finish_filter_stats(lw.stats_plan, lw.stats_scan_leaves, seg, counted_entries, counted, out);
 }
 
@@ -2754,6 +2796,7 @@ struct LoweredItem {
   bool one_slot = true;
   std::function<void(const BlockPartial&, pg_result*)> convert;
   std::vector<int> plane_columns;                 // value planes sp reads: held (PlaneHold) by every batch that launches this item
+  std::vector<std::shared_ptr<DocSet>> doc_sets;  // doc sets sp reads: alive as long as the item (pg_doc_set_release drops the item from the plan cache)
   std::vector<Lowered::SetLeaf> sets;             // dictId-set leaves of sp: nodes whose set_words == ctx_words read the batch's copy of host_words (which the item's query owns)
   // lean_kind 6 (group_lds_batch_kernel): the item is a GroupParams; its table slice is count[G] | acc[NA][G], zero-identity keys
   std::shared_ptr<GroupParams> gp;
@@ -2840,12 +2883,12 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
 // ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
 // preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
-enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Agg };
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Agg };
 // per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
 // leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
 static const struct { int id; bool writes_leaves; } kScanKernels[] = {
   {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
-  {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
+  {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_SIMPLE_VALID, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
   {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_AGG, false}};
 static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
 // general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
@@ -2909,6 +2952,25 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
   // fields: eight tiles per wave and iteration, only the matching docs' values are touched (scan_sparse_kernel)
   if (g_engine.scan_sparse && lane_private && !want_bitmap && pl.num_agg_cols > 0 && lw.tile_list != nullptr && sp.num_nodes == 1 && sp.nodes[0].kind == kLeafBitmap &&
       sp.nodes[0].exclusive == 0) return pick(ScanKernel::Sparse);
+  // The queryable docIds of an upsert / dedup segment in front of scan_simple_kernel's shape: a root AND of ONE non-exclusive doc-set leaf
+  // (first in the chain: bitmap leaves lead) and at most one dictionary-range leaf, or the doc set alone, and at most one aggregated packed
+  // column, widths up to kSimpleMaxBits -- scan_simple_valid_kernel.  The chain's entry count is a closed form there (one entry per doc of
+  // the set: run_aggregation), so stats_chain_flagged does not keep the query out.
+  if (g_engine.scan_simple_valid != 0 && g_engine.scan_simple && lane_private && !want_bitmap && lw.tile_list == nullptr && lw.side == nullptr && lw.valid_leaf >= 0 &&
+      pl.num_agg_cols <= 1 && !lw.stats_leap2_flagged && (sp.num_nodes == 1 || sp.num_nodes == 3)) {
+    const DevNode& v = sp.nodes[0];
+    const DevNode* range = sp.num_nodes == 3 ? &sp.nodes[1] : nullptr;
+    const DevAggCol* vac = pl.num_agg_cols == 1 ? &sp.agg_cols[0] : nullptr;
+    bool valid = v.op == PG_FILTER_LEAF && v.kind == kLeafBitmap && v.exclusive == 0 && v.set_words == reinterpret_cast<const uint32_t*>(pl.leaves[lw.valid_leaf].bitmap) &&
+                 (range != nullptr || vac != nullptr);
+    if (valid && range != nullptr)
+      valid = sp.nodes[2].op == PG_FILTER_AND && sp.nodes[2].num_children == 2 && range->op == PG_FILTER_LEAF && range->kind == kLeafDictRange && range->bits >= 1 && range->bits <= kSimpleMaxBits &&
+              (range->flags & kNodeLeapfrog2) == 0;
+    if (valid && vac != nullptr)
+      valid = vac->bits >= 1 && vac->bits <= kSimpleMaxBits && !vac->is_raw &&
+              !(range != nullptr && range->fwd == vac->fwd && range->bits == vac->bits && vac->need_sum != 0 && vac->need_minmax == 0 && range->exclusive == 0);
+    if (valid) return pick(ScanKernel::SimpleValid);
+  }
   // the lean kernels below: at most one leaf (without the count hooks) and one aggregated column, no tile list, no statistics they do not count
   if (want_bitmap || lw.tile_list != nullptr || sp.num_nodes > 1 || pl.num_agg_cols > 1 || (want_result && (lw.stats_leap2_flagged || lw.stats_chain_flagged))) return k;
   const DevNode* leaf = sp.num_nodes == 1 ? &sp.nodes[0] : nullptr;
@@ -2973,6 +3035,7 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Scan
     case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
     case ScanKernel::Simple: case ScanKernel::SimpleSet: lean_grid(seg, waves_scan_simple(), &g); break;
+    case ScanKernel::SimpleValid: lean_grid(seg, waves_scan_simple_valid(), &g); break;
     case ScanKernel::Raw: lean_grid(seg, waves_scan_raw(), &g); break;
     case ScanKernel::RawSet: {
       // every workgroup keeps the leaf's table in dynamic LDS: as many workgroups per CU as registers AND the tables admit; small grids two, as lean_grid
@@ -2998,6 +3061,7 @@ static bool scan_batch_kind(const ScanChoice& k, int num_agg_cols, BatchKind* ki
     case ScanKernel::Simple: case ScanKernel::SimpleSet: *kind = !lean ? BatchKind::Private : (k.kernel == ScanKernel::Simple ? BatchKind::Simple : BatchKind::SimpleSet); return true;
     case ScanKernel::Raw: *kind = !lean && k.general == ScanKernel::Private ? BatchKind::Private : BatchKind::Raw; return true;
     case ScanKernel::RawSet: return false;      // (no shared-launch form: the table belongs to the context)
+    case ScanKernel::SimpleValid: return false; // (no shared-launch form: a batch item behind a doc set runs its own kernel)
     case ScanKernel::PrivateFsm: case ScanKernel::Private: *kind = BatchKind::Private; return true;
     case ScanKernel::PrivateTyped: *kind = num_agg_cols <= 1 ? BatchKind::Typed1 : (num_agg_cols == 2 ? BatchKind::Typed2 : BatchKind::TypedMax); return g_engine.batch_more;
     default: return false;      // Sparse, Agg
@@ -3011,6 +3075,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Narrow: case ScanKernel::NarrowSingle: launch_scan_narrow(k.kernel == ScanKernel::NarrowSingle, g.blocks, stream, sp); break;
     case ScanKernel::Sparse: launch_scan_sparse(one, g.blocks, stream, sp); break;
     case ScanKernel::Simple: case ScanKernel::SimpleSet: launch_scan_simple(g.blocks, lean_threads, stream, sp, k.kernel == ScanKernel::SimpleSet); break;
+    case ScanKernel::SimpleValid: launch_scan_simple_valid(g.blocks, lean_threads, stream, sp, g_engine.scan_simple_valid == 2); break;
     case ScanKernel::Raw: launch_scan_raw(g.blocks, lean_threads, stream, sp); break;
     case ScanKernel::RawSet: launch_scan_raw_set(sp.nodes[0].lo_hi, g.blocks, g.lds, stream, sp); break;
     case ScanKernel::PrivateFsm: launch_scan_private_fsm(num_agg_cols, g.blocks, stream, sp); break;
@@ -3034,6 +3099,7 @@ struct QueryRun {
 // The query becomes an item of pg_execute_batch's shared launch; the value planes its kernel reads stay held until the batch has run
 static pg_status defer_item(QueryRun& r, std::shared_ptr<LoweredItem> item) {
   item->plane_columns = r.planes.columns;      // (none for an index-only COUNT)
+  item->doc_sets = r.lw.doc_sets;
   r.defer->item = std::move(item);
   r.defer->cacheable = !r.lw.plane_pending;
   r.defer->planes.reset(new PlaneHold(std::move(r.planes)));
@@ -3099,6 +3165,25 @@ static bool answer_from_metadata(const pg_segment* seg, const pg_query* q, int n
   }
   nothing_scanned(out, seg->num_docs, seg->num_docs);      // NonScanBasedAggregationOperator.getExecutionStatistics: (totalDocs, 0, 0, totalDocs)
   if (out_cardinality) *out_cardinality = seg->num_docs;
+  return true;
+}
+// FastFilteredCountOperator over the queryable docIds alone (COUNT(*) on an upsert segment without a user filter): the doc set's
+// cardinality was computed when it was created -- nothing is launched.  Statistics (cardinality, 0, 0, totalDocs).
+static bool answer_from_doc_set(const pg_segment* seg, const pg_query* q, int na, pg_result* out, int64_t* out_cardinality) {
+  if (q->num_filter_nodes != 1 || !q->filter || !q->predicates || q->filter[0].op != PG_FILTER_LEAF || q->filter[0].predicate < 0 || q->filter[0].predicate >= q->num_predicates) return false;
+  const pg_predicate& pr = q->predicates[q->filter[0].predicate];
+  if (pr.kind != PG_PRED_DOC_SET) return false;
+  for (int a = 0; a < na; ++a) if (q->aggregations[a].function != PG_AGG_COUNT || ((q->flags & kQueryCountReadsColumn) && q->aggregations[a].column >= 0)) return false;
+  const std::shared_ptr<DocSet> ds = find_doc_set(seg, pr.lo);
+  if (!ds) return false;                              // (the lowering reports the unknown id)
+  const int64_t card = pr.exclusive ? (int64_t)seg->num_docs - ds->cardinality : ds->cardinality;
+  memset(out, 0, sizeof(*out));
+  out->num_aggregations = na;
+  out->aggregations = (pg_agg_value*)calloc((size_t)na, sizeof(pg_agg_value));
+  for (int a = 0; a < na; ++a) empty_agg_value(&out->aggregations[a], card);
+  out->dominant_kernel = PG_KERNEL_INDEX_AND;
+  nothing_scanned(out, card, seg->num_docs);
+  if (out_cardinality) *out_cardinality = card;
   return true;
 }
 // FastFilteredCountOperator (core/plan/AggregationPlanNode.java:98-115, core/operator/query/FastFilteredCountOperator.java:66-72): COUNT(*)
@@ -3177,6 +3262,18 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   finish_geometry(seg, &lw, 0, need_queue, kBlockThreads / 64, waves_scan_agg(pl.num_agg_cols <= 1, typed), &geo);
   ScanChoice k = choose_scan_kernel(seg, lw, r.hist_col, typed, want_bitmap, out != nullptr);
   if (k.kernel == ScanKernel::Agg && (size_t)sp.wave_lds_bytes > kLdsBudget) return fail(PG_ERR_UNSUPPORTED, "query needs %d bytes of LDS per wavefront", sp.wave_lds_bytes);
+  if (k.kernel == ScanKernel::SimpleValid) {
+    // scan_simple_valid_kernel's parameter block: the doc set's words in bitmaps[0], the range leaf (if any) as the one node.  Every doc of
+    // the set is looked at once by the scan leaf behind it (ScanBasedDocIdIterator.applyAnd over the bitmap's docs): the entry count is the
+    // set's cardinality, known since pg_doc_set_create -- the kernel carries no counter.
+    sp.bitmaps[0] = pl.leaves[lw.valid_leaf].bitmap;
+    if (sp.num_nodes == 3) { sp.nodes[0] = sp.nodes[1]; sp.nodes[0].flags = 0; sp.num_nodes = 1; }
+    else sp.num_nodes = 0;
+    int64_t card = 0;
+    for (const auto& ds : lw.doc_sets) if (ds->d_words == pl.leaves[lw.valid_leaf].bitmap) card = ds->cardinality;
+    lw.stats_closed_entries = sp.num_nodes == 1 ? card : 0;
+    lw.stats_chain_flagged = false;
+  }
   const ScanGrid grid = scan_grid(seg, k, sp, geo, pl.num_agg_cols, r.hist_col);
   const int blocks = grid.blocks;
   if (k.kernel == ScanKernel::Hist) { sp.hist_slot = k.hist_slot; sp.hist_bins = seg->cols[(size_t)r.hist_col].cardinality; }
@@ -4190,6 +4287,7 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
   if (ng > kMaxGroupCols) return fail(PG_ERR_UNSUPPORTED, "more than %d group-by columns", kMaxGroupCols);
   const bool timed = (g_engine.flags & PG_CFG_TIME_KERNELS) != 0;
   if (ng == 0 && !want_bitmap && out && na > 0 && allow_metadata_plan && answer_from_metadata(seg, q, na, out, out_cardinality)) return PG_OK;
+  if (ng == 0 && !want_bitmap && out && na > 0 && answer_from_doc_set(seg, q, na, out, out_cardinality)) return PG_OK;
 
   QueryRun r(seg, q, out, ctx, defer, na, ng, want_bitmap, timed);
   Lowered& lw = r.lw;
@@ -5608,6 +5706,109 @@ pg_status pg_set_plane_budget(uint64_t budget_bytes, uint64_t* out_previous) {
   std::lock_guard<std::mutex> lk(g_planes.mu);
   if (out_previous) *out_previous = g_planes.budget_bytes;
   g_planes.budget_bytes = budget_bytes;
+  return PG_OK;
+}
+
+// ---- doc sets (include/pinot_gpu.h): the queryable docIds of an upsert / dedup segment ----
+static std::atomic<int64_t> g_next_doc_set_id{1};      // unique for the life of the process: an id that was released never names another set
+
+// The largest docId a parsed container holds (its payload lies inside the buffer: parse_roaring checked).
+static uint32_t container_last_doc(const uint8_t* data, const DevContainer& dc) {
+  const uint8_t* p = data + dc.offset;
+  uint32_t low = 0;
+  if (dc.type == 0) low = le16(p + 2ull * (dc.cardinality - 1));
+  else if (dc.type == 1) { for (int b = 8191; b >= 0; --b) if (p[b]) { low = (uint32_t)b * 8u + (31u - (uint32_t)__builtin_clz((unsigned)p[b])); break; } }
+  else if (dc.num_runs > 0) low = (uint32_t)le16(p + 2 + 4ull * (dc.num_runs - 1)) + (uint32_t)le16(p + 4 + 4ull * (dc.num_runs - 1));
+  return (dc.key << 16) + low;
+}
+
+pg_status pg_doc_set_create(pg_segment* segment, int32_t format, const void* data, uint64_t size, int64_t* out_id) {
+  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
+  if (!segment || !out_id || (size > 0 && !data)) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  if (format != PG_DOC_SET_ROARING && format != PG_DOC_SET_WORDS) return fail(PG_ERR_INVALID_ARGUMENT, "unknown doc set format %d", format);
+  const long long padded_words = (long long)std::max(segment->num_tiles, 1) * kMaxTileSteps;
+  const size_t doc_words = ((size_t)segment->num_docs + 63) / 64;
+  auto ds = std::make_shared<DocSet>();
+  ds->bytes = (uint64_t)padded_words * 8;
+  std::vector<DevContainer> kept;
+  if (format == PG_DOC_SET_WORDS) {
+    if (size != (uint64_t)doc_words * 8) return fail(PG_ERR_INVALID_ARGUMENT, "doc set: %llu bytes of words for %d docs (expected %zu)", (unsigned long long)size, segment->num_docs, doc_words * 8);
+    const uint8_t* bytes = (const uint8_t*)data;
+    for (size_t w = 0; w < doc_words; ++w) { uint64_t v; memcpy(&v, bytes + 8 * w, 8); ds->cardinality += __builtin_popcountll(v); }
+    if (doc_words > 0 && (segment->num_docs & 63)) {
+      uint64_t last; memcpy(&last, bytes + 8 * (doc_words - 1), 8);
+      if (last >> (segment->num_docs & 63)) return fail(PG_ERR_INVALID_ARGUMENT, "doc set: a bit beyond numDocs (%d) is set", segment->num_docs);
+    }
+  } else {
+    std::vector<DevContainer> dir;
+    const pg_status pst = parse_roaring((const uint8_t*)data, 0, size, &dir);
+    if (pst != PG_OK) return pst;
+    for (const DevContainer& dc : dir) {
+      if (dc.type == 2 && dc.num_runs == 0) continue;
+      if (segment->num_docs <= 0 || (dc.key << 16) >= (uint32_t)segment->num_docs || container_last_doc((const uint8_t*)data, dc) >= (uint32_t)segment->num_docs)
+        return fail(PG_ERR_INVALID_ARGUMENT, "doc set: a docId of container %u is beyond numDocs (%d)", dc.key, segment->num_docs);
+      kept.push_back(dc);
+      ds->cardinality += dc.cardinality;
+    }
+  }
+  HIP_TRY(hipSetDevice(phys_device(segment->device)));
+  hipError_t e = hipMalloc((void**)&ds->d_words, (size_t)ds->bytes);
+  if (e != hipSuccess) { (void)hipGetLastError(); ds->d_words = nullptr; return fail(PG_ERR_OUT_OF_MEMORY, "doc set: hipMalloc(%llu): %s", (unsigned long long)ds->bytes, hipGetErrorString(e)); }
+  e = hipMemset(ds->d_words, 0, (size_t)ds->bytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // (a large upload below runs on the staging pool's own streams: the zeros are there first)
+  if (format == PG_DOC_SET_WORDS) {
+    if (e == hipSuccess && size > 0) e = h2d_copy(ds->d_words, data, (size_t)size, phys_device(segment->device));
+  } else if (!kept.empty()) {
+    // the serialized bitmap and its container directory go up, roaring_expand_kernel writes the doc-order words (one 65536-doc window per workgroup)
+    uint8_t* d_bytes = nullptr;
+    DevContainer* d_cont = nullptr;
+    if (e == hipSuccess) e = hipMalloc((void**)&d_bytes, (size_t)size + 64);
+    if (e == hipSuccess) e = h2d_copy(d_bytes, data, (size_t)size, phys_device(segment->device));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_cont, kept.size() * sizeof(DevContainer));
+    if (e == hipSuccess) e = hipMemcpy(d_cont, kept.data(), kept.size() * sizeof(DevContainer), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      roaring_expand_kernel<<<dim3((unsigned)((padded_words + 1023) / 1024)), dim3(kBlockThreads), 0, 0>>>(d_bytes, d_cont, 0, (int)kept.size(), ds->d_words, padded_words, 0);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (d_bytes) (void)hipFree(d_bytes);
+    if (d_cont) (void)hipFree(d_cont);
+  }
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(PG_ERR_DEVICE, "doc set upload: %s", hipGetErrorString(e)); }
+  ds->id = g_next_doc_set_id.fetch_add(1);
+  segment->device_bytes += ds->bytes;
+  *out_id = ds->id;
+  std::lock_guard<std::mutex> lk(segment->doc_sets_mu);
+  segment->doc_sets.push_back(std::move(ds));
+  return PG_OK;
+}
+
+pg_status pg_doc_set_release(pg_segment* segment, int64_t id) {
+  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
+  if (!segment) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  std::shared_ptr<DocSet> ds;
+  {
+    std::lock_guard<std::mutex> lk(segment->doc_sets_mu);
+    for (size_t i = 0; i < segment->doc_sets.size(); ++i) if (segment->doc_sets[i]->id == id) { ds = std::move(segment->doc_sets[i]); segment->doc_sets.erase(segment->doc_sets.begin() + (long)i); break; }
+  }
+  if (!ds) return fail(PG_ERR_INVALID_ARGUMENT, "doc set %lld is unknown to segment %s (never created, or released)", (long long)id, segment->name.c_str());
+  segment->device_bytes -= ds->bytes;
+  // lowerings the segment remembers must not outlive the caller's reference: a later query with this id is refused, not served from the cache
+  std::lock_guard<std::mutex> lk(segment->plan_cache_mu);
+  auto& cache = segment->plan_cache;
+  cache.erase(std::remove_if(cache.begin(), cache.end(), [&](const std::shared_ptr<const LoweredItem>& it) {
+    for (const auto& held : it->doc_sets) if (held->id == id) return true;
+    return false;
+  }), cache.end());
+  return PG_OK;      // (the bitmap itself goes when the last query that reads it has finished: ~DocSet)
+}
+
+pg_status pg_doc_set_cardinality(const pg_segment* segment, int64_t id, int64_t* out_cardinality) {
+  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
+  if (!segment || !out_cardinality) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  const std::shared_ptr<DocSet> ds = find_doc_set(segment, id);
+  if (!ds) return fail(PG_ERR_INVALID_ARGUMENT, "doc set %lld is unknown to segment %s (never created, or released)", (long long)id, segment->name.c_str());
+  *out_cardinality = ds->cardinality;
   return PG_OK;
 }
 

@@ -281,7 +281,7 @@ enum class LeafClass { kMatchAll, kEmpty, kScan, kSorted, kBitmap };
 inline LeafClass classify(const pg_predicate& p) {
   if (p.kind == PG_PRED_MATCH_ALL || p.kind == PG_PRED_MATCH_NONE) return ((p.kind == PG_PRED_MATCH_ALL) != (p.exclusive != 0)) ? LeafClass::kMatchAll : LeafClass::kEmpty;
   if (p.kind == PG_PRED_DOC_RANGE) return LeafClass::kSorted;
-  if (p.kind == PG_PRED_IS_NULL || p.eval == PG_EVAL_INVERTED) return LeafClass::kBitmap;
+  if (p.kind == PG_PRED_IS_NULL || p.kind == PG_PRED_DOC_SET || p.eval == PG_EVAL_INVERTED) return LeafClass::kBitmap;      // (DOC_SET: BitmapBasedFilterOperator over the queryable docIds)
   return LeafClass::kScan;
 }
 

@@ -49,6 +49,10 @@ int waves_scan_sparse(bool one_slot);
 // scan_simple_kernel: one dictionary-range leaf (or none) + at most one aggregated packed column of <= 20 bits (pg_scan_simple.h)
 void launch_scan_simple(int blocks, int threads, hipStream_t stream, const ScanParams& p, bool set_leaf = false);      // threads: kBlockThreads or kWideBlockThreads; set_leaf: scan_simple_set_kernel (the one leaf is a dictId set, looked up in LDS)
 int waves_scan_simple();
+// scan_simple_valid_kernel: the same shape behind one PG_PRED_DOC_SET leaf (p.bitmaps[0] = the doc set; p.nodes[0] = the range leaf, if any);
+// skip_empty_tiles: the form whose tiles without a valid doc skip the filter column too
+void launch_scan_simple_valid(int blocks, int threads, hipStream_t stream, const ScanParams& p, bool skip_empty_tiles);
+int waves_scan_simple_valid();
 // scan_raw_kernel: one raw INT range leaf (or no filter) + at most one aggregated raw INT column, five waves per SIMD, coalesced reads (pg_scan_raw.h)
 void launch_scan_raw(int blocks, int threads, hipStream_t stream, const ScanParams& p);
 int waves_scan_raw();

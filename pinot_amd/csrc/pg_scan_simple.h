@@ -82,7 +82,12 @@ __device__ __forceinline__ void simple_agg_dispatch(int b, WP lane_words, uint32
 // batch launch: scan_lean_batch_kernel).  P: ScanParams, or its constant-address-space form there.
 // kSet: the one leaf is a dictId set over a column of at most 16 bits (scan_simple_set_kernel: a kernel of its own, so that the range form's
 // code and registers -- the headline's -- stay what they were); `set_lds`: kSetLdsWords words of the workgroup's LDS.
-template <bool kSet = false, typename P>
+// kValid: the filter is `range leaf AND doc set` or the doc set alone (scan_simple_valid_kernel: the queryable docIds of an upsert / dedup
+// segment, PG_PRED_DOC_SET, in front of the headline shape; again a kernel of its own).  p.bitmaps[0] = the doc set's doc-order words; a
+// lane's 32 docs of a tile are dword tile * 64 + lane of them (256 B per tile, coalesced), loaded with the filter column's chunk and
+// and-ed into the mask before the popcount.  p.nodes[0] is the range leaf (num_nodes == 1) or absent (num_nodes == 0).
+// kValidSkip: a tile without a valid doc does not load its filter column either (the column's load then waits for the doc set's).
+template <bool kSet = false, bool kValid = false, bool kValidSkip = false, typename P>
 __device__ __forceinline__ void scan_simple_body(const P& p, uint32_t block_index, uint32_t num_blocks, BlockPartial* red, uint32_t* fold_flag_ptr, uint32_t* set_lds = nullptr) {
   if constexpr (kSet) stage_filter_sets(p, set_lds);
   const int lane = threadIdx.x & 63;
@@ -102,6 +107,11 @@ __device__ __forceinline__ void scan_simple_body(const P& p, uint32_t block_inde
   // the fifth wave has not already bought, and the longer decode blocks cost more than they hide.)
   for (long long tile = (long long)block_index * waves_per_block + wave_in_block; tile < num_tiles; tile += total_waves) {
     uint32_t m = 0xFFFFFFFFu;
+    uint32_t valid = 0xFFFFFFFFu;
+    if constexpr (kValid) {
+      valid = reinterpret_cast<const uint32_t*>(p.bitmaps[0])[tile * 64 + lane];      // (the set is padded to whole tiles: bits past numDocs are zero)
+      if constexpr (kValidSkip) { if (__builtin_amdgcn_ballot_w64(valid != 0u) == 0ull) continue; }
+    }
     if (has_filter) {
       const GlobalWords words = global_words(L.fwd + tile * (256ll * L.bits)) + lane * L.bits;
       if constexpr (kSet) m = simple_set_dispatch(L.bits, words, set_lds);
@@ -110,6 +120,7 @@ __device__ __forceinline__ void scan_simple_body(const P& p, uint32_t block_inde
     }
     const long long rem = (long long)p.num_docs - (tile * 2048 + lane * 32);        // docs past numDocs (last tile only)
     m &= rem >= 32 ? 0xFFFFFFFFu : (rem <= 0 ? 0u : ((1u << (int)rem) - 1u));
+    if constexpr (kValid) m &= valid;
     count += (unsigned)__builtin_popcount(m);
     const unsigned long long lanes_with_matches = __builtin_amdgcn_ballot_w64(m != 0u);
     if (!has_agg || lanes_with_matches == 0ull) continue;

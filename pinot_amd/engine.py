@@ -89,6 +89,33 @@ class GpuSegment:
         _abi.check(self.lib, self.lib.pg_segment_device_bytes(self.handle, C.byref(out)))
         return int(out.value)
 
+    def create_doc_set(self, doc_ids=None, words=None):
+        """pg_doc_set_create: a doc set of this segment, from ascending docIds (sent as one serialized RoaringBitmap, expanded on the
+        device) or from dense np.uint64 words (bit d & 63 of word d >> 6, ceil(num_docs / 64) of them).  Returns its id (Pred.doc_set)."""
+        if (doc_ids is None) == (words is None):
+            raise ValueError("create_doc_set takes doc_ids or words")
+        if words is not None:
+            data, fmt = np.ascontiguousarray(words, dtype=np.uint64).view(np.uint8), _abi.PG_DOC_SET_WORDS
+        else:
+            from .segment import roaring_serialize
+            data, fmt = roaring_serialize(np.ascontiguousarray(doc_ids, dtype=np.int32), self.num_docs), _abi.PG_DOC_SET_ROARING
+        return self.create_doc_set_raw(fmt, data)
+
+    def create_doc_set_raw(self, fmt, data):
+        """pg_doc_set_create over bytes the caller serialized itself (np.uint8)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        out = C.c_int64(0)
+        _abi.check(self.lib, self.lib.pg_doc_set_create(self.handle, int(fmt), data.ctypes.data_as(C.c_void_p), int(data.shape[0]), C.byref(out)))
+        return int(out.value)
+
+    def release_doc_set(self, doc_set_id):
+        _abi.check(self.lib, self.lib.pg_doc_set_release(self.handle, int(doc_set_id)))
+
+    def doc_set_cardinality(self, doc_set_id):
+        out = C.c_int64(0)
+        _abi.check(self.lib, self.lib.pg_doc_set_cardinality(self.handle, int(doc_set_id), C.byref(out)))
+        return int(out.value)
+
     def plane_bytes(self):
         out = C.c_uint64()
         _abi.check(self.lib, self.lib.pg_segment_plane_bytes(self.handle, C.byref(out)))

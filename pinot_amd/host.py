@@ -129,6 +129,23 @@ class HostSegment:
             if st != 0:
                 raise HostError(st, (lib.ph_last_error() or b"").decode())
 
+    def set_queryable_doc_ids(self, doc_ids):
+        """The segment's queryable (valid) docIds, as an upsert / dedup table's metadata manager publishes them (ascending docIds, or a bool
+        mask); None clears them.  Every query over the segment then runs behind AND(filter, BITMAP(queryableDocIds))."""
+        import numpy as np
+        self.lib.ph_segment_set_queryable_doc_ids.restype = C.c_int32
+        self.lib.ph_segment_set_queryable_doc_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        if doc_ids is None:
+            st = self.lib.ph_segment_set_queryable_doc_ids(self.handle, None, 0)
+        else:
+            from .segment import roaring_serialize
+            doc_ids = np.asarray(doc_ids)
+            ids = np.flatnonzero(doc_ids) if doc_ids.dtype == bool else doc_ids
+            data = roaring_serialize(ids.astype(np.int32), self.data.num_docs)
+            st = self.lib.ph_segment_set_queryable_doc_ids(self.handle, data.ctypes.data_as(C.c_void_p), int(data.nbytes))
+        if st != 0:
+            raise HostError(st, (self.lib.ph_last_error() or b"").decode())
+
     def destroy(self):
         if self.handle:
             self.lib.ph_segment_destroy(self.handle)

@@ -139,6 +139,22 @@ class FakeJvm:
         finally:
             self.release(name, names, jints, jbufs)
 
+    def doc_set_create(self, handle, fmt, data):
+        """PinotGpuNative.docSetCreate over a direct ByteBuffer holding `data` (np.uint8)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        self.lib.fj_buffer.restype, self.lib.fj_buffer.argtypes = C.c_void_p, [C.c_void_p]
+        buf = C.c_void_p(self.lib.fj_buffer(data.ctypes.data))
+        try:
+            return int(self.call("docSetCreate", C.c_int64, C.c_int64(handle), C.c_int32(fmt), buf, C.c_int64(data.shape[0])))
+        finally:
+            self.release(buf)
+
+    def doc_set_release(self, handle, doc_set_id):
+        self.call("docSetRelease", None, C.c_int64(handle), C.c_int64(doc_set_id))
+
+    def doc_set_cardinality(self, handle, doc_set_id):
+        return int(self.call("docSetCardinality", C.c_int64, C.c_int64(handle), C.c_int64(doc_set_id)))
+
     def execute(self, handle, spec):
         """PinotGpuNative.execute: the Object[PGM_RESULT_ARRAYS] as a list of numpy arrays."""
         arrays, limit, flags = self.query_arrays(spec)

@@ -60,6 +60,12 @@ class Pred:
         return Pred(_abi.PG_PRED_DOC_RANGE, 0, first_doc, last_doc, exclusive=exclusive)
 
     @staticmethod
+    def doc_set(doc_set_id, exclusive=False):
+        """docId is in the doc set `doc_set_id` of the query's segment (GpuSegment.create_doc_set): the queryable docIds of an upsert /
+        dedup segment as a BitmapBasedFilterOperator (FilterPlanNode.java:88-106); exclusive=True: the flipped set over [0, numDocs)."""
+        return Pred(_abi.PG_PRED_DOC_SET, 0, doc_set_id, 0, exclusive=exclusive)
+
+    @staticmethod
     def raw_range_f64(column, lo, hi, exclusive=False):
         """lo <= value <= hi on a raw FLOAT / DOUBLE column (Float / DoubleRawValueBasedRangePredicateEvaluator)."""
         return Pred(_abi.PG_PRED_RAW_RANGE, column, f64_bits(lo), f64_bits(hi), exclusive=exclusive)

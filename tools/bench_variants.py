@@ -77,7 +77,7 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
         return lambda matched: B(col) if matched * 16 >= rows else min(B(col), matched * 64)
 
     # ---- C2 / C3 on 1 B rows: the headline's v and f, v under two dictionaries without structure, and the C3 columns ----
-    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list")):
+    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list", "C2b-valid-docs", "C2b-valid-docs-5pct")):
         t0 = time.time()
         v_irr = _shared(S, v, "v_irr", v_dictionary("irregular"))
         v_win = _shared(S, v, "v_win", v_dictionary("window"))
@@ -100,6 +100,38 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                     report(vid, "BASELINE.json configs[1], other selectivities", "SELECT SUM(v) WHERE f < %d" % t, n, lambda m, charge=charge: B(f) + charge(m), g, seg,
                            Q.QuerySpec([(Q.SUM, 0)], filter=Q.leaf(Q.Pred.dict_range(1, 0, t))),
                            extra={"dictionary": "affine", "algorithmic_bytes_note": "B(f) + (B(v) from 1/16 selectivity up, else min(B(v), matches x 64 B)): SURVEY.md 8(d)"})
+            for vid, density in (("C2b-valid-docs", 0.90), ("C2b-valid-docs-5pct", 0.05)):
+                if not want(vid):
+                    continue
+                # The headline behind the queryable docIds of an upsert table (PG_PRED_DOC_SET): a pseudo-random `density` of the docs are valid.
+                # Traffic floor: the headline's bytes + numDocs / 8 (the doc set, read once).  The oracle's twin of the set is an inverted leaf on
+                # a synthetic {0, 1} column (tests/doc_set_cases.py); here the check runs the scan form of that leaf (same docs by definition).
+                rng = np.random.default_rng(90 if density > 0.5 else 5)
+                valid = np.concatenate([rng.random(min(1 << 24, n - at)) < density for at in range(0, n, 1 << 24)]) if n > 0 else np.zeros(0, bool)
+                words = np.packbits(np.concatenate([valid, np.zeros((-n) % 64, bool)]), bitorder="little").view(np.uint64)
+                t_words = time.perf_counter()
+                words_id = g.create_doc_set(words=words)
+                words_s = time.perf_counter() - t_words
+                roaring = S.roaring_serialize(np.flatnonzero(valid).astype(np.int32), n)
+                t_roaring = time.perf_counter()
+                roaring_id = g.create_doc_set_raw(_abi.PG_DOC_SET_ROARING, roaring)
+                roaring_s = time.perf_counter() - t_roaring
+                g.release_doc_set(words_id)
+                twin = S.SegmentData("variants_valid", n, [v, f, S.Column.from_dict_ids("$validDocIds", np.array([0, 1], dtype=np.int32), valid.astype(np.int32))])
+                spec = Q.QuerySpec([(Q.SUM, 0)], filter=Q.and_(flt, Q.leaf(Q.Pred.doc_set(roaring_id))))
+                twin_spec = Q.QuerySpec([(Q.SUM, 0)], filter=Q.and_(flt, Q.leaf(Q.Pred.dict_range(2, 1, 2))))
+                charge = summed(v, n)
+                floor = (lambda m, charge=charge: B(f) + charge(m) + n // 8)
+                for switch, suffix in ((None, ""), ("0", "-general")):
+                    engine.reinit(PINOT_GPU_SCAN_SIMPLE_VALID=switch)
+                    try:
+                        report(vid + suffix, "BASELINE.json configs[1] behind the valid docs of an upsert table" + (" (PINOT_GPU_SCAN_SIMPLE_VALID=0: the general kernel)" if switch else ""),
+                               "SELECT SUM(v) WHERE f < 100 over a doc set holding a pseudo-random %g %% of the docs" % (100 * density), n, floor, g, twin, spec, oracle_spec=twin_spec,
+                               extra={"dictionary": "affine", "valid_docs": int(valid.sum()), "algorithmic_bytes_note": "the headline's bytes (SURVEY.md 8(d)) + numDocs / 8 for the doc set",
+                                      "doc_set_create_s": {"words_upload": words_s, "roaring_upload_and_expand": roaring_s, "roaring_bytes": int(roaring.nbytes)}})
+                    finally:
+                        engine.reinit(PINOT_GPU_SCAN_SIMPLE_VALID=None)
+                g.release_doc_set(roaring_id)
             if want("C2b-in-list"):
                 # InPredicateEvaluator over f's dictIds: a dictId-set leaf (the words staged in LDS once per workgroup: pg_kernels.h stage_filter_sets)
                 report("C2b-in-list", "BASELINE.json configs[1] with an IN list for a filter", "SELECT SUM(v) WHERE f IN (100 of f's 1000 values: every third of the first 300) (10%)", n, B(v) + B(f), g, seg,

@@ -340,6 +340,31 @@ def main():
             if g.check(spec) == 0:
                 check("nulls", g.execute(spec), oracle.execute(nseg, spec), None)
         ran += 1
+    # ---- doc sets (PG_PRED_DOC_SET: the queryable docIds of an upsert / dedup segment): scan_simple_valid_kernel in both of its forms, the general
+    # kernels behind the switch's other side, both upload formats (roaring_expand_kernel expands the serialized one).  The oracle's twin of the
+    # set is an inverted leaf over the same docs: the docs whose dictId of X is below 35.
+    if only is None or only.search("valid-docs"):
+        valid = S.synthetic_dict_ids(1 * 1000 + 14, 0, n, 50) < 35
+        words = np.packbits(np.concatenate([valid, np.zeros((-n) % 64, bool)]), bitorder="little").view(np.uint64)
+        twin_leaf = Q.leaf(Q.Pred.dict_range(X, 0, 35, inverted=True))
+        for env, lean in (({}, True), ({"PINOT_GPU_SCAN_SIMPLE_VALID": "2"}, True), ({"PINOT_GPU_SCAN_SIMPLE_VALID": "0"}, False)):
+            engine.reinit(**env)
+            try:
+                with engine.open(seg) as g:
+                    for fmt, dsid in (("roaring", g.create_doc_set(doc_ids=np.flatnonzero(valid).astype(np.int32))), ("words", g.create_doc_set(words=words))):
+                        for sid, make in (("range", lambda v: Q.QuerySpec([(Q.SUM, V), (Q.COUNT, -1)], filter=Q.and_(Q.leaf(Q.Pred.dict_range(F, 0, 100)), v))),
+                                          ("alone", lambda v: Q.QuerySpec([(Q.MIN, A), (Q.MAX, A)], filter=v)),
+                                          ("count", lambda v: Q.QuerySpec([(Q.COUNT, -1)], filter=Q.and_(v, Q.leaf(Q.Pred.dict_range(A, 10, 90, exclusive=True)))))):
+                            eid = "valid-docs-%s-%s%s" % (sid, fmt, "".join("-%s" % v for v in env.values()))
+                            spec = make(Q.leaf(Q.Pred.doc_set(dsid)))
+                            if g.check(spec) != 0:
+                                failed.append({"id": eid, "error": "pg_query_check declined"})
+                                continue
+                            check(eid, g.execute(spec), want_of("valid-docs-" + sid, make(twin_leaf)), "scan_simple_valid_kernel" if lean else None)
+                            ran += 1
+                        g.release_doc_set(dsid)
+            finally:
+                engine.reinit(**{k: flipped.get(k) for k in env})
     # ---- the transducer's kernels: byte-function walks, then table walks of the same machines ----
     if only is None or only.search("fsm"):
         count = args.fsm_trees if args.fsm_trees >= 0 else (400 if args.regime == "tiny" else 40)
