@@ -51,7 +51,8 @@ extern "C" {
 #define PG_ABI_VERSION 5   /* 2: pg_result.filter_entries_exact, pg_query_check, pg_config.plane_budget_bytes;
                             * 3: pg_execute_batch, pg_result.group_key_kind / group_ids64 / group_key_dict_ids (Long / ArrayMap holders);
                             * 4: PG_PRED_RAW_SET (IN / NOT IN on raw INT / LONG / FLOAT / DOUBLE columns); no struct layout changed;
-                            * 5: pg_doc_set_create / release / cardinality, PG_PRED_DOC_SET (upsert / dedup valid-doc sets); no struct layout changed */
+                            * 5: pg_doc_set_create / release / cardinality, PG_PRED_DOC_SET (upsert / dedup valid-doc sets); no struct layout changed;
+                            *    (still 5) PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids: no struct layout changed, one enumerator and one function added */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -204,8 +205,22 @@ typedef enum pg_agg_function {
   PG_AGG_SUM = 1,              /* SumAggregationFunction.java */
   PG_AGG_MIN = 2,              /* MinAggregationFunction.java */
   PG_AGG_MAX = 3,              /* MaxAggregationFunction.java */
-  PG_AGG_AVG = 4               /* AvgAggregationFunction.java (AvgPair = sum, count) */
+  PG_AGG_AVG = 4,              /* AvgAggregationFunction.java (AvgPair = sum, count) */
+  PG_AGG_DISTINCTCOUNT = 5     /* DistinctCountAggregationFunction.java on a dictionary-encoded (PG_FWD_FIXED_BIT_DICT) column of any stored type: the
+                                * set of the matching docs' dictIds (BaseDistinctAggregateAggregationFunction.java:144-155, :306-321).
+                                * pg_agg_value.count = the set's cardinality, sum = 0, sum_exact = 0, min = +inf, max = -inf; the set itself comes
+                                * from pg_result_distinct_dict_ids.  No filter (or one that matches everything), no GROUP BY, every function
+                                * answerable that way: the whole dictionary, nothing scanned (NonScanBasedAggregationOperator.java:106-112).
+                                * PG_ERR_UNSUPPORTED at plan time: a raw column; PG_QUERY_NULL_HANDLING when the column carries a null vector; a
+                                * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four DISTINCTCOUNT columns; GROUP BY
+                                * unless group_key_kind is 0, group_id_upper_bound <= numGroupsLimit (the limit can never bind), the keys are
+                                * dictionary columns or raw INT / LONG columns keyed by offset, without null docs under PG_QUERY_NULL_HANDLING,
+                                * at most four of them, and the bit matrices fit PG_DISTINCT_GROUP_MAX_BYTES. */
 } pg_agg_function;
+
+/* GROUP BY with PG_AGG_DISTINCTCOUNT: group_id_upper_bound x ceil(cardinality / 32) x 4 bytes, summed over the query's DISTINCTCOUNT columns,
+ * may not exceed this (a capacity limit: it bounds the host copy of the result; PINOT_GPU_GROUP_TABLE_BYTES bounds the device's). */
+#define PG_DISTINCT_GROUP_MAX_BYTES (1ull << 30)
 
 typedef struct pg_aggregation {
   int32_t function;            /* pg_agg_function */
@@ -260,6 +275,8 @@ typedef struct pg_query {
  * pg_result.filter_entries_exact = 0.  Everything else of the result is unchanged, and filters whose count
  * is a closed form or falls out of the kernel (no scan leaf, no AND above one, scan leaves behind index-based children) stay exact. */
 #define PG_QUERY_STATS_UPPER_BOUND_OK 2
+/* Every other bit of pg_query.flags is reserved (the library uses some between its own passes): a query that sets one is answered
+ * PG_ERR_INVALID_ARGUMENT by pg_query_check, pg_execute, pg_execute_batch and pg_filter_bitmap. */
 
 /* Intermediate result of one aggregation function, in the reference's holder types:
  * SUM/MIN/MAX -> Double, COUNT -> Long, AVG -> AvgPair(sum, count). */
@@ -290,6 +307,8 @@ typedef enum pg_kernel_id {
   PG_KERNEL_SCAN_RAW = 11,         /* scan_raw_kernel: one raw INT range leaf + at most one aggregated raw INT column, five waves per SIMD, coalesced reads */
   PG_KERNEL_SCAN_SIMPLE_VALID = 13,/* scan_simple_valid_kernel: scan_simple_kernel's shape behind one PG_PRED_DOC_SET leaf (a dword of the doc set per lane and tile) */
   PG_KERNEL_SCAN_SIMPLE = 10,      /* scan_simple_kernel: one dictionary-range leaf + at most one aggregated packed column, twice the waves per SIMD */
+  PG_KERNEL_SCAN_DISTINCT = 14,    /* scan_distinct_kernel: DISTINCTCOUNT of dictionary columns, dictId bitsets in LDS or in HBM (PINOT_GPU_DISTINCT_LDS=0: always HBM) */
+  PG_KERNEL_GROUP_DISTINCT = 15,   /* group_distinct_kernel: the same under GROUP BY, one bitset row per raw group id in HBM */
   PG_KERNEL_SCAN_HIST = 6          /* scan_hist_kernel: lane-private scan, SUM = sum_d matches[d] * dictionary[d] through an LDS histogram */
 } pg_kernel_id;
 
@@ -384,6 +403,13 @@ pg_status pg_query_check(const pg_segment* segment, const pg_query* query);
 
 pg_status pg_execute(pg_segment* segment, const pg_query* query, pg_result* out_result);
 void pg_result_free(pg_result* result);
+
+/* The dictId set behind a PG_AGG_DISTINCTCOUNT aggregation: bit (d & 31) of out_words[d >> 5], *out_num_words = ceil(cardinality / 32),
+ * bits at and above the cardinality are zero.  group_row = -1 for an aggregation-only query, else a row of group_aggregations.
+ * Engine-owned, valid until pg_result_free.  Any other aggregation index or row: PG_ERR_INVALID_ARGUMENT.
+ * (dictIds differ from segment to segment: a merge looks the values up in the segment's dictionary first.) */
+pg_status pg_result_distinct_dict_ids(const pg_result* result, int32_t aggregation, int32_t group_row,
+                                      const uint32_t** out_words, int32_t* out_num_words);
 
 /* How a group-by column's entries of pg_result.group_key_dict_ids turn into key values.  A dictionary column: *out_is_offset = 0, the
  * entry is a dictId (GroupKeyGenerator.getGroupKeys looks it up, DictionaryBasedGroupKeyGenerator.java:260-290).  A raw (no-dictionary)

@@ -78,6 +78,11 @@ uint8_t* ph_datatable_v4_build(int32_t is_group_by, int32_t num_functions, const
 char* ph_group_by_combine(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
                           const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
                           const double* mins, const double* maxs, const uint8_t* is_null, int32_t* status);
+/* The same with the cells of DISTINCTCOUNT functions given as value sets: cell (row, function) holds the LONG values
+ * set_values[set_offsets[row * functions + function] .. set_offsets[.. + 1]); the combine merges them by union, the final result is the size. */
+char* ph_group_by_combine_sets(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                          const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                          const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* set_offsets, const int64_t* set_values, int32_t* status);
 int32_t ph_group_by_table_capacity(int32_t limit, int32_t min_num_groups);          /* GroupByUtils.getTableCapacity */
 int32_t ph_group_by_trim_threshold(int32_t trim_size, int32_t trim_threshold);      /* GroupByUtils.getIndexedTableTrimThreshold */
 

@@ -18,7 +18,9 @@ import java.util.ArrayList;
 import java.util.Arrays;
 import java.util.Collection;
 import java.util.Collections;
+import java.util.HashSet;
 import java.util.List;
+import java.util.Set;
 import org.apache.commons.lang3.tuple.Pair;
 import org.apache.pinot.common.request.context.ExpressionContext;
 import org.apache.pinot.common.request.context.FilterContext;
@@ -73,6 +75,8 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     double[] _mins;
     double[] _maxs;
     int _width;                   // aggregations per row in this lane's arrays
+    Object[] _distinctSets;       // DISTINCTCOUNT lanes: int[] words of aggregation a, row r at a * rows + r (null for other functions); else null
+    int _rows;                    // rows of _distinctSets per aggregation: 1 without GROUP BY, else the lane's groups
   }
 
   private final GpuSegment _segment;
@@ -164,8 +168,11 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       throw new UnsupportedOperationException("segment " + _segment.getSegmentName() + " is no longer resident on the device");
     }
     try {
-      Object[] raw = PinotGpuNative.execute(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
-          q._aggregations, q._groupBy, q._numGroupsLimit, q._flags);
+      Object[] raw = q._hasDistinctCount
+          ? PinotGpuNative.executeWithDistinctSets(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
+              q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
+          : PinotGpuNative.execute(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
+              q._aggregations, q._groupBy, q._numGroupsLimit, q._flags);
       _segment.refreshDeviceBytes();
       return raw;
     } finally {
@@ -177,6 +184,14 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     GpuQueryLowering.Lowered q = _lanes.get(laneIndex)._query;
     // in a batch: the first lane of the first segment a combine task reaches makes the native call for every lane of every segment
     Object[] raw = _batch != null ? _batch.take(_batchSlots[laneIndex]) : executeAlone(q);
+    Object[] distinctSets = null;
+    if (q._hasDistinctCount) {
+      if (raw == null || raw.length != PinotGpuNative.PGM_DISTINCT_SLOTS) {
+        throw new IllegalStateException("native DISTINCTCOUNT result does not match jni/pinot_gpu_jni.c");
+      }
+      distinctSets = (Object[]) raw[PinotGpuNative.PGM_DISTINCT_SETS];
+      raw = (Object[]) raw[PinotGpuNative.PGM_DISTINCT_RESULT];
+    }
     if (raw == null || raw.length != PinotGpuNative.PGM_RESULT_ARRAYS) {
       throw new IllegalStateException("native result does not match jni/pg_marshal.h");
     }
@@ -189,6 +204,8 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     result._mins = (double[]) raw[PinotGpuNative.PGM_R_MINS];
     result._maxs = (double[]) raw[PinotGpuNative.PGM_R_MAXS];
     result._width = (int) result._header[PinotGpuNative.PGM_H_NUM_AGGREGATIONS];
+    result._distinctSets = distinctSets;
+    result._rows = _queryContext.getGroupByExpressions() == null ? 1 : result._groupIds.length;
     if (result._header.length != PinotGpuNative.PGM_HEADER_LEN) {
       throw new IllegalStateException("native result header does not match jni/pg_marshal.h");
     }
@@ -202,10 +219,45 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       int[] positions = _lanes.get(l)._positions;
       LaneResult result = results.get(l);
       for (int i = 0; i < positions.length; i++) {
-        out[positions[i]] = intermediate(_functions[positions[i]].getType(), result, i, nullHandling);
+        AggregationFunctionType type = _functions[positions[i]].getType();
+        out[positions[i]] = type == AggregationFunctionType.DISTINCTCOUNT ? valueSet(positions[i], result, i, 0) : intermediate(type, result, i, nullHandling);
       }
     }
     return new AggregationResultsBlock(_functions, Arrays.asList(out), _queryContext);
+  }
+
+  /**
+   * DISTINCTCOUNT: the dictId set of aggregation {@code at}, row {@code row} of the lane -> the value set the reference's function hands on
+   * (BaseDistinctAggregateAggregationFunction.convertToValueSet :75-89: every dictId looked up in the segment's dictionary, into the set
+   * type of the column's stored type -- what a DictIdsWrapper turns into in extractAggregationResult).
+   */
+  private Set<?> valueSet(int function, LaneResult r, int at, int row) {
+    int[] words = (int[]) r._distinctSets[at * r._rows + row];
+    String column = _functions[function].getInputExpressions().get(0).getIdentifier();
+    Dictionary dictionary = _indexSegment.getDataSource(column).getDictionary();
+    FieldSpec.DataType storedType = dictionary.getValueType();
+    // (java.util sets of boxed values: Set.addAll / size are all the function's merge and final result ask of them)
+    Set<Object> values = new HashSet<>();
+    for (int w = 0; w < words.length; w++) {
+      for (int bits = words[w]; bits != 0; bits &= bits - 1) {
+        int dictId = w * Integer.SIZE + Integer.numberOfTrailingZeros(bits);
+        switch (storedType) {
+          case INT:
+            values.add(dictionary.getIntValue(dictId));
+            break;
+          case LONG:
+            values.add(dictionary.getLongValue(dictId));
+            break;
+          case FLOAT:
+            values.add(dictionary.getFloatValue(dictId));
+            break;
+          default:
+            values.add(dictionary.getDoubleValue(dictId));
+            break;
+        }
+      }
+    }
+    return values;
   }
 
   /** The object extractAggregationResult of the reference's function returns (null for an empty SUM / MIN / MAX / AVG under null handling). */
@@ -252,7 +304,14 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       for (int i = 0; i < positions.length; i++) {
         AggregationFunctionType type = _functions[positions[i]].getType();
         boolean object = type == AggregationFunctionType.AVG || (nullHandling && type != AggregationFunctionType.COUNT);
-        if (object) {
+        if (type == AggregationFunctionType.DISTINCTCOUNT) {
+          // one value set per group (svAggregateGroupBySV :306-321 keeps a dictId bitmap per group; extractGroupByResult converts it)
+          ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);
+          for (int g = 0; g < rowOf.length; g++) {
+            holder.setValueForKey(rowOf[g], valueSet(positions[i], r, i, g));
+          }
+          holders[positions[i]] = holder;
+        } else if (object) {
           // AVG always, and SUM / MIN / MAX under null handling (NullableSingleInputAggregationFunction), keep an ObjectGroupByResultHolder
           // that stays null until a value arrives
           ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);

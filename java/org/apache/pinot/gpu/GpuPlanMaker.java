@@ -189,7 +189,16 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
       }
     }
     // makeInstancePlan below is planning a whole query: its lanes join the query's batch, in plan order
-    GpuBatch batch = _planningBatch.get();
+    GpuBatch planningBatch = _planningBatch.get();
+    boolean distinctCount = false;
+    for (GpuAggregationOperator.Lane lane : lanes) {
+      distinctCount |= lane._query._hasDistinctCount;
+    }
+    if (distinctCount && queryContext.hasFilteredAggregations()) {
+      return cpuPlan;      // DISTINCTCOUNT beside FILTER (WHERE ...) lanes keeps the CPU plan
+    }
+    // (a DISTINCTCOUNT lane reads its sets before the native result is released: one call of its own, PinotGpuNative.executeWithDistinctSets)
+    final GpuBatch batch = distinctCount ? null : planningBatch;
     int[] batchSlots = null;
     if (batch != null) {
       batchSlots = new int[lanes.size()];

@@ -62,6 +62,7 @@ final class GpuQueryLowering {
   static final int AGG_MIN = PinotGpuNative.PG_AGG_MIN;
   static final int AGG_MAX = PinotGpuNative.PG_AGG_MAX;
   static final int AGG_AVG = PinotGpuNative.PG_AGG_AVG;
+  static final int AGG_DISTINCTCOUNT = PinotGpuNative.PG_AGG_DISTINCTCOUNT;
   private static final int NODE_INTS = PinotGpuNative.PGM_FILTER_NODE_INTS;
   private static final int PRED_INTS = PinotGpuNative.PGM_PRED_INTS;
   private static final int PRED_LONGS = PinotGpuNative.PGM_PRED_LONGS;
@@ -86,6 +87,7 @@ final class GpuQueryLowering {
     int[] _groupBy;
     int _numGroupsLimit;
     int _flags;
+    boolean _hasDistinctCount;      // a DISTINCTCOUNT among the aggregations: executed alone through executeWithDistinctSets, never in a batch
   }
 
   /** Thrown inside the lowering when a construct has no device form; the plan maker keeps the CPU plan. */
@@ -202,6 +204,9 @@ final class GpuQueryLowering {
         case AVG:
           code = AGG_AVG;
           break;
+        case DISTINCTCOUNT:
+          code = AGG_DISTINCTCOUNT;
+          break;
         default:
           throw new NotOffloadable("aggregation function " + function.getType());
       }
@@ -220,6 +225,13 @@ final class GpuQueryLowering {
         column = _segment.columnIndex(inputs.get(0).getIdentifier());
         if (!_segment.isNumeric(column)) {
           throw new NotOffloadable("aggregation of a non-numeric column");   // the reference throws BadQueryRequestException itself
+        }
+        if (code == AGG_DISTINCTCOUNT) {
+          // dictId bitsets on the device: a dictionary column only (a raw column keeps the reference's hash set of values: CPU plan)
+          if (!_segment.hasDictionary(column)) {
+            throw new NotOffloadable("DISTINCTCOUNT on a column without a dictionary");
+          }
+          out._hasDistinctCount = true;
         }
       }
       out._aggregations[AGG_INTS * i] = code;

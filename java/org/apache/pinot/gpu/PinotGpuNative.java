@@ -81,6 +81,8 @@ public final class PinotGpuNative {
   public static final int PG_AGG_MIN = 2;
   public static final int PG_AGG_MAX = 3;
   public static final int PG_AGG_AVG = 4;
+  /** DistinctCountAggregationFunction on a dictionary column: the segment's (or the group's) dictId set comes back through executeWithDistinctSets. */
+  public static final int PG_AGG_DISTINCTCOUNT = 5;
 
   /** pg_query.flags */
   public static final int PG_QUERY_NULL_HANDLING = 1;
@@ -202,6 +204,19 @@ public final class PinotGpuNative {
    * long[] sumsI64, int[] sumExact, double[] mins, double[] maxs, int[] groupKeys (rows x group-by columns dictIds)}; throws UnsupportedOperationException for PG_ERR_UNSUPPORTED, RuntimeException (pg_last_error) otherwise.
    */
   static native Object[] execute(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
+      int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
+
+  /** Slots of executeWithDistinctSets' Object[]: the Object[PGM_RESULT_ARRAYS] of execute(), then the sets. */
+  public static final int PGM_DISTINCT_SLOTS = 2;
+  public static final int PGM_DISTINCT_RESULT = 0;
+  public static final int PGM_DISTINCT_SETS = 1;
+
+  /**
+   * pg_execute of a query with PG_AGG_DISTINCTCOUNT aggregations plus pg_result_distinct_dict_ids over its result.  Returns Object[PGM_DISTINCT_SLOTS]:
+   * what execute() returns, and Object[aggregations * rows] whose element {@code aggregation * rows + row} is the int[] of the set's words
+   * (bit d &amp; 31 of word d &gt;&gt; 5) for a DISTINCTCOUNT aggregation and null for every other function; rows = 1 without GROUP BY, else the groups.
+   */
+  static native Object[] executeWithDistinctSets(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
       int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
 
   /**

@@ -38,6 +38,8 @@ enum {
   PGM_FILTER_NODE_INTS = 3, PGM_PRED_INTS = 4, PGM_PRED_LONGS = 2, PGM_AGG_INTS = 2, PGM_COLUMN_INTS = 6, PGM_COLUMN_BUFFERS = 8,
   PGM_RESULT_ARRAYS = 9
 };
+/* PinotGpuNative.executeWithDistinctSets: Object[PGM_DISTINCT_SLOTS] = {the Object[PGM_RESULT_ARRAYS] of execute(), the DISTINCTCOUNT sets} */
+enum { PGM_DISTINCT_SLOTS = 2, PGM_DISTINCT_RESULT = 0, PGM_DISTINCT_SETS = 1 };
 /* One query of a batch call (PinotGpuNative.executeBatch): Object[PGM_QUERY_ARRAYS] = the seven flat arrays above in this order, then
  * int[PGM_Q_LIMIT_FLAGS_LEN] {numGroupsLimit, flags}. */
 enum {

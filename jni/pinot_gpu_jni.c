@@ -361,6 +361,52 @@ JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_execute(
   return result_to_java(env, &result, num_group_by);
 }
 
+/* pg_execute of a query with PG_AGG_DISTINCTCOUNT aggregations, and pg_result_distinct_dict_ids over its result before that is released.
+ * Returns Object[PGM_DISTINCT_SLOTS]: {the Object[PGM_RESULT_ARRAYS] execute() returns, Object[aggregations * rows]} -- element (aggregation * rows + row) of the
+ * second array is the int[] of the set's words (bit d & 31 of word d >> 5) for a DISTINCTCOUNT aggregation, null for every other function;
+ * rows = 1 for an aggregation-only query, else the number of groups. */
+JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeWithDistinctSets(JNIEnv* env, jclass cls, jlong handle, jintArray filterNodes,
+    jintArray predInts, jlongArray predLongs, jintArray setOffsets, jintArray setWords, jintArray aggregations, jintArray groupBy,
+    jint numGroupsLimit, jint flags) {
+  (void)cls;
+  pinned_query p;
+  if (!pin_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy, numGroupsLimit, flags)) return NULL;
+  const int32_t num_group_by = pgm_query_get(p.built)->num_group_by;
+  pg_result result;
+  const pg_status status = pg_execute((pg_segment*)(intptr_t)handle, pgm_query_get(p.built), &result);
+  release_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy);
+  if (status != PG_OK) { throw_status(env, status); return NULL; }     /* pg_execute freed the result */
+  const jsize rows = num_group_by > 0 ? (jsize)result.num_groups : 1;
+  const jsize na = (jsize)result.num_aggregations;
+  jclass object_class = (*env)->FindClass(env, "java/lang/Object");
+  jobjectArray sets = object_class ? (*env)->NewObjectArray(env, na * rows, object_class, NULL) : NULL;
+  int ok = sets != NULL;
+  for (jsize a = 0; ok && a < na; ++a) {
+    for (jsize r = 0; ok && r < rows; ++r) {
+      const uint32_t* words = NULL;
+      int32_t num_words = 0;
+      if (pg_result_distinct_dict_ids(&result, (int32_t)a, num_group_by > 0 ? (int32_t)r : -1, &words, &num_words) != PG_OK) break;      /* not a DISTINCTCOUNT: the row of nulls stays */
+      jintArray w = (*env)->NewIntArray(env, (jsize)num_words);
+      jint* dst = w ? (*env)->GetIntArrayElements(env, w, NULL) : NULL;
+      if (dst == NULL) { ok = 0; break; }
+      memcpy(dst, words, (size_t)num_words * sizeof(jint));
+      (*env)->ReleaseIntArrayElements(env, w, dst, 0);
+      (*env)->SetObjectArrayElement(env, sets, a * rows + r, w);
+      (*env)->DeleteLocalRef(env, w);
+    }
+  }
+  jobjectArray converted = result_to_java(env, &result, num_group_by);      /* releases the result */
+  if (!ok || converted == NULL) {
+    if (!(*env)->ExceptionCheck(env)) throw_new(env, "java/lang/OutOfMemoryError", "allocating the DISTINCTCOUNT sets failed");
+    return NULL;
+  }
+  jobjectArray out = (*env)->NewObjectArray(env, PGM_DISTINCT_SLOTS, object_class, NULL);
+  if (out == NULL) return NULL;
+  (*env)->SetObjectArrayElement(env, out, PGM_DISTINCT_RESULT, converted);
+  (*env)->SetObjectArrayElement(env, out, PGM_DISTINCT_SETS, sets);
+  return out;
+}
+
 /* pg_execute_batch: queries[i] (Object[PGM_QUERY_ARRAYS], slots PGM_Q_*) over handles[i] -- the segments of ONE query as the combine operator
  * would hand them to its worker threads (BaseCombineOperator.java:85-142).  Returns Object[n]: element i is the Object[PGM_RESULT_ARRAYS]
  * execute() would have returned for item i, or -- the item failed, the others did not stop for it -- a String "<pg_status>\n<message>".

@@ -38,6 +38,17 @@ std::string intermediateJson(const IntermediateResult& r) {
   if (isNullResult(r)) return "null";
   if (std::holds_alternative<int64_t>(r)) return std::to_string(std::get<int64_t>(r));
   if (std::holds_alternative<double>(r)) return num(std::get<double>(r));
+  if (std::holds_alternative<ValueSet>(r)) {
+    // the value set: INT / LONG values as they are, FLOAT / DOUBLE values from their bit images
+    const ValueSet& s = std::get<ValueSet>(r);
+    const bool floating = s.storedType == DataType::FLOAT || s.storedType == DataType::DOUBLE;
+    std::string out = "{\"values\": [";
+    for (size_t i = 0; i < s.values.size(); ++i) {
+      if (i) out += ", ";
+      if (floating) { double v; memcpy(&v, &s.values[i], 8); out += num(v); } else out += std::to_string(s.values[i]);
+    }
+    return out + "]}";
+  }
   const AvgPair& p = std::get<AvgPair>(r);
   return "[" + num(p.sum) + ", " + std::to_string(p.count) + "]";
 }
@@ -120,7 +131,7 @@ std::string reducedJson(const std::vector<ReducedRow>& rows) {
 ResultsBlock blockFromArrays(bool is_group_by, const std::vector<AggregationFunction>& functions, int32_t num_keys, const char* const* key_names,
                              const int32_t* key_types, int64_t row_begin, int64_t row_end, const int64_t* key_longs, const double* key_doubles,
                              const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums, const double* mins,
-                             const double* maxs, const uint8_t* is_null) {
+                             const double* maxs, const uint8_t* is_null, const int64_t* set_offsets = nullptr, const int64_t* set_values = nullptr) {
   ResultsBlock block;
   block.isGroupBy = is_group_by;
   const int num_functions = (int)functions.size();
@@ -128,6 +139,15 @@ ResultsBlock blockFromArrays(bool is_group_by, const std::vector<AggregationFunc
     const size_t at = (size_t)row * (size_t)num_functions + (size_t)f;
     if (is_null && is_null[at]) return std::monostate{};
     switch (functions[(size_t)f].getType()) {
+      case AggregationFunctionType::DISTINCTCOUNT: {
+        // cell `at` holds the LONG values set_values[set_offsets[at] .. set_offsets[at + 1]) (any order, duplicates allowed)
+        ValueSet s;
+        s.storedType = DataType::LONG;
+        if (set_offsets && set_values) s.values.assign(set_values + set_offsets[at], set_values + set_offsets[at + 1]);
+        std::sort(s.values.begin(), s.values.end());
+        s.values.erase(std::unique(s.values.begin(), s.values.end()), s.values.end());
+        return s;
+      }
       case AggregationFunctionType::COUNT: return counts[at];
       case AggregationFunctionType::SUM: return sums[at];
       case AggregationFunctionType::MIN: return mins[at];
@@ -599,9 +619,19 @@ uint8_t* ph_execute_sql_datatable(void** segments, int32_t num_segments, const c
 // [sum(block_rows[0..b)), +block_rows[b]) of the arrays; same array conventions as ph_datatable_v4_build, key_is_null marks NULL keys).
 // `sql` supplies the query context: aggregations (in the arrays' function order), GROUP BY columns, ORDER BY, LIMIT and the trim
 // options.  Returns {"combined": <block>, "reduced": [[key..., final...], ...], "table": {resultSize, trimSize, trimThreshold, numResizes}}.
+// ph_group_by_combine_sets: the same with the cells of DISTINCTCOUNT functions given as value sets -- cell (row, function) holds the LONG
+// values set_values[set_offsets[row * functions + function] .. set_offsets[.. + 1]); the combine merges them by union.
+char* ph_group_by_combine_sets(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                               const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                               const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* set_offsets, const int64_t* set_values, int32_t* status);
 char* ph_group_by_combine(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
                           const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
                           const double* mins, const double* maxs, const uint8_t* is_null, int32_t* status) {
+  return ph_group_by_combine_sets(sql, num_blocks, block_rows, key_types, key_longs, key_doubles, key_strings, key_is_null, counts, sums, mins, maxs, is_null, nullptr, nullptr, status);
+}
+char* ph_group_by_combine_sets(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                               const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                               const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* set_offsets, const int64_t* set_values, int32_t* status) {
   std::string out;
   *status = guarded([&] {
     const QueryContext q = getQueryContext(sql);
@@ -614,7 +644,7 @@ char* ph_group_by_combine(const char* sql, int32_t num_blocks, const int64_t* bl
     int64_t row = 0;
     for (int b = 0; b < num_blocks; ++b) {
       ResultsBlock block = blockFromArrays(true, functions, (int32_t)key_names.size(), key_names.data(), key_types, row, row + block_rows[b], key_longs, key_doubles,
-                                           key_strings, key_is_null, counts, sums, mins, maxs, is_null);
+                                           key_strings, key_is_null, counts, sums, mins, maxs, is_null, set_offsets, set_values);
       trimSegmentGroupByBlock(&block, q);          // the segment operator's own trim comes first (GroupByOperator.java:119-135)
       blocks.push_back(std::move(block));
       row += block_rows[b];

@@ -133,6 +133,8 @@ class Builder {      // DataTableBuilderV4 + BaseDataTableBuilder
 void put(std::map<int, std::pair<char, std::string>>* m, int id, char type, const std::string& value) { (*m)[id] = {type, value}; }
 
 void setIntermediate(Builder* b, int column, const AggregationFunction& f, const IntermediateResult& r, std::vector<int32_t>* nullRows, int row, bool isGroupBy) {
+  // ObjectSerDeUtils' set formats (IntSet, LongSet, ...: object types 10+) are not written here
+  if (f.getType() == AggregationFunctionType::DISTINCTCOUNT) throw UnsupportedOperationException("DataTable V4 bytes of a DISTINCTCOUNT value set are not written on this path");
   const ColumnType t = intermediateType(f.getType());
   if (isNullResult(r)) {                               // null handling: placeholder + the column's null bitmap (AggregationResultsBlock.java:119-122)
     // AggregationResultsBlock.getDataTable adds row 0 to the null bitmap for EVERY null result, OBJECT included (:119-122); only

@@ -43,6 +43,7 @@ std::vector<OrderByValue> TableResizer::orderByValues(const Record& r) const {
       const AggregationFunction& f = _functions.at((size_t)ob.index);
       if (isNullResult(v)) out.emplace_back(std::monostate{});
       else if (f.getType() == AggregationFunctionType::COUNT) out.emplace_back(std::get<int64_t>(v));
+      else if (f.getType() == AggregationFunctionType::DISTINCTCOUNT) out.emplace_back((int64_t)std::get<ValueSet>(v).values.size());      // an INT final result
       else out.emplace_back(f.extractFinalResult(v));
     }
   }
@@ -202,6 +203,7 @@ std::vector<ReducedRow> reduceGroupBy(const ResultsBlock& combined, const QueryC
     for (size_t a = 0; a < g.functions.size(); ++a) {
       if (isNullResult(r.values[a])) row.finals.emplace_back(std::monostate{});
       else if (g.functions[a].getType() == AggregationFunctionType::COUNT) row.finals.emplace_back(std::get<int64_t>(r.values[a]));
+      else if (g.functions[a].getType() == AggregationFunctionType::DISTINCTCOUNT) row.finals.emplace_back((int64_t)std::get<ValueSet>(r.values[a]).values.size());
       else row.finals.emplace_back(g.functions[a].extractFinalResult(r.values[a]));
     }
     rows.push_back(std::move(row));

@@ -206,7 +206,9 @@ struct FilterContext {                               // common/request/context/F
   Predicate predicate;
 };
 
-enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG };   // sspi/AggregationFunctionType.java
+enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT };   // sspi/AggregationFunctionType.java (ordinals = pg_agg_function)
+// DISTINCTCOUNT(col) / DISTINCT_COUNT(col) (the reference canonicalises function names by dropping underscores): the engine returns a segment's
+// dictId set (PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids), the mirror turns it into the value set that segments merge (ValueSet below).
 
 struct AggregationExpression {
   AggregationFunctionType function;
@@ -279,7 +281,11 @@ PredicateEvaluator getPredicateEvaluator(const Predicate& predicate, const DataS
 
 // ---- query/aggregation/function ----------------------------------------------------------------------------------
 struct AvgPair { double sum = 0.0; int64_t count = 0; };                  // segl/customobject/AvgPair.java:26-45
-using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate>;   // Long / Double / AvgPair / null (null handling only)
+// DISTINCTCOUNT's intermediate result: the VALUE set (BaseDistinctAggregateAggregationFunction.convertToValueSet :75-89 -- dictIds looked up in
+// the segment's dictionary), kept as the ascending 64-bit images of the values tagged with the stored type: INT / LONG the value, FLOAT /
+// DOUBLE the IEEE-754 bits of the value as a double.  merge = set union (:109-121); the final result is the size, an INT (:66-68).
+struct ValueSet { DataType storedType = DataType::INT; std::vector<int64_t> values; };
+using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet>;   // Long / Double / AvgPair / null (null handling only) / value set
 inline bool isNullResult(const IntermediateResult& r) { return std::holds_alternative<std::monostate>(r); }
 
 class AggregationFunction {                         // query/aggregation/function/AggregationFunction.java:42-145
@@ -290,6 +296,8 @@ class AggregationFunction {                         // query/aggregation/functio
   const std::string& getColumn() const { return _column; }
   std::string getResultColumnName() const;
   IntermediateResult fromDevice(const pg_agg_value& v) const;            // extractAggregationResult / extractGroupByResult
+  // DISTINCTCOUNT: the dictId set of pg_result_distinct_dict_ids (bit d & 31 of words[d >> 5]) -> the value set, through the column's dictionary
+  IntermediateResult fromDeviceSet(const uint32_t* words, int32_t numWords, const DataSource& dataSource) const;
   IntermediateResult merge(const IntermediateResult& a, const IntermediateResult& b) const;
   double extractFinalResult(const IntermediateResult& r) const;          // COUNT returns the long as a double-exact value
  private:
@@ -492,6 +500,7 @@ struct GpuAbi {
   decltype(&pg_execute) execute;
   decltype(&pg_execute_batch) execute_batch;
   decltype(&pg_result_free) result_free;
+  decltype(&pg_result_distinct_dict_ids) result_distinct_dict_ids;
   decltype(&pg_filter_bitmap) filter_bitmap;
   decltype(&pg_group_key_info) group_key_info;
   decltype(&pg_group_key_values) group_key_values;

@@ -47,6 +47,7 @@ const GpuAbi& gpuAbi() {
     abi.execute = (decltype(abi.execute))sym("pg_execute");
     abi.execute_batch = (decltype(abi.execute_batch))sym("pg_execute_batch");
     abi.result_free = (decltype(abi.result_free))sym("pg_result_free");
+    abi.result_distinct_dict_ids = (decltype(abi.result_distinct_dict_ids))sym("pg_result_distinct_dict_ids");
     abi.filter_bitmap = (decltype(abi.filter_bitmap))sym("pg_filter_bitmap");
     abi.group_key_info = (decltype(abi.group_key_info))sym("pg_group_key_info");
     abi.group_key_values = (decltype(abi.group_key_values))sym("pg_group_key_values");
@@ -161,7 +162,7 @@ void ImmutableSegment::setQueryableDocIds(const void* roaringBytes, uint64_t siz
 // AggregationFunction
 // ---------------------------------------------------------------------------------------------------------------
 std::string AggregationFunction::getResultColumnName() const {
-  static const char* names[] = {"count", "sum", "min", "max", "avg"};
+  static const char* names[] = {"count", "sum", "min", "max", "avg", "distinctcount"};
   return std::string(names[(int)_type]) + "(" + _column + ")";
 }
 
@@ -175,8 +176,26 @@ IntermediateResult AggregationFunction::fromDevice(const pg_agg_value& v) const 
     case AggregationFunctionType::MIN: return v.min;                       // Double, +inf when nothing matched
     case AggregationFunctionType::MAX: return v.max;                       // Double, -inf when nothing matched
     case AggregationFunctionType::AVG: return AvgPair{v.sum, v.count};     // AvgPair(sum, count)
+    case AggregationFunctionType::DISTINCTCOUNT: return ValueSet{};         // (no doc reached the holder: the empty set; a set comes through fromDeviceSet)
   }
   return 0.0;
+}
+
+IntermediateResult AggregationFunction::fromDeviceSet(const uint32_t* words, int32_t numWords, const DataSource& ds) const {
+  ValueSet set;
+  set.storedType = ds.dataType;
+  const bool floating = ds.dataType == DataType::FLOAT || ds.dataType == DataType::DOUBLE;
+  for (int32_t w = 0; w < numWords; ++w) {
+    for (uint32_t bits = words[w]; bits != 0u; bits &= bits - 1u) {
+      const int d = w * 32 + __builtin_ctz(bits);
+      int64_t image;
+      if (floating) { const double v = ds.dictionary->getDoubleValue(d); memcpy(&image, &v, 8); }
+      else image = ds.dictionary->getLongValue(d);
+      set.values.push_back(image);
+    }
+  }
+  std::sort(set.values.begin(), set.values.end());      // (a sorted dictionary gives ascending longs already; double images of negative values do not ascend)
+  return set;
 }
 
 IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const IntermediateResult& b) const {
@@ -184,6 +203,15 @@ IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const
   if (isNullResult(a)) return b;
   if (isNullResult(b)) return a;
   switch (_type) {
+    case AggregationFunctionType::DISTINCTCOUNT: {                                             // BaseDistinctAggregateAggregationFunction.merge :109-121: set union
+      const ValueSet& x = std::get<ValueSet>(a);
+      const ValueSet& y = std::get<ValueSet>(b);
+      ValueSet r;
+      r.storedType = x.values.empty() ? y.storedType : x.storedType;
+      r.values.reserve(x.values.size() + y.values.size());
+      std::set_union(x.values.begin(), x.values.end(), y.values.begin(), y.values.end(), std::back_inserter(r.values));
+      return r;
+    }
     case AggregationFunctionType::COUNT: return std::get<int64_t>(a) + std::get<int64_t>(b);   // CountAggregationFunction.merge
     case AggregationFunctionType::SUM: return std::get<double>(a) + std::get<double>(b);        // SumAggregationFunction.merge :223-233
     // Min / MaxAggregationFunction.merge (:237-251): `if (r1 < r2) return r1; return r2;` / `if (r1 > r2) ...` -- a primitive compare, not
@@ -205,6 +233,7 @@ double AggregationFunction::extractFinalResult(const IntermediateResult& r) cons
   if (isNullResult(r)) return std::nan("");           // the final result is null (printed as such by the callers)
   switch (_type) {
     case AggregationFunctionType::COUNT: return (double)std::get<int64_t>(r);
+    case AggregationFunctionType::DISTINCTCOUNT: return (double)std::get<ValueSet>(r).values.size();   // extractFinalResult :66-68: the set's size (an INT)
     case AggregationFunctionType::AVG: {                                    // AvgAggregationFunction.extractFinalResult :209-218
       const AvgPair& p = std::get<AvgPair>(r);
       return p.count == 0 ? -INFINITY : p.sum / (double)p.count;            // DEFAULT_FINAL_RESULT = Double.NEGATIVE_INFINITY
@@ -480,6 +509,12 @@ std::unique_ptr<LoweredQuery> lowerQuery(const ImmutableSegment& seg, const Quer
     if (root.kind != PhysNode::MATCH_ALL) flattenFilter(root, lq.get());      // a filter that matches everything is no filter (MatchAllFilterOperator)
   }
   for (const auto& a : qc.aggregations) {
+    if (a.function == AggregationFunctionType::DISTINCTCOUNT) {
+      // the engine takes a dictionary column of a numeric stored type (pg_query_check says so for raw columns; FILTER (WHERE ...) lanes beside
+      // a DISTINCTCOUNT are declined by makeSegmentPlanNode)
+      if (a.column == "*") throw QueryException("'*' is only valid in COUNT(*)");
+      if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException("DISTINCTCOUNT(" + a.column + ") on a STRING column keeps the CPU plan");
+    }
     pg_aggregation pa;
     pa.function = (int32_t)a.function;
     pa.column = a.column == "*" ? -1 : seg.getColumnIndex(a.column);
@@ -627,7 +662,7 @@ class GpuAggregationOperator : public Operator {
     if (_queryContext.groupByExpressions.empty()) {
       block.isGroupBy = false;
       block.aggregation.functions = functions;
-      for (int a = 0; a < na; ++a) block.aggregation.results.push_back(functions[(size_t)a].fromDevice(res.aggregations[a]));
+      for (int a = 0; a < na; ++a) block.aggregation.results.push_back(fromResult(functions[(size_t)a], res, a, -1, res.aggregations[a]));
     } else {
       block.isGroupBy = true;
       GroupByResultsBlock& g = block.groupBy;
@@ -675,7 +710,7 @@ class GpuAggregationOperator : public Operator {
         }
         g.groupKeys.push_back(std::move(key));
         std::vector<IntermediateResult> row;
-        for (int a = 0; a < na; ++a) row.push_back(functions[(size_t)a].fromDevice(res.group_aggregations[(size_t)i * (size_t)na + (size_t)a]));
+        for (int a = 0; a < na; ++a) row.push_back(fromResult(functions[(size_t)a], res, a, i, res.group_aggregations[(size_t)i * (size_t)na + (size_t)a]));
         g.results.push_back(std::move(row));
       }
     }
@@ -683,6 +718,15 @@ class GpuAggregationOperator : public Operator {
     _stats = block.stats;
     trimSegmentGroupByBlock(&block, _queryContext);      // GroupByOperator.java:119-135 (ORDER BY + minSegmentGroupTrimSize)
     return block;
+  }
+
+  // one function's holder out of the device result: DISTINCTCOUNT through the set accessor and the column's dictionary (before the result is freed)
+  IntermediateResult fromResult(const AggregationFunction& f, const pg_result& res, int aggregation, int groupRow, const pg_agg_value& v) const {
+    if (f.getType() != AggregationFunctionType::DISTINCTCOUNT) return f.fromDevice(v);
+    const uint32_t* words = nullptr;
+    int32_t numWords = 0;
+    checkStatus(gpuAbi().result_distinct_dict_ids(&res, aggregation, groupRow, &words, &numWords), "reading a DISTINCTCOUNT set");
+    return f.fromDeviceSet(words, numWords, _segment->getDataSource(f.getColumn()));
   }
 
   std::string toExplainString() const override { return _queryContext.groupByExpressions.empty() ? "GPU_AGGREGATE" : "GPU_GROUP_BY"; }
@@ -917,6 +961,8 @@ std::unique_ptr<PlanNode> GpuPlanMaker::makeSegmentPlanNode(const SegmentContext
   bool anyFiltered = false;
   for (const auto& a : qc.aggregations) anyFiltered |= a.hasFilter;
   if (!anyFiltered) return std::make_unique<GpuAggregationPlanNode>(seg, qc, lowerQuery(*seg, qc));
+  for (const auto& a : qc.aggregations)
+    if (a.function == AggregationFunctionType::DISTINCTCOUNT) throw UnsupportedOperationException("DISTINCTCOUNT in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
   std::vector<std::string> keys;                       // lane order = first appearance, the unfiltered lane keyed ""
   std::vector<QueryContext> laneQueries;
   std::vector<std::vector<int>> positions;

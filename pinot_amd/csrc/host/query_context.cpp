@@ -383,19 +383,26 @@ QueryContext getQueryContext(const std::string& sql) {
       selectedColumns.push_back(fn.text);
       continue;
     }
-    std::string u = fn.text;
-    for (auto& c : u) c = (char)toupper((unsigned char)c);
+    std::string u;
+    for (char c : fn.text) if (c != '_') u.push_back((char)toupper((unsigned char)c));      // AggregationFunctionType.getNormalizedAggregationFunctionName: underscores dropped
     AggregationExpression e;
     if (u == "COUNT") e.function = AggregationFunctionType::COUNT;
     else if (u == "SUM") e.function = AggregationFunctionType::SUM;
     else if (u == "MIN") e.function = AggregationFunctionType::MIN;
     else if (u == "MAX") e.function = AggregationFunctionType::MAX;
     else if (u == "AVG") e.function = AggregationFunctionType::AVG;
-    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG are offloaded, got " + fn.text);
+    else if (u == "DISTINCTCOUNT") e.function = AggregationFunctionType::DISTINCTCOUNT;
+    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT are offloaded, got " + fn.text);
     lx.expectSymbol("(");
     if (lx.acceptSymbol("*")) e.column = "*";
     else {
       const Token c = lx.next();
+      // COUNT(DISTINCT col): CalciteSqlParser rewrites it to DISTINCTCOUNT; that rewrite is not part of this path
+      if (e.function == AggregationFunctionType::COUNT && c.kind == Token::IDENT && lx.peek().kind == Token::IDENT) {
+        std::string d = c.text;
+        for (auto& ch : d) ch = (char)toupper((unsigned char)ch);
+        if (d == "DISTINCT") throw QueryException("COUNT(DISTINCT " + lx.peek().text + ") is not parsed on this path: write DISTINCTCOUNT(" + lx.peek().text + ")");
+      }
       if (c.kind != Token::IDENT) throw UnsupportedOperationException("only identifier arguments are offloaded (ProjectPlanNode.java:85-86)");
       e.column = c.text;
       if (!(lx.peek().kind == Token::SYMBOL && lx.peek().text == ")"))
@@ -454,8 +461,8 @@ QueryContext getQueryContext(const std::string& sql) {
       if (first.kind != Token::IDENT) throw QueryException("expected an ORDER BY expression near '" + first.text + "'");
       OrderByExpressionContext ob;
       if (lx.acceptSymbol("(")) {
-        std::string u = first.text;
-        for (auto& c : u) c = (char)toupper((unsigned char)c);
+        std::string u;
+        for (char c : first.text) if (c != '_') u.push_back((char)toupper((unsigned char)c));
         std::string column;
         if (lx.acceptSymbol("*")) column = "*";
         else {
@@ -467,7 +474,7 @@ QueryContext getQueryContext(const std::string& sql) {
         int found = -1;
         for (size_t a = 0; a < q.aggregations.size() && found < 0; ++a) {
           const AggregationExpression& e = q.aggregations[a];
-          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG"};
+          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT"};
           if (!e.hasFilter && u == names[(int)e.function] && (e.column == column || (e.function == AggregationFunctionType::COUNT && (column == "*" || e.column == "*")))) found = (int)a;
         }
         if (found < 0) {
@@ -475,9 +482,10 @@ QueryContext getQueryContext(const std::string& sql) {
           // generateAggregationFunctions: SELECT expressions first, then HAVING / ORDER BY); the result does not show it
           AggregationExpression e;
           int kind = -1;
-          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG"};
+          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG"};      // (a DISTINCTCOUNT that is only ordered by keeps the CPU plan)
           for (int k = 0; k < 5; ++k) if (u == names[k]) kind = k;
-          if (kind < 0) throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG are offloaded, got " + first.text);
+          if (u == "DISTINCTCOUNT") throw UnsupportedOperationException("a DISTINCTCOUNT that appears only in ORDER BY keeps the CPU plan (select it to order by it on this path)");
+          if (kind < 0) throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT are offloaded, got " + first.text);
           e.function = (AggregationFunctionType)kind;
           e.column = column;
           if (e.function != AggregationFunctionType::COUNT && column == "*") throw QueryException("'*' is only valid in COUNT(*)");

@@ -234,6 +234,31 @@ struct ScanParams {
                                    // SimpleSet 13: scan_lean_batch_kernel runs those three at five waves per SIMD)
 };
 
+// ---- DISTINCTCOUNT on dictionary columns (pg_scan_distinct.h): dictId bitsets ----
+constexpr int kMaxDistinctKeys = 4;      // group_distinct_kernel: group-by key columns
+struct DistinctCol {
+  const uint8_t* fwd;      // the column's packed dictId stream
+  uint32_t* set_bits;      // HBM, zero before the launch: bit (d & 31) of word d >> 5; GROUP BY: row g starts at word g * words
+  int32_t bits;            // packed width
+  int32_t words;           // ceil(cardinality / 32)
+  int32_t lds_off;         // LDS tier: first word of this column's bitset in the workgroup's dynamic LDS
+  int32_t pad;
+};
+struct DistinctKey {
+  const uint8_t* fwd;      // the key column's packed dictId stream (a raw INT key: its key image)
+  int32_t bits;
+  uint32_t mult;           // raw group id = sum over the keys of dictId * mult
+};
+struct DistinctParams {
+  ScanParams scan;         // the filter, the tile list, the record of count / filter entries (no aggregated column: num_agg_cols = 0)
+  int32_t num_cols;        // DISTINCTCOUNT columns, at most kMaxAggCols
+  int32_t num_keys;        // group_distinct_kernel only
+  int32_t lds_words;       // LDS tier: words of all bitsets together (they sit side by side from word 0)
+  int32_t pad;
+  DistinctCol cols[kMaxAggCols];
+  DistinctKey keys[kMaxDistinctKeys];
+};
+
 // raw_set_bitmap_kernel (pg_scan_raw_set.h): the match bitmap of one PG_PRED_RAW_SET leaf
 struct RawSetBitmapParams {
   const uint8_t* fwd;                   // the raw column's first value byte (padded to whole 2048-doc tiles)

@@ -77,6 +77,7 @@ struct Engine {
                              // does in a launch of its own, -1 (default) = 1: at every size
   int fold_one_counter = 1;  // PINOT_GPU_FOLD_ONE_COUNTER=0: grids of at most 64 workgroups also arrive on eight shard counters + the top one
   bool poll_result = true;   // PINOT_GPU_POLL_RESULT=0: pg_execute always waits with hipStreamSynchronize instead of spinning on the pinned record's sequence number
+  bool distinct_lds = true;  // PINOT_GPU_DISTINCT_LDS=0: DISTINCTCOUNT keeps its dictId bitsets in HBM at every cardinality (scan_distinct_kernel<false>; tests of that tier on small dictionaries)
   bool set_lds = true;       // PINOT_GPU_SET_LDS=0: dictId-set leaves (IN lists) of the lane-private scan kernels read their words from memory per doc (rounds 2-6a)
   bool lane_skip = true;     // PINOT_GPU_LANE_SKIP=0: the aggregating kernels load a tile's value bytes for every lane, matches or not
   bool batch_blocks_per_cu_forced = false;
@@ -261,6 +262,8 @@ struct ExecCtx {
   size_t leap_capacity = 0;
   WindowInfo* d_window_info = nullptr;          // index_and_kernel: {tile mask, matching docs} of every 65 536-doc window
   size_t tile_list_capacity = 0, window_info_capacity = 0;
+  uint32_t* d_distinct = nullptr;               // DISTINCTCOUNT: the query's dictId bitsets / bit matrices (pg_scan_distinct.h), zeroed ahead of every launch
+  size_t distinct_capacity = 0;                 // in 32-bit words (part of pg_segment.device_bytes)
 };
 
 }  // namespace
@@ -349,6 +352,7 @@ void destroy_ctx(ExecCtx* c) {
   if (c->d_and_counters) (void)hipFree(c->d_and_counters);
   if (c->h_and_shards) (void)hipHostFree(c->h_and_shards);
   if (c->d_window_info) (void)hipFree(c->d_window_info);
+  if (c->d_distinct) (void)hipFree(c->d_distinct);
   if (c->d_arena) (void)hipFree(c->d_arena);
   if (c->h_groups) (void)hipHostFree(c->h_groups);
   if (c->d_filter_entries) (void)hipFree(c->d_filter_entries);
@@ -416,6 +420,29 @@ pg_status ensure_bitmap(pg_segment* seg, ExecCtx* c, size_t index) {
     c->d_bitmaps.push_back(p);
   }
   return PG_OK;
+}
+
+// Words behind the last bitset row: the dictIds a column's WIDTH admits beyond its cardinality (a forward index that breaks the dictionary's
+// bound then still writes inside the allocation).  Counted in the plan-time byte checks (plan_distinct).
+inline size_t distinct_slack_words(int bits, int cardinality) {
+  const size_t by_width = (((size_t)1 << bits) + 31) / 32, by_card = ((size_t)std::max(cardinality, 0) + 31) / 32;
+  return (by_width > by_card ? by_width - by_card : 0) + 1;
+}
+constexpr size_t kDistinctKeepWords = (size_t)64 << 20;      // a bit matrix above 256 MB is freed after the query instead of staying with the context
+pg_status ensure_distinct(pg_segment* seg, ExecCtx* c, size_t words) {
+  if (c->distinct_capacity >= words) return PG_OK;
+  if (c->d_distinct) { (void)hipFree(c->d_distinct); seg->device_bytes -= c->distinct_capacity * 4; }
+  c->d_distinct = nullptr; c->distinct_capacity = 0;
+  HIP_TRY(hipMalloc((void**)&c->d_distinct, words * 4));
+  c->distinct_capacity = words;
+  seg->device_bytes += words * 4;
+  return PG_OK;
+}
+void trim_distinct(pg_segment* seg, ExecCtx* c) {
+  if (c->distinct_capacity <= kDistinctKeepWords) return;
+  (void)hipFree(c->d_distinct);
+  seg->device_bytes -= c->distinct_capacity * 4;
+  c->d_distinct = nullptr; c->distinct_capacity = 0;
 }
 
 pg_status ensure_set(ExecCtx* c, size_t index, size_t bytes) {
@@ -997,6 +1024,8 @@ struct Lowered {
   int valid_leaf = -1;
   int64_t stats_closed_entries = -1;           // >= 0: numEntriesScannedInFilter as a closed form (scan_simple_valid_kernel: the doc set's cardinality)
   uint32_t* sp_leaf_out[kMaxLeaves] = {};      // out: ScanParams.leaf_out, by LEAF node ordinal
+  // the bitset pass of a DISTINCTCOUNT query (kQueryDistinctPass): plan slots of its DISTINCTCOUNT columns and of group_distinct_kernel's keys
+  std::vector<int> distinct_slots, distinct_key_slots;
 };
 
 int slot_for(Lowered* lw, const pg_segment* seg, int column, bool plane = false) {
@@ -1990,6 +2019,7 @@ pg_status pg_init(const pg_config* config) {
   auto env_on = [](const char* name) { const char* v = getenv(name); return !(v && v[0] == '0'); };
   g_engine.lean_batch = env_on("PINOT_GPU_LEAN_BATCH");
   g_engine.set_lds = env_on("PINOT_GPU_SET_LDS");
+  g_engine.distinct_lds = env_on("PINOT_GPU_DISTINCT_LDS");
   g_engine.partition_two_level = env_on("PINOT_GPU_PARTITION_TWO_LEVEL");
   g_engine.fsm_perm = env_on("PINOT_GPU_FSM_PERM");
   g_engine.fsm_stats = env_on("PINOT_GPU_FSM_STATS");
@@ -2493,8 +2523,18 @@ pg_status pg_group_key_values(pg_segment* segment, int32_t column, int64_t* out_
   return PG_OK;
 }
 
+// What pg_result.internal points at: the dictId sets of the result's PG_AGG_DISTINCTCOUNT aggregations (pg_result_distinct_dict_ids).
+struct DistinctSet {
+  int aggregation = 0;                  // index into pg_query.aggregations
+  int num_words = 0;                    // ceil(cardinality / 32)
+  int rows = 1;
+  std::vector<uint32_t> words;          // [rows * num_words]: one row (aggregation only), or one per row of group_aggregations
+};
+struct ResultInternal { std::vector<DistinctSet> distinct; };
+
 void pg_result_free(pg_result* r) {
   if (!r) return;
+  delete static_cast<ResultInternal*>(r->internal);
   free(r->aggregations);
   free(r->group_ids);
   free(r->group_ids64);
@@ -2508,6 +2548,10 @@ constexpr int32_t kQueryHashHolder = 1 << 30;      // internal pg_query.flags bi
 // or not the column has null docs (CountAggregationFunction.getInputExpressions :69-71), so the column is projected and counts in
 // numEntriesScannedPostFilter; without the option COUNT(column) is COUNT(*) and reads nothing
 constexpr int32_t kQueryCountReadsColumn = 1 << 29;
+// internal pg_query.flags bit (execute_distinct -> execute_impl): the bitset pass of a PG_AGG_DISTINCTCOUNT query.  Its aggregations are COUNT(*)
+// and DISTINCTCOUNT only; group_by_columns are the key columns of group_distinct_kernel (the pass itself is an aggregation-only launch:
+// which groups exist, and every other function, is the ordinary query's business -- check_distinct_plan / execute_distinct).
+constexpr int32_t kQueryDistinctPass = 1 << 28;
 
 // ---- plan-time eligibility (pg_query_check) ----
 // Every reason pg_execute can answer PG_ERR_UNSUPPORTED for, decided from the query and the segment's metadata alone: no context, no
@@ -2613,7 +2657,8 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
     if (leaves > kMaxLeaves) return fail(PG_ERR_UNSUPPORTED, "more than %d filter leaves", kMaxLeaves);
     if (max_depth + (extra_and_leaves > 0 ? 1 : 0) > kStackDepth) return fail(PG_ERR_UNSUPPORTED, "filter tree deeper than %d", kStackDepth);
   }
-  const int na = q->num_aggregations, ng = q->num_group_by;
+  const bool distinct_pass = (q->flags & kQueryDistinctPass) != 0;      // (its keys were checked with the ordinary query: check_distinct_plan)
+  const int na = q->num_aggregations, ng = distinct_pass ? 0 : q->num_group_by;
   if (na < 0 || ng < 0 || (na > 0 && !q->aggregations) || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
   if (ng > kMaxGroupCols) return fail(PG_ERR_UNSUPPORTED, "more than %d group-by columns", kMaxGroupCols);
   std::vector<int> key_cols, agg_cols, key_cards;
@@ -2660,7 +2705,8 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
   std::vector<std::pair<int, int>> group_aggs;     // distinct (column, SUM | MIN | MAX)
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
+    if (ag.function < PG_AGG_COUNT || ag.function > (distinct_pass ? PG_AGG_DISTINCTCOUNT : PG_AGG_AVG) || (distinct_pass && ag.function != PG_AGG_COUNT && ag.function != PG_AGG_DISTINCTCOUNT))
+      return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.function == PG_AGG_COUNT) continue;
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
     if (std::find(agg_cols.begin(), agg_cols.end(), ag.column) == agg_cols.end()) agg_cols.push_back(ag.column);
@@ -2713,6 +2759,10 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
     else if (pr.kind == PG_PRED_DICT_SET && pr.eval != PG_EVAL_INVERTED) use(pr.column, false);
   }
   for (int c : key_cols) use(c, false);
+  if (distinct_pass) for (int g = 0; g < q->num_group_by; ++g) {
+    const int c = q->group_by_columns[g];
+    if (c >= 0 && c < num_cols_total) use(seg->cols[(size_t)c].encoding == PG_FWD_FIXED_BIT_DICT ? c : std::max(seg->cols[(size_t)c].keyimage_column, 0), false);
+  }
   for (int c : agg_cols) use(c, plane[(size_t)c] != 0);
   const int bound = (int)streams.size();
   if (bound > kMaxCols) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
@@ -2883,13 +2933,13 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
 // ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
 // preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
-enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Agg };
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Agg };
 // per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
 // leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
 static const struct { int id; bool writes_leaves; } kScanKernels[] = {
   {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
   {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_SIMPLE_VALID, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
-  {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_AGG, false}};
+  {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_DISTINCT, true}, {PG_KERNEL_GROUP_DISTINCT, true}, {PG_KERNEL_SCAN_AGG, false}};
 static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
 // general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
 // specialised kernel that won keeps it: the index handling, the leap-frog count and the batch's fallbacks go by the family.
@@ -2906,6 +2956,9 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
   // A kLeafRawSet leaf exists only in a query lowered for scan_raw_set_kernel (raw_set_lean_shape: the shape test below for scan_raw_kernel,
   // applied to the query before its filter was lowered); no other kernel evaluates that kind.
   if (sp.num_nodes == 1 && sp.nodes[0].op == PG_FILTER_LEAF && sp.nodes[0].kind == kLeafRawSet) { k.general = ScanKernel::Private; return pick(ScanKernel::RawSet); }
+  // The bitset pass of a DISTINCTCOUNT query: kernels of their own (pg_scan_distinct.h) with the lane-private filter -- check_distinct_plan
+  // declined the leaves that filter does not evaluate.  Everything that goes by the family (tile lists, the entry counts) is Private's.
+  if (!lw.distinct_slots.empty()) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Distinct : ScanKernel::GroupDistinct); }
   // The lane-private kernel (no LDS, plain global loads) takes every query whose leaves and aggregations it implements:
   // scan / set / bitmap leaves and raw INT ranges; COUNT, and SUM through a value plane / MIN / MAX on dictionary columns.
   // (the per-wave phase counters of PG_CFG_PROFILE_WAVES exist in the LDS-staged kernel only)
@@ -2994,7 +3047,7 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
 }
 // threads: the workgroup the kernel's records are counted in (profile_waves); lds: Agg's staged layout, or Hist's histogram with the set
 // area at hist_set_off; wide: scan_simple / scan_raw launch workgroups of kWideBlockThreads (PINOT_GPU_WIDE_BLOCKS=1)
-struct ScanGrid { int blocks = 1, threads = kBlockThreads; size_t lds = 0, hist_set_off = 0; bool wide = false; };
+struct ScanGrid { int blocks = 1, threads = kBlockThreads; size_t lds = 0, hist_set_off = 0; bool wide = false, distinct_lds = false; };
 // A segment whose tiles all fit the chip at once (one tile per wave: a 10 M-row segment at five waves per SIMD) is latency from end
 // to end -- launch, one round of loads, the hand-off of the workgroups' records to the fold.  Ten waves per workgroup there: 2.5x
 // fewer records, and a folding workgroup of 640 threads takes them in ONE round of loads (256 threads took five for 1221 records).
@@ -3012,7 +3065,8 @@ static void lean_grid(const pg_segment* seg, int wave_cap, ScanGrid* g) {
   g->blocks = grid_blocks(seg, tiles2k, wpb, bpc);
 }
 // The chosen kernel's grid (`geo`: the layout finish_geometry made for the LDS-staged kernel).  PrivateFsm is chosen after the grid: Private's.
-static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const ScanParams& sp, const Geometry& geo, int num_agg_cols, int hist_col) {
+static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Lowered& lw, const Geometry& geo, int num_agg_cols, int hist_col) {
+  const ScanParams& sp = lw.sp;
   ScanGrid g;
   const long long tiles = doc_tiles(seg);
   const int wpb = kBlockThreads / 64, hist_waves = kHistBlockThreads / 64;
@@ -3029,6 +3083,31 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Scan
       g.threads = kHistBlockThreads;
       g.blocks = grid_blocks(seg, tiles, hist_waves, std::max(1, std::min(waves_scan_hist(k.hist_cw, k.hist_guarded) / hist_waves, (int)((160 * 1024 - 2048) / (g.lds + 256)))));
       if (g_engine.hist_blocks > 0) g.blocks = std::min(g.blocks, g_engine.hist_blocks);
+      break;
+    }
+    case ScanKernel::Distinct: case ScanKernel::GroupDistinct: {
+      // LDS tier: the columns' bitsets side by side, the filter's set area behind them, the reduction records over their start at the end -- one
+      // bitset per workgroup of 16 wavefronts, as many workgroups per CU as LDS and registers admit (the Hist case's sizing).  Else the bitsets
+      // stay in HBM: workgroups of four wavefronts, the set area (if any) 16 bytes in (set_leaves_in_lds = 1 + offset must exceed 1).
+      bool has_set = false;
+      if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) has_set |= sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet;
+      size_t bit_bytes = 0;
+      for (int slot : lw.distinct_slots) bit_bytes += (size_t)((lw.plan.cols[slot].cardinality + 31) / 32) * 4;
+      bit_bytes = (bit_bytes + 15) & ~(size_t)15;
+      const size_t records = sizeof(BlockPartial) * (kHistBlockThreads / 64) + 16;
+      size_t lds_tier = bit_bytes + (has_set ? (size_t)kSetLdsWords * 4 : 0);
+      if (lds_tier > kLdsBudget && bit_bytes <= kLdsBudget) { has_set = false; lds_tier = bit_bytes; }      // (the sets stay in memory rather than push the bitsets out)
+      g.distinct_lds = k.kernel == ScanKernel::Distinct && g_engine.distinct_lds && std::max(lds_tier, records) <= kLdsBudget;
+      if (g.distinct_lds) {
+        g.hist_set_off = has_set ? bit_bytes : 0;
+        g.lds = std::max(lds_tier, records);
+        g.threads = kHistBlockThreads;
+        g.blocks = grid_blocks(seg, tiles, hist_waves, std::max(1, std::min(waves_scan_distinct(true) / hist_waves, (int)((160 * 1024 - 2048) / (g.lds + 256)))));
+      } else {
+        g.hist_set_off = has_set ? 16 : 0;
+        g.lds = std::max((size_t)(has_set ? 16 + kSetLdsWords * 4 : 0), sizeof(BlockPartial) * (size_t)wpb + 16);
+        g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, (k.kernel == ScanKernel::Distinct ? waves_scan_distinct(false) : waves_group_distinct()) / wpb));
+      }
       break;
     }
     case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
@@ -3082,6 +3161,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Private: launch_scan_private(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::Agg: launch_scan_agg(g_engine.use_dma, one, typed, g.blocks, g.threads, g.lds, stream, sp); break;
+    case ScanKernel::Distinct: case ScanKernel::GroupDistinct: break;      // (launched with their own parameter block: run_aggregation)
   }
 }
 // What the phases of execute_impl share about one query
@@ -3229,13 +3309,32 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   PlanParams& pl = lw.plan; const int na = r.na, num_cols_total = (int)seg->cols.size(); const bool want_bitmap = r.want_bitmap, timed = r.timed;
   pg_status st = PG_OK;
   std::vector<int> agg_slot_of((size_t)std::max(na, 1), -1);
+  const bool distinct_pass = (q->flags & kQueryDistinctPass) != 0 && !want_bitmap;
+  std::vector<int> distinct_of((size_t)std::max(na, 1), -1);      // per aggregation: its bitset (index into lw.distinct_slots)
+  std::vector<int> distinct_key_cards;
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
     if (ag.function == PG_AGG_COUNT) {
       if ((q->flags & kQueryCountReadsColumn) && ag.column >= 0 && ag.column < num_cols_total) r.add_projected(ag.column);
       continue;
     }
-    if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
+    if (ag.function == PG_AGG_DISTINCTCOUNT && distinct_pass) {
+      // a column of the bitset pass: its dictId stream, one bitset per distinct column (the same column twice shares it)
+      if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
+      if (seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on raw column %s", seg->cols[(size_t)ag.column].name.c_str());
+      r.add_projected(ag.column);
+      const int s = slot_for(&lw, seg, ag.column, false);
+      if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+      pl.cols[s].in_agg = 1;
+      size_t dc = std::find(lw.distinct_slots.begin(), lw.distinct_slots.end(), s) - lw.distinct_slots.begin();
+      if (dc == lw.distinct_slots.size()) {
+        if (dc >= (size_t)kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d DISTINCTCOUNT columns", kMaxAggCols);
+        lw.distinct_slots.push_back(s);
+      }
+      distinct_of[(size_t)a] = (int)dc;
+      continue;
+    }
+    if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG || distinct_pass) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
     r.add_projected(ag.column);
     int s = slot_for(&lw, seg, ag.column, lw.plane_cols[(size_t)ag.column] != 0);
@@ -3251,6 +3350,22 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) pl.agg_cols[ac].need_sum = 1;
     if (ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) pl.agg_cols[ac].need_minmax = 1;
     agg_slot_of[(size_t)a] = ac;
+  }
+  if (distinct_pass) {
+    if (lw.distinct_slots.empty()) return fail(PG_ERR_INTERNAL, "a DISTINCTCOUNT pass without a DISTINCTCOUNT column");
+    // group_distinct_kernel's keys: dictionary columns, raw INT / LONG columns through their key images (built by the ordinary query before this pass)
+    for (int g = 0; g < q->num_group_by; ++g) {
+      int c = q->group_by_columns[g];
+      if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
+      r.add_projected(c);
+      if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) { st = ensure_key_image(seg, c, &c); if (st != PG_OK) return st; }
+      if ((int)lw.distinct_key_slots.size() >= kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT with more than %d group-by columns", kMaxDistinctKeys);
+      const int s = slot_for(&lw, seg, c, false);
+      if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+      pl.cols[s].in_agg = 1;
+      lw.distinct_key_slots.push_back(s);
+      distinct_key_cards.push_back(std::max(seg->cols[(size_t)c].cardinality, 1));
+    }
   }
   bool need_queue = false, typed = false;
   for (int i = 0; i < pl.num_agg_cols; ++i) {
@@ -3274,7 +3389,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     lw.stats_closed_entries = sp.num_nodes == 1 ? card : 0;
     lw.stats_chain_flagged = false;
   }
-  const ScanGrid grid = scan_grid(seg, k, sp, geo, pl.num_agg_cols, r.hist_col);
+  const ScanGrid grid = scan_grid(seg, k, lw, geo, pl.num_agg_cols, r.hist_col);
   const int blocks = grid.blocks;
   if (k.kernel == ScanKernel::Hist) { sp.hist_slot = k.hist_slot; sp.hist_bins = seg->cols[(size_t)r.hist_col].cardinality; }
   sp.speculate = 1;
@@ -3363,7 +3478,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       const pg_aggregation& ag = q->aggregations[a];
       pg_agg_value& v = out->aggregations[a];
       empty_agg_value(&v, (int64_t)fp.count);
-      if (ag.function == PG_AGG_COUNT) continue;
+      if (ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT) continue;      // (a DISTINCTCOUNT's count is its bitset's: filled in behind the copy)
       const int ac = agg_slot_of[(size_t)a];
       const ColumnDev& col = seg->cols[(size_t)ag.column];
       const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
@@ -3427,7 +3542,48 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   sp.lane_skip = g_engine.lane_skip ? 1 : 0;
   sp.set_leaves_in_lds = 0;
   if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
-  if (k.kernel == ScanKernel::Hist) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram kernel keeps the area in its dynamic LDS, behind the counters)
+  const bool is_distinct = k.kernel == ScanKernel::Distinct || k.kernel == ScanKernel::GroupDistinct;
+  if (k.kernel == ScanKernel::Hist || is_distinct) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / bitset kernels keep the area in their dynamic LDS, behind the counters / bitsets)
+  // The bitset pass: one zeroed bitset per DISTINCTCOUNT column in the context's scratch -- under GROUP BY a matrix of one row per raw group id --
+  // and one copy of all of them behind the kernel.  Behind the last row: room for the dictIds the column's WIDTH admits beyond its cardinality,
+  // so that a forward index that breaks the dictionary's bound cannot make the kernel write outside the allocation.
+  DistinctParams dp;
+  std::vector<std::vector<uint32_t>> distinct_host;      // per bitset: where its copy lands -- the vector that becomes the result's DistinctSet, no second host copy
+  std::vector<size_t> distinct_first;      // per bitset: its first word in the scratch
+  long long distinct_rows = 1;
+  struct SyncOnExit { hipStream_t stream; bool armed; ~SyncOnExit() { if (armed) (void)hipStreamSynchronize(stream); } } distinct_copy{ctx->stream, false};      // (nothing frees distinct_host under the copy)
+  if (is_distinct) {
+    memset(&dp, 0, sizeof(dp));
+    for (int card : distinct_key_cards) distinct_rows *= card;
+    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT GROUP BY over %lld raw keys", distinct_rows);
+    size_t total = 0, slack = 0;
+    int lds_off = 0;
+    dp.num_cols = (int32_t)lw.distinct_slots.size();
+    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+      const DevColumn& dc = pl.cols[lw.distinct_slots[c]];
+      DistinctCol& col = dp.cols[c];
+      col.fwd = dc.fwd; col.bits = dc.bits; col.words = (dc.cardinality + 31) / 32; col.lds_off = lds_off;
+      lds_off += col.words;
+      distinct_first.push_back(total);
+      total += (size_t)distinct_rows * (size_t)col.words;
+      slack = std::max(slack, distinct_slack_words(dc.bits, dc.cardinality));
+    }
+    dp.lds_words = grid.distinct_lds ? lds_off : 0;
+    dp.num_keys = (int32_t)lw.distinct_key_slots.size();
+    uint32_t mult = 1;
+    for (size_t g = 0; g < lw.distinct_key_slots.size(); ++g) {
+      const DevColumn& kc = pl.cols[lw.distinct_key_slots[g]];
+      dp.keys[g].fwd = kc.fwd; dp.keys[g].bits = kc.bits; dp.keys[g].mult = mult;
+      mult *= (uint32_t)distinct_key_cards[g];
+    }
+    st = ensure_distinct(seg, ctx, total + slack); if (st != PG_OK) return st;
+    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) dp.cols[c].set_bits = ctx->d_distinct + distinct_first[c];
+    HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, (total + slack) * 4, ctx->stream));
+    if (out) {
+      distinct_host.resize(lw.distinct_slots.size());
+      for (size_t c = 0; c < lw.distinct_slots.size(); ++c) distinct_host[c].resize((size_t)distinct_rows * (size_t)dp.cols[c].words);
+    }
+  }
   sp.sparse_lanes = g_engine.sparse_lanes;
   sp.fold_one_counter = g_engine.fold_one_counter;
   if (defer_index_and) {
@@ -3470,11 +3626,21 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     st = read_index_and_shards(ctx, pl.num_agg_cols, &g); if (st != PG_OK) return st;
     *ctx->h_partial = g;
   } else {
-    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm;
+    // (the bitsets' copy follows the kernel on the stream: the polled record does not cover it)
+    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm || is_distinct;
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    launch_scan_kernel(k, grid, pl.num_agg_cols, typed, ctx->stream, sp);
+    if (is_distinct) {
+      dp.scan = sp;
+      if (k.kernel == ScanKernel::Distinct) launch_scan_distinct(grid.distinct_lds, grid.blocks, grid.lds, ctx->stream, dp);
+      else launch_group_distinct(grid.blocks, grid.lds, ctx->stream, dp);
+    } else launch_scan_kernel(k, grid, pl.num_agg_cols, typed, ctx->stream, sp);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    if (is_distinct && !distinct_host.empty()) {
+      distinct_copy.armed = true;
+      for (size_t c = 0; c < distinct_host.size(); ++c)
+        if (!distinct_host[c].empty()) HIP_TRY(hipMemcpyAsync(distinct_host[c].data(), ctx->d_distinct + distinct_first[c], distinct_host[c].size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     if (!folded) {
       finalize_partials_kernel<<<dim3(1), dim3(kBlockThreads), 0, ctx->stream>>>(ctx->d_partials, blocks, g_engine.direct_result ? ctx->h_record_dev : nullptr, seq,
                                                                                   sp.fold_slots, sp.fold_typed, sp.profile);
@@ -3530,6 +3696,29 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   }
   if (out_cardinality) *out_cardinality = (int64_t)fp.count;
   if (out) convert(fp, out);
+  if (out && is_distinct) {
+    // (the stream was synchronised: the bitsets are in distinct_host)  One set per DISTINCTCOUNT aggregation; aggregation only: its count is
+    // the set's cardinality.  Under GROUP BY the rows are raw group ids: execute_distinct keeps the rows of the groups that exist.
+    distinct_copy.armed = false;
+    std::unique_ptr<ResultInternal> sets(new ResultInternal());
+    for (int a = na - 1; a >= 0; --a) {      // (the last aggregation on a column takes the copy itself, earlier ones on the same column a copy of it)
+      const int dc = distinct_of[(size_t)a];
+      if (dc < 0) continue;
+      DistinctSet ds;
+      ds.aggregation = a; ds.num_words = dp.cols[dc].words; ds.rows = (int)distinct_rows;
+      bool again = false;
+      for (int b = 0; b < a; ++b) again |= distinct_of[(size_t)b] == dc;
+      if (again) ds.words = distinct_host[(size_t)dc]; else ds.words = std::move(distinct_host[(size_t)dc]);
+      if (lw.distinct_key_slots.empty()) {
+        int64_t card = 0;
+        for (uint32_t w : ds.words) card += __builtin_popcount(w);
+        out->aggregations[a].count = card;
+      }
+      sets->distinct.push_back(std::move(ds));
+    }
+    out->internal = sets.release();
+  }
+  if (is_distinct) trim_distinct(seg, ctx);
   if (out && k.kernel == ScanKernel::PrivateFsm) {
     // (the stream was synchronised: the walk's count is in the pinned counter)
     out->stats.num_entries_scanned_in_filter = (int64_t)*ctx->h_filter_entries;
@@ -4282,8 +4471,9 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
   const bool want_bitmap = host_bitmap != nullptr || d_out_bitmap_request != nullptr;
   const int na = want_bitmap ? 0 : q->num_aggregations;
-  const int ng = want_bitmap ? 0 : q->num_group_by;
+  const int ng = (want_bitmap || (q->flags & kQueryDistinctPass)) ? 0 : q->num_group_by;      // (the bitset pass of a DISTINCTCOUNT query is an aggregation-only launch: its group-by columns are the kernel's keys)
   if (na < 0 || ng < 0 || (na > 0 && !q->aggregations) || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
+  if ((q->flags & kQueryDistinctPass) && !want_bitmap && (q->num_group_by < 0 || (q->num_group_by > 0 && !q->group_by_columns))) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
   if (ng > kMaxGroupCols) return fail(PG_ERR_UNSUPPORTED, "more than %d group-by columns", kMaxGroupCols);
   const bool timed = (g_engine.flags & PG_CFG_TIME_KERNELS) != 0;
   if (ng == 0 && !want_bitmap && out && na > 0 && allow_metadata_plan && answer_from_metadata(seg, q, na, out, out_cardinality)) return PG_OK;
@@ -4936,6 +5126,202 @@ static pg_status execute_one(pg_segment* segment, const pg_query* query, pg_resu
   return st;
 }
 
+// ---- PG_AGG_DISTINCTCOUNT: the dictId bitsets of dictionary columns (pg_scan_distinct.h) ----
+// A query with a DISTINCTCOUNT is answered in up to two runs over the same filter, on the same stream one after the other:
+//   the ordinary query  -- the caller's aggregation list with every DISTINCTCOUNT turned into COUNT(*): every other function, the
+//                          statistics and (GROUP BY) the list of groups that exist come from the paths they take today, untouched;
+//   the bitset pass     -- the same list with everything BUT the DISTINCTCOUNTs turned into COUNT(*), flagged kQueryDistinctPass: one launch
+//                          of scan_distinct_kernel / group_distinct_kernel behind the same lowered filter.
+// `DISTINCTCOUNT(c1..c4) [, COUNT(*)]` without GROUP BY is the pass alone: its kernel counts the docs and the filter entries itself.
+// No filter (or one that matches everything), no GROUP BY, every function answerable from metadata: nothing is launched, every bit below the
+// cardinality is set (AggregationPlanNode.java:50-54,170-173; NonScanBasedAggregationOperator.java:106-112).
+// pg_query.flags bits above the public ones are the library's own (execute_null_handling / execute_distinct -> execute_impl): a caller that sets
+// one is refused at every entry point that takes a query.
+constexpr int32_t kQueryPublicFlags = PG_QUERY_NULL_HANDLING | PG_QUERY_STATS_UPPER_BOUND_OK;
+static bool reserved_flags(const pg_query* q) { return q != nullptr && (q->flags & ~kQueryPublicFlags) != 0; }
+static pg_status fail_reserved_flags(const pg_query* q) { return fail(PG_ERR_INVALID_ARGUMENT, "pg_query.flags 0x%x sets reserved bits", (unsigned)q->flags); }
+static bool has_distinct(const pg_query* q) {
+  if (!q || !q->aggregations) return false;
+  for (int a = 0; a < q->num_aggregations; ++a) if (q->aggregations[a].function == PG_AGG_DISTINCTCOUNT) return true;
+  return false;
+}
+static pg_status check_ordinary_query(const pg_segment* segment, const pg_query* query);
+struct DistinctPlan {
+  std::vector<pg_aggregation> base_aggs, pass_aggs;
+  pg_query base, pass;
+  bool from_dictionary = false;      // NonScanBasedAggregationOperator: the whole dictionary
+  bool pass_alone = false;           // DISTINCTCOUNT(..) [, COUNT(*)] without GROUP BY: one launch
+  int num_projected = 0;             // distinct columns the whole query projects (numEntriesScannedPostFilter = numDocsScanned x this)
+};
+// Every reason a DISTINCTCOUNT query is declined for, from the query and the segment's metadata alone (pg_query_check and pg_execute both
+// come through here), and the two queries that answer it.
+static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, DistinctPlan* plan) {
+  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
+  const int num_cols_total = (int)seg->cols.size();
+  const int na = q->num_aggregations, ng = q->num_group_by;
+  const bool null_handling = (q->flags & PG_QUERY_NULL_HANDLING) != 0;
+  if (na < 0 || ng < 0 || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
+  if (q->num_filter_nodes > 0 && (!q->filter || !q->predicates)) return fail(PG_ERR_INVALID_ARGUMENT, "filter nodes without predicates");
+  std::vector<int> distinct_cols, projected;
+  auto project = [&](int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); };
+  bool only_distinct_and_count = true, nullable_input = false;
+  for (int a = 0; a < na; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if (ag.function == PG_AGG_COUNT) {
+      if (null_handling && ag.column >= 0) { project(ag.column); only_distinct_and_count = false; }
+      continue;
+    }
+    if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
+    project(ag.column);
+    nullable_input |= seg->cols[(size_t)ag.column].d_null_bitmap != nullptr;
+    if (ag.function != PG_AGG_DISTINCTCOUNT) { only_distinct_and_count = false; continue; }
+    const ColumnDev& col = seg->cols[(size_t)ag.column];
+    if (col.encoding != PG_FWD_FIXED_BIT_DICT)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on raw (no-dictionary) column %s: the reference keeps a hash set of values there -- CPU plan", col.name.c_str());
+    if (null_handling && col.d_null_bitmap != nullptr)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on column %s, which carries a null value vector, under null handling -- CPU plan", col.name.c_str());
+    if (std::find(distinct_cols.begin(), distinct_cols.end(), ag.column) == distinct_cols.end()) distinct_cols.push_back(ag.column);
+  }
+  if ((int)distinct_cols.size() > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d DISTINCTCOUNT columns", kMaxAggCols);
+  // the bitset kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it
+  bool match_all = q->num_filter_nodes == 0;
+  for (int n = 0; n < q->num_filter_nodes; ++n) {
+    if (q->filter[n].op != PG_FILTER_LEAF) continue;
+    if (q->filter[n].predicate < 0 || q->filter[n].predicate >= q->num_predicates) return fail(PG_ERR_INVALID_ARGUMENT, "filter node %d: bad predicate index", n);
+    const pg_predicate& pr = q->predicates[q->filter[n].predicate];
+    if (pr.kind == PG_PRED_RAW_RANGE && pr.column >= 0 && pr.column < num_cols_total && seg->cols[(size_t)pr.column].stored_type != PG_TYPE_INT)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT beside a range predicate on raw LONG / FLOAT / DOUBLE column %s -- CPU plan", seg->cols[(size_t)pr.column].name.c_str());
+    if (q->num_filter_nodes == 1) match_all = (pr.kind == PG_PRED_MATCH_ALL && !pr.exclusive) || (pr.kind == PG_PRED_MATCH_NONE && pr.exclusive);
+  }
+  if (ng > 0) {
+    // GROUP BY, first cut: an int key space that numGroupsLimit can never cut, keys the kernel decodes as dictIds, a bit matrix within the cap
+    if (ng > kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT with more than %d group-by columns -- CPU plan", kMaxDistinctKeys);
+    std::vector<int> cards;
+    for (int g = 0; g < ng; ++g) {
+      int c = q->group_by_columns[g];
+      if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
+      project(c);
+      if (null_handling && seg->cols[(size_t)c].d_null_bitmap != nullptr)
+        return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped by nullable column %s under null handling -- CPU plan", seg->cols[(size_t)c].name.c_str());
+      if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
+        const int image = seg->cols[(size_t)c].keyimage_column;
+        if (image < 0 || seg->cols[(size_t)image].rank_image)
+          return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped by raw column %s, which is not keyed by offset -- CPU plan", seg->cols[(size_t)c].name.c_str());
+        c = image;
+      }
+      cards.push_back(seg->cols[(size_t)c].cardinality);
+    }
+    HashPlan hash_plan;
+    const pg_status hst = plan_hash_holder(seg, cards, &hash_plan);
+    if (hst != PG_OK) return hst;
+    if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", hash_plan.kind);
+    unsigned long long product = 1;
+    for (int card : cards) product *= (unsigned long long)std::max(card, 1);
+    const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
+    if (product > (unsigned long long)limit)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", product, limit);
+    unsigned long long matrix = 0, slack = 0;
+    for (int c : distinct_cols) {
+      matrix += product * (unsigned long long)((seg->cols[(size_t)c].cardinality + 31) / 32) * 4ull;
+      slack = std::max<unsigned long long>(slack, distinct_slack_words(seg->cols[(size_t)c].bits, seg->cols[(size_t)c].cardinality) * 4ull);
+    }
+    matrix += slack;      // (the room behind the last row is part of the device allocation)
+    if (matrix > PG_DISTINCT_GROUP_MAX_BYTES)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT bit matrices of %llu bytes exceed PG_DISTINCT_GROUP_MAX_BYTES (%llu) -- CPU plan", matrix, (unsigned long long)PG_DISTINCT_GROUP_MAX_BYTES);
+    if (matrix > g_engine.group_table_bytes)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT bit matrices of %llu bytes exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", matrix, (unsigned long long)g_engine.group_table_bytes);
+  }
+  plan->num_projected = (int)projected.size();
+  plan->base_aggs.assign(q->aggregations, q->aggregations + na);
+  plan->pass_aggs.assign(q->aggregations, q->aggregations + na);
+  for (int a = 0; a < na; ++a) {
+    if (q->aggregations[a].function == PG_AGG_DISTINCTCOUNT) plan->base_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+    else plan->pass_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+  }
+  plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
+  plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
+  plan->pass.flags |= kQueryDistinctPass;
+  // the dictionary answers under the conditions of the MIN / MAX dictionary path (answer_from_metadata): every function of the query that way
+  plan->from_dictionary = ng == 0 && match_all && !(null_handling && nullable_input);
+  for (int a = 0; a < na && plan->from_dictionary; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    plan->from_dictionary = ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT ||
+                            ((ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) && seg->cols[(size_t)ag.column].encoding == PG_FWD_FIXED_BIT_DICT);
+  }
+  plan->pass_alone = ng == 0 && !plan->from_dictionary && only_distinct_and_count;
+  if (!plan->pass_alone) plan->pass.flags |= PG_QUERY_STATS_UPPER_BOUND_OK;      // (the ordinary query brings the statistics)
+  pg_status st = plan->pass_alone ? PG_OK : check_ordinary_query(seg, &plan->base);
+  if (st == PG_OK && !plan->from_dictionary) st = check_ordinary_query(seg, &plan->pass);
+  return st;
+}
+static void distinct_agg_value(pg_agg_value* v, int64_t cardinality) { memset(v, 0, sizeof(*v)); empty_agg_value(v, cardinality); }
+
+static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result* out) {
+  if (!out) return fail(PG_ERR_INVALID_ARGUMENT, "null result");
+  memset(out, 0, sizeof(*out));
+  if (!seg || !q) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  DistinctPlan plan;
+  pg_status st = plan_distinct(seg, q, &plan);
+  if (st != PG_OK) return st;
+  const int na = q->num_aggregations;
+  if (plan.pass_alone) return execute_one(seg, &plan.pass, out, nullptr);
+  st = execute_one(seg, &plan.base, out, nullptr);
+  if (st != PG_OK) return st;
+  out->stats.num_entries_scanned_post_filter = plan.from_dictionary ? 0 : out->stats.num_docs_scanned * (int64_t)plan.num_projected;
+  std::unique_ptr<ResultInternal> sets(new ResultInternal());
+  if (plan.from_dictionary) {
+    for (int a = 0; a < na; ++a) {
+      if (q->aggregations[a].function != PG_AGG_DISTINCTCOUNT) continue;
+      const int card = seg->cols[(size_t)q->aggregations[a].column].cardinality;
+      DistinctSet ds;
+      ds.aggregation = a; ds.num_words = (card + 31) / 32;
+      ds.words.assign((size_t)ds.num_words, 0xFFFFFFFFu);
+      if (card & 31) ds.words.back() = (1u << (card & 31)) - 1u;
+      distinct_agg_value(&out->aggregations[a], card);
+      sets->distinct.push_back(std::move(ds));
+    }
+    out->internal = sets.release();
+    return PG_OK;
+  }
+  pg_result pass;
+  st = execute_one(seg, &plan.pass, &pass, nullptr);
+  if (st != PG_OK) { pg_result_free(out); return st; }
+  std::unique_ptr<ResultInternal> got(static_cast<ResultInternal*>(pass.internal));
+  pass.internal = nullptr;
+  out->device_ms += pass.device_ms;
+  if (pass.dominant_kernel_ms >= out->dominant_kernel_ms) { out->dominant_kernel_ms = pass.dominant_kernel_ms; out->dominant_kernel = pass.dominant_kernel; }
+  if (!got) { pg_result_free(&pass); pg_result_free(out); return fail(PG_ERR_INTERNAL, "the DISTINCTCOUNT pass returned no sets"); }
+  if (q->num_group_by == 0) {
+    for (const DistinctSet& ds : got->distinct) out->aggregations[ds.aggregation] = pass.aggregations[ds.aggregation];
+    out->internal = got.release();
+    pg_result_free(&pass);
+    return PG_OK;
+  }
+  pg_result_free(&pass);
+  // GROUP BY: the rows of the groups the ordinary query reports (group_ids: ascending raw ids, key kind 0) out of each matrix
+  const int num_groups = out->num_groups;
+  // (compacted in place: group_ids ascend, so row k of the result never lies behind the matrix row it is taken from -- no second buffer)
+  for (DistinctSet& m : got->distinct) {
+    int64_t previous = -1;
+    for (int k = 0; k < num_groups; ++k) {
+      const int64_t row = out->group_ids[k];
+      if (row <= previous || row >= m.rows) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the DISTINCTCOUNT matrix of %d rows, or out of order", (long long)row, m.rows); }
+      previous = row;
+      const uint32_t* src = m.words.data() + (size_t)row * (size_t)m.num_words;
+      int64_t card = 0;
+      for (int w = 0; w < m.num_words; ++w) card += __builtin_popcount(src[w]);
+      if (row != k) memmove(m.words.data() + (size_t)k * (size_t)m.num_words, src, (size_t)m.num_words * 4);
+      distinct_agg_value(&out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation], card);
+    }
+    m.rows = num_groups;
+    m.words.resize((size_t)num_groups * (size_t)m.num_words);
+    m.words.shrink_to_fit();
+    sets->distinct.push_back(std::move(m));
+  }
+  out->internal = sets.release();
+  return PG_OK;
+}
+
 // (pg_execute: below, behind the batch machinery -- a small group-by runs as a one-item launch of the batch's group-by kernel)
 
 // ---- pg_execute_batch ----
@@ -5569,6 +5955,8 @@ pg_status finish_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_res
 // all-zero table slice comes back whole and the host keeps the slots whose count is not zero (§4.1k).  Its lowering is remembered in the
 // segment's plan cache like a batch item's.  Everything else takes execute_one as before.  PINOT_GPU_GROUP_ONE_LAUNCH=0: never.
 pg_status pg_execute(pg_segment* segment, const pg_query* query, pg_result* out_result) {
+  if (reserved_flags(query)) { if (out_result) memset(out_result, 0, sizeof(*out_result)); return fail_reserved_flags(query); }
+  if (has_distinct(query)) return execute_distinct(segment, query, out_result);
   // (PG_CFG_PROFILE_WAVES: the per-wave phase counters live in the kernels execute_one launches itself, and its HIP events bracket ALL of a
   //  query's launches -- the deferred form would leave profile_* empty and report the kernel bracket only)
   if (!(g_engine.group_one_launch && g_engine.batch_launch && g_engine.batch_group && segment && query && out_result && query->num_group_by > 0 &&
@@ -5645,12 +6033,14 @@ pg_status pg_execute_batch(pg_segment* const* segments, const pg_query* const* q
   if (todo_count > 0) run_items(todo_count, all_small ? threads : std::min(threads, todo_count), all_small ? 8 : 1, !all_small, [&](int t) {
     const int i = todo[(size_t)t];
     if (!segments[i] || !queries[i]) { statuses[i] = PG_ERR_INVALID_ARGUMENT; errors[(size_t)i] = "null segment or query"; return; }
+    if (reserved_flags(queries[i])) { statuses[i] = fail_reserved_flags(queries[i]); errors[(size_t)i] = g_error; return; }
     const auto t_item = trace ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
     // (a query that may enter the plan cache is lowered from a copy of its own: the item's conversion reads the query after this call has returned)
     const pg_query* q = queries[i];
     std::shared_ptr<const OwnedQuery> copy;
     if (!keys.empty() && !keys[(size_t)i].empty()) { copy = own_query(q); q = &copy->q; }
-    statuses[i] = execute_one(segments[i], q, &results[i], g_engine.batch_launch ? &defs[(size_t)i] : nullptr);
+    // (a DISTINCTCOUNT item runs as a pg_execute of its own: no shared launch)
+    statuses[i] = has_distinct(q) ? execute_distinct(segments[i], q, &results[i]) : execute_one(segments[i], q, &results[i], g_engine.batch_launch ? &defs[(size_t)i] : nullptr);
     if (statuses[i] == kDeferred && copy && defs[(size_t)i].cacheable) remember_item(segments[i], std::move(keys[(size_t)i]), copy, &defs[(size_t)i]);
     else if (statuses[i] == kDeferred && copy) std::const_pointer_cast<LoweredItem>(defs[(size_t)i].item)->query = copy;
     if (trace) item_us[(size_t)i] = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t_item).count();
@@ -5815,6 +6205,28 @@ pg_status pg_doc_set_cardinality(const pg_segment* segment, int64_t id, int64_t*
 pg_status pg_query_check(const pg_segment* segment, const pg_query* query) {
   if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
   if (!segment || !query) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  if (reserved_flags(query)) return fail_reserved_flags(query);
+  if (has_distinct(query)) { DistinctPlan plan; return plan_distinct(segment, query, &plan); }
+  return check_ordinary_query(segment, query);
+}
+
+pg_status pg_result_distinct_dict_ids(const pg_result* result, int32_t aggregation, int32_t group_row, const uint32_t** out_words, int32_t* out_num_words) {
+  if (!result || !out_words || !out_num_words) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  *out_words = nullptr; *out_num_words = 0;
+  const ResultInternal* sets = static_cast<const ResultInternal*>(result->internal);
+  if (aggregation < 0 || aggregation >= result->num_aggregations) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d out of range", aggregation);
+  const DistinctSet* ds = nullptr;
+  if (sets) for (const DistinctSet& s : sets->distinct) if (s.aggregation == aggregation) ds = &s;
+  if (!ds) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d is not a PG_AGG_DISTINCTCOUNT", aggregation);
+  const bool grouped = result->group_aggregations != nullptr;
+  if (grouped ? (group_row < 0 || group_row >= result->num_groups || group_row >= ds->rows) : group_row != -1)
+    return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
+  *out_words = ds->words.data() + (size_t)(grouped ? group_row : 0) * (size_t)ds->num_words;
+  *out_num_words = ds->num_words;
+  return PG_OK;
+}
+
+static pg_status check_ordinary_query(const pg_segment* segment, const pg_query* query) {
   if (!(query->flags & PG_QUERY_NULL_HANDLING)) return check_query_plan(segment, query, 0);
   // enableNullHandling: the query that runs is the rewritten one (execute_null_handling): the filter's getTrues() over three-valued
   // leaves, one more IS NOT NULL leaf for every aggregated column that has null docs
@@ -5845,6 +6257,7 @@ pg_status pg_query_check(const pg_segment* segment, const pg_query* query) {
 
 pg_status pg_filter_bitmap(pg_segment* segment, const pg_query* query, uint64_t* out_words, int64_t num_words, int64_t* out_cardinality) {
   if (!out_words) return fail(PG_ERR_INVALID_ARGUMENT, "null bitmap buffer");
+  if (reserved_flags(query)) return fail_reserved_flags(query);
   if (query && (query->flags & PG_QUERY_NULL_HANDLING)) return execute_null_handling(segment, query, nullptr, out_words, num_words, out_cardinality);
   return execute_impl(segment, query, nullptr, nullptr, out_words, num_words, out_cardinality);
 }

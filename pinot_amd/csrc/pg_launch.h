@@ -98,6 +98,14 @@ int waves_scan_hist(int counter_bits, bool guarded);
 void launch_scan_hist_batch(int counter_bits, int total_blocks, size_t lds, hipStream_t stream, const ScanParams* items, const uint32_t* block_first, int num_items);
 int waves_scan_hist_batch(int counter_bits);
 
+// scan_distinct_kernel<lds tier>: DISTINCTCOUNT of up to kMaxAggCols dictionary columns as dictId bitsets, in `lds` bytes of dynamic LDS
+// (workgroups of kHistBlockThreads) or straight in HBM (workgroups of 256; `lds`: the filter's set area + the reduction scratch) -- pg_scan_distinct.h
+void launch_scan_distinct(bool lds_tier, int blocks, size_t lds, hipStream_t stream, const DistinctParams& dp);
+int waves_scan_distinct(bool lds_tier);
+// group_distinct_kernel: the same under GROUP BY, one bitset row per raw group id in HBM
+void launch_group_distinct(int blocks, size_t lds, hipStream_t stream, const DistinctParams& dp);
+int waves_group_distinct();
+
 // scan_private_typed_kernel: lane-private scan for raw / 8-byte aggregated columns (pg_scan_typed.h)
 void launch_scan_private_typed(int agg_cols, int blocks, hipStream_t stream, const ScanParams& p);      // instantiated for 1, 2 and kMaxAggCols slots
 int waves_scan_private_typed(int agg_cols);

@@ -52,7 +52,7 @@ class Engine:
         _abi.check(self.lib, self.lib.pg_execute_batch(handles, queries, n, results, statuses))
         out = []
         for i in range(n):
-            out.append((int(statuses[i]), Result(results[i], specs[i]) if statuses[i] == _abi.PG_OK else None))
+            out.append((int(statuses[i]), Result(results[i], specs[i], self.lib) if statuses[i] == _abi.PG_OK else None))
             self.lib.pg_result_free(C.byref(results[i]))
         return out
 
@@ -132,7 +132,7 @@ class GpuSegment:
         else:
             _abi.check(self.lib, self.lib.pg_execute(self.handle, C.byref(spec.c), C.byref(res)))
         try:
-            return Result(res, spec)
+            return Result(res, spec, self.lib)
         finally:
             self.lib.pg_result_free(C.byref(res))
 

@@ -217,12 +217,13 @@ KEY_INT, KEY_LONG, KEY_FLOAT, KEY_DOUBLE, KEY_STRING = range(5)      # DataType 
 def group_by_combine(sql, blocks, key_types):
     """GroupByCombineOperator + GroupByDataTableReducer over group-by blocks built on the host (no device): the IndexedTable / TableResizer
     mirror of pinot_amd/csrc/host/indexed_table.cpp.  `blocks`: one list of rows per segment, a row = (key values, cells) with one cell
-    (count, sum, min, max, is_null) per aggregation of `sql`, None as a key value = NULL.  Returns {"combined", "reduced", "table"}."""
+    (count, sum, min, max, is_null) per aggregation of `sql`, None as a key value = NULL; the cell of a DISTINCTCOUNT function carries a sixth
+    element, the segment's value set as an iterable of ints.  Returns {"combined", "reduced", "table"}."""
     lib = _lib()
     P = C.POINTER
-    lib.ph_group_by_combine.restype = C.c_void_p
-    lib.ph_group_by_combine.argtypes = [C.c_char_p, C.c_int32, P(C.c_int64), P(C.c_int32), P(C.c_int64), P(C.c_double), P(C.c_char_p), P(C.c_uint8), P(C.c_int64),
-                                        P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_uint8), P(C.c_int32)]
+    lib.ph_group_by_combine_sets.restype = C.c_void_p
+    lib.ph_group_by_combine_sets.argtypes = [C.c_char_p, C.c_int32, P(C.c_int64), P(C.c_int32), P(C.c_int64), P(C.c_double), P(C.c_char_p), P(C.c_uint8), P(C.c_int64),
+                                             P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_uint8), P(C.c_int64), P(C.c_int64), P(C.c_int32)]
     rows = [r for b in blocks for r in b]
     nk = len(key_types)
     nf = len(rows[0][1]) if rows else 1
@@ -232,6 +233,7 @@ def group_by_combine(sql, blocks, key_types):
     kl, kd, ks, kn = (C.c_int64 * max(nr * nk, 1))(), (C.c_double * max(nr * nk, 1))(), (C.c_char_p * max(nr * nk, 1))(), (C.c_uint8 * max(nr * nk, 1))()
     counts, sums = (C.c_int64 * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))()
     mins, maxs, nulls = (C.c_double * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))(), (C.c_uint8 * max(nr * nf, 1))()
+    set_offsets, set_values = [], []
     for r, (key_values, cells) in enumerate(rows):
         for k, v in enumerate(key_values):
             at = r * nk + k
@@ -244,11 +246,16 @@ def group_by_combine(sql, blocks, key_types):
                 ks[at] = str(v).encode()
             else:
                 kd[at] = float(v)
-        for f, (c, s, mn, mx, is_null) in enumerate(cells):
+        for f, cell in enumerate(cells):
+            c, s, mn, mx, is_null = cell[:5]
             at = r * nf + f
             counts[at], sums[at], mins[at], maxs[at], nulls[at] = int(c), float(s), float(mn), float(mx), int(bool(is_null))
+            set_offsets.append(len(set_values))
+            set_values.extend(int(v) for v in (cell[5] if len(cell) > 5 else ()))
+    set_offsets.append(len(set_values))
+    so, sv = (C.c_int64 * len(set_offsets))(*set_offsets), (C.c_int64 * max(len(set_values), 1))(*set_values)
     st = C.c_int32()
-    return _take_json(lib, lib.ph_group_by_combine(sql.encode(), len(blocks), br, kt, kl, kd, ks, kn, counts, sums, mins, maxs, nulls, C.byref(st)), st)
+    return _take_json(lib, lib.ph_group_by_combine_sets(sql.encode(), len(blocks), br, kt, kl, kd, ks, kn, counts, sums, mins, maxs, nulls, so, sv, C.byref(st)), st)
 
 
 def execute_sql_datatable(segments, sql, max_execution_threads=0):

@@ -167,6 +167,18 @@ class FakeJvm:
         finally:
             self.release(*arrays)
 
+    def execute_with_distinct_sets(self, handle, spec):
+        """PinotGpuNative.executeWithDistinctSets: [the Object[PGM_RESULT_ARRAYS] as numpy arrays, the sets: aggregation * rows + row -> int32 words or None]."""
+        arrays, limit, flags = self.query_arrays(spec)
+        try:
+            out = self.call("executeWithDistinctSets", C.c_void_p, C.c_int64(handle), *arrays, C.c_int32(limit), C.c_int32(flags))
+            try:
+                return self.to_python(out)
+            finally:
+                self.release(C.c_void_p(out))
+        finally:
+            self.release(*arrays)
+
     def query_check(self, handle, spec):
         arrays, limit, flags = self.query_arrays(spec)
         try:

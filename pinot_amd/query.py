@@ -116,6 +116,7 @@ def not_(child):
 
 
 COUNT, SUM, MIN, MAX, AVG = _abi.PG_AGG_COUNT, _abi.PG_AGG_SUM, _abi.PG_AGG_MIN, _abi.PG_AGG_MAX, _abi.PG_AGG_AVG
+DISTINCTCOUNT = _abi.PG_AGG_DISTINCTCOUNT      # on a dictionary-encoded column: the set of dictIds (AggValue.dict_ids)
 
 
 class QuerySpec:
@@ -185,14 +186,18 @@ class QuerySpec:
 
 
 class AggValue:
-    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max")
+    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max", "dict_ids")
 
-    def __init__(self, v):
+    def __init__(self, v, dict_ids=None):
         self.count, self.sum, self.sum_i64, self.sum_exact, self.min, self.max = (
             int(v.count), float(v.sum), int(v.sum_i64), bool(v.sum_exact), float(v.min), float(v.max))
+        self.dict_ids = dict_ids      # DISTINCTCOUNT: the sorted dictIds of the set (numpy int32); None for every other function
 
     def intermediate(self, function):
-        """The reference's intermediate result type: COUNT -> Long, SUM/MIN/MAX -> Double, AVG -> (sum, count)."""
+        """The reference's intermediate result type: COUNT -> Long, SUM/MIN/MAX -> Double, AVG -> (sum, count), DISTINCTCOUNT -> the
+        segment's dictId set (the values behind it are what segments merge: dictIds differ from segment to segment)."""
+        if function == DISTINCTCOUNT:
+            return self.dict_ids
         if function == COUNT:
             return self.count
         if function == SUM:
@@ -210,7 +215,9 @@ class AggValue:
 class Result:
     """Python copy of a `pg_result` (the C result is freed by the caller right after conversion)."""
 
-    def __init__(self, res, spec):
+    def __init__(self, res, spec, lib=None):
+        """lib: the library that produced `res` (its pg_result_distinct_dict_ids reads the DISTINCTCOUNT sets before the caller frees the result);
+        None = the loaded one."""
         self.functions = [f for f, _ in spec.aggregations]
         self.stats = (int(res.stats.num_docs_scanned), int(res.stats.num_entries_scanned_in_filter),
                       int(res.stats.num_entries_scanned_post_filter), int(res.stats.num_total_docs))
@@ -219,7 +226,16 @@ class Result:
         self.dominant_kernel = _abi.KERNEL_NAMES.get(int(getattr(res, "dominant_kernel", -1)), "")
         self.filter_entries_exact = bool(res.filter_entries_exact)      # stats[1] is the reference's count, not an upper bound
         na = int(res.num_aggregations)
-        self.aggregations = [AggValue(res.aggregations[a]) for a in range(na)] if res.aggregations else []
+        def dict_ids(a, row):
+            if self.functions[a] != DISTINCTCOUNT:
+                return None
+            the_lib = lib if lib is not None else _abi.load_gpu_library()
+            words, n = C.POINTER(C.c_uint32)(), C.c_int32()
+            _abi.check(the_lib, the_lib.pg_result_distinct_dict_ids(C.byref(res), a, row, C.byref(words), C.byref(n)))
+            bits = np.unpackbits(np.ctypeslib.as_array(words, shape=(n.value,)).view(np.uint8), bitorder="little") if n.value else np.zeros(0, np.uint8)
+            return np.flatnonzero(bits).astype(np.int32)
+
+        self.aggregations = [AggValue(res.aggregations[a], dict_ids(a, -1)) for a in range(na)] if res.aggregations else []
         self.groups = {}
         self.group_id_upper_bound = int(res.group_id_upper_bound)
         self.num_groups_limit_reached = bool(res.num_groups_limit_reached)
@@ -232,7 +248,7 @@ class Result:
             tup = tuple(int(res.group_key_dict_ids[g * ng + j]) for j in range(ng)) if res.group_key_dict_ids else None
             self.group_keys.append(tup)
             gid = int(res.group_ids[g]) if self.group_key_kind == 0 else tup
-            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a]) for a in range(na)]
+            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a], dict_ids(a, g)) for a in range(na)]
         self.group_ids64 = [int(res.group_ids64[g]) for g in range(int(res.num_groups))] if (self.group_key_kind == 1 and res.group_ids64) else None
 
     def intermediates(self):

@@ -43,7 +43,8 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
         return {"value": ran / secs, "unit": "rows/s", "cores": 1, "kind": "port",
                 "sample": "the first %d of %d rows of the same segment and query through the C oracle on one host core; %.2f s" % (ran, seg.num_docs, secs)}
 
-    def report(vid, config, query, rows, nbytes, gseg, seg, spec, oracle_spec=None, extra=None, cpu_rows=0):
+    def report(vid, config, query, rows, nbytes, gseg, seg, spec, oracle_spec=None, extra=None, cpu_rows=0, model_check=None):
+        """model_check: got -> bool, for queries the oracle does not know (DISTINCTCOUNT: the numpy model of tests/distinct_cases.py, in chunks)."""
         t = timer.run(gseg, spec, steps, warmup)
         rec = {"id": vid, "config": config, "query": query, "rows": rows}
         rec.update(t)
@@ -56,7 +57,11 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                     "rows_per_s": rows / ms * 1e3})
         rec["docs_matched"] = got.stats[0]
         rec["bit_exact_vs_oracle"] = None
-        if check:
+        if check and model_check is not None:
+            t0 = time.perf_counter()
+            rec["exact_vs_model"] = bool(model_check(got))
+            rec["model_check_s"] = time.perf_counter() - t0
+        elif check:
             t0 = time.perf_counter()
             wanted = oracle.execute_sliced(seg, oracle_spec or spec)
             rec["bit_exact_vs_oracle"] = bool(oracle.matches_sliced(got, wanted, [f for f, _ in spec.aggregations]) and got.stats[0] == wanted["docs_scanned"])
@@ -77,7 +82,7 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
         return lambda matched: B(col) if matched * 16 >= rows else min(B(col), matched * 64)
 
     # ---- C2 / C3 on 1 B rows: the headline's v and f, v under two dictionaries without structure, and the C3 columns ----
-    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list", "C2b-valid-docs", "C2b-valid-docs-5pct")):
+    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list", "C2b-valid-docs", "C2b-valid-docs-5pct", "C2b-distinct", "C3-distinct")):
         t0 = time.time()
         v_irr = _shared(S, v, "v_irr", v_dictionary("irregular"))
         v_win = _shared(S, v, "v_win", v_dictionary("window"))
@@ -143,6 +148,34 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                 if want(vid):
                     report(vid, "BASELINE.md C2a (predicate on the summed column)", "SELECT SUM(%s) WHERE %s BETWEEN dict[45000] AND dict[54999] (10%%)" % (seg.columns[ci].name, seg.columns[ci].name),
                            n, B(v), g, seg, Q.QuerySpec([(Q.SUM, ci)], filter=Q.leaf(Q.Pred.dict_range(ci, 45000, 55000))), extra={"dictionary": "affine" if ci == 0 else "irregular"})
+            # DISTINCTCOUNT on the same dictId streams (pg_scan_distinct.h): the model is np.unique over the matching docs, walked in chunks of 16 M docs
+            def dict_id_chunks(*cols):
+                for at in range(0, n, 1 << 24):
+                    docs = np.arange(at, min(n, at + (1 << 24)), dtype=np.int32)
+                    yield at, [oracle.read_dict_ids(seg.columns[c].fwd, seg.columns[c].bits, n, docs) for c in cols]
+
+            if want("C2b-distinct"):
+                def c2b_model(got):
+                    seen = np.zeros(seg.columns[2].cardinality, dtype=bool)
+                    docs = 0
+                    for _, (ids, fids) in dict_id_chunks(2, 1):
+                        hit = fids < 100
+                        docs += int(hit.sum())
+                        seen[ids[hit]] = True
+                    return np.array_equal(got.aggregations[0].dict_ids, np.flatnonzero(seen)) and got.aggregations[0].count == int(seen.sum()) and got.stats[0] == docs
+                report("C2b-distinct", "BASELINE.json configs[1] with DISTINCTCOUNT for SUM: C2b-irregular's two dictId streams, an OR per matching doc where the histogram has an add",
+                       "SELECT DISTINCTCOUNT(v_irr) WHERE f < 100 (10%)", n, B(v) + B(f), g, seg, Q.QuerySpec([(Q.DISTINCTCOUNT, 2)], filter=flt), model_check=c2b_model)
+            if want("C3-distinct"):
+                def c3_model(got):
+                    ka, kk = seg.columns[5].cardinality, seg.columns[4].cardinality
+                    seen = np.zeros(kk * ka, dtype=bool)
+                    for _, (aids, kids) in dict_id_chunks(5, 4):
+                        seen[kids.astype(np.int64) * ka + aids] = True
+                    seen = seen.reshape(kk, ka)
+                    present = np.flatnonzero(seen.any(axis=1))
+                    return sorted(got.groups) == [int(x) for x in present] and all(np.array_equal(got.groups[int(gid)][0].dict_ids, np.flatnonzero(seen[gid])) for gid in present)
+                report("C3-distinct", "BASELINE.json configs[2] with DISTINCTCOUNT: C3's key and one of its value streams, a [1000 x 3125-word] bit matrix in HBM",
+                       "SELECT DISTINCTCOUNT(a) GROUP BY k (1000 groups)", n, B(k) + B(a), g, seg, Q.QuerySpec([(Q.DISTINCTCOUNT, 5)], group_by=[4]), model_check=c3_model)
             if want("C3"):
                 report("C3", "BASELINE.json configs[2]", "SELECT SUM(a), MAX(b) GROUP BY k (1000 groups)", n, B(k) + B(a) + B(b), g, seg, Q.QuerySpec([(Q.SUM, 5), (Q.MAX, 6)], group_by=[4]),
                        cpu_rows=200_000_000)

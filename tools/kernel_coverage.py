@@ -365,6 +365,38 @@ def main():
                         g.release_doc_set(dsid)
             finally:
                 engine.reinit(**{k: flipped.get(k) for k in env})
+    # ---- DISTINCTCOUNT on dictionary columns (pg_scan_distinct.h): scan_distinct_kernel in both tiers (the switch sends the small dictionaries to
+    # the HBM tier), group_distinct_kernel behind an ordinary group-by.  The oracle has no such function: the sets are held against the numpy
+    # model of tests/distinct_cases.py (np.unique over the docs oracle.filter_bitmap matches), every other function against the oracle.
+    if only is None or only.search("distinct"):
+        import distinct_cases as DC
+        f100 = Q.leaf(Q.Pred.dict_range(F, 0, 100))
+        shapes = (("scan", Q.QuerySpec([(Q.DISTINCTCOUNT, W8), (Q.DISTINCTCOUNT, A), (Q.COUNT, -1)], filter=f100), "scan_distinct_kernel"),
+                  ("group", Q.QuerySpec([(Q.DISTINCTCOUNT, A), (Q.SUM, V), (Q.DISTINCTCOUNT, W32)], filter=Q.leaf(Q.Pred.dict_range(F, 0, 500)), group_by=[B]), "group_distinct_kernel"))
+        models = {}
+        for env in ({}, {"PINOT_GPU_DISTINCT_LDS": "0"}):
+            engine.reinit(**env)
+            try:
+                with engine.open(seg) as g:
+                    for sid, spec, family in shapes:
+                        eid = "distinct-%s%s" % (sid, "-hbm" if env else "")
+                        if g.check(spec) != 0:
+                            failed.append({"id": eid, "error": "pg_query_check declined"})
+                            continue
+                        if sid not in models:
+                            models[sid] = DC.model(seg, spec)
+                        for rep in range(2):
+                            got = g.execute(spec)
+                            try:
+                                DC.assert_sets_equal(got, seg, spec, want=models[sid])
+                                DC.assert_other_functions_equal(got, seg, spec)
+                                if not flipped:
+                                    assert got.dominant_kernel == family, "dominant kernel %s, expected %s" % (got.dominant_kernel, family)
+                            except AssertionError as e:
+                                failed.append({"id": eid, "error": str(e)[:300]})
+                        ran += 1
+            finally:
+                engine.reinit(**{k: flipped.get(k) for k in env})
     # ---- the transducer's kernels: byte-function walks, then table walks of the same machines ----
     if only is None or only.search("fsm"):
         count = args.fsm_trees if args.fsm_trees >= 0 else (400 if args.regime == "tiny" else 40)
