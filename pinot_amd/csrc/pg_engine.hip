@@ -86,6 +86,8 @@ struct Engine {
   bool scan_raw_set = true;  // PINOT_GPU_SCAN_RAW_SET=0: a lone IN / NOT IN leaf on a raw column takes the membership pre-pass + the general kernels, like every other shape (pg_scan_raw_set.h)
   int scan_simple_valid = 1;  // PINOT_GPU_SCAN_SIMPLE_VALID=0: `range leaf AND doc set` / the doc set alone stays in the general lane-private kernel; 2: the form of
                              // scan_simple_valid_kernel whose tiles without a valid doc skip the filter column too (pg_scan_simple.h)
+  int scan_simple_pipe = 1;   // PINOT_GPU_SCAN_SIMPLE_PIPE: 0 never scan_simple_pipe_kernel, 1 by the estimated selectivity of the leaf (choose_scan_kernel), 2 whenever
+                             // the shape allows, whatever the estimate (pg_scan_simple_pipe.h)
   bool scan_simple = true;   // PINOT_GPU_SCAN_SIMPLE=0: one-leaf / one-column queries stay in scan_private_kernel (half the waves per SIMD)
   bool scan_sparse = true;   // PINOT_GPU_SCAN_SPARSE=0: index-led aggregations scan their listed tiles in scan_private_kernel (one tile per wave and iteration)
   // (read at every pg_init like the rest: they were function-local statics, fixed at their first use in the process, until the kernel
@@ -2010,6 +2012,8 @@ pg_status pg_init(const pg_config* config) {
   g_engine.scan_simple = !(ssm && ssm[0] == '0');
   const char* ssv = getenv("PINOT_GPU_SCAN_SIMPLE_VALID");
   g_engine.scan_simple_valid = ssv ? (ssv[0] == '0' ? 0 : (ssv[0] == '2' ? 2 : 1)) : 1;
+  const char* spp = getenv("PINOT_GPU_SCAN_SIMPLE_PIPE");
+  g_engine.scan_simple_pipe = spp ? (spp[0] == '0' ? 0 : (spp[0] == '2' ? 2 : 1)) : 1;
   const char* srw = getenv("PINOT_GPU_SCAN_RAW");
   g_engine.scan_raw = !(srw && srw[0] == '0');
   const char* srs = getenv("PINOT_GPU_SCAN_RAW_SET");
@@ -2947,7 +2951,12 @@ struct ScanChoice {
   ScanKernel kernel = ScanKernel::Agg, general = ScanKernel::Agg;
   int hist_slot = -1, hist_cw = 0;         // Hist: the aggregation slot the histogram counts, its counter bits ...
   bool hist_guarded = false;               // ... and whether they are the guarded tier's
+  bool pipe = false;                       // Simple: scan_simple_pipe_kernel, the form with both columns' loads pipelined across tiles (same id, same batch kind)
 };
+// scan_simple_pipe_kernel always loads the aggregated column: it wins where scan_simple_kernel's lane skip and sparse walk have nothing to
+// skip.  The leaf's selectivity is estimated as span / cardinality of its column (1 - that for an exclusive leaf); at or above this many
+// per cent the pipelined form is taken (DESIGN.md 4.1g has the table the figure comes from).
+constexpr int kPipeMinSelectivityPct = 5;
 static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, int hist_col, bool typed, bool want_bitmap, bool want_result) {
   const PlanParams& pl = lw.plan; const ScanParams& sp = lw.sp;
   const bool profile = (g_engine.flags & PG_CFG_PROFILE_WAVES) != 0;
@@ -3038,6 +3047,12 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
                 (leaf == nullptr || ((leaf->kind == kLeafDictRange || set) && leaf->bits >= 1 && leaf->bits <= kSimpleMaxBits));
   if (simple && ac != nullptr)
     simple = ac->bits >= 1 && ac->bits <= kSimpleMaxBits && !ac->is_raw && !(leaf != nullptr && leaf->fwd == ac->fwd && leaf->bits == ac->bits && ac->need_sum != 0 && ac->need_minmax == 0 && leaf->exclusive == 0);
+  if (simple && !set && leaf != nullptr && ac != nullptr && g_engine.scan_simple_pipe != 0 && scan_simple_pipe_shape(leaf->bits, ac->bits)) {
+    const DevColumn& fc = pl.cols[pl.leaves[pl.nodes[0].leaf].col];
+    const unsigned long long values = fc.is_plane ? 1ull << leaf->bits : (unsigned long long)std::max(fc.cardinality, 1);      // (a range over a value plane: span is in plane units)
+    const unsigned long long inside = std::min<unsigned long long>(leaf->span, values), taken = leaf->exclusive ? values - inside : inside;
+    k.pipe = g_engine.scan_simple_pipe == 2 || taken * 100ull >= (unsigned long long)kPipeMinSelectivityPct * values;
+  }
   if (simple) return pick(set ? ScanKernel::SimpleSet : ScanKernel::Simple);
   // The same idea for raw INT columns (BASELINE.json configs[0]'s scan pair): one raw-range leaf (or no filter) in front of at most one
   // aggregated raw INT column -- scan_raw_kernel, five waves per SIMD, coalesced reads (pg_scan_raw.h).
@@ -3113,7 +3128,7 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Lowe
     case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
     case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
-    case ScanKernel::Simple: case ScanKernel::SimpleSet: lean_grid(seg, waves_scan_simple(), &g); break;
+    case ScanKernel::Simple: case ScanKernel::SimpleSet: lean_grid(seg, k.pipe ? waves_scan_simple_pipe() : waves_scan_simple(), &g); break;
     case ScanKernel::SimpleValid: lean_grid(seg, waves_scan_simple_valid(), &g); break;
     case ScanKernel::Raw: lean_grid(seg, waves_scan_raw(), &g); break;
     case ScanKernel::RawSet: {
@@ -3153,7 +3168,10 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Hist: launch_scan_hist(k.hist_cw, k.hist_guarded, g.blocks, g.lds, stream, sp); break;
     case ScanKernel::Narrow: case ScanKernel::NarrowSingle: launch_scan_narrow(k.kernel == ScanKernel::NarrowSingle, g.blocks, stream, sp); break;
     case ScanKernel::Sparse: launch_scan_sparse(one, g.blocks, stream, sp); break;
-    case ScanKernel::Simple: case ScanKernel::SimpleSet: launch_scan_simple(g.blocks, lean_threads, stream, sp, k.kernel == ScanKernel::SimpleSet); break;
+    case ScanKernel::Simple: case ScanKernel::SimpleSet:
+      if (k.pipe) launch_scan_simple_pipe(g.blocks, lean_threads, stream, sp);
+      else launch_scan_simple(g.blocks, lean_threads, stream, sp, k.kernel == ScanKernel::SimpleSet);
+      break;
     case ScanKernel::SimpleValid: launch_scan_simple_valid(g.blocks, lean_threads, stream, sp, g_engine.scan_simple_valid == 2); break;
     case ScanKernel::Raw: launch_scan_raw(g.blocks, lean_threads, stream, sp); break;
     case ScanKernel::RawSet: launch_scan_raw_set(sp.nodes[0].lo_hi, g.blocks, g.lds, stream, sp); break;

@@ -49,6 +49,11 @@ int waves_scan_sparse(bool one_slot);
 // scan_simple_kernel: one dictionary-range leaf (or none) + at most one aggregated packed column of <= 20 bits (pg_scan_simple.h)
 void launch_scan_simple(int blocks, int threads, hipStream_t stream, const ScanParams& p, bool set_leaf = false);      // threads: kBlockThreads or kWideBlockThreads; set_leaf: scan_simple_set_kernel (the one leaf is a dictId set, looked up in LDS)
 int waves_scan_simple();
+// scan_simple_pipe_kernel<NF4, NV4>: one dictionary-range leaf AND one aggregated packed column, the two columns' loads pipelined across tiles;
+// N = sixteen-byte loads per lane and column (pg_scan_simple_pipe.h).  scan_simple_pipe_shape: the width pair has an instantiation.
+bool scan_simple_pipe_shape(int filter_bits, int value_bits);
+void launch_scan_simple_pipe(int blocks, int threads, hipStream_t stream, const ScanParams& p);
+int waves_scan_simple_pipe();          // the least over the instantiations
 // scan_simple_valid_kernel: the same shape behind one PG_PRED_DOC_SET leaf (p.bitmaps[0] = the doc set; p.nodes[0] = the range leaf, if any);
 // skip_empty_tiles: the form whose tiles without a valid doc skip the filter column too
 void launch_scan_simple_valid(int blocks, int threads, hipStream_t stream, const ScanParams& p, bool skip_empty_tiles);

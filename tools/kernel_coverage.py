@@ -83,6 +83,17 @@ def table(Q, n):
     add = lambda *e: T.append(e)
     # ---- the lane-private scan kernels ----
     add("simple", {}, "scan_simple_kernel", Q.QuerySpec([(Q.SUM, V)], filter=f_lt(100)))
+    # scan_simple_pipe_kernel<NF4, NV4>: f < 100 above takes <3, 5> by the rule (10 % of the filter's dictionary); a 1 % filter keeps
+    # scan_simple_kernel itself; with the switch at 2 every class of sixteen-byte loads per column, as the filter and as the aggregated
+    # column (<4, 5>, <5, 3>, <5, 4> and <5, 5> are not instantiated -- they spill at five waves per SIMD: those pairs stay with scan_simple_kernel)
+    add("simple-selective", {}, "scan_simple_kernel", Q.QuerySpec([(Q.SUM, V)], filter=f_lt(10)))
+    pipe_filters = [(B, 2, 9), (A, 20, 150), (F, 0, 100), (K4, 1000, 30000), (V, 10000, 60000)]      # 4, 8, 10, 16 and 17 bits
+    pipe_values = [C2, X, K, W16, V]                                                                # 2, 6, 10, 16 and 17 bits
+    for nf4, (fcol, lo, hi) in enumerate(pipe_filters, 1):
+        for nv4, vcol in enumerate(pipe_values, 1):
+            if (nf4, nv4) not in ((4, 5), (5, 3), (5, 4), (5, 5)):
+                add("pipe-%d-%d" % (nf4, nv4), {"PINOT_GPU_SCAN_SIMPLE_PIPE": "2"}, "scan_simple_kernel",
+                    Q.QuerySpec([(Q.MAX, vcol), (Q.COUNT, -1)] + ([(Q.SUM, V)] if vcol == V else []), filter=L(Q.Pred.dict_range(fcol, lo, hi))))
     add("simple-set", {}, "scan_simple_kernel", Q.QuerySpec([(Q.SUM, V), (Q.COUNT, -1)], filter=L(Q.Pred.dict_set(F, list(range(0, 300, 3)), 1000))))      # scan_simple_set_kernel: the one leaf an IN list, its words in LDS
     add("raw", {}, "scan_raw_kernel", Q.QuerySpec([(Q.COUNT, -1)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))
     add("raw-sum", {}, "scan_raw_kernel", Q.QuerySpec([(Q.SUM, RI), (Q.MAX, RI)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))
