@@ -359,6 +359,8 @@ __device__ __forceinline__ void index_and_body(const P& ap, const uint32_t num_w
               const unsigned long long first = off + 2ull;
               const uint32_t lead = (uint32_t)(first & 3ull);
               const uint8_t* origin = ch.inv + (first - lead);
+              // (plain dword loads, not the buffer loads of the pieces above: with lead != 0 the posting's last pair reads the dword behind
+              //  it, up to 3 bytes past the column's index -- d_inv is allocated inv_size + 64 bytes for this, pg_segment_open)
               for (uint32_t r = lane; r < runs; r += 64u) {
                 uint32_t pair = *reinterpret_cast<const uint32_t*>(origin + 4u * r);
                 if (lead != 0u) pair = __builtin_amdgcn_alignbyte(*reinterpret_cast<const uint32_t*>(origin + 4u * r + 4u), pair, lead);
