@@ -52,7 +52,8 @@ extern "C" {
                             * 3: pg_execute_batch, pg_result.group_key_kind / group_ids64 / group_key_dict_ids (Long / ArrayMap holders);
                             * 4: PG_PRED_RAW_SET (IN / NOT IN on raw INT / LONG / FLOAT / DOUBLE columns); no struct layout changed;
                             * 5: pg_doc_set_create / release / cardinality, PG_PRED_DOC_SET (upsert / dedup valid-doc sets); no struct layout changed;
-                            *    (still 5) PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids: no struct layout changed, one enumerator and one function added */
+                            *    (still 5) PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids: no struct layout changed, one enumerator and one function added;
+                            *    (still 5) PG_AGG_PERCENTILE, pg_result_percentile_counts: no struct layout changed, one enumerator and one function added */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -206,7 +207,7 @@ typedef enum pg_agg_function {
   PG_AGG_MIN = 2,              /* MinAggregationFunction.java */
   PG_AGG_MAX = 3,              /* MaxAggregationFunction.java */
   PG_AGG_AVG = 4,              /* AvgAggregationFunction.java (AvgPair = sum, count) */
-  PG_AGG_DISTINCTCOUNT = 5     /* DistinctCountAggregationFunction.java on a dictionary-encoded (PG_FWD_FIXED_BIT_DICT) column of any stored type: the
+  PG_AGG_DISTINCTCOUNT = 5,    /* DistinctCountAggregationFunction.java on a dictionary-encoded (PG_FWD_FIXED_BIT_DICT) column of any stored type: the
                                 * set of the matching docs' dictIds (BaseDistinctAggregateAggregationFunction.java:144-155, :306-321).
                                 * pg_agg_value.count = the set's cardinality, sum = 0, sum_exact = 0, min = +inf, max = -inf; the set itself comes
                                 * from pg_result_distinct_dict_ids.  No filter (or one that matches everything), no GROUP BY, every function
@@ -216,11 +217,27 @@ typedef enum pg_agg_function {
                                 * unless group_key_kind is 0, group_id_upper_bound <= numGroupsLimit (the limit can never bind), the keys are
                                 * dictionary columns or raw INT / LONG columns keyed by offset, without null docs under PG_QUERY_NULL_HANDLING,
                                 * at most four of them, and the bit matrices fit PG_DISTINCT_GROUP_MAX_BYTES. */
+  PG_AGG_PERCENTILE = 6        /* PercentileAggregationFunction.java (the exact PERCENTILE<p>(col) / PERCENTILE(col, p)) on a dictionary-encoded column of any
+                                * stored type: the list of the matching docs' values (:77-100) as "how many matching docs carry each dictId" -- the
+                                * dictionary is sorted.  The percentile does not cross the ABI: the list is the intermediate result whatever p is.
+                                * pg_agg_value.count = the docs aggregated (the list's length), sum = 0, sum_exact = 0, min = +inf, max = -inf; the list
+                                * comes from pg_result_percentile_counts.  No metadata fast path: the reference scans even without a filter, and
+                                * numEntriesScannedPostFilter = docs scanned x the distinct columns the whole query projects.
+                                * PG_ERR_UNSUPPORTED at plan time: a raw column; PG_QUERY_NULL_HANDLING when the column carries a null vector; a
+                                * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four PERCENTILE columns; a
+                                * PG_AGG_DISTINCTCOUNT in the same query; GROUP BY outside the conditions PG_AGG_DISTINCTCOUNT sets, or counter
+                                * matrices above PG_PERCENTILE_GROUP_MAX_BYTES. */
 } pg_agg_function;
 
 /* GROUP BY with PG_AGG_DISTINCTCOUNT: group_id_upper_bound x ceil(cardinality / 32) x 4 bytes, summed over the query's DISTINCTCOUNT columns,
  * may not exceed this (a capacity limit: it bounds the host copy of the result; PINOT_GPU_GROUP_TABLE_BYTES bounds the device's). */
 #define PG_DISTINCT_GROUP_MAX_BYTES (1ull << 30)
+/* GROUP BY with PG_AGG_PERCENTILE: group_id_upper_bound x cardinality x 4 bytes, summed over the query's PERCENTILE columns (plus the room behind
+ * the last counter: 2^bits - cardinality counters), may not exceed this -- the same kind of capacity limit. */
+#define PG_PERCENTILE_GROUP_MAX_BYTES (1ull << 30)
+/* Diagnostics: the 32-bit counters of all PERCENTILE columns of a query that scan_counts_kernel keeps in LDS when the filter stages no dictId
+ * set there (with one: 2048 fewer); above it, or with PINOT_GPU_PERCENTILE_LDS=0, the counters live in HBM. */
+#define PG_PERCENTILE_LDS_MAX_COUNTERS 39036
 
 typedef struct pg_aggregation {
   int32_t function;            /* pg_agg_function */
@@ -309,6 +326,8 @@ typedef enum pg_kernel_id {
   PG_KERNEL_SCAN_SIMPLE = 10,      /* scan_simple_kernel: one dictionary-range leaf + at most one aggregated packed column, twice the waves per SIMD */
   PG_KERNEL_SCAN_DISTINCT = 14,    /* scan_distinct_kernel: DISTINCTCOUNT of dictionary columns, dictId bitsets in LDS or in HBM (PINOT_GPU_DISTINCT_LDS=0: always HBM) */
   PG_KERNEL_GROUP_DISTINCT = 15,   /* group_distinct_kernel: the same under GROUP BY, one bitset row per raw group id in HBM */
+  PG_KERNEL_SCAN_COUNTS = 16,      /* scan_counts_kernel: PERCENTILE of dictionary columns, 32-bit dictId counters in LDS or in HBM (PINOT_GPU_PERCENTILE_LDS=0: always HBM) */
+  PG_KERNEL_GROUP_COUNTS = 17,     /* group_counts_kernel: the same under GROUP BY, one counter row per raw group id in HBM */
   PG_KERNEL_SCAN_HIST = 6          /* scan_hist_kernel: lane-private scan, SUM = sum_d matches[d] * dictionary[d] through an LDS histogram */
 } pg_kernel_id;
 
@@ -410,6 +429,14 @@ void pg_result_free(pg_result* result);
  * (dictIds differ from segment to segment: a merge looks the values up in the segment's dictionary first.) */
 pg_status pg_result_distinct_dict_ids(const pg_result* result, int32_t aggregation, int32_t group_row,
                                       const uint32_t** out_words, int32_t* out_num_words);
+
+/* The value list behind a PG_AGG_PERCENTILE aggregation, sparse and in dictionary order: out_dict_ids[i] ascending, out_counts[i] > 0 the matching
+ * docs that carry it, *out_num pairs (0: no doc matched; the pointers may then be NULL).  The sorted list of PercentileAggregationFunction is
+ * dictionary[out_dict_ids[i]] repeated out_counts[i] times.  group_row = -1 for an aggregation-only query, else a row of group_aggregations.
+ * Engine-owned, valid until pg_result_free.  Any other aggregation index or row: PG_ERR_INVALID_ARGUMENT.  (A count is exact in 32 bits: a
+ * segment has fewer than 2^31 docs.) */
+pg_status pg_result_percentile_counts(const pg_result* result, int32_t aggregation, int32_t group_row,
+                                      const int32_t** out_dict_ids, const uint32_t** out_counts, int32_t* out_num);
 
 /* How a group-by column's entries of pg_result.group_key_dict_ids turn into key values.  A dictionary column: *out_is_offset = 0, the
  * entry is a dictId (GroupKeyGenerator.getGroupKeys looks it up, DictionaryBasedGroupKeyGenerator.java:260-290).  A raw (no-dictionary)

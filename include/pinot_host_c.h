@@ -83,6 +83,13 @@ char* ph_group_by_combine(const char* sql, int32_t num_blocks, const int64_t* bl
 char* ph_group_by_combine_sets(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
                           const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
                           const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* set_offsets, const int64_t* set_values, int32_t* status);
+/* The combine of PERCENTILE value lists: cell (row, function) of a PERCENTILE function holds the runs (run_values[i], run_counts[i]) for i in
+ * [run_offsets[row * functions + function], run_offsets[.. + 1]); the combine merges them run-wise, the final result is the percentile of `sql`.
+ * GROUP BY: as ph_group_by_combine; aggregation only: one row per block, {"combined": <block>}. */
+char* ph_combine_counts(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                        const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                        const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* run_offsets, const double* run_values,
+                        const int64_t* run_counts, int32_t* status);
 int32_t ph_group_by_table_capacity(int32_t limit, int32_t min_num_groups);          /* GroupByUtils.getTableCapacity */
 int32_t ph_group_by_trim_threshold(int32_t trim_size, int32_t trim_threshold);      /* GroupByUtils.getIndexedTableTrimThreshold */
 

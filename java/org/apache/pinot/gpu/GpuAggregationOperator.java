@@ -14,6 +14,7 @@
  */
 package org.apache.pinot.gpu;
 
+import it.unimi.dsi.fastutil.doubles.DoubleArrayList;
 import java.util.ArrayList;
 import java.util.Arrays;
 import java.util.Collection;
@@ -76,7 +77,9 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     double[] _maxs;
     int _width;                   // aggregations per row in this lane's arrays
     Object[] _distinctSets;       // DISTINCTCOUNT lanes: int[] words of aggregation a, row r at a * rows + r (null for other functions); else null
-    int _rows;                    // rows of _distinctSets per aggregation: 1 without GROUP BY, else the lane's groups
+    int _rows;                    // rows of _distinctSets / _percentileIds per aggregation: 1 without GROUP BY, else the lane's groups
+    Object[] _percentileIds;      // PERCENTILE lanes: int[] ascending dictIds of aggregation a, row r at a * rows + r (null for other functions); else null
+    Object[] _percentileCounts;   // ... and the int[] of how many matching docs carry each
   }
 
   private final GpuSegment _segment;
@@ -168,7 +171,10 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       throw new UnsupportedOperationException("segment " + _segment.getSegmentName() + " is no longer resident on the device");
     }
     try {
-      Object[] raw = q._hasDistinctCount
+      Object[] raw = q._hasPercentile
+          ? PinotGpuNative.executeWithPercentileCounts(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
+              q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
+          : q._hasDistinctCount
           ? PinotGpuNative.executeWithDistinctSets(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
               q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
           : PinotGpuNative.execute(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
@@ -192,6 +198,16 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       distinctSets = (Object[]) raw[PinotGpuNative.PGM_DISTINCT_SETS];
       raw = (Object[]) raw[PinotGpuNative.PGM_DISTINCT_RESULT];
     }
+    Object[] percentileIds = null;
+    Object[] percentileCounts = null;
+    if (q._hasPercentile) {
+      if (raw == null || raw.length != PinotGpuNative.PGM_PERCENTILE_SLOTS) {
+        throw new IllegalStateException("native PERCENTILE result does not match jni/pinot_gpu_jni.c");
+      }
+      percentileIds = (Object[]) raw[PinotGpuNative.PGM_PERCENTILE_DICT_IDS];
+      percentileCounts = (Object[]) raw[PinotGpuNative.PGM_PERCENTILE_COUNTS];
+      raw = (Object[]) raw[PinotGpuNative.PGM_PERCENTILE_RESULT];
+    }
     if (raw == null || raw.length != PinotGpuNative.PGM_RESULT_ARRAYS) {
       throw new IllegalStateException("native result does not match jni/pg_marshal.h");
     }
@@ -205,6 +221,8 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     result._maxs = (double[]) raw[PinotGpuNative.PGM_R_MAXS];
     result._width = (int) result._header[PinotGpuNative.PGM_H_NUM_AGGREGATIONS];
     result._distinctSets = distinctSets;
+    result._percentileIds = percentileIds;
+    result._percentileCounts = percentileCounts;
     result._rows = _queryContext.getGroupByExpressions() == null ? 1 : result._groupIds.length;
     if (result._header.length != PinotGpuNative.PGM_HEADER_LEN) {
       throw new IllegalStateException("native result header does not match jni/pg_marshal.h");
@@ -220,7 +238,8 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       LaneResult result = results.get(l);
       for (int i = 0; i < positions.length; i++) {
         AggregationFunctionType type = _functions[positions[i]].getType();
-        out[positions[i]] = type == AggregationFunctionType.DISTINCTCOUNT ? valueSet(positions[i], result, i, 0) : intermediate(type, result, i, nullHandling);
+        out[positions[i]] = type == AggregationFunctionType.DISTINCTCOUNT ? valueSet(positions[i], result, i, 0)
+            : type == AggregationFunctionType.PERCENTILE ? valueList(positions[i], result, i, 0, nullHandling) : intermediate(type, result, i, nullHandling);
       }
     }
     return new AggregationResultsBlock(_functions, Arrays.asList(out), _queryContext);
@@ -255,6 +274,33 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
             values.add(dictionary.getDoubleValue(dictId));
             break;
         }
+      }
+    }
+    return values;
+  }
+
+  /**
+   * PERCENTILE: the (dictId, count) pairs of aggregation {@code at}, row {@code row} of the lane -> the DoubleArrayList the reference's function
+   * hands on (PercentileAggregationFunction.aggregate :77-100 appends every matching doc's value; the order does not matter, extractFinalResult
+   * sorts): dictionary.getDoubleValue(dictId), count times, dictIds ascending.  An empty list under null handling is the null holder.
+   */
+  private DoubleArrayList valueList(int function, LaneResult r, int at, int row, boolean nullHandling) {
+    int[] dictIds = (int[]) r._percentileIds[at * r._rows + row];
+    int[] counts = (int[]) r._percentileCounts[at * r._rows + row];
+    if (nullHandling && dictIds.length == 0) {
+      return null;
+    }
+    String column = _functions[function].getInputExpressions().get(0).getIdentifier();
+    Dictionary dictionary = _indexSegment.getDataSource(column).getDictionary();
+    long size = 0;
+    for (int count : counts) {
+      size += count;
+    }
+    DoubleArrayList values = new DoubleArrayList((int) size);
+    for (int i = 0; i < dictIds.length; i++) {
+      double value = dictionary.getDoubleValue(dictIds[i]);
+      for (int n = 0; n < counts[i]; n++) {
+        values.add(value);
       }
     }
     return values;
@@ -304,7 +350,14 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       for (int i = 0; i < positions.length; i++) {
         AggregationFunctionType type = _functions[positions[i]].getType();
         boolean object = type == AggregationFunctionType.AVG || (nullHandling && type != AggregationFunctionType.COUNT);
-        if (type == AggregationFunctionType.DISTINCTCOUNT) {
+        if (type == AggregationFunctionType.PERCENTILE) {
+          // one value list per group (aggregateGroupBySV keeps a DoubleArrayList per group key)
+          ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);
+          for (int g = 0; g < rowOf.length; g++) {
+            holder.setValueForKey(rowOf[g], valueList(positions[i], r, i, g, nullHandling));
+          }
+          holders[positions[i]] = holder;
+        } else if (type == AggregationFunctionType.DISTINCTCOUNT) {
           // one value set per group (svAggregateGroupBySV :306-321 keeps a dictId bitmap per group; extractGroupByResult converts it)
           ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);
           for (int g = 0; g < rowOf.length; g++) {

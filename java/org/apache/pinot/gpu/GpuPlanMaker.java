@@ -191,14 +191,20 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
     // makeInstancePlan below is planning a whole query: its lanes join the query's batch, in plan order
     GpuBatch planningBatch = _planningBatch.get();
     boolean distinctCount = false;
+    boolean percentile = false;
     for (GpuAggregationOperator.Lane lane : lanes) {
       distinctCount |= lane._query._hasDistinctCount;
+      percentile |= lane._query._hasPercentile;
     }
-    if (distinctCount && queryContext.hasFilteredAggregations()) {
-      return cpuPlan;      // DISTINCTCOUNT beside FILTER (WHERE ...) lanes keeps the CPU plan
+    if ((distinctCount || percentile) && queryContext.hasFilteredAggregations()) {
+      return cpuPlan;      // DISTINCTCOUNT / PERCENTILE beside FILTER (WHERE ...) lanes keeps the CPU plan
+    }
+    if (distinctCount && percentile) {
+      return cpuPlan;      // the engine declines the two in one query
     }
     // (a DISTINCTCOUNT lane reads its sets before the native result is released: one call of its own, PinotGpuNative.executeWithDistinctSets)
-    final GpuBatch batch = distinctCount ? null : planningBatch;
+    // (a PERCENTILE lane likewise: PinotGpuNative.executeWithPercentileCounts)
+    final GpuBatch batch = (distinctCount || percentile) ? null : planningBatch;
     int[] batchSlots = null;
     if (batch != null) {
       batchSlots = new int[lanes.size()];

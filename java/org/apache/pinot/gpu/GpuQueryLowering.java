@@ -63,6 +63,7 @@ final class GpuQueryLowering {
   static final int AGG_MAX = PinotGpuNative.PG_AGG_MAX;
   static final int AGG_AVG = PinotGpuNative.PG_AGG_AVG;
   static final int AGG_DISTINCTCOUNT = PinotGpuNative.PG_AGG_DISTINCTCOUNT;
+  static final int AGG_PERCENTILE = PinotGpuNative.PG_AGG_PERCENTILE;
   private static final int NODE_INTS = PinotGpuNative.PGM_FILTER_NODE_INTS;
   private static final int PRED_INTS = PinotGpuNative.PGM_PRED_INTS;
   private static final int PRED_LONGS = PinotGpuNative.PGM_PRED_LONGS;
@@ -88,6 +89,7 @@ final class GpuQueryLowering {
     int _numGroupsLimit;
     int _flags;
     boolean _hasDistinctCount;      // a DISTINCTCOUNT among the aggregations: executed alone through executeWithDistinctSets, never in a batch
+    boolean _hasPercentile;         // a PERCENTILE among the aggregations: executed alone through executeWithPercentileCounts, never in a batch
   }
 
   /** Thrown inside the lowering when a construct has no device form; the plan maker keeps the CPU plan. */
@@ -207,6 +209,11 @@ final class GpuQueryLowering {
         case DISTINCTCOUNT:
           code = AGG_DISTINCTCOUNT;
           break;
+        case PERCENTILE:
+          // the exact PercentileAggregationFunction (PERCENTILE50(col) / PERCENTILE(col, 50)); the percentile itself stays with the function object:
+          // the device returns the whole value list whatever it is
+          code = AGG_PERCENTILE;
+          break;
         default:
           throw new NotOffloadable("aggregation function " + function.getType());
       }
@@ -232,6 +239,13 @@ final class GpuQueryLowering {
             throw new NotOffloadable("DISTINCTCOUNT on a column without a dictionary");
           }
           out._hasDistinctCount = true;
+        }
+        if (code == AGG_PERCENTILE) {
+          // dictId count histograms on the device: a dictionary column only (a raw column keeps the reference's DoubleArrayList: CPU plan)
+          if (!_segment.hasDictionary(column)) {
+            throw new NotOffloadable("PERCENTILE on a column without a dictionary");
+          }
+          out._hasPercentile = true;
         }
       }
       out._aggregations[AGG_INTS * i] = code;

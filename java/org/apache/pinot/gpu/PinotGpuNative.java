@@ -83,6 +83,8 @@ public final class PinotGpuNative {
   public static final int PG_AGG_AVG = 4;
   /** DistinctCountAggregationFunction on a dictionary column: the segment's (or the group's) dictId set comes back through executeWithDistinctSets. */
   public static final int PG_AGG_DISTINCTCOUNT = 5;
+  /** PercentileAggregationFunction on a dictionary column: the value list comes back as (dictId, count) pairs through executeWithPercentileCounts. */
+  public static final int PG_AGG_PERCENTILE = 6;
 
   /** pg_query.flags */
   public static final int PG_QUERY_NULL_HANDLING = 1;
@@ -217,6 +219,21 @@ public final class PinotGpuNative {
    * (bit d &amp; 31 of word d &gt;&gt; 5) for a DISTINCTCOUNT aggregation and null for every other function; rows = 1 without GROUP BY, else the groups.
    */
   static native Object[] executeWithDistinctSets(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
+      int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
+
+  /** Slots of executeWithPercentileCounts' Object[]: the Object[PGM_RESULT_ARRAYS] of execute(), then the lists' dictIds and their counts. */
+  public static final int PGM_PERCENTILE_SLOTS = 3;
+  public static final int PGM_PERCENTILE_RESULT = 0;
+  public static final int PGM_PERCENTILE_DICT_IDS = 1;
+  public static final int PGM_PERCENTILE_COUNTS = 2;
+
+  /**
+   * pg_execute of a query with PG_AGG_PERCENTILE aggregations plus pg_result_percentile_counts over its result.  Returns Object[PGM_PERCENTILE_SLOTS]:
+   * what execute() returns, and two Object[aggregations * rows] whose elements {@code aggregation * rows + row} are the int[] of the list's ascending
+   * dictIds and the int[] of how many matching docs carry each, for a PERCENTILE aggregation, and null for every other function; rows = 1 without
+   * GROUP BY, else the groups.
+   */
+  static native Object[] executeWithPercentileCounts(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
       int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
 
   /**

@@ -407,6 +407,61 @@ JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeW
   return out;
 }
 
+/* pg_execute of a query with PG_AGG_PERCENTILE aggregations, and pg_result_percentile_counts over its result before that is released.
+ * Returns Object[PGM_PERCENTILE_SLOTS]: {the Object[PGM_RESULT_ARRAYS] execute() returns, Object[aggregations * rows], Object[aggregations * rows]} -- element
+ * (aggregation * rows + row) of the second array is the int[] of the list's ascending dictIds, of the third the int[] of their counts (non-zero;
+ * a count is below 2^31) for a PERCENTILE aggregation, null in both for every other function; rows = 1 for an aggregation-only query, else the
+ * number of groups. */
+JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeWithPercentileCounts(JNIEnv* env, jclass cls, jlong handle, jintArray filterNodes,
+    jintArray predInts, jlongArray predLongs, jintArray setOffsets, jintArray setWords, jintArray aggregations, jintArray groupBy,
+    jint numGroupsLimit, jint flags) {
+  (void)cls;
+  pinned_query p;
+  if (!pin_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy, numGroupsLimit, flags)) return NULL;
+  const int32_t num_group_by = pgm_query_get(p.built)->num_group_by;
+  pg_result result;
+  const pg_status status = pg_execute((pg_segment*)(intptr_t)handle, pgm_query_get(p.built), &result);
+  release_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy);
+  if (status != PG_OK) { throw_status(env, status); return NULL; }     /* pg_execute freed the result */
+  const jsize rows = num_group_by > 0 ? (jsize)result.num_groups : 1;
+  const jsize na = (jsize)result.num_aggregations;
+  jclass object_class = (*env)->FindClass(env, "java/lang/Object");
+  jobjectArray ids = object_class ? (*env)->NewObjectArray(env, na * rows, object_class, NULL) : NULL;
+  jobjectArray counts = ids ? (*env)->NewObjectArray(env, na * rows, object_class, NULL) : NULL;
+  int ok = counts != NULL;
+  for (jsize a = 0; ok && a < na; ++a) {
+    for (jsize r = 0; ok && r < rows; ++r) {
+      const int32_t* dict_ids = NULL;
+      const uint32_t* doc_counts = NULL;
+      int32_t num = 0;
+      if (pg_result_percentile_counts(&result, (int32_t)a, num_group_by > 0 ? (int32_t)r : -1, &dict_ids, &doc_counts, &num) != PG_OK) break;      /* not a PERCENTILE: the row of nulls stays */
+      jintArray both[2] = {(*env)->NewIntArray(env, (jsize)num), NULL};
+      both[1] = both[0] ? (*env)->NewIntArray(env, (jsize)num) : NULL;
+      if (both[1] == NULL) { ok = 0; break; }
+      for (int which = 0; ok && which < 2; ++which) {
+        jint* dst = (*env)->GetIntArrayElements(env, both[which], NULL);
+        if (dst == NULL) { ok = 0; break; }
+        if (num > 0) memcpy(dst, which == 0 ? (const void*)dict_ids : (const void*)doc_counts, (size_t)num * sizeof(jint));
+        (*env)->ReleaseIntArrayElements(env, both[which], dst, 0);
+        (*env)->SetObjectArrayElement(env, which == 0 ? ids : counts, a * rows + r, both[which]);
+      }
+      (*env)->DeleteLocalRef(env, both[0]);
+      (*env)->DeleteLocalRef(env, both[1]);
+    }
+  }
+  jobjectArray converted = result_to_java(env, &result, num_group_by);      /* releases the result */
+  if (!ok || converted == NULL) {
+    if (!(*env)->ExceptionCheck(env)) throw_new(env, "java/lang/OutOfMemoryError", "allocating the PERCENTILE lists failed");
+    return NULL;
+  }
+  jobjectArray out = (*env)->NewObjectArray(env, PGM_PERCENTILE_SLOTS, object_class, NULL);
+  if (out == NULL) return NULL;
+  (*env)->SetObjectArrayElement(env, out, PGM_PERCENTILE_RESULT, converted);
+  (*env)->SetObjectArrayElement(env, out, PGM_PERCENTILE_DICT_IDS, ids);
+  (*env)->SetObjectArrayElement(env, out, PGM_PERCENTILE_COUNTS, counts);
+  return out;
+}
+
 /* pg_execute_batch: queries[i] (Object[PGM_QUERY_ARRAYS], slots PGM_Q_*) over handles[i] -- the segments of ONE query as the combine operator
  * would hand them to its worker threads (BaseCombineOperator.java:85-142).  Returns Object[n]: element i is the Object[PGM_RESULT_ARRAYS]
  * execute() would have returned for item i, or -- the item failed, the others did not stop for it -- a String "<pg_status>\n<message>".

@@ -49,6 +49,15 @@ std::string intermediateJson(const IntermediateResult& r) {
     }
     return out + "]}";
   }
+  if (std::holds_alternative<ValueCounts>(r)) {
+    // the value list as its ascending runs
+    const ValueCounts& l = std::get<ValueCounts>(r);
+    std::string out = "{\"values\": [";
+    for (size_t i = 0; i < l.values.size(); ++i) out += (i ? ", " : "") + num(l.values[i]);
+    out += "], \"counts\": [";
+    for (size_t i = 0; i < l.counts.size(); ++i) out += (i ? ", " : "") + std::to_string(l.counts[i]);
+    return out + "]}";
+  }
   const AvgPair& p = std::get<AvgPair>(r);
   return "[" + num(p.sum) + ", " + std::to_string(p.count) + "]";
 }
@@ -131,7 +140,8 @@ std::string reducedJson(const std::vector<ReducedRow>& rows) {
 ResultsBlock blockFromArrays(bool is_group_by, const std::vector<AggregationFunction>& functions, int32_t num_keys, const char* const* key_names,
                              const int32_t* key_types, int64_t row_begin, int64_t row_end, const int64_t* key_longs, const double* key_doubles,
                              const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums, const double* mins,
-                             const double* maxs, const uint8_t* is_null, const int64_t* set_offsets = nullptr, const int64_t* set_values = nullptr) {
+                             const double* maxs, const uint8_t* is_null, const int64_t* set_offsets = nullptr, const int64_t* set_values = nullptr,
+                             const int64_t* run_offsets = nullptr, const double* run_values = nullptr, const int64_t* run_counts = nullptr) {
   ResultsBlock block;
   block.isGroupBy = is_group_by;
   const int num_functions = (int)functions.size();
@@ -147,6 +157,20 @@ ResultsBlock blockFromArrays(bool is_group_by, const std::vector<AggregationFunc
         std::sort(s.values.begin(), s.values.end());
         s.values.erase(std::unique(s.values.begin(), s.values.end()), s.values.end());
         return s;
+      }
+      case AggregationFunctionType::PERCENTILE: {
+        // cell `at` holds the runs (run_values[i], run_counts[i]), i in [run_offsets[at], run_offsets[at + 1]): any order, values may repeat
+        ValueCounts l;
+        if (run_offsets && run_values && run_counts) {
+          std::vector<std::pair<double, int64_t>> runs;
+          for (int64_t i = run_offsets[at]; i < run_offsets[at + 1]; ++i) if (run_counts[i] > 0) runs.emplace_back(run_values[i], run_counts[i]);
+          std::sort(runs.begin(), runs.end());
+          for (const auto& run : runs) {
+            if (!l.values.empty() && l.values.back() == run.first) l.counts.back() += run.second;
+            else { l.values.push_back(run.first); l.counts.push_back(run.second); }
+          }
+        }
+        return l;
       }
       case AggregationFunctionType::COUNT: return counts[at];
       case AggregationFunctionType::SUM: return sums[at];
@@ -415,7 +439,7 @@ char* ph_parse_sql(const char* sql, int32_t* status) {
     std::ostringstream o;
     o << "{\"table\": \"" << jsonEscape(q.tableName) << "\", \"aggregations\": [";
     for (size_t i = 0; i < q.aggregations.size(); ++i)
-      o << (i ? ", " : "") << "\"" << jsonEscape(AggregationFunction(q.aggregations[i].function, q.aggregations[i].column).getResultColumnName()
+      o << (i ? ", " : "") << "\"" << jsonEscape(AggregationFunction(q.aggregations[i]).getResultColumnName()
                                                 + (q.aggregations[i].hasFilter ? " FILTER(WHERE " + q.aggregations[i].filterText + ")" : std::string())) << "\"";
     o << "], \"groupBy\": [";
     for (size_t i = 0; i < q.groupByExpressions.size(); ++i) o << (i ? ", " : "") << "\"" << jsonEscape(q.groupByExpressions[i]) << "\"";
@@ -425,7 +449,7 @@ char* ph_parse_sql(const char* sql, int32_t* status) {
       o << ", \"orderBy\": [";
       for (size_t i = 0; i < q.orderByExpressions.size(); ++i) {
         const OrderByExpressionContext& ob = q.orderByExpressions[i];
-        const std::string text = ob.isAggregation ? AggregationFunction(q.aggregations[(size_t)ob.index].function, q.aggregations[(size_t)ob.index].column).getResultColumnName()
+        const std::string text = ob.isAggregation ? AggregationFunction(q.aggregations[(size_t)ob.index]).getResultColumnName()
                                                   : q.groupByExpressions[(size_t)ob.index];
         o << (i ? ", " : "") << "{\"expression\": \"" << jsonEscape(text) << "\", \"asc\": " << (ob.isAsc ? "true" : "false") << ", \"nullsLast\": "
           << (ob.isNullsLast() ? "true" : "false") << "}";
@@ -637,7 +661,7 @@ char* ph_group_by_combine_sets(const char* sql, int32_t num_blocks, const int64_
     const QueryContext q = getQueryContext(sql);
     if (q.groupByExpressions.empty()) throw QueryException("ph_group_by_combine needs a GROUP BY query");
     std::vector<AggregationFunction> functions;
-    for (const auto& a : q.aggregations) functions.emplace_back(a.function, a.column, q.nullHandlingEnabled);
+    for (const auto& a : q.aggregations) functions.emplace_back(a, q.nullHandlingEnabled);
     std::vector<const char*> key_names;
     for (const auto& g : q.groupByExpressions) key_names.push_back(g.c_str());
     std::vector<ResultsBlock> blocks;
@@ -661,6 +685,48 @@ char* ph_group_by_combine_sets(const char* sql, int32_t num_blocks, const int64_
     o << "{\"combined\": " << blockJson(combined) << ", \"reduced\": " << reducedJson(reduced) << ", \"resultTable\": " << resultTableJson(toResultTable(reduced, combined, q))
       << ", \"table\": {\"resultSize\": " << sizes.resultSize()
       << ", \"trimSize\": " << sizes.trimSize() << ", \"trimThreshold\": " << sizes.trimThreshold() << ", \"numResizes\": " << table.getNumResizes() << "}}";
+    out = o.str();
+  });
+  return *status == 0 ? strdup(out.c_str()) : nullptr;
+}
+
+// The combine of PERCENTILE value lists built on the host (no device): one block per segment, the cells of PERCENTILE functions given as runs --
+// cell (row, function) holds (run_values[i], run_counts[i]) for i in [run_offsets[row * functions + function], run_offsets[.. + 1]).  A GROUP BY
+// query goes the way of ph_group_by_combine (same array conventions and result); an aggregation-only query has one row per block, is merged
+// with AggregationResultsBlockMerger's mergeResultsBlocks and returns {"combined": <block>}.
+char* ph_combine_counts(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                        const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                        const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* run_offsets, const double* run_values,
+                        const int64_t* run_counts, int32_t* status) {
+  std::string out;
+  *status = guarded([&] {
+    const QueryContext q = getQueryContext(sql);
+    std::vector<AggregationFunction> functions;
+    for (const auto& a : q.aggregations) functions.emplace_back(a, q.nullHandlingEnabled);
+    std::vector<const char*> key_names;
+    for (const auto& g : q.groupByExpressions) key_names.push_back(g.c_str());
+    const bool grouped = !q.groupByExpressions.empty();
+    std::vector<ResultsBlock> blocks;
+    int64_t row = 0;
+    for (int b = 0; b < num_blocks; ++b) {
+      if (!grouped && block_rows[b] != 1) throw QueryException("an aggregation-only block has one row");
+      ResultsBlock block = blockFromArrays(grouped, functions, (int32_t)key_names.size(), key_names.data(), key_types, row, row + block_rows[b], key_longs, key_doubles,
+                                           key_strings, key_is_null, counts, sums, mins, maxs, is_null, nullptr, nullptr, run_offsets, run_values, run_counts);
+      if (grouped) trimSegmentGroupByBlock(&block, q);
+      blocks.push_back(std::move(block));
+      row += block_rows[b];
+    }
+    if (blocks.empty()) throw QueryException("no blocks");
+    std::ostringstream o;
+    if (!grouped) {
+      ResultsBlock merged = blocks[0];
+      for (size_t i = 1; i < blocks.size(); ++i) mergeResultsBlocks(&merged, blocks[i]);
+      o << "{\"combined\": " << blockJson(merged) << "}";
+    } else {
+      const ResultsBlock combined = combineGroupByBlocks(blocks, q);
+      const std::vector<ReducedRow> reduced = reduceGroupBy(combined, q);
+      o << "{\"combined\": " << blockJson(combined) << ", \"reduced\": " << reducedJson(reduced) << ", \"resultTable\": " << resultTableJson(toResultTable(reduced, combined, q)) << "}";
+    }
     out = o.str();
   });
   return *status == 0 ? strdup(out.c_str()) : nullptr;

@@ -206,13 +206,19 @@ struct FilterContext {                               // common/request/context/F
   Predicate predicate;
 };
 
-enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT };   // sspi/AggregationFunctionType.java (ordinals = pg_agg_function)
+enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE };   // sspi/AggregationFunctionType.java (ordinals = pg_agg_function)
 // DISTINCTCOUNT(col) / DISTINCT_COUNT(col) (the reference canonicalises function names by dropping underscores): the engine returns a segment's
 // dictId set (PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids), the mirror turns it into the value set that segments merge (ValueSet below).
+
+// PERCENTILE<digits>(col) (the int form, AggregationFunctionFactory.java:88-91) / PERCENTILE(col, p) with a numeric or quoted literal (the double
+// form, :133-141): the exact PercentileAggregationFunction.  The engine returns how many matching docs carry each dictId (PG_AGG_PERCENTILE,
+// pg_result_percentile_counts), the mirror turns that into the value list that segments merge (ValueCounts below).
 
 struct AggregationExpression {
   AggregationFunctionType function;
   std::string column;                                // "*" for COUNT(*)
+  double percentile = 0.0;                           // PERCENTILE: p in [0, 100]
+  bool percentileIntForm = false;                    // PERCENTILE50(col) -> "percentile50(col)"; PERCENTILE(col, 50) -> "percentile(col, 50.0)"
   // SUM(x) FILTER (WHERE ...): FilteredAggregationFunction (core/query/aggregation/function/FilterableAggregationFunction / QueryContext
   // filtered aggregations); evaluated as one "swim lane" per distinct filter like FilteredAggregationOperator
   bool hasFilter = false;
@@ -285,25 +291,36 @@ struct AvgPair { double sum = 0.0; int64_t count = 0; };                  // seg
 // the segment's dictionary), kept as the ascending 64-bit images of the values tagged with the stored type: INT / LONG the value, FLOAT /
 // DOUBLE the IEEE-754 bits of the value as a double.  merge = set union (:109-121); the final result is the size, an INT (:66-68).
 struct ValueSet { DataType storedType = DataType::INT; std::vector<int64_t> values; };
-using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet>;   // Long / Double / AvgPair / null (null handling only) / value set
+// PERCENTILE's intermediate result: the DoubleArrayList of PercentileAggregationFunction (:77-100) as ascending runs of (value, count) -- the
+// list's order does not matter (extractFinalResult sorts it, :155-172).  merge = the run-wise merge (addAll up to order).
+struct ValueCounts { std::vector<double> values; std::vector<int64_t> counts; int64_t size() const { int64_t n = 0; for (int64_t c : counts) n += c; return n; } };
+using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet, ValueCounts>;   // Long / Double / AvgPair / null (null handling only) / value set / value list
 inline bool isNullResult(const IntermediateResult& r) { return std::holds_alternative<std::monostate>(r); }
 
 class AggregationFunction {                         // query/aggregation/function/AggregationFunction.java:42-145
  public:
   AggregationFunction(AggregationFunctionType type, std::string column, bool nullHandlingEnabled = false)
       : _type(type), _column(std::move(column)), _nullHandlingEnabled(nullHandlingEnabled) {}
+  AggregationFunction(const AggregationExpression& e, bool nullHandlingEnabled = false)
+      : _type(e.function), _column(e.column), _nullHandlingEnabled(nullHandlingEnabled), _percentile(e.percentile), _percentileIntForm(e.percentileIntForm) {}
+  double getPercentile() const { return _percentile; }
   AggregationFunctionType getType() const { return _type; }
   const std::string& getColumn() const { return _column; }
   std::string getResultColumnName() const;
   IntermediateResult fromDevice(const pg_agg_value& v) const;            // extractAggregationResult / extractGroupByResult
   // DISTINCTCOUNT: the dictId set of pg_result_distinct_dict_ids (bit d & 31 of words[d >> 5]) -> the value set, through the column's dictionary
   IntermediateResult fromDeviceSet(const uint32_t* words, int32_t numWords, const DataSource& dataSource) const;
+  // PERCENTILE: the (dictId, count) pairs of pg_result_percentile_counts -> runs of (value, count), the values as Dictionary.getDoubleValue
+  // gives them (getDoubleValuesSV); two LONG values that land on one double merge into one run
+  IntermediateResult fromDeviceCounts(const int32_t* dictIds, const uint32_t* counts, int32_t num, const DataSource& dataSource) const;
   IntermediateResult merge(const IntermediateResult& a, const IntermediateResult& b) const;
   double extractFinalResult(const IntermediateResult& r) const;          // COUNT returns the long as a double-exact value
  private:
   AggregationFunctionType _type;
   std::string _column;
   bool _nullHandlingEnabled;                          // NullableSingleInputAggregationFunction._nullHandlingEnabled
+  double _percentile = 0.0;                           // PERCENTILE only
+  bool _percentileIntForm = false;
 };
 
 // ---- operator/ExecutionStatistics.java:25-64 ---------------------------------------------------------------------
@@ -501,6 +518,7 @@ struct GpuAbi {
   decltype(&pg_execute_batch) execute_batch;
   decltype(&pg_result_free) result_free;
   decltype(&pg_result_distinct_dict_ids) result_distinct_dict_ids;
+  decltype(&pg_result_percentile_counts) result_percentile_counts;
   decltype(&pg_filter_bitmap) filter_bitmap;
   decltype(&pg_group_key_info) group_key_info;
   decltype(&pg_group_key_values) group_key_values;

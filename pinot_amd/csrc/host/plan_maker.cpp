@@ -48,6 +48,7 @@ const GpuAbi& gpuAbi() {
     abi.execute_batch = (decltype(abi.execute_batch))sym("pg_execute_batch");
     abi.result_free = (decltype(abi.result_free))sym("pg_result_free");
     abi.result_distinct_dict_ids = (decltype(abi.result_distinct_dict_ids))sym("pg_result_distinct_dict_ids");
+    abi.result_percentile_counts = (decltype(abi.result_percentile_counts))sym("pg_result_percentile_counts");
     abi.filter_bitmap = (decltype(abi.filter_bitmap))sym("pg_filter_bitmap");
     abi.group_key_info = (decltype(abi.group_key_info))sym("pg_group_key_info");
     abi.group_key_values = (decltype(abi.group_key_values))sym("pg_group_key_values");
@@ -162,7 +163,15 @@ void ImmutableSegment::setQueryableDocIds(const void* roaringBytes, uint64_t siz
 // AggregationFunction
 // ---------------------------------------------------------------------------------------------------------------
 std::string AggregationFunction::getResultColumnName() const {
-  static const char* names[] = {"count", "sum", "min", "max", "avg", "distinctcount"};
+  static const char* names[] = {"count", "sum", "min", "max", "avg", "distinctcount", "percentile"};
+  if (_type == AggregationFunctionType::PERCENTILE) {
+    // PercentileAggregationFunction.getResultColumnName :63-66: version 0 "percentile50(col)", version 1 "percentile(col, 50.0)" (Double.toString)
+    if (_percentileIntForm) return "percentile" + std::to_string((int)_percentile) + "(" + _column + ")";
+    char b[40];
+    if (_percentile == std::floor(_percentile)) snprintf(b, sizeof(b), "%.1f", _percentile);
+    else for (int digits = 1; digits <= 17; ++digits) { snprintf(b, sizeof(b), "%.*g", digits, _percentile); if (strtod(b, nullptr) == _percentile) break; }
+    return "percentile(" + _column + ", " + b + ")";
+  }
   return std::string(names[(int)_type]) + "(" + _column + ")";
 }
 
@@ -177,6 +186,7 @@ IntermediateResult AggregationFunction::fromDevice(const pg_agg_value& v) const 
     case AggregationFunctionType::MAX: return v.max;                       // Double, -inf when nothing matched
     case AggregationFunctionType::AVG: return AvgPair{v.sum, v.count};     // AvgPair(sum, count)
     case AggregationFunctionType::DISTINCTCOUNT: return ValueSet{};         // (no doc reached the holder: the empty set; a set comes through fromDeviceSet)
+    case AggregationFunctionType::PERCENTILE: return ValueCounts{};         // (the empty list; a list comes through fromDeviceCounts)
   }
   return 0.0;
 }
@@ -198,6 +208,17 @@ IntermediateResult AggregationFunction::fromDeviceSet(const uint32_t* words, int
   return set;
 }
 
+IntermediateResult AggregationFunction::fromDeviceCounts(const int32_t* dictIds, const uint32_t* counts, int32_t num, const DataSource& ds) const {
+  ValueCounts list;
+  list.values.reserve((size_t)num); list.counts.reserve((size_t)num);
+  for (int32_t i = 0; i < num; ++i) {
+    const double v = ds.dictionary->getDoubleValue(dictIds[i]);      // ascending: the dictionary is sorted and the conversion is monotone
+    if (!list.values.empty() && list.values.back() == v) list.counts.back() += (int64_t)counts[i];      // (two LONGs on one double)
+    else { list.values.push_back(v); list.counts.push_back((int64_t)counts[i]); }
+  }
+  return list;
+}
+
 IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const IntermediateResult& b) const {
   // SumAggregationFunction.merge :223-233 and friends under null handling: a null side yields the other side
   if (isNullResult(a)) return b;
@@ -210,6 +231,22 @@ IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const
       r.storedType = x.values.empty() ? y.storedType : x.storedType;
       r.values.reserve(x.values.size() + y.values.size());
       std::set_union(x.values.begin(), x.values.end(), y.values.begin(), y.values.end(), std::back_inserter(r.values));
+      return r;
+    }
+    case AggregationFunctionType::PERCENTILE: {                                                // PercentileAggregationFunction.merge :143-147: addAll, up to order
+      const ValueCounts& x = std::get<ValueCounts>(a);
+      const ValueCounts& y = std::get<ValueCounts>(b);
+      ValueCounts r;
+      r.values.reserve(x.values.size() + y.values.size()); r.counts.reserve(x.values.size() + y.values.size());
+      size_t i = 0, j = 0;
+      while (i < x.values.size() || j < y.values.size()) {
+        const bool takeX = j == y.values.size() || (i < x.values.size() && x.values[i] <= y.values[j]);
+        const double v = takeX ? x.values[i] : y.values[j];
+        int64_t n = 0;
+        if (i < x.values.size() && x.values[i] == v) n += x.counts[i++];
+        if (j < y.values.size() && y.values[j] == v) n += y.counts[j++];
+        r.values.push_back(v); r.counts.push_back(n);
+      }
       return r;
     }
     case AggregationFunctionType::COUNT: return std::get<int64_t>(a) + std::get<int64_t>(b);   // CountAggregationFunction.merge
@@ -234,6 +271,17 @@ double AggregationFunction::extractFinalResult(const IntermediateResult& r) cons
   switch (_type) {
     case AggregationFunctionType::COUNT: return (double)std::get<int64_t>(r);
     case AggregationFunctionType::DISTINCTCOUNT: return (double)std::get<ValueSet>(r).values.size();   // extractFinalResult :66-68: the set's size (an INT)
+    case AggregationFunctionType::PERCENTILE: {
+      // PercentileAggregationFunction.extractFinalResult :155-172: empty -> DEFAULT_FINAL_RESULT = -inf; else sort and take
+      // values[(int) ((long) size * percentile / 100)] (long x double / 100, truncated), the last value when percentile == 100
+      const ValueCounts& list = std::get<ValueCounts>(r);
+      const int64_t size = list.size();
+      if (size == 0) return -INFINITY;
+      const int64_t index = _percentile == 100.0 ? size - 1 : (int64_t)(int32_t)((double)size * _percentile / 100.0);
+      int64_t seen = 0;
+      for (size_t i = 0; i < list.values.size(); ++i) { seen += list.counts[i]; if (index < seen) return list.values[i]; }
+      return list.values.back();
+    }
     case AggregationFunctionType::AVG: {                                    // AvgAggregationFunction.extractFinalResult :209-218
       const AvgPair& p = std::get<AvgPair>(r);
       return p.count == 0 ? -INFINITY : p.sum / (double)p.count;            // DEFAULT_FINAL_RESULT = Double.NEGATIVE_INFINITY
@@ -509,6 +557,10 @@ std::unique_ptr<LoweredQuery> lowerQuery(const ImmutableSegment& seg, const Quer
     if (root.kind != PhysNode::MATCH_ALL) flattenFilter(root, lq.get());      // a filter that matches everything is no filter (MatchAllFilterOperator)
   }
   for (const auto& a : qc.aggregations) {
+    if (a.function == AggregationFunctionType::PERCENTILE) {
+      if (a.column == "*") throw QueryException("'*' is only valid in COUNT(*)");
+      if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException("PERCENTILE(" + a.column + ") on a STRING column keeps the CPU plan");
+    }
     if (a.function == AggregationFunctionType::DISTINCTCOUNT) {
       // the engine takes a dictionary column of a numeric stored type (pg_query_check says so for raw columns; FILTER (WHERE ...) lanes beside
       // a DISTINCTCOUNT are declined by makeSegmentPlanNode)
@@ -521,7 +573,7 @@ std::unique_ptr<LoweredQuery> lowerQuery(const ImmutableSegment& seg, const Quer
     if (pa.column >= 0) {
       const DataSource& ds = seg.getDataSource(a.column);
       if (!isNumeric(ds.dataType) && a.function != AggregationFunctionType::COUNT)
-        throw QueryException("Cannot compute " + AggregationFunction(a.function, a.column).getResultColumnName() + " for non-numeric type: STRING");
+        throw QueryException("Cannot compute " + AggregationFunction(a).getResultColumnName() + " for non-numeric type: STRING");
       // COUNT(col) == COUNT(*) unless null handling is on (CountAggregationFunction.java:44-50)
       if (a.function == AggregationFunctionType::COUNT && !qc.nullHandlingEnabled) pa.column = -1;
     }
@@ -650,7 +702,7 @@ class GpuAggregationOperator : public Operator {
     else checkStatus(gpuAbi().execute(_segment->handle(), &_lowered->query, &res), what.c_str());
     ResultsBlock block;
     std::vector<AggregationFunction> functions;
-    for (const auto& a : _queryContext.aggregations) functions.emplace_back(a.function, a.column, _queryContext.nullHandlingEnabled);
+    for (const auto& a : _queryContext.aggregations) functions.emplace_back(a, _queryContext.nullHandlingEnabled);
     block.stats.numDocsScanned = res.stats.num_docs_scanned;
     block.stats.numEntriesScannedInFilter = res.stats.num_entries_scanned_in_filter;
     block.stats.numEntriesScannedPostFilter = res.stats.num_entries_scanned_post_filter;
@@ -722,6 +774,16 @@ class GpuAggregationOperator : public Operator {
 
   // one function's holder out of the device result: DISTINCTCOUNT through the set accessor and the column's dictionary (before the result is freed)
   IntermediateResult fromResult(const AggregationFunction& f, const pg_result& res, int aggregation, int groupRow, const pg_agg_value& v) const {
+    if (f.getType() == AggregationFunctionType::PERCENTILE) {
+      const int32_t* dictIds = nullptr;
+      const uint32_t* counts = nullptr;
+      int32_t num = 0;
+      checkStatus(gpuAbi().result_percentile_counts(&res, aggregation, groupRow, &dictIds, &counts, &num), "reading a PERCENTILE list");
+      IntermediateResult list = f.fromDeviceCounts(dictIds, counts, num, _segment->getDataSource(f.getColumn()));
+      // NullableSingleInputAggregationFunction: under null handling a holder no value reached stays null
+      if (_queryContext.nullHandlingEnabled && num == 0) return std::monostate{};
+      return list;
+    }
     if (f.getType() != AggregationFunctionType::DISTINCTCOUNT) return f.fromDevice(v);
     const uint32_t* words = nullptr;
     int32_t numWords = 0;
@@ -852,7 +914,7 @@ class GpuFilteredAggregationOperator : public Operator {
     if (!_queryContext.groupByExpressions.empty()) return nextGroupByBlock();
     ResultsBlock block;
     block.isGroupBy = false;
-    for (const auto& a : _queryContext.aggregations) block.aggregation.functions.emplace_back(a.function, a.column, _queryContext.nullHandlingEnabled);
+    for (const auto& a : _queryContext.aggregations) block.aggregation.functions.emplace_back(a, _queryContext.nullHandlingEnabled);
     block.aggregation.results.resize(_queryContext.aggregations.size());
     for (auto& lane : _lanes) {
       ResultsBlock b = lane.op->nextBlock();
@@ -876,12 +938,12 @@ class GpuFilteredAggregationOperator : public Operator {
     GroupByResultsBlock& g = block.groupBy;
     g.groupByColumns = _queryContext.groupByExpressions;
     for (const auto& c : g.groupByColumns) g.groupByTypes.push_back(_segment->getDataSource(c).dataType);
-    for (const auto& a : _queryContext.aggregations) g.functions.emplace_back(a.function, a.column, _queryContext.nullHandlingEnabled);
+    for (const auto& a : _queryContext.aggregations) g.functions.emplace_back(a, _queryContext.nullHandlingEnabled);
     pg_agg_value empty;
     memset(&empty, 0, sizeof(empty));
     empty.min = INFINITY; empty.max = -INFINITY;
     std::vector<IntermediateResult> defaults;
-    for (const auto& f : g.functions) defaults.push_back(AggregationFunction(f.getType(), f.getColumn(), _queryContext.nullHandlingEnabled).fromDevice(empty));
+    for (const auto& f : g.functions) defaults.push_back(f.fromDevice(empty));
     std::map<std::vector<int32_t>, size_t> rowOf;         // the key's dictIds -> row (the same in every lane, whichever holder the key space calls for)
     for (auto& lane : _lanes) {
       ResultsBlock b = lane.op->nextBlock();
@@ -963,6 +1025,8 @@ std::unique_ptr<PlanNode> GpuPlanMaker::makeSegmentPlanNode(const SegmentContext
   if (!anyFiltered) return std::make_unique<GpuAggregationPlanNode>(seg, qc, lowerQuery(*seg, qc));
   for (const auto& a : qc.aggregations)
     if (a.function == AggregationFunctionType::DISTINCTCOUNT) throw UnsupportedOperationException("DISTINCTCOUNT in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
+  for (const auto& a : qc.aggregations)
+    if (a.function == AggregationFunctionType::PERCENTILE) throw UnsupportedOperationException("PERCENTILE in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
   std::vector<std::string> keys;                       // lane order = first appearance, the unfiltered lane keyed ""
   std::vector<QueryContext> laneQueries;
   std::vector<std::vector<int>> positions;

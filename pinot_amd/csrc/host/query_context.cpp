@@ -392,7 +392,20 @@ QueryContext getQueryContext(const std::string& sql) {
     else if (u == "MAX") e.function = AggregationFunctionType::MAX;
     else if (u == "AVG") e.function = AggregationFunctionType::AVG;
     else if (u == "DISTINCTCOUNT") e.function = AggregationFunctionType::DISTINCTCOUNT;
-    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT are offloaded, got " + fn.text);
+    else if (u.rfind("PERCENTILE", 0) == 0) {
+      // AggregationFunctionFactory.java:68-140: PERCENTILE<digits>(col) is the exact function with an int percentile, PERCENTILE(col, p) the same
+      // with a double; every other PERCENTILE... spelling (EST, TDIGEST, KLL, RAW..., ...MV, SMARTTDIGEST) is another function
+      const std::string rest = u.substr(10);
+      const bool digits = !rest.empty() && std::all_of(rest.begin(), rest.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+      if (!rest.empty() && !digits) throw QueryException("percentile function " + fn.text + " is not offloaded (only the exact PERCENTILE<p>(col) / PERCENTILE(col, p))");
+      e.function = AggregationFunctionType::PERCENTILE;
+      e.percentileIntForm = digits;
+      if (digits) {
+        if (rest.size() > 3 || atoi(rest.c_str()) > 100) throw QueryException("Invalid percentile: " + rest);      // parsePercentileToInt: [0, 100]
+        e.percentile = (double)atoi(rest.c_str());
+      }
+    }
+    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT/PERCENTILE are offloaded, got " + fn.text);
     lx.expectSymbol("(");
     if (lx.acceptSymbol("*")) e.column = "*";
     else {
@@ -405,6 +418,16 @@ QueryContext getQueryContext(const std::string& sql) {
       }
       if (c.kind != Token::IDENT) throw UnsupportedOperationException("only identifier arguments are offloaded (ProjectPlanNode.java:85-86)");
       e.column = c.text;
+      if (e.function == AggregationFunctionType::PERCENTILE && !e.percentileIntForm) {
+        // the second argument: a numeric literal or a quoted one (arguments.get(1).getLiteral().getDoubleValue()), 0.0 to 100.0
+        if (!lx.acceptSymbol(",")) throw QueryException("PERCENTILE(" + c.text + ") needs a percentile: PERCENTILE(col, p) or PERCENTILE<p>(col)");
+        const Token p = lx.next();
+        char* end = nullptr;
+        const double v = strtod(p.text.c_str(), &end);
+        if ((p.kind != Token::NUMBER && p.kind != Token::STRING) || p.text.empty() || end == p.text.c_str() || *end != '\0') throw QueryException("Invalid percentile: " + p.text);
+        if (!(v >= 0.0 && v <= 100.0)) throw QueryException("Invalid percentile: " + p.text);
+        e.percentile = v;
+      }
       if (!(lx.peek().kind == Token::SYMBOL && lx.peek().text == ")"))
         throw UnsupportedOperationException("only identifier arguments are offloaded (transform expressions keep the CPU plan, ProjectPlanNode.java:85-86)");
     }
@@ -474,7 +497,7 @@ QueryContext getQueryContext(const std::string& sql) {
         int found = -1;
         for (size_t a = 0; a < q.aggregations.size() && found < 0; ++a) {
           const AggregationExpression& e = q.aggregations[a];
-          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT"};
+          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "PERCENTILE()"};      // (a PERCENTILE is ordered by through its alias)
           if (!e.hasFilter && u == names[(int)e.function] && (e.column == column || (e.function == AggregationFunctionType::COUNT && (column == "*" || e.column == "*")))) found = (int)a;
         }
         if (found < 0) {
@@ -484,6 +507,7 @@ QueryContext getQueryContext(const std::string& sql) {
           int kind = -1;
           static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG"};      // (a DISTINCTCOUNT that is only ordered by keeps the CPU plan)
           for (int k = 0; k < 5; ++k) if (u == names[k]) kind = k;
+          if (u.rfind("PERCENTILE", 0) == 0) throw UnsupportedOperationException("ORDER BY a PERCENTILE expression keeps the CPU plan (select it with an alias and order by the alias on this path)");
           if (u == "DISTINCTCOUNT") throw UnsupportedOperationException("a DISTINCTCOUNT that appears only in ORDER BY keeps the CPU plan (select it to order by it on this path)");
           if (kind < 0) throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT are offloaded, got " + first.text);
           e.function = (AggregationFunctionType)kind;

@@ -235,6 +235,8 @@ struct ScanParams {
 };
 
 // ---- DISTINCTCOUNT on dictionary columns (pg_scan_distinct.h): dictId bitsets ----
+// PERCENTILE (pg_scan_counts.h) launches with the same block: DistinctCol.set_bits are then 32-bit counters, one per dictId, and
+// DistinctCol.words / lds_off / DistinctParams.lds_words count counters (words = the cardinality; GROUP BY: row g starts at counter g * words).
 constexpr int kMaxDistinctKeys = 4;      // group_distinct_kernel: group-by key columns
 struct DistinctCol {
   const uint8_t* fwd;      // the column's packed dictId stream

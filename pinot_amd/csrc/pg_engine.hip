@@ -78,6 +78,7 @@ struct Engine {
   int fold_one_counter = 1;  // PINOT_GPU_FOLD_ONE_COUNTER=0: grids of at most 64 workgroups also arrive on eight shard counters + the top one
   bool poll_result = true;   // PINOT_GPU_POLL_RESULT=0: pg_execute always waits with hipStreamSynchronize instead of spinning on the pinned record's sequence number
   bool distinct_lds = true;  // PINOT_GPU_DISTINCT_LDS=0: DISTINCTCOUNT keeps its dictId bitsets in HBM at every cardinality (scan_distinct_kernel<false>; tests of that tier on small dictionaries)
+  bool percentile_lds = true;  // PINOT_GPU_PERCENTILE_LDS=0: PERCENTILE keeps its dictId counters in HBM at every cardinality (scan_counts_kernel<false>; tests of that tier on small dictionaries)
   bool set_lds = true;       // PINOT_GPU_SET_LDS=0: dictId-set leaves (IN lists) of the lane-private scan kernels read their words from memory per doc (rounds 2-6a)
   bool lane_skip = true;     // PINOT_GPU_LANE_SKIP=0: the aggregating kernels load a tile's value bytes for every lane, matches or not
   bool batch_blocks_per_cu_forced = false;
@@ -264,7 +265,8 @@ struct ExecCtx {
   size_t leap_capacity = 0;
   WindowInfo* d_window_info = nullptr;          // index_and_kernel: {tile mask, matching docs} of every 65 536-doc window
   size_t tile_list_capacity = 0, window_info_capacity = 0;
-  uint32_t* d_distinct = nullptr;               // DISTINCTCOUNT: the query's dictId bitsets / bit matrices (pg_scan_distinct.h), zeroed ahead of every launch
+  uint32_t* d_distinct = nullptr;               // DISTINCTCOUNT: the query's dictId bitsets / bit matrices (pg_scan_distinct.h); PERCENTILE: its dictId counters / counter
+                                                // matrices (pg_scan_counts.h) -- one scratch (a query has one or the other), zeroed ahead of every launch
   size_t distinct_capacity = 0;                 // in 32-bit words (part of pg_segment.device_bytes)
 };
 
@@ -428,6 +430,11 @@ pg_status ensure_bitmap(pg_segment* seg, ExecCtx* c, size_t index) {
 // bound then still writes inside the allocation).  Counted in the plan-time byte checks (plan_distinct).
 inline size_t distinct_slack_words(int bits, int cardinality) {
   const size_t by_width = (((size_t)1 << bits) + 31) / 32, by_card = ((size_t)std::max(cardinality, 0) + 31) / 32;
+  return (by_width > by_card ? by_width - by_card : 0) + 1;
+}
+// The same for the 32-bit counters of PERCENTILE (pg_scan_counts.h): 2^bits - cardinality counters behind the last one (plan_percentile counts them).
+inline size_t counts_slack_words(int bits, int cardinality) {
+  const size_t by_width = (size_t)1 << bits, by_card = (size_t)std::max(cardinality, 0);
   return (by_width > by_card ? by_width - by_card : 0) + 1;
 }
 constexpr size_t kDistinctKeepWords = (size_t)64 << 20;      // a bit matrix above 256 MB is freed after the query instead of staying with the context
@@ -1028,6 +1035,7 @@ struct Lowered {
   uint32_t* sp_leaf_out[kMaxLeaves] = {};      // out: ScanParams.leaf_out, by LEAF node ordinal
   // the bitset pass of a DISTINCTCOUNT query (kQueryDistinctPass): plan slots of its DISTINCTCOUNT columns and of group_distinct_kernel's keys
   std::vector<int> distinct_slots, distinct_key_slots;
+  bool counts_pass = false;                    // kQueryCountsPass: the slots are PERCENTILE columns, the kernels scan_counts_kernel / group_counts_kernel (32-bit counters per dictId)
 };
 
 int slot_for(Lowered* lw, const pg_segment* seg, int column, bool plane = false) {
@@ -2024,6 +2032,7 @@ pg_status pg_init(const pg_config* config) {
   g_engine.lean_batch = env_on("PINOT_GPU_LEAN_BATCH");
   g_engine.set_lds = env_on("PINOT_GPU_SET_LDS");
   g_engine.distinct_lds = env_on("PINOT_GPU_DISTINCT_LDS");
+  g_engine.percentile_lds = env_on("PINOT_GPU_PERCENTILE_LDS");
   g_engine.partition_two_level = env_on("PINOT_GPU_PARTITION_TWO_LEVEL");
   g_engine.fsm_perm = env_on("PINOT_GPU_FSM_PERM");
   g_engine.fsm_stats = env_on("PINOT_GPU_FSM_STATS");
@@ -2534,7 +2543,18 @@ struct DistinctSet {
   int rows = 1;
   std::vector<uint32_t> words;          // [rows * num_words]: one row (aggregation only), or one per row of group_aggregations
 };
-struct ResultInternal { std::vector<DistinctSet> distinct; };
+// The value list behind a PG_AGG_PERCENTILE aggregation, sparse and in dictionary order (pg_result_percentile_counts): row r holds the pairs
+// [offsets[r], offsets[r + 1]) of (dict_ids, counts) -- ascending dictIds with a non-zero count.
+struct CountList {
+  int aggregation = 0;
+  int rows = 1;                         // one (aggregation only), or one per row of group_aggregations
+  std::vector<size_t> offsets;          // [rows + 1]
+  std::vector<int32_t> dict_ids;
+  std::vector<uint32_t> counts;
+};
+// `distinct` also carries the counts pass's dense counter rows (num_words = the cardinality) from run_aggregation to execute_percentile, which
+// compacts them into `counts`: the dense matrix does not outlive pg_execute.
+struct ResultInternal { std::vector<DistinctSet> distinct; std::vector<CountList> counts; };
 
 void pg_result_free(pg_result* r) {
   if (!r) return;
@@ -2556,6 +2576,12 @@ constexpr int32_t kQueryCountReadsColumn = 1 << 29;
 // and DISTINCTCOUNT only; group_by_columns are the key columns of group_distinct_kernel (the pass itself is an aggregation-only launch:
 // which groups exist, and every other function, is the ordinary query's business -- check_distinct_plan / execute_distinct).
 constexpr int32_t kQueryDistinctPass = 1 << 28;
+// internal pg_query.flags bit (execute_percentile -> execute_impl): the counts pass of a PG_AGG_PERCENTILE query -- the bitset pass's shape with
+// COUNT(*) and PERCENTILE aggregations, launched as scan_counts_kernel / group_counts_kernel (pg_scan_counts.h).  Never together with kQueryDistinctPass.
+constexpr int32_t kQueryCountsPass = 1 << 27;
+constexpr int32_t kQuerySetPass = kQueryDistinctPass | kQueryCountsPass;
+// the one function besides COUNT(*) a pass query carries, -1: not a pass
+static inline int set_pass_function(int32_t flags) { return (flags & kQueryCountsPass) ? PG_AGG_PERCENTILE : ((flags & kQueryDistinctPass) ? PG_AGG_DISTINCTCOUNT : -1); }
 
 // ---- plan-time eligibility (pg_query_check) ----
 // Every reason pg_execute can answer PG_ERR_UNSUPPORTED for, decided from the query and the segment's metadata alone: no context, no
@@ -2661,7 +2687,8 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
     if (leaves > kMaxLeaves) return fail(PG_ERR_UNSUPPORTED, "more than %d filter leaves", kMaxLeaves);
     if (max_depth + (extra_and_leaves > 0 ? 1 : 0) > kStackDepth) return fail(PG_ERR_UNSUPPORTED, "filter tree deeper than %d", kStackDepth);
   }
-  const bool distinct_pass = (q->flags & kQueryDistinctPass) != 0;      // (its keys were checked with the ordinary query: check_distinct_plan)
+  const int pass_function = set_pass_function(q->flags);
+  const bool distinct_pass = pass_function >= 0;      // the bitset / counts pass (its keys were checked with the ordinary query: plan_distinct / plan_percentile)
   const int na = q->num_aggregations, ng = distinct_pass ? 0 : q->num_group_by;
   if (na < 0 || ng < 0 || (na > 0 && !q->aggregations) || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
   if (ng > kMaxGroupCols) return fail(PG_ERR_UNSUPPORTED, "more than %d group-by columns", kMaxGroupCols);
@@ -2709,7 +2736,7 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
   std::vector<std::pair<int, int>> group_aggs;     // distinct (column, SUM | MIN | MAX)
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    if (ag.function < PG_AGG_COUNT || ag.function > (distinct_pass ? PG_AGG_DISTINCTCOUNT : PG_AGG_AVG) || (distinct_pass && ag.function != PG_AGG_COUNT && ag.function != PG_AGG_DISTINCTCOUNT))
+    if (distinct_pass ? (ag.function != PG_AGG_COUNT && ag.function != pass_function) : (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG))
       return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.function == PG_AGG_COUNT) continue;
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
@@ -2937,13 +2964,14 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
 // ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
 // preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
-enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Agg };
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Counts, GroupCounts, Agg };
 // per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
 // leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
 static const struct { int id; bool writes_leaves; } kScanKernels[] = {
   {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
   {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_SIMPLE_VALID, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
-  {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_DISTINCT, true}, {PG_KERNEL_GROUP_DISTINCT, true}, {PG_KERNEL_SCAN_AGG, false}};
+  {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_DISTINCT, true}, {PG_KERNEL_GROUP_DISTINCT, true}, {PG_KERNEL_SCAN_COUNTS, true}, {PG_KERNEL_GROUP_COUNTS, true},
+  {PG_KERNEL_SCAN_AGG, false}};
 static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
 // general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
 // specialised kernel that won keeps it: the index handling, the leap-frog count and the batch's fallbacks go by the family.
@@ -2967,7 +2995,9 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
   if (sp.num_nodes == 1 && sp.nodes[0].op == PG_FILTER_LEAF && sp.nodes[0].kind == kLeafRawSet) { k.general = ScanKernel::Private; return pick(ScanKernel::RawSet); }
   // The bitset pass of a DISTINCTCOUNT query: kernels of their own (pg_scan_distinct.h) with the lane-private filter -- check_distinct_plan
   // declined the leaves that filter does not evaluate.  Everything that goes by the family (tile lists, the entry counts) is Private's.
-  if (!lw.distinct_slots.empty()) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Distinct : ScanKernel::GroupDistinct); }
+  if (!lw.distinct_slots.empty() && !lw.counts_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Distinct : ScanKernel::GroupDistinct); }
+  // The counts pass of a PERCENTILE query: the same, with 32-bit counters per dictId (pg_scan_counts.h).
+  if (!lw.distinct_slots.empty()) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Counts : ScanKernel::GroupCounts); }
   // The lane-private kernel (no LDS, plain global loads) takes every query whose leaves and aggregations it implements:
   // scan / set / bitmap leaves and raw INT ranges; COUNT, and SUM through a value plane / MIN / MAX on dictionary columns.
   // (the per-wave phase counters of PG_CFG_PROFILE_WAVES exist in the LDS-staged kernel only)
@@ -3062,6 +3092,9 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
 }
 // threads: the workgroup the kernel's records are counted in (profile_waves); lds: Agg's staged layout, or Hist's histogram with the set
 // area at hist_set_off; wide: scan_simple / scan_raw launch workgroups of kWideBlockThreads (PINOT_GPU_WIDE_BLOCKS=1)
+// scan_counts_kernel's LDS tier: the reduction records of a workgroup of kHistBlockThreads, and the counters that fit beside them without a staged set
+constexpr size_t kCountsRecordBytes = sizeof(BlockPartial) * (kHistBlockThreads / 64) + 16;
+static_assert((kLdsBudget - kCountsRecordBytes) / 4 == PG_PERCENTILE_LDS_MAX_COUNTERS, "include/pinot_gpu.h states the LDS tier's reach");
 struct ScanGrid { int blocks = 1, threads = kBlockThreads; size_t lds = 0, hist_set_off = 0; bool wide = false, distinct_lds = false; };
 // A segment whose tiles all fit the chip at once (one tile per wave: a 10 M-row segment at five waves per SIMD) is latency from end
 // to end -- launch, one round of loads, the hand-off of the workgroups' records to the fold.  Ten waves per workgroup there: 2.5x
@@ -3125,6 +3158,30 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Lowe
       }
       break;
     }
+    case ScanKernel::Counts: case ScanKernel::GroupCounts: {
+      // The Distinct case with 32-bit counters.  LDS tier: the columns' counters side by side, the filter's set area behind them; it applies while
+      // counters + set area + the reduction records fit kLdsBudget (the records overlay the counters' start once the workgroup has flushed them:
+      // the sum, not the maximum, is the rule -- PG_PERCENTILE_LDS_MAX_COUNTERS states it for a filter without a staged set).
+      bool has_set = false;
+      if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) has_set |= sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet;
+      size_t counter_bytes = 0;
+      for (int slot : lw.distinct_slots) counter_bytes += (size_t)std::max(lw.plan.cols[slot].cardinality, 0) * 4;
+      counter_bytes = (counter_bytes + 15) & ~(size_t)15;
+      size_t lds_tier = counter_bytes + (has_set ? (size_t)kSetLdsWords * 4 : 0);
+      if (lds_tier + kCountsRecordBytes > kLdsBudget && counter_bytes + kCountsRecordBytes <= kLdsBudget) { has_set = false; lds_tier = counter_bytes; }      // (the sets stay in memory rather than push the counters out)
+      g.distinct_lds = k.kernel == ScanKernel::Counts && g_engine.percentile_lds && lds_tier + kCountsRecordBytes <= kLdsBudget;
+      if (g.distinct_lds) {
+        g.hist_set_off = has_set ? counter_bytes : 0;
+        g.lds = std::max(lds_tier, kCountsRecordBytes);
+        g.threads = kHistBlockThreads;
+        g.blocks = grid_blocks(seg, tiles, hist_waves, std::max(1, std::min(waves_scan_counts(true) / hist_waves, (int)((160 * 1024 - 2048) / (g.lds + 256)))));
+      } else {
+        g.hist_set_off = has_set ? 16 : 0;
+        g.lds = std::max((size_t)(has_set ? 16 + kSetLdsWords * 4 : 0), sizeof(BlockPartial) * (size_t)wpb + 16);
+        g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, (k.kernel == ScanKernel::Counts ? waves_scan_counts(false) : waves_group_counts()) / wpb));
+      }
+      break;
+    }
     case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
     case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
@@ -3179,7 +3236,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Private: launch_scan_private(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::Agg: launch_scan_agg(g_engine.use_dma, one, typed, g.blocks, g.threads, g.lds, stream, sp); break;
-    case ScanKernel::Distinct: case ScanKernel::GroupDistinct: break;      // (launched with their own parameter block: run_aggregation)
+    case ScanKernel::Distinct: case ScanKernel::GroupDistinct: case ScanKernel::Counts: case ScanKernel::GroupCounts: break;      // (launched with their own parameter block: run_aggregation)
   }
 }
 // What the phases of execute_impl share about one query
@@ -3327,7 +3384,10 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   PlanParams& pl = lw.plan; const int na = r.na, num_cols_total = (int)seg->cols.size(); const bool want_bitmap = r.want_bitmap, timed = r.timed;
   pg_status st = PG_OK;
   std::vector<int> agg_slot_of((size_t)std::max(na, 1), -1);
-  const bool distinct_pass = (q->flags & kQueryDistinctPass) != 0 && !want_bitmap;
+  const bool distinct_pass = (q->flags & kQuerySetPass) != 0 && !want_bitmap;      // the bitset pass (DISTINCTCOUNT) or the counts pass (PERCENTILE)
+  const int pass_function = set_pass_function(q->flags);
+  const char* const pass_name = pass_function == PG_AGG_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT";
+  lw.counts_pass = distinct_pass && pass_function == PG_AGG_PERCENTILE;
   std::vector<int> distinct_of((size_t)std::max(na, 1), -1);      // per aggregation: its bitset (index into lw.distinct_slots)
   std::vector<int> distinct_key_cards;
   for (int a = 0; a < na; ++a) {
@@ -3336,17 +3396,17 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       if ((q->flags & kQueryCountReadsColumn) && ag.column >= 0 && ag.column < num_cols_total) r.add_projected(ag.column);
       continue;
     }
-    if (ag.function == PG_AGG_DISTINCTCOUNT && distinct_pass) {
-      // a column of the bitset pass: its dictId stream, one bitset per distinct column (the same column twice shares it)
+    if (distinct_pass && ag.function == pass_function) {
+      // a column of the bitset / counts pass: its dictId stream, one bitset / counter vector per distinct column (the same column twice shares it)
       if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
-      if (seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on raw column %s", seg->cols[(size_t)ag.column].name.c_str());
+      if (seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT) return fail(PG_ERR_UNSUPPORTED, "%s on raw column %s", pass_name, seg->cols[(size_t)ag.column].name.c_str());
       r.add_projected(ag.column);
       const int s = slot_for(&lw, seg, ag.column, false);
       if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
       pl.cols[s].in_agg = 1;
       size_t dc = std::find(lw.distinct_slots.begin(), lw.distinct_slots.end(), s) - lw.distinct_slots.begin();
       if (dc == lw.distinct_slots.size()) {
-        if (dc >= (size_t)kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d DISTINCTCOUNT columns", kMaxAggCols);
+        if (dc >= (size_t)kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d %s columns", kMaxAggCols, pass_name);
         lw.distinct_slots.push_back(s);
       }
       distinct_of[(size_t)a] = (int)dc;
@@ -3370,14 +3430,14 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     agg_slot_of[(size_t)a] = ac;
   }
   if (distinct_pass) {
-    if (lw.distinct_slots.empty()) return fail(PG_ERR_INTERNAL, "a DISTINCTCOUNT pass without a DISTINCTCOUNT column");
+    if (lw.distinct_slots.empty()) return fail(PG_ERR_INTERNAL, "a %s pass without a %s column", pass_name, pass_name);
     // group_distinct_kernel's keys: dictionary columns, raw INT / LONG columns through their key images (built by the ordinary query before this pass)
     for (int g = 0; g < q->num_group_by; ++g) {
       int c = q->group_by_columns[g];
       if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
       r.add_projected(c);
       if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) { st = ensure_key_image(seg, c, &c); if (st != PG_OK) return st; }
-      if ((int)lw.distinct_key_slots.size() >= kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT with more than %d group-by columns", kMaxDistinctKeys);
+      if ((int)lw.distinct_key_slots.size() >= kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "%s with more than %d group-by columns", pass_name, kMaxDistinctKeys);
       const int s = slot_for(&lw, seg, c, false);
       if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
       pl.cols[s].in_agg = 1;
@@ -3496,7 +3556,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       const pg_aggregation& ag = q->aggregations[a];
       pg_agg_value& v = out->aggregations[a];
       empty_agg_value(&v, (int64_t)fp.count);
-      if (ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT) continue;      // (a DISTINCTCOUNT's count is its bitset's: filled in behind the copy)
+      if (ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT || ag.function == PG_AGG_PERCENTILE) continue;      // (a DISTINCTCOUNT's count is its bitset's: filled in behind the copy; a PERCENTILE's is the docs aggregated)
       const int ac = agg_slot_of[(size_t)a];
       const ColumnDev& col = seg->cols[(size_t)ag.column];
       const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
@@ -3560,7 +3620,8 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   sp.lane_skip = g_engine.lane_skip ? 1 : 0;
   sp.set_leaves_in_lds = 0;
   if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
-  const bool is_distinct = k.kernel == ScanKernel::Distinct || k.kernel == ScanKernel::GroupDistinct;
+  const bool is_counts = k.kernel == ScanKernel::Counts || k.kernel == ScanKernel::GroupCounts;      // 32-bit counters: a row is `cardinality` words
+  const bool is_distinct = k.kernel == ScanKernel::Distinct || k.kernel == ScanKernel::GroupDistinct || is_counts;
   if (k.kernel == ScanKernel::Hist || is_distinct) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / bitset kernels keep the area in their dynamic LDS, behind the counters / bitsets)
   // The bitset pass: one zeroed bitset per DISTINCTCOUNT column in the context's scratch -- under GROUP BY a matrix of one row per raw group id --
   // and one copy of all of them behind the kernel.  Behind the last row: room for the dictIds the column's WIDTH admits beyond its cardinality,
@@ -3573,18 +3634,18 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   if (is_distinct) {
     memset(&dp, 0, sizeof(dp));
     for (int card : distinct_key_cards) distinct_rows *= card;
-    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT GROUP BY over %lld raw keys", distinct_rows);
+    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "%s GROUP BY over %lld raw keys", pass_name, distinct_rows);
     size_t total = 0, slack = 0;
     int lds_off = 0;
     dp.num_cols = (int32_t)lw.distinct_slots.size();
     for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
       const DevColumn& dc = pl.cols[lw.distinct_slots[c]];
       DistinctCol& col = dp.cols[c];
-      col.fwd = dc.fwd; col.bits = dc.bits; col.words = (dc.cardinality + 31) / 32; col.lds_off = lds_off;
+      col.fwd = dc.fwd; col.bits = dc.bits; col.words = is_counts ? std::max(dc.cardinality, 0) : (dc.cardinality + 31) / 32; col.lds_off = lds_off;
       lds_off += col.words;
       distinct_first.push_back(total);
       total += (size_t)distinct_rows * (size_t)col.words;
-      slack = std::max(slack, distinct_slack_words(dc.bits, dc.cardinality));
+      slack = std::max(slack, is_counts ? counts_slack_words(dc.bits, dc.cardinality) : distinct_slack_words(dc.bits, dc.cardinality));
     }
     dp.lds_words = grid.distinct_lds ? lds_off : 0;
     dp.num_keys = (int32_t)lw.distinct_key_slots.size();
@@ -3650,7 +3711,9 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     if (is_distinct) {
       dp.scan = sp;
       if (k.kernel == ScanKernel::Distinct) launch_scan_distinct(grid.distinct_lds, grid.blocks, grid.lds, ctx->stream, dp);
-      else launch_group_distinct(grid.blocks, grid.lds, ctx->stream, dp);
+      else if (k.kernel == ScanKernel::GroupDistinct) launch_group_distinct(grid.blocks, grid.lds, ctx->stream, dp);
+      else if (k.kernel == ScanKernel::Counts) launch_scan_counts(grid.distinct_lds, grid.blocks, grid.lds, ctx->stream, dp);
+      else launch_group_counts(grid.blocks, grid.lds, ctx->stream, dp);
     } else launch_scan_kernel(k, grid, pl.num_agg_cols, typed, ctx->stream, sp);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
@@ -3727,7 +3790,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       bool again = false;
       for (int b = 0; b < a; ++b) again |= distinct_of[(size_t)b] == dc;
       if (again) ds.words = distinct_host[(size_t)dc]; else ds.words = std::move(distinct_host[(size_t)dc]);
-      if (lw.distinct_key_slots.empty()) {
+      if (lw.distinct_key_slots.empty() && !is_counts) {      // (PERCENTILE: count stays the docs aggregated, the list's length)
         int64_t card = 0;
         for (uint32_t w : ds.words) card += __builtin_popcount(w);
         out->aggregations[a].count = card;
@@ -4489,9 +4552,9 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
   const bool want_bitmap = host_bitmap != nullptr || d_out_bitmap_request != nullptr;
   const int na = want_bitmap ? 0 : q->num_aggregations;
-  const int ng = (want_bitmap || (q->flags & kQueryDistinctPass)) ? 0 : q->num_group_by;      // (the bitset pass of a DISTINCTCOUNT query is an aggregation-only launch: its group-by columns are the kernel's keys)
+  const int ng = (want_bitmap || (q->flags & kQuerySetPass)) ? 0 : q->num_group_by;      // (the bitset pass of a DISTINCTCOUNT query is an aggregation-only launch: its group-by columns are the kernel's keys)
   if (na < 0 || ng < 0 || (na > 0 && !q->aggregations) || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
-  if ((q->flags & kQueryDistinctPass) && !want_bitmap && (q->num_group_by < 0 || (q->num_group_by > 0 && !q->group_by_columns))) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
+  if ((q->flags & kQuerySetPass) && !want_bitmap && (q->num_group_by < 0 || (q->num_group_by > 0 && !q->group_by_columns))) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
   if (ng > kMaxGroupCols) return fail(PG_ERR_UNSUPPORTED, "more than %d group-by columns", kMaxGroupCols);
   const bool timed = (g_engine.flags & PG_CFG_TIME_KERNELS) != 0;
   if (ng == 0 && !want_bitmap && out && na > 0 && allow_metadata_plan && answer_from_metadata(seg, q, na, out, out_cardinality)) return PG_OK;
@@ -5340,6 +5403,193 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
   return PG_OK;
 }
 
+// ---- PG_AGG_PERCENTILE: the dictId count histograms of dictionary columns (pg_scan_counts.h) ----
+// The DISTINCTCOUNT scheme with counters: the ordinary query (every PERCENTILE turned into COUNT(*)) brings every other function, the statistics
+// and the list of groups; the counts pass (everything BUT the PERCENTILEs turned into COUNT(*), flagged kQueryCountsPass) is one launch of
+// scan_counts_kernel / group_counts_kernel behind the same lowered filter.  `PERCENTILE(c1..c4) [, COUNT(*)]` without GROUP BY is the pass alone.
+// There is no metadata fast path: the reference scans even without a filter (its plain golden's statistics are (docs, 0, docs x columns, docs)).
+// The percentile itself is not part of the query: the list is the intermediate result whatever p is.
+static bool has_percentile(const pg_query* q) {
+  if (!q || !q->aggregations) return false;
+  for (int a = 0; a < q->num_aggregations; ++a) if (q->aggregations[a].function == PG_AGG_PERCENTILE) return true;
+  return false;
+}
+struct PercentilePlan {
+  std::vector<pg_aggregation> base_aggs, pass_aggs;
+  pg_query base, pass;
+  bool pass_alone = false;           // PERCENTILE(..) [, COUNT(*)] without GROUP BY: one launch
+  int num_projected = 0;             // distinct columns the whole query projects (numEntriesScannedPostFilter = numDocsScanned x this)
+  unsigned long long scratch_bytes = 0;      // the counters (GROUP BY: the matrices) with the slack behind the last one: what the pass allocates
+};
+// Every reason a PERCENTILE query is declined for, from the query and the segment's metadata alone (pg_query_check and pg_execute both come
+// through here), and the two queries that answer it.
+static pg_status plan_percentile(const pg_segment* seg, const pg_query* q, PercentilePlan* plan) {
+  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
+  const int num_cols_total = (int)seg->cols.size();
+  const int na = q->num_aggregations, ng = q->num_group_by;
+  const bool null_handling = (q->flags & PG_QUERY_NULL_HANDLING) != 0;
+  if (na < 0 || ng < 0 || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
+  if (q->num_filter_nodes > 0 && (!q->filter || !q->predicates)) return fail(PG_ERR_INVALID_ARGUMENT, "filter nodes without predicates");
+  std::vector<int> pct_cols, projected;
+  auto project = [&](int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); };
+  bool only_percentile_and_count = true;
+  for (int a = 0; a < na; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if (ag.function == PG_AGG_DISTINCTCOUNT) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE beside DISTINCTCOUNT in one query -- CPU plan");
+    if (ag.function == PG_AGG_COUNT) {
+      if (null_handling && ag.column >= 0) { project(ag.column); only_percentile_and_count = false; }
+      continue;
+    }
+    if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
+    project(ag.column);
+    if (ag.function != PG_AGG_PERCENTILE) { only_percentile_and_count = false; continue; }
+    const ColumnDev& col = seg->cols[(size_t)ag.column];
+    if (col.encoding != PG_FWD_FIXED_BIT_DICT)
+      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE on raw (no-dictionary) column %s: the value list has no dictId form there -- CPU plan", col.name.c_str());
+    if (null_handling && col.d_null_bitmap != nullptr)
+      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE on column %s, which carries a null value vector, under null handling -- CPU plan", col.name.c_str());
+    if (std::find(pct_cols.begin(), pct_cols.end(), ag.column) == pct_cols.end()) pct_cols.push_back(ag.column);
+  }
+  if ((int)pct_cols.size() > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d PERCENTILE columns", kMaxAggCols);
+  // the counts kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it
+  for (int n = 0; n < q->num_filter_nodes; ++n) {
+    if (q->filter[n].op != PG_FILTER_LEAF) continue;
+    if (q->filter[n].predicate < 0 || q->filter[n].predicate >= q->num_predicates) return fail(PG_ERR_INVALID_ARGUMENT, "filter node %d: bad predicate index", n);
+    const pg_predicate& pr = q->predicates[q->filter[n].predicate];
+    if (pr.kind == PG_PRED_RAW_RANGE && pr.column >= 0 && pr.column < num_cols_total && seg->cols[(size_t)pr.column].stored_type != PG_TYPE_INT)
+      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE beside a range predicate on raw LONG / FLOAT / DOUBLE column %s -- CPU plan", seg->cols[(size_t)pr.column].name.c_str());
+  }
+  unsigned long long product = 1;
+  if (ng > 0) {
+    // GROUP BY under plan_distinct's conditions: an int key space that numGroupsLimit can never cut, keys the kernel decodes as dictIds
+    if (ng > kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE with more than %d group-by columns -- CPU plan", kMaxDistinctKeys);
+    std::vector<int> cards;
+    for (int g = 0; g < ng; ++g) {
+      int c = q->group_by_columns[g];
+      if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
+      project(c);
+      if (null_handling && seg->cols[(size_t)c].d_null_bitmap != nullptr)
+        return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped by nullable column %s under null handling -- CPU plan", seg->cols[(size_t)c].name.c_str());
+      if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
+        const int image = seg->cols[(size_t)c].keyimage_column;
+        if (image < 0 || seg->cols[(size_t)image].rank_image)
+          return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped by raw column %s, which is not keyed by offset -- CPU plan", seg->cols[(size_t)c].name.c_str());
+        c = image;
+      }
+      cards.push_back(seg->cols[(size_t)c].cardinality);
+    }
+    HashPlan hash_plan;
+    const pg_status hst = plan_hash_holder(seg, cards, &hash_plan);
+    if (hst != PG_OK) return hst;
+    if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", hash_plan.kind);
+    for (int card : cards) product *= (unsigned long long)std::max(card, 1);
+    const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
+    if (product > (unsigned long long)limit)
+      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", product, limit);
+  }
+  // the scratch: group_id_upper_bound x cardinality x 4 bytes per column, and behind the last counter the 2^bits - cardinality counters a
+  // dictId beyond the dictionary's bound could reach (counts_slack_words)
+  unsigned long long matrix = 0, slack = 0;
+  for (int c : pct_cols) {
+    matrix += product * (unsigned long long)std::max(seg->cols[(size_t)c].cardinality, 0) * 4ull;
+    slack = std::max<unsigned long long>(slack, counts_slack_words(seg->cols[(size_t)c].bits, seg->cols[(size_t)c].cardinality) * 4ull);
+  }
+  matrix += slack;
+  plan->scratch_bytes = matrix;
+  if (ng > 0) {
+    if (matrix > PG_PERCENTILE_GROUP_MAX_BYTES)
+      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE counter matrices of %llu bytes exceed PG_PERCENTILE_GROUP_MAX_BYTES (%llu) -- CPU plan", matrix, (unsigned long long)PG_PERCENTILE_GROUP_MAX_BYTES);
+    if (matrix > g_engine.group_table_bytes)
+      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE counter matrices of %llu bytes exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", matrix, (unsigned long long)g_engine.group_table_bytes);
+  }
+  plan->num_projected = (int)projected.size();
+  plan->base_aggs.assign(q->aggregations, q->aggregations + na);
+  plan->pass_aggs.assign(q->aggregations, q->aggregations + na);
+  for (int a = 0; a < na; ++a) {
+    if (q->aggregations[a].function == PG_AGG_PERCENTILE) plan->base_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+    else plan->pass_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+  }
+  plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
+  plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
+  plan->pass.flags |= kQueryCountsPass;
+  plan->pass_alone = ng == 0 && only_percentile_and_count;
+  if (!plan->pass_alone) plan->pass.flags |= PG_QUERY_STATS_UPPER_BOUND_OK;      // (the ordinary query brings the statistics)
+  pg_status st = plan->pass_alone ? PG_OK : check_ordinary_query(seg, &plan->base);
+  if (st == PG_OK) st = check_ordinary_query(seg, &plan->pass);
+  return st;
+}
+
+// Row `row` of a dense counter matrix -> the pairs of a CountList; returns the docs counted.
+static int64_t append_count_row(CountList* list, const uint32_t* dense, int cardinality) {
+  int64_t docs = 0;
+  for (int d = 0; d < cardinality; ++d) {
+    if (dense[d] == 0u) continue;
+    list->dict_ids.push_back(d);
+    list->counts.push_back(dense[d]);
+    docs += dense[d];
+  }
+  list->offsets.push_back(list->dict_ids.size());
+  return docs;
+}
+
+static pg_status execute_percentile(pg_segment* seg, const pg_query* q, pg_result* out) {
+  if (!out) return fail(PG_ERR_INVALID_ARGUMENT, "null result");
+  memset(out, 0, sizeof(*out));
+  if (!seg || !q) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  PercentilePlan plan;
+  pg_status st = plan_percentile(seg, q, &plan);
+  if (st != PG_OK) return st;
+  const int na = q->num_aggregations;
+  pg_result pass;
+  memset(&pass, 0, sizeof(pass));
+  if (plan.pass_alone) {
+    st = execute_one(seg, &plan.pass, out, nullptr);
+    if (st != PG_OK) return st;
+  } else {
+    st = execute_one(seg, &plan.base, out, nullptr);
+    if (st != PG_OK) return st;
+    out->stats.num_entries_scanned_post_filter = out->stats.num_docs_scanned * (int64_t)plan.num_projected;
+    st = execute_one(seg, &plan.pass, &pass, nullptr);
+    if (st != PG_OK) { pg_result_free(out); memset(out, 0, sizeof(*out)); return st; }
+    out->device_ms += pass.device_ms;
+    if (pass.dominant_kernel_ms >= out->dominant_kernel_ms) { out->dominant_kernel_ms = pass.dominant_kernel_ms; out->dominant_kernel = pass.dominant_kernel; }
+  }
+  pg_result& from = plan.pass_alone ? *out : pass;
+  std::unique_ptr<ResultInternal> got(static_cast<ResultInternal*>(from.internal));
+  from.internal = nullptr;
+  pg_result_free(&pass);
+  auto give_up = [&](const char* what) { pg_result_free(out); memset(out, 0, sizeof(*out)); return fail(PG_ERR_INTERNAL, "%s", what); };
+  if (!got) return give_up("the PERCENTILE pass returned no counters");
+  // the dense rows -> (dictId, count) pairs; GROUP BY: only the rows of the groups the ordinary query reports (group_ids: ascending raw ids, key kind 0)
+  std::unique_ptr<ResultInternal> lists(new ResultInternal());
+  const bool grouped = q->num_group_by > 0;
+  for (const DistinctSet& m : got->distinct) {
+    CountList list;
+    list.aggregation = m.aggregation;
+    list.offsets.push_back(0);
+    if (!grouped) {
+      const int64_t docs = append_count_row(&list, m.words.data(), m.num_words);
+      memset(&out->aggregations[m.aggregation], 0, sizeof(pg_agg_value));
+      empty_agg_value(&out->aggregations[m.aggregation], docs);
+    } else {
+      list.rows = out->num_groups;
+      for (int k = 0; k < out->num_groups; ++k) {
+        const int64_t row = out->group_ids[k];
+        if (row < 0 || row >= m.rows) return give_up("a group id outside the PERCENTILE counter matrix");
+        const int64_t docs = append_count_row(&list, m.words.data() + (size_t)row * (size_t)m.num_words, m.num_words);
+        pg_agg_value* v = &out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation];
+        memset(v, 0, sizeof(*v));
+        empty_agg_value(v, docs);
+      }
+    }
+    list.dict_ids.shrink_to_fit(); list.counts.shrink_to_fit();
+    lists->counts.push_back(std::move(list));
+  }
+  got.reset();      // (the dense matrices end here)
+  out->internal = lists.release();
+  return PG_OK;
+}
+
 // (pg_execute: below, behind the batch machinery -- a small group-by runs as a one-item launch of the batch's group-by kernel)
 
 // ---- pg_execute_batch ----
@@ -5974,6 +6224,7 @@ pg_status finish_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_res
 // segment's plan cache like a batch item's.  Everything else takes execute_one as before.  PINOT_GPU_GROUP_ONE_LAUNCH=0: never.
 pg_status pg_execute(pg_segment* segment, const pg_query* query, pg_result* out_result) {
   if (reserved_flags(query)) { if (out_result) memset(out_result, 0, sizeof(*out_result)); return fail_reserved_flags(query); }
+  if (has_percentile(query)) return execute_percentile(segment, query, out_result);
   if (has_distinct(query)) return execute_distinct(segment, query, out_result);
   // (PG_CFG_PROFILE_WAVES: the per-wave phase counters live in the kernels execute_one launches itself, and its HIP events bracket ALL of a
   //  query's launches -- the deferred form would leave profile_* empty and report the kernel bracket only)
@@ -6057,8 +6308,8 @@ pg_status pg_execute_batch(pg_segment* const* segments, const pg_query* const* q
     const pg_query* q = queries[i];
     std::shared_ptr<const OwnedQuery> copy;
     if (!keys.empty() && !keys[(size_t)i].empty()) { copy = own_query(q); q = &copy->q; }
-    // (a DISTINCTCOUNT item runs as a pg_execute of its own: no shared launch)
-    statuses[i] = has_distinct(q) ? execute_distinct(segments[i], q, &results[i]) : execute_one(segments[i], q, &results[i], g_engine.batch_launch ? &defs[(size_t)i] : nullptr);
+    // (a DISTINCTCOUNT / PERCENTILE item runs as a pg_execute of its own: no shared launch)
+    statuses[i] = has_percentile(q) ? execute_percentile(segments[i], q, &results[i]) : has_distinct(q) ? execute_distinct(segments[i], q, &results[i]) : execute_one(segments[i], q, &results[i], g_engine.batch_launch ? &defs[(size_t)i] : nullptr);
     if (statuses[i] == kDeferred && copy && defs[(size_t)i].cacheable) remember_item(segments[i], std::move(keys[(size_t)i]), copy, &defs[(size_t)i]);
     else if (statuses[i] == kDeferred && copy) std::const_pointer_cast<LoweredItem>(defs[(size_t)i].item)->query = copy;
     if (trace) item_us[(size_t)i] = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t_item).count();
@@ -6224,6 +6475,7 @@ pg_status pg_query_check(const pg_segment* segment, const pg_query* query) {
   if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
   if (!segment || !query) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
   if (reserved_flags(query)) return fail_reserved_flags(query);
+  if (has_percentile(query)) { PercentilePlan plan; return plan_percentile(segment, query, &plan); }
   if (has_distinct(query)) { DistinctPlan plan; return plan_distinct(segment, query, &plan); }
   return check_ordinary_query(segment, query);
 }
@@ -6241,6 +6493,24 @@ pg_status pg_result_distinct_dict_ids(const pg_result* result, int32_t aggregati
     return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
   *out_words = ds->words.data() + (size_t)(grouped ? group_row : 0) * (size_t)ds->num_words;
   *out_num_words = ds->num_words;
+  return PG_OK;
+}
+
+pg_status pg_result_percentile_counts(const pg_result* result, int32_t aggregation, int32_t group_row, const int32_t** out_dict_ids, const uint32_t** out_counts, int32_t* out_num) {
+  if (!result || !out_dict_ids || !out_counts || !out_num) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  *out_dict_ids = nullptr; *out_counts = nullptr; *out_num = 0;
+  const ResultInternal* lists = static_cast<const ResultInternal*>(result->internal);
+  if (aggregation < 0 || aggregation >= result->num_aggregations) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d out of range", aggregation);
+  const CountList* cl = nullptr;
+  if (lists) for (const CountList& l : lists->counts) if (l.aggregation == aggregation) cl = &l;
+  if (!cl) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d is not a PG_AGG_PERCENTILE", aggregation);
+  const bool grouped = result->group_aggregations != nullptr;
+  if (grouped ? (group_row < 0 || group_row >= result->num_groups || group_row >= cl->rows) : group_row != -1)
+    return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
+  const size_t row = grouped ? (size_t)group_row : 0, first = cl->offsets[row];
+  *out_dict_ids = cl->dict_ids.data() + first;
+  *out_counts = cl->counts.data() + first;
+  *out_num = (int32_t)(cl->offsets[row + 1] - first);
   return PG_OK;
 }
 

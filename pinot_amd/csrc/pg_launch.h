@@ -111,6 +111,14 @@ int waves_scan_distinct(bool lds_tier);
 void launch_group_distinct(int blocks, size_t lds, hipStream_t stream, const DistinctParams& dp);
 int waves_group_distinct();
 
+// scan_counts_kernel<lds tier>: PERCENTILE of up to kMaxAggCols dictionary columns as 32-bit dictId counters, in `lds` bytes of dynamic LDS
+// (workgroups of kHistBlockThreads) or straight in HBM (workgroups of 256; `lds`: the filter's set area + the reduction scratch) -- pg_scan_counts.h
+void launch_scan_counts(bool lds_tier, int blocks, size_t lds, hipStream_t stream, const DistinctParams& dp);
+int waves_scan_counts(bool lds_tier);
+// group_counts_kernel: the same under GROUP BY, one counter row per raw group id in HBM
+void launch_group_counts(int blocks, size_t lds, hipStream_t stream, const DistinctParams& dp);
+int waves_group_counts();
+
 // scan_private_typed_kernel: lane-private scan for raw / 8-byte aggregated columns (pg_scan_typed.h)
 void launch_scan_private_typed(int agg_cols, int blocks, hipStream_t stream, const ScanParams& p);      // instantiated for 1, 2 and kMaxAggCols slots
 int waves_scan_private_typed(int agg_cols);

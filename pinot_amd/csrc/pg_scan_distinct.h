@@ -27,13 +27,13 @@
 // Count and filter entries travel in the workgroups' records exactly as scan_hist_body's do (publish_block_partial).
 #pragma once
 #include "pg_kernels.h"
+#include "pg_group_rows.h"      // distinct_rows16: the raw group ids of group_distinct_kernel (shared with pg_scan_counts.h)
 
 namespace pg {
 
 #ifndef PG_DISTINCT_LDS_SKIP
 #define PG_DISTINCT_LDS_SKIP 0      // 1: the LDS tier reads the word and skips the OR when the bit is there (A/B builds: make variant DEFS=-DPG_DISTINCT_LDS_SKIP=1)
 #endif
-constexpr int kDistinctBlockThreads = 256;      // the HBM tiers; the LDS tier shares one bitset among kHistBlockThreads
 
 // Sixteen docs (half H) of the lane's chunk of one DISTINCTCOUNT column.  rows: kGroup -- the docs' raw group ids.
 template <bool kLds, bool kGroup, int H>
@@ -64,24 +64,6 @@ __device__ __forceinline__ void distinct16(int b, const uint32_t* __restrict__ l
       const uint32_t bit = 1u << (v[j] & 31u);
       if ((*w & bit) == 0u) atomicOr(w, bit);
     }
-  }
-}
-
-// The raw group ids of sixteen docs: sum over the key columns of dictId * mult (group_private_kernel's key arithmetic; the key space is
-// an int, so 32-bit arithmetic does not wrap).
-template <int H>
-__device__ __forceinline__ void distinct_rows16(const DistinctParams& dp, long long tile, int lane, uint32_t (&rows)[16]) {
-#pragma unroll
-  for (int j = 0; j < 16; ++j) rows[j] = 0u;
-#pragma unroll
-  for (int k = 0; k < kMaxDistinctKeys; ++k) {
-    if (k >= dp.num_keys) break;
-    const DistinctKey& key = dp.keys[k];
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(key.fwd + tile * (256ll * key.bits)) + lane * key.bits;
-    uint32_t v[16];
-    decode16_private_dispatch<H>(key.bits, words, v);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) rows[j] += v[j] * key.mult;
   }
 }
 

@@ -258,6 +258,56 @@ def group_by_combine(sql, blocks, key_types):
     return _take_json(lib, lib.ph_group_by_combine_sets(sql.encode(), len(blocks), br, kt, kl, kd, ks, kn, counts, sums, mins, maxs, nulls, so, sv, C.byref(st)), st)
 
 
+def combine_counts(sql, blocks, key_types=()):
+    """The combine of PERCENTILE value lists built on the host (no device): ph_combine_counts.  `blocks`: one list of rows per segment, a row =
+    (key values, cells) as for group_by_combine; the cell of a PERCENTILE function carries a sixth element, the segment's list as a pair
+    (values, counts) of equal-length sequences (runs in any order).  An aggregation-only `sql` takes one row with an empty key per block and
+    returns {"combined"}; a GROUP BY one returns {"combined", "reduced", "resultTable"}."""
+    import numpy as np
+    lib = _lib()
+    P = C.POINTER
+    lib.ph_combine_counts.restype = C.c_void_p
+    lib.ph_combine_counts.argtypes = [C.c_char_p, C.c_int32, P(C.c_int64), P(C.c_int32), P(C.c_int64), P(C.c_double), P(C.c_char_p), P(C.c_uint8), P(C.c_int64),
+                                      P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_uint8), C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int32)]
+    rows = [r for b in blocks for r in b]
+    nk = len(key_types)
+    nf = len(rows[0][1]) if rows else 1
+    nr = len(rows)
+    br = (C.c_int64 * max(len(blocks), 1))(*[len(b) for b in blocks])
+    kt = (C.c_int32 * max(nk, 1))(*key_types)
+    kl, kd, ks, kn = (C.c_int64 * max(nr * nk, 1))(), (C.c_double * max(nr * nk, 1))(), (C.c_char_p * max(nr * nk, 1))(), (C.c_uint8 * max(nr * nk, 1))()
+    counts, sums = (C.c_int64 * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))()
+    mins, maxs, nulls = (C.c_double * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))(), (C.c_uint8 * max(nr * nf, 1))()
+    offsets, values, run_counts = [0], [], []
+    for r, (key_values, cells) in enumerate(rows):
+        for k, v in enumerate(key_values):
+            at = r * nk + k
+            if v is None:
+                kn[at] = 1
+                ks[at] = b""
+            elif key_types[k] in (KEY_INT, KEY_LONG):
+                kl[at] = int(v)
+            elif key_types[k] == KEY_STRING:
+                ks[at] = str(v).encode()
+            else:
+                kd[at] = float(v)
+        for f, cell in enumerate(cells):
+            c, s, mn, mx, is_null = cell[:5]
+            at = r * nf + f
+            counts[at], sums[at], mins[at], maxs[at], nulls[at] = int(c), float(s), float(mn), float(mx), int(bool(is_null))
+            if len(cell) > 5:
+                values.append(np.asarray(cell[5][0], dtype=np.float64))
+                run_counts.append(np.asarray(cell[5][1], dtype=np.int64))
+                assert values[-1].shape == run_counts[-1].shape
+            offsets.append(offsets[-1] + (len(cell[5][0]) if len(cell) > 5 else 0))
+    ro = np.asarray(offsets, dtype=np.int64)
+    rv = np.ascontiguousarray(np.concatenate(values) if values else np.zeros(1), dtype=np.float64)
+    rc = np.ascontiguousarray(np.concatenate(run_counts) if run_counts else np.zeros(1), dtype=np.int64)
+    st = C.c_int32()
+    return _take_json(lib, lib.ph_combine_counts(sql.encode(), len(blocks), br, kt, kl, kd, ks, kn, counts, sums, mins, maxs, nulls, ro.ctypes.data, rv.ctypes.data,
+                                                 rc.ctypes.data, C.byref(st)), st)
+
+
 def execute_sql_datatable(segments, sql, max_execution_threads=0):
     """The DataTable V4 bytes a server would send the broker for `sql` over these segments (combine, then
     InstanceResponseBlock.toDataTable().toBytes(); pinot_amd/csrc/host/datatable_v4.cpp)."""

@@ -179,6 +179,19 @@ class FakeJvm:
         finally:
             self.release(*arrays)
 
+    def execute_with_percentile_counts(self, handle, spec):
+        """PinotGpuNative.executeWithPercentileCounts: [the Object[PGM_RESULT_ARRAYS] as numpy arrays, the lists' dictIds, their counts: aggregation * rows + row ->
+        int32 array or None]."""
+        arrays, limit, flags = self.query_arrays(spec)
+        try:
+            out = self.call("executeWithPercentileCounts", C.c_void_p, C.c_int64(handle), *arrays, C.c_int32(limit), C.c_int32(flags))
+            try:
+                return self.to_python(out)
+            finally:
+                self.release(C.c_void_p(out))
+        finally:
+            self.release(*arrays)
+
     def query_check(self, handle, spec):
         arrays, limit, flags = self.query_arrays(spec)
         try:

@@ -117,6 +117,7 @@ def not_(child):
 
 COUNT, SUM, MIN, MAX, AVG = _abi.PG_AGG_COUNT, _abi.PG_AGG_SUM, _abi.PG_AGG_MIN, _abi.PG_AGG_MAX, _abi.PG_AGG_AVG
 DISTINCTCOUNT = _abi.PG_AGG_DISTINCTCOUNT      # on a dictionary-encoded column: the set of dictIds (AggValue.dict_ids)
+PERCENTILE = _abi.PG_AGG_PERCENTILE            # on a dictionary-encoded column: the value list as (dictIds, counts) (AggValue.dict_id_counts)
 
 
 class QuerySpec:
@@ -186,18 +187,21 @@ class QuerySpec:
 
 
 class AggValue:
-    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max", "dict_ids")
+    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max", "dict_ids", "dict_id_counts")
 
-    def __init__(self, v, dict_ids=None):
+    def __init__(self, v, dict_ids=None, dict_id_counts=None):
         self.count, self.sum, self.sum_i64, self.sum_exact, self.min, self.max = (
             int(v.count), float(v.sum), int(v.sum_i64), bool(v.sum_exact), float(v.min), float(v.max))
         self.dict_ids = dict_ids      # DISTINCTCOUNT: the sorted dictIds of the set (numpy int32); None for every other function
+        self.dict_id_counts = dict_id_counts      # PERCENTILE: (ascending dictIds int32, their non-zero counts uint32); None for every other function
 
     def intermediate(self, function):
         """The reference's intermediate result type: COUNT -> Long, SUM/MIN/MAX -> Double, AVG -> (sum, count), DISTINCTCOUNT -> the
         segment's dictId set (the values behind it are what segments merge: dictIds differ from segment to segment)."""
         if function == DISTINCTCOUNT:
             return self.dict_ids
+        if function == PERCENTILE:
+            return self.dict_id_counts
         if function == COUNT:
             return self.count
         if function == SUM:
@@ -235,7 +239,17 @@ class Result:
             bits = np.unpackbits(np.ctypeslib.as_array(words, shape=(n.value,)).view(np.uint8), bitorder="little") if n.value else np.zeros(0, np.uint8)
             return np.flatnonzero(bits).astype(np.int32)
 
-        self.aggregations = [AggValue(res.aggregations[a], dict_ids(a, -1)) for a in range(na)] if res.aggregations else []
+        def dict_id_counts(a, row):
+            if self.functions[a] != PERCENTILE:
+                return None
+            the_lib = lib if lib is not None else _abi.load_gpu_library()
+            ids, counts, n = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint32)(), C.c_int32()
+            _abi.check(the_lib, the_lib.pg_result_percentile_counts(C.byref(res), a, row, C.byref(ids), C.byref(counts), C.byref(n)))
+            if not n.value:
+                return np.zeros(0, np.int32), np.zeros(0, np.uint32)
+            return np.ctypeslib.as_array(ids, shape=(n.value,)).copy(), np.ctypeslib.as_array(counts, shape=(n.value,)).copy()
+
+        self.aggregations = [AggValue(res.aggregations[a], dict_ids(a, -1), dict_id_counts(a, -1)) for a in range(na)] if res.aggregations else []
         self.groups = {}
         self.group_id_upper_bound = int(res.group_id_upper_bound)
         self.num_groups_limit_reached = bool(res.num_groups_limit_reached)
@@ -248,7 +262,7 @@ class Result:
             tup = tuple(int(res.group_key_dict_ids[g * ng + j]) for j in range(ng)) if res.group_key_dict_ids else None
             self.group_keys.append(tup)
             gid = int(res.group_ids[g]) if self.group_key_kind == 0 else tup
-            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a], dict_ids(a, g)) for a in range(na)]
+            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a], dict_ids(a, g), dict_id_counts(a, g)) for a in range(na)]
         self.group_ids64 = [int(res.group_ids64[g]) for g in range(int(res.num_groups))] if (self.group_key_kind == 1 and res.group_ids64) else None
 
     def intermediates(self):

@@ -82,7 +82,7 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
         return lambda matched: B(col) if matched * 16 >= rows else min(B(col), matched * 64)
 
     # ---- C2 / C3 on 1 B rows: the headline's v and f, v under two dictionaries without structure, and the C3 columns ----
-    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list", "C2b-valid-docs", "C2b-valid-docs-5pct", "C2b-distinct", "C3-distinct")):
+    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list", "C2b-valid-docs", "C2b-valid-docs-5pct", "C2b-distinct", "C3-distinct", "C2b-percentile", "C3-percentile")):
         t0 = time.time()
         v_irr = _shared(S, v, "v_irr", v_dictionary("irregular"))
         v_win = _shared(S, v, "v_win", v_dictionary("window"))
@@ -176,6 +176,30 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                     return sorted(got.groups) == [int(x) for x in present] and all(np.array_equal(got.groups[int(gid)][0].dict_ids, np.flatnonzero(seen[gid])) for gid in present)
                 report("C3-distinct", "BASELINE.json configs[2] with DISTINCTCOUNT: C3's key and one of its value streams, a [1000 x 3125-word] bit matrix in HBM",
                        "SELECT DISTINCTCOUNT(a) GROUP BY k (1000 groups)", n, B(k) + B(a), g, seg, Q.QuerySpec([(Q.DISTINCTCOUNT, 5)], group_by=[4]), model_check=c3_model)
+            # PERCENTILE on the same dictId streams (pg_scan_counts.h): the model is np.bincount over the matching docs, walked in the same chunks.
+            # v_irr and a hold 100 000 dictIds each -- beyond the 39 036 counters of the LDS tier: both variants run the HBM kernels.
+            if want("C2b-percentile"):
+                def c2b_counts_model(got):
+                    counts = np.zeros(seg.columns[2].cardinality, dtype=np.int64)
+                    for _, (ids, fids) in dict_id_chunks(2, 1):
+                        counts += np.bincount(ids[fids < 100], minlength=counts.shape[0])
+                    d, c = got.aggregations[0].dict_id_counts
+                    return np.array_equal(d, np.flatnonzero(counts)) and np.array_equal(c.astype(np.int64), counts[counts > 0]) and got.aggregations[0].count == int(counts.sum()) == got.stats[0]
+                report("C2b-percentile", "BASELINE.json configs[1] with PERCENTILE for SUM: C2b-irregular's two dictId streams, one device-scope add per matching doc (100 000 dictIds: the HBM tier)",
+                       "SELECT PERCENTILE50(v_irr) WHERE f < 100 (10%)", n, B(v) + B(f), g, seg, Q.QuerySpec([(Q.PERCENTILE, 2)], filter=flt), model_check=c2b_counts_model)
+            if want("C3-percentile"):
+                def c3_counts_model(got):
+                    ka, kk = seg.columns[5].cardinality, seg.columns[4].cardinality
+                    counts = np.zeros(kk * ka, dtype=np.int64)
+                    for _, (aids, kids) in dict_id_chunks(5, 4):
+                        counts += np.bincount(kids.astype(np.int64) * ka + aids, minlength=counts.shape[0])
+                    counts = counts.reshape(kk, ka)
+                    present = np.flatnonzero(counts.any(axis=1))
+                    return sorted(got.groups) == [int(x) for x in present] and all(
+                        np.array_equal(got.groups[int(gid)][0].dict_id_counts[0], np.flatnonzero(counts[gid])) and
+                        np.array_equal(got.groups[int(gid)][0].dict_id_counts[1].astype(np.int64), counts[gid][counts[gid] > 0]) for gid in present)
+                report("C3-percentile", "BASELINE.json configs[2] with PERCENTILE: C3's key and one of its value streams, a [1000 x 100000] counter matrix (400 MB) in HBM",
+                       "SELECT PERCENTILE50(a) GROUP BY k (1000 groups)", n, B(k) + B(a), g, seg, Q.QuerySpec([(Q.PERCENTILE, 5)], group_by=[4]), model_check=c3_counts_model)
             if want("C3"):
                 report("C3", "BASELINE.json configs[2]", "SELECT SUM(a), MAX(b) GROUP BY k (1000 groups)", n, B(k) + B(a) + B(b), g, seg, Q.QuerySpec([(Q.SUM, 5), (Q.MAX, 6)], group_by=[4]),
                        cpu_rows=200_000_000)

@@ -408,6 +408,38 @@ def main():
                         ran += 1
             finally:
                 engine.reinit(**{k: flipped.get(k) for k in env})
+    # ---- PERCENTILE on dictionary columns (pg_scan_counts.h): scan_counts_kernel in both tiers (30 200 counters fit the LDS tier; the switch sends
+    # them to the HBM tier), group_counts_kernel behind an ordinary group-by.  The oracle has no such function: the lists are held against the numpy model of
+    # tests/percentile_cases.py (np.unique(..., return_counts=True) over the docs oracle.filter_bitmap matches), every other function against the oracle.
+    if only is None or only.search("percentile"):
+        import percentile_cases as PC
+        f100 = Q.leaf(Q.Pred.dict_range(F, 0, 100))
+        shapes = (("scan", Q.QuerySpec([(Q.PERCENTILE, W32), (Q.PERCENTILE, A), (Q.COUNT, -1)], filter=f100), "scan_counts_kernel"),
+                  ("group", Q.QuerySpec([(Q.PERCENTILE, A), (Q.SUM, V), (Q.PERCENTILE, W32)], filter=Q.leaf(Q.Pred.dict_range(F, 0, 500)), group_by=[B]), "group_counts_kernel"))
+        models = {}
+        for env in ({}, {"PINOT_GPU_PERCENTILE_LDS": "0"}):
+            engine.reinit(**env)
+            try:
+                with engine.open(seg) as g:
+                    for sid, spec, family in shapes:
+                        eid = "percentile-%s%s" % (sid, "-hbm" if env else "")
+                        if g.check(spec) != 0:
+                            failed.append({"id": eid, "error": "pg_query_check declined"})
+                            continue
+                        if sid not in models:
+                            models[sid] = PC.model(seg, spec)
+                        for rep in range(2):
+                            got = g.execute(spec)
+                            try:
+                                PC.assert_counts_equal(got, seg, spec, want=models[sid])
+                                PC.assert_other_functions_equal(got, seg, spec)
+                                if not flipped and sid == "scan":
+                                    assert got.dominant_kernel == family, "dominant kernel %s, expected %s" % (got.dominant_kernel, family)
+                            except AssertionError as e:
+                                failed.append({"id": eid, "error": str(e)[:300]})
+                        ran += 1
+            finally:
+                engine.reinit(**{k: flipped.get(k) for k in env})
     # ---- the transducer's kernels: byte-function walks, then table walks of the same machines ----
     if only is None or only.search("fsm"):
         count = args.fsm_trees if args.fsm_trees >= 0 else (400 if args.regime == "tiny" else 40)
