@@ -53,7 +53,8 @@ extern "C" {
                             * 4: PG_PRED_RAW_SET (IN / NOT IN on raw INT / LONG / FLOAT / DOUBLE columns); no struct layout changed;
                             * 5: pg_doc_set_create / release / cardinality, PG_PRED_DOC_SET (upsert / dedup valid-doc sets); no struct layout changed;
                             *    (still 5) PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids: no struct layout changed, one enumerator and one function added;
-                            *    (still 5) PG_AGG_PERCENTILE, pg_result_percentile_counts: no struct layout changed, one enumerator and one function added */
+                            *    (still 5) PG_AGG_PERCENTILE, pg_result_percentile_counts: no struct layout changed, one enumerator and one function added;
+                            *    (still 5) PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns, pg_result_value_counts: no struct layout changed, one function added */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -212,8 +213,14 @@ typedef enum pg_agg_function {
                                 * pg_agg_value.count = the set's cardinality, sum = 0, sum_exact = 0, min = +inf, max = -inf; the set itself comes
                                 * from pg_result_distinct_dict_ids.  No filter (or one that matches everything), no GROUP BY, every function
                                 * answerable that way: the whole dictionary, nothing scanned (NonScanBasedAggregationOperator.java:106-112).
-                                * PG_ERR_UNSUPPORTED at plan time: a raw column; PG_QUERY_NULL_HANDLING when the column carries a null vector; a
-                                * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four DISTINCTCOUNT columns; GROUP BY
+                                * On a raw (PG_FWD_RAW_FIXED_BYTE, uncompressed) INT / LONG / FLOAT / DOUBLE column, under PINOT_GPU_COLLECT=1 (without the
+                                * switch such a column is PG_ERR_UNSUPPORTED at plan time): the set of the matching docs' VALUES
+                                * (the Int / Long / Float / DoubleOpenHashSet), always scanned; pg_agg_value.count = the distinct values, the set comes
+                                * from pg_result_value_counts (the run values; pg_result_distinct_dict_ids answers PG_ERR_INVALID_ARGUMENT).
+                                * PG_ERR_UNSUPPORTED at plan time: PG_QUERY_NULL_HANDLING when the column carries a null vector; a
+                                * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four DISTINCTCOUNT columns; raw and
+                                * dictionary DISTINCTCOUNT columns in one query; a raw column's lists above PG_COLLECT_MAX_BYTES (STRING / BYTES and chunk-
+                                * compressed raw columns are never resident: pg_segment_open declines them); GROUP BY
                                 * unless group_key_kind is 0, group_id_upper_bound <= numGroupsLimit (the limit can never bind), the keys are
                                 * dictionary columns or raw INT / LONG columns keyed by offset, without null docs under PG_QUERY_NULL_HANDLING,
                                 * at most four of them, and the bit matrices fit PG_DISTINCT_GROUP_MAX_BYTES. */
@@ -223,8 +230,13 @@ typedef enum pg_agg_function {
                                 * pg_agg_value.count = the docs aggregated (the list's length), sum = 0, sum_exact = 0, min = +inf, max = -inf; the list
                                 * comes from pg_result_percentile_counts.  No metadata fast path: the reference scans even without a filter, and
                                 * numEntriesScannedPostFilter = docs scanned x the distinct columns the whole query projects.
-                                * PG_ERR_UNSUPPORTED at plan time: a raw column; PG_QUERY_NULL_HANDLING when the column carries a null vector; a
-                                * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four PERCENTILE columns; a
+                                * On a raw (PG_FWD_RAW_FIXED_BYTE, uncompressed) INT / LONG / FLOAT / DOUBLE column, under PINOT_GPU_COLLECT=1 (without the
+                                * switch such a column is PG_ERR_UNSUPPORTED at plan time): the same list as sorted (value,
+                                * count) runs from pg_result_value_counts (pg_result_percentile_counts answers PG_ERR_INVALID_ARGUMENT).
+                                * PG_ERR_UNSUPPORTED at plan time: PG_QUERY_NULL_HANDLING when the column carries a null vector; a
+                                * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four PERCENTILE columns; raw and
+                                * dictionary PERCENTILE columns in one query; a raw column's lists above PG_COLLECT_MAX_BYTES (STRING / BYTES and chunk-
+                                * compressed raw columns are never resident: pg_segment_open declines them); a
                                 * PG_AGG_DISTINCTCOUNT in the same query; GROUP BY outside the conditions PG_AGG_DISTINCTCOUNT sets, or counter
                                 * matrices above PG_PERCENTILE_GROUP_MAX_BYTES. */
 } pg_agg_function;
@@ -235,6 +247,10 @@ typedef enum pg_agg_function {
 /* GROUP BY with PG_AGG_PERCENTILE: group_id_upper_bound x cardinality x 4 bytes, summed over the query's PERCENTILE columns (plus the room behind
  * the last counter: 2^bits - cardinality counters), may not exceed this -- the same kind of capacity limit. */
 #define PG_PERCENTILE_GROUP_MAX_BYTES (1ull << 30)
+/* PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns: numDocs x (16 x the query's such columns + 8 under GROUP BY) bytes -- every doc's 64-bit
+ * order image, unsorted and sorted, and its raw group id twice -- may not exceed this: the same kind of capacity limit (and
+ * PINOT_GPU_GROUP_TABLE_BYTES bounds it too).  Priced with numDocs, not with the filter's matches, so that pg_query_check can decide it. */
+#define PG_COLLECT_MAX_BYTES (1ull << 30)
 /* Diagnostics: the 32-bit counters of all PERCENTILE columns of a query that scan_counts_kernel keeps in LDS when the filter stages no dictId
  * set there (with one: 2048 fewer); above it, or with PINOT_GPU_PERCENTILE_LDS=0, the counters live in HBM. */
 #define PG_PERCENTILE_LDS_MAX_COUNTERS 39036
@@ -328,6 +344,8 @@ typedef enum pg_kernel_id {
   PG_KERNEL_GROUP_DISTINCT = 15,   /* group_distinct_kernel: the same under GROUP BY, one bitset row per raw group id in HBM */
   PG_KERNEL_SCAN_COUNTS = 16,      /* scan_counts_kernel: PERCENTILE of dictionary columns, 32-bit dictId counters in LDS or in HBM (PINOT_GPU_PERCENTILE_LDS=0: always HBM) */
   PG_KERNEL_GROUP_COUNTS = 17,     /* group_counts_kernel: the same under GROUP BY, one counter row per raw group id in HBM */
+  PG_KERNEL_SCAN_COLLECT = 18,     /* scan_collect_kernel: PERCENTILE / DISTINCTCOUNT of raw columns, the matching docs' order images compacted into lists (sorted and run-length encoded behind it) */
+  PG_KERNEL_GROUP_COLLECT = 19,    /* group_collect_kernel: the same under GROUP BY, every doc's raw group id beside its images */
   PG_KERNEL_SCAN_HIST = 6          /* scan_hist_kernel: lane-private scan, SUM = sum_d matches[d] * dictionary[d] through an LDS histogram */
 } pg_kernel_id;
 
@@ -437,6 +455,16 @@ pg_status pg_result_distinct_dict_ids(const pg_result* result, int32_t aggregati
  * segment has fewer than 2^31 docs.) */
 pg_status pg_result_percentile_counts(const pg_result* result, int32_t aggregation, int32_t group_row,
                                       const int32_t** out_dict_ids, const uint32_t** out_counts, int32_t* out_num);
+
+/* The values behind a PG_AGG_PERCENTILE or PG_AGG_DISTINCTCOUNT aggregation on a RAW column, as sorted runs: out_value_bits[i] ascending in
+ * Double.compare's order for FLOAT / DOUBLE (-0.0 below 0.0, every NaN the one canonical NaN, above +Infinity) and in numeric order for INT / LONG,
+ * out_counts[i] > 0 the matching docs that carry the value, *out_num runs (0: no doc matched; the pointers may then be NULL).  Value bits follow
+ * pg_group_key_values: the long value (INT / LONG), the IEEE-754 bits of the double (FLOAT widened exactly, DOUBLE).  PERCENTILE's sorted list is
+ * value i repeated out_counts[i] times; DISTINCTCOUNT's set is the values.  group_row = -1 for an aggregation-only query, else a row of
+ * group_aggregations.  Engine-owned, valid until pg_result_free.  An aggregation on a dictionary column, any other aggregation index or row:
+ * PG_ERR_INVALID_ARGUMENT. */
+pg_status pg_result_value_counts(const pg_result* result, int32_t aggregation, int32_t group_row,
+                                 const int64_t** out_value_bits, const uint32_t** out_counts, int32_t* out_num);
 
 /* How a group-by column's entries of pg_result.group_key_dict_ids turn into key values.  A dictionary column: *out_is_offset = 0, the
  * entry is a dictId (GroupKeyGenerator.getGroupKeys looks it up, DictionaryBasedGroupKeyGenerator.java:260-290).  A raw (no-dictionary)

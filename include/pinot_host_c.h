@@ -90,6 +90,12 @@ char* ph_combine_counts(const char* sql, int32_t num_blocks, const int64_t* bloc
                         const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
                         const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* run_offsets, const double* run_values,
                         const int64_t* run_counts, int32_t* status);
+/* The sorted runs of a raw column (pg_result_value_counts: value bits, counts) as the intermediate results that segments merge, without a device.
+ * stored_type: 0 INT, 1 LONG, 2 FLOAT, 3 DOUBLE.  PERCENTILE's list: runs of (double, count) as getDoubleValuesSV gives the values -- two LONGs on one
+ * double merge into one run; DISTINCTCOUNT's set: the stored type's 64-bit images, ascending as longs.  The out arrays hold `num` entries; returns
+ * how many were written. */
+int32_t ph_value_counts_from_device(int32_t stored_type, const int64_t* value_bits, const uint32_t* counts, int32_t num, double* out_values, int64_t* out_counts);
+int32_t ph_value_set_from_device(int32_t stored_type, const int64_t* value_bits, int32_t num, int64_t* out_values);
 int32_t ph_group_by_table_capacity(int32_t limit, int32_t min_num_groups);          /* GroupByUtils.getTableCapacity */
 int32_t ph_group_by_trim_threshold(int32_t trim_size, int32_t trim_threshold);      /* GroupByUtils.getIndexedTableTrimThreshold */
 

@@ -80,6 +80,8 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     int _rows;                    // rows of _distinctSets / _percentileIds per aggregation: 1 without GROUP BY, else the lane's groups
     Object[] _percentileIds;      // PERCENTILE lanes: int[] ascending dictIds of aggregation a, row r at a * rows + r (null for other functions); else null
     Object[] _percentileCounts;   // ... and the int[] of how many matching docs carry each
+    Object[] _valueBits;          // DISTINCTCOUNT / PERCENTILE lanes over RAW columns: long[] ascending value bits of aggregation a, row r at a * rows + r; else null
+    Object[] _valueCounts;        // ... and the int[] of how many matching docs carry each
   }
 
   private final GpuSegment _segment;
@@ -171,7 +173,10 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       throw new UnsupportedOperationException("segment " + _segment.getSegmentName() + " is no longer resident on the device");
     }
     try {
-      Object[] raw = q._hasPercentile
+      Object[] raw = q._rawValueLists
+          ? PinotGpuNative.executeWithValueLists(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
+              q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
+          : q._hasPercentile
           ? PinotGpuNative.executeWithPercentileCounts(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
               q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
           : q._hasDistinctCount
@@ -190,8 +195,18 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     GpuQueryLowering.Lowered q = _lanes.get(laneIndex)._query;
     // in a batch: the first lane of the first segment a combine task reaches makes the native call for every lane of every segment
     Object[] raw = _batch != null ? _batch.take(_batchSlots[laneIndex]) : executeAlone(q);
+    Object[] valueBits = null;
+    Object[] valueCounts = null;
+    if (q._rawValueLists) {
+      if (raw == null || raw.length != PinotGpuNative.PGM_VALUES_SLOTS) {
+        throw new IllegalStateException("native value-list result does not match jni/pinot_gpu_jni.c");
+      }
+      valueBits = (Object[]) raw[PinotGpuNative.PGM_VALUES_BITS];
+      valueCounts = (Object[]) raw[PinotGpuNative.PGM_VALUES_COUNTS];
+      raw = (Object[]) raw[PinotGpuNative.PGM_VALUES_RESULT];
+    }
     Object[] distinctSets = null;
-    if (q._hasDistinctCount) {
+    if (q._hasDistinctCount && !q._rawValueLists) {
       if (raw == null || raw.length != PinotGpuNative.PGM_DISTINCT_SLOTS) {
         throw new IllegalStateException("native DISTINCTCOUNT result does not match jni/pinot_gpu_jni.c");
       }
@@ -200,7 +215,7 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     }
     Object[] percentileIds = null;
     Object[] percentileCounts = null;
-    if (q._hasPercentile) {
+    if (q._hasPercentile && !q._rawValueLists) {
       if (raw == null || raw.length != PinotGpuNative.PGM_PERCENTILE_SLOTS) {
         throw new IllegalStateException("native PERCENTILE result does not match jni/pinot_gpu_jni.c");
       }
@@ -223,6 +238,8 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     result._distinctSets = distinctSets;
     result._percentileIds = percentileIds;
     result._percentileCounts = percentileCounts;
+    result._valueBits = valueBits;
+    result._valueCounts = valueCounts;
     result._rows = _queryContext.getGroupByExpressions() == null ? 1 : result._groupIds.length;
     if (result._header.length != PinotGpuNative.PGM_HEADER_LEN) {
       throw new IllegalStateException("native result header does not match jni/pg_marshal.h");
@@ -251,6 +268,9 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
    * type of the column's stored type -- what a DictIdsWrapper turns into in extractAggregationResult).
    */
   private Set<?> valueSet(int function, LaneResult r, int at, int row) {
+    if (r._valueBits != null) {
+      return rawValueSet(function, r, at, row);
+    }
     int[] words = (int[]) r._distinctSets[at * r._rows + row];
     String column = _functions[function].getInputExpressions().get(0).getIdentifier();
     Dictionary dictionary = _indexSegment.getDataSource(column).getDictionary();
@@ -285,6 +305,9 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
    * sorts): dictionary.getDoubleValue(dictId), count times, dictIds ascending.  An empty list under null handling is the null holder.
    */
   private DoubleArrayList valueList(int function, LaneResult r, int at, int row, boolean nullHandling) {
+    if (r._valueBits != null) {
+      return rawValueList(function, r, at, row, nullHandling);
+    }
     int[] dictIds = (int[]) r._percentileIds[at * r._rows + row];
     int[] counts = (int[]) r._percentileCounts[at * r._rows + row];
     if (nullHandling && dictIds.length == 0) {
@@ -299,6 +322,62 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     DoubleArrayList values = new DoubleArrayList((int) size);
     for (int i = 0; i < dictIds.length; i++) {
       double value = dictionary.getDoubleValue(dictIds[i]);
+      for (int n = 0; n < counts[i]; n++) {
+        values.add(value);
+      }
+    }
+    return values;
+  }
+
+  /**
+   * DISTINCTCOUNT on a raw column: the run values of aggregation {@code at}, row {@code row} -> the set the reference's function keeps for a column
+   * without a dictionary (DistinctCountAggregationFunction: an Int / Long / Float / DoubleOpenHashSet by the stored type).  The bits are the long value
+   * of INT / LONG and the bits of the double of FLOAT (widened exactly: the narrowing gives the float back) / DOUBLE.
+   */
+  private Set<?> rawValueSet(int function, LaneResult r, int at, int row) {
+    long[] bits = (long[]) r._valueBits[at * r._rows + row];
+    String column = _functions[function].getInputExpressions().get(0).getIdentifier();
+    FieldSpec.DataType storedType = _indexSegment.getDataSource(column).getDataSourceMetadata().getDataType().getStoredType();
+    Set<Object> values = new HashSet<>();
+    for (long b : bits) {
+      switch (storedType) {
+        case INT:
+          values.add((int) b);
+          break;
+        case LONG:
+          values.add(b);
+          break;
+        case FLOAT:
+          values.add((float) Double.longBitsToDouble(b));
+          break;
+        default:
+          values.add(Double.longBitsToDouble(b));
+          break;
+      }
+    }
+    return values;
+  }
+
+  /**
+   * PERCENTILE on a raw column: the (value bits, count) runs of aggregation {@code at}, row {@code row} -> the DoubleArrayList of the reference's
+   * function: the value as getDoubleValuesSV gives it ((double) of an INT / LONG, the double behind the bits of a FLOAT / DOUBLE), count times, ascending.
+   */
+  private DoubleArrayList rawValueList(int function, LaneResult r, int at, int row, boolean nullHandling) {
+    long[] bits = (long[]) r._valueBits[at * r._rows + row];
+    int[] counts = (int[]) r._valueCounts[at * r._rows + row];
+    if (nullHandling && bits.length == 0) {
+      return null;
+    }
+    String column = _functions[function].getInputExpressions().get(0).getIdentifier();
+    FieldSpec.DataType storedType = _indexSegment.getDataSource(column).getDataSourceMetadata().getDataType().getStoredType();
+    boolean floating = storedType == FieldSpec.DataType.FLOAT || storedType == FieldSpec.DataType.DOUBLE;
+    long size = 0;
+    for (int count : counts) {
+      size += count;
+    }
+    DoubleArrayList values = new DoubleArrayList((int) size);
+    for (int i = 0; i < bits.length; i++) {
+      double value = floating ? Double.longBitsToDouble(bits[i]) : (double) bits[i];
       for (int n = 0; n < counts[i]; n++) {
         values.add(value);
       }

@@ -203,7 +203,7 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
       return cpuPlan;      // the engine declines the two in one query
     }
     // (a DISTINCTCOUNT lane reads its sets before the native result is released: one call of its own, PinotGpuNative.executeWithDistinctSets)
-    // (a PERCENTILE lane likewise: PinotGpuNative.executeWithPercentileCounts)
+    // (a PERCENTILE lane likewise: PinotGpuNative.executeWithPercentileCounts; either function on raw columns: PinotGpuNative.executeWithValueLists)
     final GpuBatch batch = (distinctCount || percentile) ? null : planningBatch;
     int[] batchSlots = null;
     if (batch != null) {

@@ -90,6 +90,7 @@ final class GpuQueryLowering {
     int _flags;
     boolean _hasDistinctCount;      // a DISTINCTCOUNT among the aggregations: executed alone through executeWithDistinctSets, never in a batch
     boolean _hasPercentile;         // a PERCENTILE among the aggregations: executed alone through executeWithPercentileCounts, never in a batch
+    boolean _rawValueLists;         // those DISTINCTCOUNT / PERCENTILE columns are RAW (no dictionary): executed through executeWithValueLists instead
   }
 
   /** Thrown inside the lowering when a construct has no device form; the plan maker keeps the CPU plan. */
@@ -233,19 +234,20 @@ final class GpuQueryLowering {
         if (!_segment.isNumeric(column)) {
           throw new NotOffloadable("aggregation of a non-numeric column");   // the reference throws BadQueryRequestException itself
         }
-        if (code == AGG_DISTINCTCOUNT) {
-          // dictId bitsets on the device: a dictionary column only (a raw column keeps the reference's hash set of values: CPU plan)
-          if (!_segment.hasDictionary(column)) {
-            throw new NotOffloadable("DISTINCTCOUNT on a column without a dictionary");
+        if (code == AGG_DISTINCTCOUNT || code == AGG_PERCENTILE) {
+          // a dictionary column: dictId bitsets / dictId count histograms on the device; a raw INT / LONG / FLOAT / DOUBLE column: the matching docs'
+          // values collected, sorted and run-length encoded (PinotGpuNative.executeWithValueLists).  One query takes one of the two forms: the engine
+          // declines a mix, and so does this lowering
+          boolean raw = !_segment.hasDictionary(column);
+          if ((out._hasDistinctCount || out._hasPercentile) && raw != out._rawValueLists) {
+            throw new NotOffloadable("DISTINCTCOUNT / PERCENTILE on raw and dictionary columns in one query");
           }
-          out._hasDistinctCount = true;
-        }
-        if (code == AGG_PERCENTILE) {
-          // dictId count histograms on the device: a dictionary column only (a raw column keeps the reference's DoubleArrayList: CPU plan)
-          if (!_segment.hasDictionary(column)) {
-            throw new NotOffloadable("PERCENTILE on a column without a dictionary");
+          out._rawValueLists = raw;
+          if (code == AGG_DISTINCTCOUNT) {
+            out._hasDistinctCount = true;
+          } else {
+            out._hasPercentile = true;
           }
-          out._hasPercentile = true;
         }
       }
       out._aggregations[AGG_INTS * i] = code;

@@ -236,6 +236,21 @@ public final class PinotGpuNative {
   static native Object[] executeWithPercentileCounts(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
       int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
 
+  /** Slots of executeWithValueLists' Object[]: the Object[PGM_RESULT_ARRAYS] of execute(), then the raw columns' run values (value bits) and their counts. */
+  public static final int PGM_VALUES_SLOTS = 3;
+  public static final int PGM_VALUES_RESULT = 0;
+  public static final int PGM_VALUES_BITS = 1;
+  public static final int PGM_VALUES_COUNTS = 2;
+
+  /**
+   * pg_execute of a query with PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT aggregations on RAW (no-dictionary) columns plus pg_result_value_counts over its
+   * result.  Returns Object[PGM_VALUES_SLOTS]: what execute() returns, and two Object[aggregations * rows] whose elements {@code aggregation * rows + row}
+   * are the long[] of the list's ascending value bits (the long value of INT / LONG, Double.doubleToRawLongBits of the widened FLOAT / the DOUBLE) and
+   * the int[] of how many matching docs carry each, for such an aggregation, and null for every other function; rows = 1 without GROUP BY, else the groups.
+   */
+  static native Object[] executeWithValueLists(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
+      int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
+
   /**
    * pg_execute_batch: {@code queries[i]} (Object[PGM_QUERY_ARRAYS], slots PGM_Q_*) over {@code handles[i]} -- the segments of ONE query, the
    * way BaseCombineOperator hands them to its worker threads, in one native call (aggregations over scan / sorted leaves share one

@@ -42,6 +42,8 @@ enum {
 enum { PGM_DISTINCT_SLOTS = 2, PGM_DISTINCT_RESULT = 0, PGM_DISTINCT_SETS = 1 };
 /* PinotGpuNative.executeWithPercentileCounts: Object[PGM_PERCENTILE_SLOTS] = {the Object[PGM_RESULT_ARRAYS] of execute(), the PERCENTILE lists' dictIds, their counts} */
 enum { PGM_PERCENTILE_SLOTS = 3, PGM_PERCENTILE_RESULT = 0, PGM_PERCENTILE_DICT_IDS = 1, PGM_PERCENTILE_COUNTS = 2 };
+/* PinotGpuNative.executeWithValueLists: Object[PGM_VALUES_SLOTS] = {the Object[PGM_RESULT_ARRAYS] of execute(), the raw columns' run values (value bits), their counts} */
+enum { PGM_VALUES_SLOTS = 3, PGM_VALUES_RESULT = 0, PGM_VALUES_BITS = 1, PGM_VALUES_COUNTS = 2 };
 /* One query of a batch call (PinotGpuNative.executeBatch): Object[PGM_QUERY_ARRAYS] = the seven flat arrays above in this order, then
  * int[PGM_Q_LIMIT_FLAGS_LEN] {numGroupsLimit, flags}. */
 enum {

@@ -462,6 +462,62 @@ JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeW
   return out;
 }
 
+/* pg_execute of a query with PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT aggregations on RAW columns, and pg_result_value_counts over its result before that is
+ * released.  Returns Object[PGM_VALUES_SLOTS]: {the Object[PGM_RESULT_ARRAYS] execute() returns, Object[aggregations * rows], Object[aggregations * rows]} --
+ * element (aggregation * rows + row) of the second array is the long[] of the list's ascending value bits (the long value of INT / LONG, the IEEE-754
+ * bits of the double of FLOAT / DOUBLE), of the third the int[] of their counts (non-zero; a count is below 2^31) for such an aggregation, null in both
+ * for every other function; rows = 1 for an aggregation-only query, else the number of groups. */
+JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeWithValueLists(JNIEnv* env, jclass cls, jlong handle, jintArray filterNodes,
+    jintArray predInts, jlongArray predLongs, jintArray setOffsets, jintArray setWords, jintArray aggregations, jintArray groupBy,
+    jint numGroupsLimit, jint flags) {
+  (void)cls;
+  pinned_query p;
+  if (!pin_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy, numGroupsLimit, flags)) return NULL;
+  const int32_t num_group_by = pgm_query_get(p.built)->num_group_by;
+  pg_result result;
+  const pg_status status = pg_execute((pg_segment*)(intptr_t)handle, pgm_query_get(p.built), &result);
+  release_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy);
+  if (status != PG_OK) { throw_status(env, status); return NULL; }     /* pg_execute freed the result */
+  const jsize rows = num_group_by > 0 ? (jsize)result.num_groups : 1;
+  const jsize na = (jsize)result.num_aggregations;
+  jclass object_class = (*env)->FindClass(env, "java/lang/Object");
+  jobjectArray bits = object_class ? (*env)->NewObjectArray(env, na * rows, object_class, NULL) : NULL;
+  jobjectArray counts = bits ? (*env)->NewObjectArray(env, na * rows, object_class, NULL) : NULL;
+  int ok = counts != NULL;
+  for (jsize a = 0; ok && a < na; ++a) {
+    for (jsize r = 0; ok && r < rows; ++r) {
+      const int64_t* value_bits = NULL;
+      const uint32_t* doc_counts = NULL;
+      int32_t num = 0;
+      if (pg_result_value_counts(&result, (int32_t)a, num_group_by > 0 ? (int32_t)r : -1, &value_bits, &doc_counts, &num) != PG_OK) break;      /* not a raw column's list: the row of nulls stays */
+      jlongArray jbits = (*env)->NewLongArray(env, (jsize)num);
+      jintArray jcounts = jbits ? (*env)->NewIntArray(env, (jsize)num) : NULL;
+      if (jcounts == NULL) { ok = 0; break; }
+      jlong* dst_bits = (*env)->GetLongArrayElements(env, jbits, NULL);
+      jint* dst_counts = dst_bits ? (*env)->GetIntArrayElements(env, jcounts, NULL) : NULL;
+      if (dst_counts == NULL) { if (dst_bits) (*env)->ReleaseLongArrayElements(env, jbits, dst_bits, 0); ok = 0; break; }
+      if (num > 0) { memcpy(dst_bits, value_bits, (size_t)num * sizeof(jlong)); memcpy(dst_counts, doc_counts, (size_t)num * sizeof(jint)); }
+      (*env)->ReleaseLongArrayElements(env, jbits, dst_bits, 0);
+      (*env)->ReleaseIntArrayElements(env, jcounts, dst_counts, 0);
+      (*env)->SetObjectArrayElement(env, bits, a * rows + r, jbits);
+      (*env)->SetObjectArrayElement(env, counts, a * rows + r, jcounts);
+      (*env)->DeleteLocalRef(env, jbits);
+      (*env)->DeleteLocalRef(env, jcounts);
+    }
+  }
+  jobjectArray converted = result_to_java(env, &result, num_group_by);      /* releases the result */
+  if (!ok || converted == NULL) {
+    if (!(*env)->ExceptionCheck(env)) throw_new(env, "java/lang/OutOfMemoryError", "allocating the value lists failed");
+    return NULL;
+  }
+  jobjectArray out = (*env)->NewObjectArray(env, PGM_VALUES_SLOTS, object_class, NULL);
+  if (out == NULL) return NULL;
+  (*env)->SetObjectArrayElement(env, out, PGM_VALUES_RESULT, converted);
+  (*env)->SetObjectArrayElement(env, out, PGM_VALUES_BITS, bits);
+  (*env)->SetObjectArrayElement(env, out, PGM_VALUES_COUNTS, counts);
+  return out;
+}
+
 /* pg_execute_batch: queries[i] (Object[PGM_QUERY_ARRAYS], slots PGM_Q_*) over handles[i] -- the segments of ONE query as the combine operator
  * would hand them to its worker threads (BaseCombineOperator.java:85-142).  Returns Object[n]: element i is the Object[PGM_RESULT_ARRAYS]
  * execute() would have returned for item i, or -- the item failed, the others did not stop for it -- a String "<pg_status>\n<message>".

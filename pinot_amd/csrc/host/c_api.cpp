@@ -164,9 +164,13 @@ ResultsBlock blockFromArrays(bool is_group_by, const std::vector<AggregationFunc
         if (run_offsets && run_values && run_counts) {
           std::vector<std::pair<double, int64_t>> runs;
           for (int64_t i = run_offsets[at]; i < run_offsets[at + 1]; ++i) if (run_counts[i] > 0) runs.emplace_back(run_values[i], run_counts[i]);
-          std::sort(runs.begin(), runs.end());
+          // (NaN last, as Double.compare has it: operator< alone is no ordering once a NaN is among the values)
+          std::sort(runs.begin(), runs.end(), [](const std::pair<double, int64_t>& p, const std::pair<double, int64_t>& q) {
+            const bool pn = p.first != p.first, qn = q.first != q.first;
+            return (pn || qn) ? (!pn && qn) : p < q;
+          });
           for (const auto& run : runs) {
-            if (!l.values.empty() && l.values.back() == run.first) l.counts.back() += run.second;
+            if (!l.values.empty() && (l.values.back() == run.first || (l.values.back() != l.values.back() && run.first != run.first))) l.counts.back() += run.second;
             else { l.values.push_back(run.first); l.counts.push_back(run.second); }
           }
         }
@@ -730,6 +734,19 @@ char* ph_combine_counts(const char* sql, int32_t num_blocks, const int64_t* bloc
     out = o.str();
   });
   return *status == 0 ? strdup(out.c_str()) : nullptr;
+}
+
+// The host side of pg_result_value_counts without a device (CPU tests, the stand-alone sanitizer program): the runs of a raw column as the
+// intermediate results that segments merge.  stored_type: 0 INT, 1 LONG, 2 FLOAT, 3 DOUBLE; the out arrays hold `num` entries; returns how many were written.
+int32_t ph_value_counts_from_device(int32_t stored_type, const int64_t* value_bits, const uint32_t* counts, int32_t num, double* out_values, int64_t* out_counts) {
+  const ValueCounts list = ValueCounts::fromDeviceValues((DataType)stored_type, value_bits, counts, num);
+  for (size_t i = 0; i < list.values.size(); ++i) { out_values[i] = list.values[i]; out_counts[i] = list.counts[i]; }
+  return (int32_t)list.values.size();
+}
+int32_t ph_value_set_from_device(int32_t stored_type, const int64_t* value_bits, int32_t num, int64_t* out_values) {
+  const ValueSet set = ValueSet::fromDeviceValues((DataType)stored_type, value_bits, num);
+  for (size_t i = 0; i < set.values.size(); ++i) out_values[i] = set.values[i];
+  return (int32_t)set.values.size();
 }
 
 // GroupByUtils.getTableCapacity / getIndexedTableTrimThreshold (core/util/GroupByUtils.java:48-73)

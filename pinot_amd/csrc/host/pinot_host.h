@@ -290,10 +290,25 @@ struct AvgPair { double sum = 0.0; int64_t count = 0; };                  // seg
 // DISTINCTCOUNT's intermediate result: the VALUE set (BaseDistinctAggregateAggregationFunction.convertToValueSet :75-89 -- dictIds looked up in
 // the segment's dictionary), kept as the ascending 64-bit images of the values tagged with the stored type: INT / LONG the value, FLOAT /
 // DOUBLE the IEEE-754 bits of the value as a double.  merge = set union (:109-121); the final result is the size, an INT (:66-68).
-struct ValueSet { DataType storedType = DataType::INT; std::vector<int64_t> values; };
+struct ValueSet {
+  DataType storedType = DataType::INT;
+  std::vector<int64_t> values;
+  // A raw (no-dictionary) column: the run values of pg_result_value_counts are the set already -- the Int / Long / Float / DoubleOpenHashSet's
+  // elements as value bits, ascending in Double.compare's order for FLOAT / DOUBLE.  Kept as they are (the stored type's images stay distinct: two
+  // LONGs on one double, -0.0 and 0.0), re-sorted as 64-bit images: the order the merge's set_union takes.
+  static ValueSet fromDeviceValues(DataType storedType, const int64_t* valueBits, int32_t num);
+};
 // PERCENTILE's intermediate result: the DoubleArrayList of PercentileAggregationFunction (:77-100) as ascending runs of (value, count) -- the
 // list's order does not matter (extractFinalResult sorts it, :155-172).  merge = the run-wise merge (addAll up to order).
-struct ValueCounts { std::vector<double> values; std::vector<int64_t> counts; int64_t size() const { int64_t n = 0; for (int64_t c : counts) n += c; return n; } };
+struct ValueCounts {
+  std::vector<double> values;
+  std::vector<int64_t> counts;
+  int64_t size() const { int64_t n = 0; for (int64_t c : counts) n += c; return n; }
+  // A raw (no-dictionary) column: the (value bits, count) runs of pg_result_value_counts -> runs of (double, count) as getDoubleValuesSV gives the
+  // values -- (double) of an INT / LONG, the double behind the bits of a FLOAT (widened) / DOUBLE.  Two LONGs that land on one double merge into
+  // one run (they are neighbours: the conversion is monotone).
+  static ValueCounts fromDeviceValues(DataType storedType, const int64_t* valueBits, const uint32_t* counts, int32_t num);
+};
 using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet, ValueCounts>;   // Long / Double / AvgPair / null (null handling only) / value set / value list
 inline bool isNullResult(const IntermediateResult& r) { return std::holds_alternative<std::monostate>(r); }
 
@@ -519,6 +534,7 @@ struct GpuAbi {
   decltype(&pg_result_free) result_free;
   decltype(&pg_result_distinct_dict_ids) result_distinct_dict_ids;
   decltype(&pg_result_percentile_counts) result_percentile_counts;
+  decltype(&pg_result_value_counts) result_value_counts;
   decltype(&pg_filter_bitmap) filter_bitmap;
   decltype(&pg_group_key_info) group_key_info;
   decltype(&pg_group_key_values) group_key_values;

@@ -49,6 +49,7 @@ const GpuAbi& gpuAbi() {
     abi.result_free = (decltype(abi.result_free))sym("pg_result_free");
     abi.result_distinct_dict_ids = (decltype(abi.result_distinct_dict_ids))sym("pg_result_distinct_dict_ids");
     abi.result_percentile_counts = (decltype(abi.result_percentile_counts))sym("pg_result_percentile_counts");
+    abi.result_value_counts = (decltype(abi.result_value_counts))sym("pg_result_value_counts");
     abi.filter_bitmap = (decltype(abi.filter_bitmap))sym("pg_filter_bitmap");
     abi.group_key_info = (decltype(abi.group_key_info))sym("pg_group_key_info");
     abi.group_key_values = (decltype(abi.group_key_values))sym("pg_group_key_values");
@@ -219,6 +220,28 @@ IntermediateResult AggregationFunction::fromDeviceCounts(const int32_t* dictIds,
   return list;
 }
 
+ValueSet ValueSet::fromDeviceValues(DataType storedType, const int64_t* valueBits, int32_t num) {
+  ValueSet set;
+  set.storedType = storedType;
+  if (num > 0) set.values.assign(valueBits, valueBits + num);
+  std::sort(set.values.begin(), set.values.end());      // (the device's order is the values'; double images of negative values do not ascend as longs)
+  return set;
+}
+
+ValueCounts ValueCounts::fromDeviceValues(DataType storedType, const int64_t* valueBits, const uint32_t* counts, int32_t num) {
+  ValueCounts list;
+  list.values.reserve((size_t)std::max(num, 0)); list.counts.reserve((size_t)std::max(num, 0));
+  const bool floating = storedType == DataType::FLOAT || storedType == DataType::DOUBLE;
+  for (int32_t i = 0; i < num; ++i) {
+    double v;
+    if (floating) memcpy(&v, &valueBits[i], 8); else v = (double)valueBits[i];
+    // (two LONGs on one double; a FLOAT / DOUBLE column's runs are distinct values already -- -0.0 and 0.0 stay two runs, in Double.compare's order)
+    if (!floating && !list.values.empty() && list.values.back() == v) list.counts.back() += (int64_t)counts[i];
+    else { list.values.push_back(v); list.counts.push_back((int64_t)counts[i]); }
+  }
+  return list;
+}
+
 IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const IntermediateResult& b) const {
   // SumAggregationFunction.merge :223-233 and friends under null handling: a null side yields the other side
   if (isNullResult(a)) return b;
@@ -240,11 +263,14 @@ IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const
       r.values.reserve(x.values.size() + y.values.size()); r.counts.reserve(x.values.size() + y.values.size());
       size_t i = 0, j = 0;
       while (i < x.values.size() || j < y.values.size()) {
-        const bool takeX = j == y.values.size() || (i < x.values.size() && x.values[i] <= y.values[j]);
+        // (a raw DOUBLE / FLOAT column can hold NaN: it sorts last, as Double.compare has it, and equals itself here -- with plain == neither side
+        //  would ever advance past it)
+        auto same = [](double p, double q) { return p == q || (p != p && q != q); };
+        const bool takeX = j == y.values.size() || (i < x.values.size() && (x.values[i] <= y.values[j] || y.values[j] != y.values[j]));
         const double v = takeX ? x.values[i] : y.values[j];
         int64_t n = 0;
-        if (i < x.values.size() && x.values[i] == v) n += x.counts[i++];
-        if (j < y.values.size() && y.values[j] == v) n += y.counts[j++];
+        if (i < x.values.size() && same(x.values[i], v)) n += x.counts[i++];
+        if (j < y.values.size() && same(y.values[j], v)) n += y.counts[j++];
         r.values.push_back(v); r.counts.push_back(n);
       }
       return r;
@@ -562,7 +588,7 @@ std::unique_ptr<LoweredQuery> lowerQuery(const ImmutableSegment& seg, const Quer
       if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException("PERCENTILE(" + a.column + ") on a STRING column keeps the CPU plan");
     }
     if (a.function == AggregationFunctionType::DISTINCTCOUNT) {
-      // the engine takes a dictionary column of a numeric stored type (pg_query_check says so for raw columns; FILTER (WHERE ...) lanes beside
+      // the engine takes a dictionary or raw column of a numeric stored type (pg_query_check says what else it declines; FILTER (WHERE ...) lanes beside
       // a DISTINCTCOUNT are declined by makeSegmentPlanNode)
       if (a.column == "*") throw QueryException("'*' is only valid in COUNT(*)");
       if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException("DISTINCTCOUNT(" + a.column + ") on a STRING column keeps the CPU plan");
@@ -774,6 +800,18 @@ class GpuAggregationOperator : public Operator {
 
   // one function's holder out of the device result: DISTINCTCOUNT through the set accessor and the column's dictionary (before the result is freed)
   IntermediateResult fromResult(const AggregationFunction& f, const pg_result& res, int aggregation, int groupRow, const pg_agg_value& v) const {
+    // a raw (no-dictionary) column: the sorted runs of pg_result_value_counts, for either function
+    const bool collected = f.getType() == AggregationFunctionType::PERCENTILE || f.getType() == AggregationFunctionType::DISTINCTCOUNT;
+    if (collected && _segment->getDataSource(f.getColumn()).dictionary == nullptr) {
+      const DataSource& ds = _segment->getDataSource(f.getColumn());
+      const int64_t* valueBits = nullptr;
+      const uint32_t* counts = nullptr;
+      int32_t num = 0;
+      checkStatus(gpuAbi().result_value_counts(&res, aggregation, groupRow, &valueBits, &counts, &num), "reading a raw column's value list");
+      if (f.getType() == AggregationFunctionType::DISTINCTCOUNT) return ValueSet::fromDeviceValues(ds.dataType, valueBits, num);
+      if (_queryContext.nullHandlingEnabled && num == 0) return std::monostate{};      // (as the dictionary form below)
+      return ValueCounts::fromDeviceValues(ds.dataType, valueBits, counts, num);
+    }
     if (f.getType() == AggregationFunctionType::PERCENTILE) {
       const int32_t* dictIds = nullptr;
       const uint32_t* counts = nullptr;

@@ -261,6 +261,19 @@ struct DistinctParams {
   DistinctKey keys[kMaxDistinctKeys];
 };
 
+// ---- PERCENTILE / DISTINCTCOUNT on raw columns (pg_scan_collect.h): the matching docs' order images, compacted into lists ----
+struct CollectParams {
+  DistinctParams d;                               // scan: the filter and the record; num_cols: collected columns (cols[] unused); num_keys / keys: group_collect_kernel's raw group ids
+  const uint8_t* fwd[kMaxAggCols];                // the raw columns' first value byte (big-endian 4- or 8-byte values, padded to whole 2048-doc tiles)
+  int32_t vkind[kMaxAggCols];                     // their ValueKind
+  unsigned long long* out_images[kMaxAggCols];    // [capacity] per column: slot s holds the order image (pg_order_image.h) of the s-th reserved doc
+  uint32_t* out_rows;                             // [capacity] group_collect_kernel: the same doc's raw group id
+  unsigned long long* cursor;                     // [1] zero before the launch: slots reserved so far; at the end the filter's match count
+  uint32_t* flags;                                // [1] zero before the launch; kCollectOverflow: a wave's reservation went past `capacity` (it wrote nothing)
+  unsigned long long capacity;                    // slots behind every out_* pointer
+};
+constexpr uint32_t kCollectOverflow = 1u;
+
 // raw_set_bitmap_kernel (pg_scan_raw_set.h): the match bitmap of one PG_PRED_RAW_SET leaf
 struct RawSetBitmapParams {
   const uint8_t* fwd;                   // the raw column's first value byte (padded to whole 2048-doc tiles)

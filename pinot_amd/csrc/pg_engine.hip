@@ -78,6 +78,7 @@ struct Engine {
   int fold_one_counter = 1;  // PINOT_GPU_FOLD_ONE_COUNTER=0: grids of at most 64 workgroups also arrive on eight shard counters + the top one
   bool poll_result = true;   // PINOT_GPU_POLL_RESULT=0: pg_execute always waits with hipStreamSynchronize instead of spinning on the pinned record's sequence number
   bool distinct_lds = true;  // PINOT_GPU_DISTINCT_LDS=0: DISTINCTCOUNT keeps its dictId bitsets in HBM at every cardinality (scan_distinct_kernel<false>; tests of that tier on small dictionaries)
+  bool collect = false;        // PINOT_GPU_COLLECT=1: PERCENTILE / DISTINCTCOUNT on raw columns take the collect pass (pg_scan_collect.h); unset: declined as before, the CPU plan keeps them
   bool percentile_lds = true;  // PINOT_GPU_PERCENTILE_LDS=0: PERCENTILE keeps its dictId counters in HBM at every cardinality (scan_counts_kernel<false>; tests of that tier on small dictionaries)
   bool set_lds = true;       // PINOT_GPU_SET_LDS=0: dictId-set leaves (IN lists) of the lane-private scan kernels read their words from memory per doc (rounds 2-6a)
   bool lane_skip = true;     // PINOT_GPU_LANE_SKIP=0: the aggregating kernels load a tile's value bytes for every lane, matches or not
@@ -1036,6 +1037,7 @@ struct Lowered {
   // the bitset pass of a DISTINCTCOUNT query (kQueryDistinctPass): plan slots of its DISTINCTCOUNT columns and of group_distinct_kernel's keys
   std::vector<int> distinct_slots, distinct_key_slots;
   bool counts_pass = false;                    // kQueryCountsPass: the slots are PERCENTILE columns, the kernels scan_counts_kernel / group_counts_kernel (32-bit counters per dictId)
+  bool collect_pass = false;                   // kQueryCollectPass: the slots are RAW columns, the kernels scan_collect_kernel / group_collect_kernel (pg_scan_collect.h)
 };
 
 int slot_for(Lowered* lw, const pg_segment* seg, int column, bool plane = false) {
@@ -2033,6 +2035,7 @@ pg_status pg_init(const pg_config* config) {
   g_engine.set_lds = env_on("PINOT_GPU_SET_LDS");
   g_engine.distinct_lds = env_on("PINOT_GPU_DISTINCT_LDS");
   g_engine.percentile_lds = env_on("PINOT_GPU_PERCENTILE_LDS");
+  { const char* cv = getenv("PINOT_GPU_COLLECT"); g_engine.collect = cv != nullptr && cv[0] == '1'; }
   g_engine.partition_two_level = env_on("PINOT_GPU_PARTITION_TWO_LEVEL");
   g_engine.fsm_perm = env_on("PINOT_GPU_FSM_PERM");
   g_engine.fsm_stats = env_on("PINOT_GPU_FSM_STATS");
@@ -2554,7 +2557,20 @@ struct CountList {
 };
 // `distinct` also carries the counts pass's dense counter rows (num_words = the cardinality) from run_aggregation to execute_percentile, which
 // compacts them into `counts`: the dense matrix does not outlive pg_execute.
-struct ResultInternal { std::vector<DistinctSet> distinct; std::vector<CountList> counts; };
+// The values behind a PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT aggregation on a raw column, as sorted runs (pg_result_value_counts): row r holds
+// the runs [offsets[r], offsets[r + 1]) of (value_bits, counts).  From run_aggregation to execute_percentile / execute_distinct under GROUP BY the
+// runs of ALL raw group ids travel in one row with run_rows beside them (ascending raw group id, then ascending value): finish_value_lists cuts
+// them into the rows of the groups that exist.
+struct ValueList {
+  int aggregation = 0;
+  int rows = 1;
+  std::vector<size_t> offsets;          // [rows + 1]
+  std::vector<int64_t> value_bits;      // the long value (INT / LONG), the IEEE-754 bits of the double (FLOAT widened / DOUBLE)
+  std::vector<uint32_t> counts;
+  std::vector<uint32_t> run_rows;       // in transit only: the raw group id of every run
+  bool grouped_in_transit = false;
+};
+struct ResultInternal { std::vector<DistinctSet> distinct; std::vector<CountList> counts; std::vector<ValueList> values; };
 
 void pg_result_free(pg_result* r) {
   if (!r) return;
@@ -2579,6 +2595,9 @@ constexpr int32_t kQueryDistinctPass = 1 << 28;
 // internal pg_query.flags bit (execute_percentile -> execute_impl): the counts pass of a PG_AGG_PERCENTILE query -- the bitset pass's shape with
 // COUNT(*) and PERCENTILE aggregations, launched as scan_counts_kernel / group_counts_kernel (pg_scan_counts.h).  Never together with kQueryDistinctPass.
 constexpr int32_t kQueryCountsPass = 1 << 27;
+// internal pg_query.flags bit, set beside one of the two above: the pass's columns are RAW columns -- their values are collected into lists, sorted
+// and run-length encoded (scan_collect_kernel / group_collect_kernel, pg_scan_collect.h) instead of counted per dictId.
+constexpr int32_t kQueryCollectPass = 1 << 26;
 constexpr int32_t kQuerySetPass = kQueryDistinctPass | kQueryCountsPass;
 // the one function besides COUNT(*) a pass query carries, -1: not a pass
 static inline int set_pass_function(int32_t flags) { return (flags & kQueryCountsPass) ? PG_AGG_PERCENTILE : ((flags & kQueryDistinctPass) ? PG_AGG_DISTINCTCOUNT : -1); }
@@ -2964,14 +2983,14 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
 // ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
 // preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
-enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Counts, GroupCounts, Agg };
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Counts, GroupCounts, Collect, GroupCollect, Agg };
 // per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
 // leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
 static const struct { int id; bool writes_leaves; } kScanKernels[] = {
   {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
   {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_SIMPLE_VALID, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
   {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_DISTINCT, true}, {PG_KERNEL_GROUP_DISTINCT, true}, {PG_KERNEL_SCAN_COUNTS, true}, {PG_KERNEL_GROUP_COUNTS, true},
-  {PG_KERNEL_SCAN_AGG, false}};
+  {PG_KERNEL_SCAN_COLLECT, true}, {PG_KERNEL_GROUP_COLLECT, true}, {PG_KERNEL_SCAN_AGG, false}};
 static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
 // general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
 // specialised kernel that won keeps it: the index handling, the leap-frog count and the batch's fallbacks go by the family.
@@ -2995,6 +3014,8 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
   if (sp.num_nodes == 1 && sp.nodes[0].op == PG_FILTER_LEAF && sp.nodes[0].kind == kLeafRawSet) { k.general = ScanKernel::Private; return pick(ScanKernel::RawSet); }
   // The bitset pass of a DISTINCTCOUNT query: kernels of their own (pg_scan_distinct.h) with the lane-private filter -- check_distinct_plan
   // declined the leaves that filter does not evaluate.  Everything that goes by the family (tile lists, the entry counts) is Private's.
+  // On raw columns both passes collect the values (pg_scan_collect.h).
+  if (!lw.distinct_slots.empty() && lw.collect_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Collect : ScanKernel::GroupCollect); }
   if (!lw.distinct_slots.empty() && !lw.counts_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Distinct : ScanKernel::GroupDistinct); }
   // The counts pass of a PERCENTILE query: the same, with 32-bit counters per dictId (pg_scan_counts.h).
   if (!lw.distinct_slots.empty()) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Counts : ScanKernel::GroupCounts); }
@@ -3182,6 +3203,15 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Lowe
       }
       break;
     }
+    case ScanKernel::Collect: case ScanKernel::GroupCollect: {
+      // the HBM tier of the two cases above: workgroups of four wavefronts, the filter's set area (if any) 16 bytes in, the reduction records over the start
+      bool has_set = false;
+      if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) has_set |= sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet;
+      g.hist_set_off = has_set ? 16 : 0;
+      g.lds = std::max((size_t)(has_set ? 16 + kSetLdsWords * 4 : 0), sizeof(BlockPartial) * (size_t)wpb + 16);
+      g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, (k.kernel == ScanKernel::Collect ? waves_scan_collect() : waves_group_collect()) / wpb));
+      break;
+    }
     case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
     case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
@@ -3236,7 +3266,8 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Private: launch_scan_private(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::Agg: launch_scan_agg(g_engine.use_dma, one, typed, g.blocks, g.threads, g.lds, stream, sp); break;
-    case ScanKernel::Distinct: case ScanKernel::GroupDistinct: case ScanKernel::Counts: case ScanKernel::GroupCounts: break;      // (launched with their own parameter block: run_aggregation)
+    case ScanKernel::Distinct: case ScanKernel::GroupDistinct: case ScanKernel::Counts: case ScanKernel::GroupCounts:
+    case ScanKernel::Collect: case ScanKernel::GroupCollect: break;      // (launched with their own parameter block: run_aggregation)
   }
 }
 // What the phases of execute_impl share about one query
@@ -3388,6 +3419,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   const int pass_function = set_pass_function(q->flags);
   const char* const pass_name = pass_function == PG_AGG_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT";
   lw.counts_pass = distinct_pass && pass_function == PG_AGG_PERCENTILE;
+  lw.collect_pass = distinct_pass && (q->flags & kQueryCollectPass) != 0;
   std::vector<int> distinct_of((size_t)std::max(na, 1), -1);      // per aggregation: its bitset (index into lw.distinct_slots)
   std::vector<int> distinct_key_cards;
   for (int a = 0; a < na; ++a) {
@@ -3399,7 +3431,9 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     if (distinct_pass && ag.function == pass_function) {
       // a column of the bitset / counts pass: its dictId stream, one bitset / counter vector per distinct column (the same column twice shares it)
       if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
-      if (seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT) return fail(PG_ERR_UNSUPPORTED, "%s on raw column %s", pass_name, seg->cols[(size_t)ag.column].name.c_str());
+      // (the collect pass: a raw column's value bytes, one list per distinct column)
+      if (lw.collect_pass ? seg->cols[(size_t)ag.column].encoding != PG_FWD_RAW_FIXED_BYTE : seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT)
+        return fail(PG_ERR_UNSUPPORTED, "%s on %s column %s", pass_name, lw.collect_pass ? "dictionary" : "raw", seg->cols[(size_t)ag.column].name.c_str());
       r.add_projected(ag.column);
       const int s = slot_for(&lw, seg, ag.column, false);
       if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
@@ -3622,7 +3656,8 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
   const bool is_counts = k.kernel == ScanKernel::Counts || k.kernel == ScanKernel::GroupCounts;      // 32-bit counters: a row is `cardinality` words
   const bool is_distinct = k.kernel == ScanKernel::Distinct || k.kernel == ScanKernel::GroupDistinct || is_counts;
-  if (k.kernel == ScanKernel::Hist || is_distinct) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / bitset kernels keep the area in their dynamic LDS, behind the counters / bitsets)
+  const bool is_collect = k.kernel == ScanKernel::Collect || k.kernel == ScanKernel::GroupCollect;      // raw columns: lists of order images, sorted behind the kernel
+  if (k.kernel == ScanKernel::Hist || is_distinct || is_collect) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / bitset kernels keep the area in their dynamic LDS, behind the counters / bitsets)
   // The bitset pass: one zeroed bitset per DISTINCTCOUNT column in the context's scratch -- under GROUP BY a matrix of one row per raw group id --
   // and one copy of all of them behind the kernel.  Behind the last row: room for the dictIds the column's WIDTH admits beyond its cardinality,
   // so that a forward index that breaks the dictionary's bound cannot make the kernel write outside the allocation.
@@ -3662,6 +3697,50 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       distinct_host.resize(lw.distinct_slots.size());
       for (size_t c = 0; c < lw.distinct_slots.size(); ++c) distinct_host[c].resize((size_t)distinct_rows * (size_t)dp.cols[c].words);
     }
+  }
+  // The collect pass: one list of `capacity` 64-bit images per raw column in the same scratch (GROUP BY: the docs' raw group ids beside them),
+  // the sort's second buffers, the run arrays and rocPRIM's scratch behind them.  The capacity is the segment's docs -- what the plan-time
+  // bound was priced with (plan_collect_bytes) -- so no reservation of a matching doc can fail; the kernel checks every one all the same.
+  CollectParams cp;
+  struct CollectLayout { size_t images[kMaxAggCols], work, heads, position, rows, rows_a, rows_b, temp, temp_bytes, total; } cl{};
+  unsigned long long collect_head[3] = {0ull, 0ull, 0ull};      // what the kernel leaves in the scratch's first line: the cursor, the flag word, (later) a column's runs
+  constexpr size_t kCollectHeadBytes = 256;
+  size_t collect_capacity = 0;
+  if (is_collect) {
+    memset(&cp, 0, sizeof(cp));
+    for (int card : distinct_key_cards) distinct_rows *= card;
+    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "%s GROUP BY over %lld raw keys", pass_name, distinct_rows);
+    const bool grouped = !lw.distinct_key_slots.empty();
+    collect_capacity = (size_t)std::max<long long>((long long)seg->num_docs, 1);
+    HIP_TRY(collect_sort_temp_bytes(collect_capacity, grouped, &cl.temp_bytes));
+    auto take = [&cl](size_t bytes) { const size_t at = cl.total; cl.total += (bytes + 255) & ~(size_t)255; return at; };
+    (void)take(kCollectHeadBytes);
+    cp.d.num_cols = (int32_t)lw.distinct_slots.size();
+    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) cl.images[c] = take(collect_capacity * 8);
+    cl.work = take(collect_capacity * 8);
+    cl.heads = take(collect_capacity * 4);
+    cl.position = take(collect_capacity * 4);
+    if (grouped) { cl.rows = take(collect_capacity * 4); cl.rows_a = take(collect_capacity * 4); cl.rows_b = take(collect_capacity * 4); }
+    cl.temp = take(std::max<size_t>(cl.temp_bytes, 256));
+    st = ensure_distinct(seg, ctx, cl.total / 4); if (st != PG_OK) return st;
+    uint8_t* const base = reinterpret_cast<uint8_t*>(ctx->d_distinct);
+    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+      const DevColumn& dc = pl.cols[lw.distinct_slots[c]];
+      cp.fwd[c] = dc.fwd; cp.vkind[c] = dc.vkind;
+      cp.out_images[c] = reinterpret_cast<unsigned long long*>(base + cl.images[c]);
+    }
+    cp.out_rows = grouped ? reinterpret_cast<uint32_t*>(base + cl.rows) : nullptr;
+    cp.cursor = reinterpret_cast<unsigned long long*>(base);
+    cp.flags = reinterpret_cast<uint32_t*>(base + 8);
+    cp.capacity = (unsigned long long)collect_capacity;
+    cp.d.num_keys = (int32_t)lw.distinct_key_slots.size();
+    uint32_t mult = 1;
+    for (size_t g = 0; g < lw.distinct_key_slots.size(); ++g) {
+      const DevColumn& kc = pl.cols[lw.distinct_key_slots[g]];
+      cp.d.keys[g].fwd = kc.fwd; cp.d.keys[g].bits = kc.bits; cp.d.keys[g].mult = mult;
+      mult *= (uint32_t)distinct_key_cards[g];
+    }
+    HIP_TRY(hipMemsetAsync(base, 0, kCollectHeadBytes, ctx->stream));
   }
   sp.sparse_lanes = g_engine.sparse_lanes;
   sp.fold_one_counter = g_engine.fold_one_counter;
@@ -3706,9 +3785,13 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     *ctx->h_partial = g;
   } else {
     // (the bitsets' copy follows the kernel on the stream: the polled record does not cover it)
-    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm || is_distinct;
+    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm || is_distinct || is_collect;
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    if (is_distinct) {
+    if (is_collect) {
+      cp.d.scan = sp;
+      if (k.kernel == ScanKernel::Collect) launch_scan_collect(grid.blocks, grid.lds, ctx->stream, cp);
+      else launch_group_collect(grid.blocks, grid.lds, ctx->stream, cp);
+    } else if (is_distinct) {
       dp.scan = sp;
       if (k.kernel == ScanKernel::Distinct) launch_scan_distinct(grid.distinct_lds, grid.blocks, grid.lds, ctx->stream, dp);
       else if (k.kernel == ScanKernel::GroupDistinct) launch_group_distinct(grid.blocks, grid.lds, ctx->stream, dp);
@@ -3721,6 +3804,10 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       distinct_copy.armed = true;
       for (size_t c = 0; c < distinct_host.size(); ++c)
         if (!distinct_host[c].empty()) HIP_TRY(hipMemcpyAsync(distinct_host[c].data(), ctx->d_distinct + distinct_first[c], distinct_host[c].size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (is_collect) {
+      distinct_copy.armed = true;
+      HIP_TRY(hipMemcpyAsync(collect_head, ctx->d_distinct, 16, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (!folded) {
       finalize_partials_kernel<<<dim3(1), dim3(kBlockThreads), 0, ctx->stream>>>(ctx->d_partials, blocks, g_engine.direct_result ? ctx->h_record_dev : nullptr, seq,
@@ -3798,6 +3885,67 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       sets->distinct.push_back(std::move(ds));
     }
     out->internal = sets.release();
+  }
+  if (is_collect) {
+    // (the stream was synchronised: the cursor and the flag word are in collect_head)  The cursor's final value is the filter's match count.
+    distinct_copy.armed = false;
+    struct Trim { pg_segment* seg; ExecCtx* ctx; ~Trim() { trim_distinct(seg, ctx); } } trim_on_exit{seg, ctx};
+    const unsigned long long n = collect_head[0];
+    if ((uint32_t)collect_head[1] & kCollectOverflow) return fail(PG_ERR_INTERNAL, "%s: the value lists overflowed their capacity of %zu docs (cursor %llu)", pass_name, collect_capacity, n);
+    if (n != fp.count) return fail(PG_ERR_INTERNAL, "%s: %llu values were collected for %llu matching docs", pass_name, n, (unsigned long long)fp.count);
+    if (out) {
+      const bool grouped = !lw.distinct_key_slots.empty();
+      uint8_t* const base = reinterpret_cast<uint8_t*>(ctx->d_distinct);
+      int row_bits = 1;
+      while (row_bits < 32 && (1ll << row_bits) < distinct_rows) ++row_bits;
+      std::vector<ValueList> per_col(lw.distinct_slots.size());
+      std::vector<uint32_t> first;
+      for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+        ValueList& vl = per_col[c];
+        vl.grouped_in_transit = grouped;
+        if (n == 0) continue;
+        CollectSort cs;
+        cs.images = cp.out_images[c]; cs.images_work = reinterpret_cast<unsigned long long*>(base + cl.work);
+        cs.rows = cp.out_rows; cs.rows_a = reinterpret_cast<uint32_t*>(base + cl.rows_a); cs.rows_b = reinterpret_cast<uint32_t*>(base + cl.rows_b);
+        cs.row_bits = row_bits;
+        cs.heads = reinterpret_cast<uint32_t*>(base + cl.heads); cs.position = reinterpret_cast<uint32_t*>(base + cl.position);
+        cs.num_runs = reinterpret_cast<uint32_t*>(base + 16);
+        cs.temp = base + cl.temp; cs.temp_bytes = std::max<size_t>(cl.temp_bytes, 256);
+        CollectRuns runs;
+        HIP_TRY(collect_sort_runs(cs, (size_t)n, seg->num_cus, ctx->stream, &runs));
+        uint32_t num_runs = 0;
+        HIP_TRY(hipMemcpyAsync(&num_runs, cs.num_runs, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (num_runs == 0u || (unsigned long long)num_runs > n) return fail(PG_ERR_INTERNAL, "%s: %u runs in a list of %llu values", pass_name, num_runs, n);
+        // only the runs cross the bus: their images, the index of their first entry and (GROUP BY) their raw group ids
+        vl.value_bits.resize(num_runs); first.resize(num_runs);
+        HIP_TRY(hipMemcpyAsync(vl.value_bits.data(), runs.images, (size_t)num_runs * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(first.data(), runs.first, (size_t)num_runs * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (grouped) { vl.run_rows.resize(num_runs); HIP_TRY(hipMemcpyAsync(vl.run_rows.data(), runs.rows, (size_t)num_runs * 4, hipMemcpyDeviceToHost, ctx->stream)); }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        const bool floating = cp.vkind[c] == kValF64 || cp.vkind[c] == kValF32;
+        vl.counts.resize(num_runs);
+        for (uint32_t j = 0; j < num_runs; ++j) {
+          vl.value_bits[j] = (int64_t)rank_image_value_bits((unsigned long long)vl.value_bits[j], floating);
+          vl.counts[j] = (j + 1 < num_runs ? first[j + 1] : (uint32_t)n) - first[j];
+        }
+      }
+      std::unique_ptr<ResultInternal> lists(new ResultInternal());
+      for (int a = na - 1; a >= 0; --a) {      // (the last aggregation on a column takes the runs themselves, earlier ones on the same column a copy)
+        const int dc = distinct_of[(size_t)a];
+        if (dc < 0) continue;
+        bool again = false;
+        for (int b = 0; b < a; ++b) again |= distinct_of[(size_t)b] == dc;
+        ValueList vl;
+        if (again) vl = per_col[(size_t)dc]; else vl = std::move(per_col[(size_t)dc]);
+        vl.aggregation = a;
+        vl.offsets = {0, vl.value_bits.size()};
+        // aggregation only: PERCENTILE's count is the list's length (the docs aggregated: convert put it there), DISTINCTCOUNT's the number of runs
+        if (!grouped && pass_function == PG_AGG_DISTINCTCOUNT) out->aggregations[a].count = (int64_t)vl.value_bits.size();
+        lists->values.push_back(std::move(vl));
+      }
+      out->internal = lists.release();
+    }
   }
   if (is_distinct) trim_distinct(seg, ctx);
   if (out && k.kernel == ScanKernel::PrivateFsm) {
@@ -5227,6 +5375,62 @@ static bool has_distinct(const pg_query* q) {
   return false;
 }
 static pg_status check_ordinary_query(const pg_segment* segment, const pg_query* query);
+// ---- PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns: the collect pass (pg_scan_collect.h) ----
+// A raw (no-dictionary) column has no dictId to count or to set a bit for: the pass writes the order image of every matching doc's value into a
+// list per column, sorts it and run-length encodes it (run_aggregation); the runs are pg_result_value_counts' answer.  The query runs exactly as
+// the dictionary forms do -- the ordinary query, then the pass behind the same filter, or the pass alone -- with kQueryCollectPass set beside the
+// pass's own flag.  A query's PERCENTILE / DISTINCTCOUNT columns are all raw or all dictionary-encoded.
+// The plan-time bound of the lists: every doc could match (pg_query_check knows no better, and pg_execute must agree with it).
+static pg_status plan_collect_bytes(const pg_segment* seg, const char* function, size_t columns, bool grouped) {
+  const unsigned long long bytes = (unsigned long long)std::max<int64_t>(seg->num_docs, 0) * (16ull * (unsigned long long)columns + (grouped ? 8ull : 0ull));
+  if (bytes > PG_COLLECT_MAX_BYTES)
+    return fail(PG_ERR_UNSUPPORTED, "%s value lists of %llu bytes over raw columns exceed PG_COLLECT_MAX_BYTES (%llu) -- CPU plan", function, bytes, (unsigned long long)PG_COLLECT_MAX_BYTES);
+  if (bytes > g_engine.group_table_bytes)
+    return fail(PG_ERR_UNSUPPORTED, "%s value lists of %llu bytes over raw columns exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", function, bytes, (unsigned long long)g_engine.group_table_bytes);
+  return PG_OK;
+}
+// A raw column the pass can read: fixed-width numeric values.  (pg_segment_open keeps nothing else resident -- chunk-compressed, STRING and BYTES
+// columns are refused there -- so this is a safety net behind it.)
+static pg_status plan_collect_column(const ColumnDev& col, const char* function) {
+  // The pass is opt-in (PINOT_GPU_COLLECT=1): a deployment that has not asked for it sees the decline it has always seen, and its plans do not change
+  // under it -- the lists cost up to 16 bytes of HBM per doc and column for the length of a query, which the dictionary forms never did.
+  if (!g_engine.collect)
+    return fail(PG_ERR_UNSUPPORTED, "%s on raw (no-dictionary) column %s: the collect pass is off (PINOT_GPU_COLLECT=1 turns it on) -- CPU plan", function, col.name.c_str());
+  if (col.encoding != PG_FWD_RAW_FIXED_BYTE || col.stored_type < PG_TYPE_INT || col.stored_type > PG_TYPE_DOUBLE || col.d_fwd == nullptr)
+    return fail(PG_ERR_UNSUPPORTED, "%s on column %s: neither dictionary-encoded nor raw fixed-width INT / LONG / FLOAT / DOUBLE -- CPU plan", function, col.name.c_str());
+  return PG_OK;
+}
+// The pass's lists -> the result's.  Aggregation only: they are final.  GROUP BY: the runs of all raw group ids, cut into the rows of the groups the
+// ordinary query reports (group_ids: ascending raw ids, key kind 0); a row's count is its list's length (PERCENTILE) or its runs (DISTINCTCOUNT).
+static pg_status finish_value_lists(const pg_query* q, pg_result* out, ResultInternal* got, int function) {
+  const int na = q->num_aggregations;
+  if (q->num_group_by == 0) return PG_OK;
+  const int num_groups = out->num_groups;
+  for (ValueList& m : got->values) {
+    if (!m.grouped_in_transit) return fail(PG_ERR_INTERNAL, "a value list without group ids under GROUP BY");
+    ValueList cut;
+    cut.aggregation = m.aggregation; cut.rows = num_groups;
+    cut.offsets.reserve((size_t)num_groups + 1);
+    cut.offsets.push_back(0);
+    const size_t num_runs = m.value_bits.size();
+    size_t r = 0;
+    for (int k = 0; k < num_groups; ++k) {
+      const uint32_t row = (uint32_t)out->group_ids[k];
+      if (r < num_runs && m.run_rows[r] < row) return fail(PG_ERR_INTERNAL, "values of raw group id %u, which the ordinary query does not report", m.run_rows[r]);
+      int64_t docs = 0, runs = 0;
+      for (; r < num_runs && m.run_rows[r] == row; ++r, ++runs) docs += m.counts[r];
+      cut.offsets.push_back(r);
+      pg_agg_value* v = &out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation];
+      memset(v, 0, sizeof(*v));
+      empty_agg_value(v, function == PG_AGG_PERCENTILE ? docs : runs);
+    }
+    if (r != num_runs) return fail(PG_ERR_INTERNAL, "values of raw group id %u, which the ordinary query does not report", m.run_rows[r]);
+    // (the runs are already in the rows' order: only the offsets are new)
+    cut.value_bits = std::move(m.value_bits); cut.counts = std::move(m.counts);
+    m = std::move(cut);
+  }
+  return PG_OK;
+}
 struct DistinctPlan {
   std::vector<pg_aggregation> base_aggs, pass_aggs;
   pg_query base, pass;
@@ -5243,7 +5447,7 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
   const bool null_handling = (q->flags & PG_QUERY_NULL_HANDLING) != 0;
   if (na < 0 || ng < 0 || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
   if (q->num_filter_nodes > 0 && (!q->filter || !q->predicates)) return fail(PG_ERR_INVALID_ARGUMENT, "filter nodes without predicates");
-  std::vector<int> distinct_cols, projected;
+  std::vector<int> distinct_cols, raw_cols, projected;
   auto project = [&](int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); };
   bool only_distinct_and_count = true, nullable_input = false;
   for (int a = 0; a < na; ++a) {
@@ -5257,13 +5461,17 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
     nullable_input |= seg->cols[(size_t)ag.column].d_null_bitmap != nullptr;
     if (ag.function != PG_AGG_DISTINCTCOUNT) { only_distinct_and_count = false; continue; }
     const ColumnDev& col = seg->cols[(size_t)ag.column];
-    if (col.encoding != PG_FWD_FIXED_BIT_DICT)
-      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on raw (no-dictionary) column %s: the reference keeps a hash set of values there -- CPU plan", col.name.c_str());
+    // a raw column: its values are collected, sorted and run-length encoded (the collect pass); a dictionary column: its dictId bitset
+    const bool raw = col.encoding != PG_FWD_FIXED_BIT_DICT;
+    if (raw) { const pg_status cst = plan_collect_column(col, "DISTINCTCOUNT"); if (cst != PG_OK) return cst; }
     if (null_handling && col.d_null_bitmap != nullptr)
       return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on column %s, which carries a null value vector, under null handling -- CPU plan", col.name.c_str());
-    if (std::find(distinct_cols.begin(), distinct_cols.end(), ag.column) == distinct_cols.end()) distinct_cols.push_back(ag.column);
+    std::vector<int>& into = raw ? raw_cols : distinct_cols;
+    if (std::find(into.begin(), into.end(), ag.column) == into.end()) into.push_back(ag.column);
   }
-  if ((int)distinct_cols.size() > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d DISTINCTCOUNT columns", kMaxAggCols);
+  if (!raw_cols.empty() && !distinct_cols.empty())
+    return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on raw column %s and dictionary column %s in one query -- CPU plan", seg->cols[(size_t)raw_cols[0]].name.c_str(), seg->cols[(size_t)distinct_cols[0]].name.c_str());
+  if ((int)(distinct_cols.size() + raw_cols.size()) > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d DISTINCTCOUNT columns", kMaxAggCols);
   // the bitset kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it
   bool match_all = q->num_filter_nodes == 0;
   for (int n = 0; n < q->num_filter_nodes; ++n) {
@@ -5322,8 +5530,14 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
   plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
   plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
   plan->pass.flags |= kQueryDistinctPass;
+  if (!raw_cols.empty()) {
+    const pg_status cst = plan_collect_bytes(seg, "DISTINCTCOUNT", raw_cols.size(), ng > 0);
+    if (cst != PG_OK) return cst;
+    plan->pass.flags |= kQueryCollectPass;
+  }
   // the dictionary answers under the conditions of the MIN / MAX dictionary path (answer_from_metadata): every function of the query that way
-  plan->from_dictionary = ng == 0 && match_all && !(null_handling && nullable_input);
+  // (a raw column has no dictionary to read: it is always scanned)
+  plan->from_dictionary = ng == 0 && match_all && !(null_handling && nullable_input) && raw_cols.empty();
   for (int a = 0; a < na && plan->from_dictionary; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
     plan->from_dictionary = ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT ||
@@ -5372,6 +5586,15 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
   out->device_ms += pass.device_ms;
   if (pass.dominant_kernel_ms >= out->dominant_kernel_ms) { out->dominant_kernel_ms = pass.dominant_kernel_ms; out->dominant_kernel = pass.dominant_kernel; }
   if (!got) { pg_result_free(&pass); pg_result_free(out); return fail(PG_ERR_INTERNAL, "the DISTINCTCOUNT pass returned no sets"); }
+  if (!got->values.empty()) {
+    // raw columns: sorted runs instead of bitsets
+    if (q->num_group_by == 0) for (const ValueList& vl : got->values) out->aggregations[vl.aggregation] = pass.aggregations[vl.aggregation];
+    pg_result_free(&pass);
+    st = finish_value_lists(q, out, got.get(), PG_AGG_DISTINCTCOUNT);
+    if (st != PG_OK) { pg_result_free(out); return st; }
+    out->internal = got.release();
+    return PG_OK;
+  }
   if (q->num_group_by == 0) {
     for (const DistinctSet& ds : got->distinct) out->aggregations[ds.aggregation] = pass.aggregations[ds.aggregation];
     out->internal = got.release();
@@ -5430,7 +5653,7 @@ static pg_status plan_percentile(const pg_segment* seg, const pg_query* q, Perce
   const bool null_handling = (q->flags & PG_QUERY_NULL_HANDLING) != 0;
   if (na < 0 || ng < 0 || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
   if (q->num_filter_nodes > 0 && (!q->filter || !q->predicates)) return fail(PG_ERR_INVALID_ARGUMENT, "filter nodes without predicates");
-  std::vector<int> pct_cols, projected;
+  std::vector<int> pct_cols, raw_cols, projected;
   auto project = [&](int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); };
   bool only_percentile_and_count = true;
   for (int a = 0; a < na; ++a) {
@@ -5444,13 +5667,17 @@ static pg_status plan_percentile(const pg_segment* seg, const pg_query* q, Perce
     project(ag.column);
     if (ag.function != PG_AGG_PERCENTILE) { only_percentile_and_count = false; continue; }
     const ColumnDev& col = seg->cols[(size_t)ag.column];
-    if (col.encoding != PG_FWD_FIXED_BIT_DICT)
-      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE on raw (no-dictionary) column %s: the value list has no dictId form there -- CPU plan", col.name.c_str());
+    // a raw column: its values are collected, sorted and run-length encoded (the collect pass); a dictionary column: its dictId counters
+    const bool raw = col.encoding != PG_FWD_FIXED_BIT_DICT;
+    if (raw) { const pg_status cst = plan_collect_column(col, "PERCENTILE"); if (cst != PG_OK) return cst; }
     if (null_handling && col.d_null_bitmap != nullptr)
       return fail(PG_ERR_UNSUPPORTED, "PERCENTILE on column %s, which carries a null value vector, under null handling -- CPU plan", col.name.c_str());
-    if (std::find(pct_cols.begin(), pct_cols.end(), ag.column) == pct_cols.end()) pct_cols.push_back(ag.column);
+    std::vector<int>& into = raw ? raw_cols : pct_cols;
+    if (std::find(into.begin(), into.end(), ag.column) == into.end()) into.push_back(ag.column);
   }
-  if ((int)pct_cols.size() > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d PERCENTILE columns", kMaxAggCols);
+  if (!raw_cols.empty() && !pct_cols.empty())
+    return fail(PG_ERR_UNSUPPORTED, "PERCENTILE on raw column %s and dictionary column %s in one query -- CPU plan", seg->cols[(size_t)raw_cols[0]].name.c_str(), seg->cols[(size_t)pct_cols[0]].name.c_str());
+  if ((int)(pct_cols.size() + raw_cols.size()) > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d PERCENTILE columns", kMaxAggCols);
   // the counts kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it
   for (int n = 0; n < q->num_filter_nodes; ++n) {
     if (q->filter[n].op != PG_FILTER_LEAF) continue;
@@ -5512,6 +5739,11 @@ static pg_status plan_percentile(const pg_segment* seg, const pg_query* q, Perce
   plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
   plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
   plan->pass.flags |= kQueryCountsPass;
+  if (!raw_cols.empty()) {
+    const pg_status cst = plan_collect_bytes(seg, "PERCENTILE", raw_cols.size(), ng > 0);
+    if (cst != PG_OK) return cst;
+    plan->pass.flags |= kQueryCollectPass;
+  }
   plan->pass_alone = ng == 0 && only_percentile_and_count;
   if (!plan->pass_alone) plan->pass.flags |= PG_QUERY_STATS_UPPER_BOUND_OK;      // (the ordinary query brings the statistics)
   pg_status st = plan->pass_alone ? PG_OK : check_ordinary_query(seg, &plan->base);
@@ -5560,6 +5792,13 @@ static pg_status execute_percentile(pg_segment* seg, const pg_query* q, pg_resul
   pg_result_free(&pass);
   auto give_up = [&](const char* what) { pg_result_free(out); memset(out, 0, sizeof(*out)); return fail(PG_ERR_INTERNAL, "%s", what); };
   if (!got) return give_up("the PERCENTILE pass returned no counters");
+  if (!got->values.empty()) {
+    // raw columns: the pass's sorted runs are the list (aggregation only: convert left the docs aggregated in every PERCENTILE's count)
+    st = finish_value_lists(q, out, got.get(), PG_AGG_PERCENTILE);
+    if (st != PG_OK) { pg_result_free(out); memset(out, 0, sizeof(*out)); return st; }
+    out->internal = got.release();
+    return PG_OK;
+  }
   // the dense rows -> (dictId, count) pairs; GROUP BY: only the rows of the groups the ordinary query reports (group_ids: ascending raw ids, key kind 0)
   std::unique_ptr<ResultInternal> lists(new ResultInternal());
   const bool grouped = q->num_group_by > 0;
@@ -6511,6 +6750,24 @@ pg_status pg_result_percentile_counts(const pg_result* result, int32_t aggregati
   *out_dict_ids = cl->dict_ids.data() + first;
   *out_counts = cl->counts.data() + first;
   *out_num = (int32_t)(cl->offsets[row + 1] - first);
+  return PG_OK;
+}
+
+pg_status pg_result_value_counts(const pg_result* result, int32_t aggregation, int32_t group_row, const int64_t** out_value_bits, const uint32_t** out_counts, int32_t* out_num) {
+  if (!result || !out_value_bits || !out_counts || !out_num) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  *out_value_bits = nullptr; *out_counts = nullptr; *out_num = 0;
+  const ResultInternal* lists = static_cast<const ResultInternal*>(result->internal);
+  if (aggregation < 0 || aggregation >= result->num_aggregations) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d out of range", aggregation);
+  const ValueList* vl = nullptr;
+  if (lists) for (const ValueList& l : lists->values) if (l.aggregation == aggregation) vl = &l;
+  if (!vl) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d is not a PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on a raw column", aggregation);
+  const bool grouped = result->group_aggregations != nullptr;
+  if (grouped ? (group_row < 0 || group_row >= result->num_groups || group_row >= vl->rows) : group_row != -1)
+    return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
+  const size_t row = grouped ? (size_t)group_row : 0, first = vl->offsets[row];
+  *out_value_bits = vl->value_bits.data() + first;
+  *out_counts = vl->counts.data() + first;
+  *out_num = (int32_t)(vl->offsets[row + 1] - first);
   return PG_OK;
 }
 

@@ -119,6 +119,33 @@ int waves_scan_counts(bool lds_tier);
 void launch_group_counts(int blocks, size_t lds, hipStream_t stream, const DistinctParams& dp);
 int waves_group_counts();
 
+// scan_collect_kernel: PERCENTILE / DISTINCTCOUNT of up to kMaxAggCols raw columns -- the matching docs' order images compacted into one list
+// per column (workgroups of 256; `lds`: the filter's set area + the reduction scratch) -- pg_scan_collect.h
+void launch_scan_collect(int blocks, size_t lds, hipStream_t stream, const CollectParams& cp);
+int waves_scan_collect();
+// group_collect_kernel: the same under GROUP BY, every doc's raw group id beside its images
+void launch_group_collect(int blocks, size_t lds, hipStream_t stream, const CollectParams& cp);
+int waves_group_collect();
+// One column's list -> its sorted runs, on `stream`, nothing synchronised: rocPRIM radix sort (GROUP BY: stable by image carrying the row, then
+// stable by row over row_bits bits), collect_run_heads_kernel, rocPRIM inclusive scan, collect_run_compact_kernel.
+struct CollectSort {
+  unsigned long long* images;        // [n] in: the list (spent afterwards)
+  unsigned long long* images_work;   // [n] scratch
+  const uint32_t* rows;              // [n] in, kept: the docs' raw group ids, or nullptr without GROUP BY
+  uint32_t *rows_a, *rows_b;         // [n] each, scratch (GROUP BY)
+  int row_bits;                      // bits of the largest raw group id (GROUP BY)
+  uint32_t *heads, *position;        // [n] each, scratch
+  uint32_t* num_runs;                // [1] out
+  void* temp; size_t temp_bytes;     // rocPRIM's scratch: collect_sort_temp_bytes(n) or more
+};
+struct CollectRuns {                 // where the runs are, device pointers into the scratch above: run j of *num_runs
+  unsigned long long* images;        // its order image, ascending (GROUP BY: ascending inside a row)
+  uint32_t* first;                   // the list index of its first entry (its count: the next run's first, or n, minus this)
+  uint32_t* rows;                    // GROUP BY: its raw group id, ascending
+};
+hipError_t collect_sort_temp_bytes(size_t n, bool grouped, size_t* out_bytes);
+hipError_t collect_sort_runs(const CollectSort& s, size_t n, int num_cus, hipStream_t stream, CollectRuns* out);
+
 // scan_private_typed_kernel: lane-private scan for raw / 8-byte aggregated columns (pg_scan_typed.h)
 void launch_scan_private_typed(int agg_cols, int blocks, hipStream_t stream, const ScanParams& p);      // instantiated for 1, 2 and kMaxAggCols slots
 int waves_scan_private_typed(int agg_cols);

@@ -25,23 +25,9 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "pg_device.h"
+#include "pg_order_image.h"
 
 namespace pg {
-
-__device__ __forceinline__ unsigned long long order_image_of_double_bits(unsigned long long b) {
-  if ((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) b = 0x7FF8000000000000ull;      // every NaN is Double.NaN
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-
-__device__ __forceinline__ unsigned long long order_image(const uint8_t* __restrict__ raw, int vkind, long long doc) {
-  if (vkind == kValI32) return (unsigned long long)(long long)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(raw)[doc]) ^ (1ull << 63);
-  if (vkind == kValI64) return __builtin_bswap64(reinterpret_cast<const unsigned long long*>(raw)[doc]) ^ (1ull << 63);
-  if (vkind == kValF32) {
-    const float f = __uint_as_float(__builtin_bswap32(reinterpret_cast<const uint32_t*>(raw)[doc]));
-    return order_image_of_double_bits((unsigned long long)__double_as_longlong((double)f));      // (float -> double is exact)
-  }
-  return order_image_of_double_bits(__builtin_bswap64(reinterpret_cast<const unsigned long long*>(raw)[doc]));
-}
 
 // ---- the hash table: 16-byte slots {image, rank}; kRankEmpty marks a free slot (the one image equal to it travels in a flag of its own) ----
 constexpr unsigned long long kRankEmpty = ~0ull;

@@ -308,6 +308,33 @@ def combine_counts(sql, blocks, key_types=()):
                                                  rc.ctypes.data, C.byref(st)), st)
 
 
+def value_counts_from_device(stored_type, value_bits, counts):
+    """ValueCounts::fromDeviceValues: the runs of a raw column (pg_result_value_counts) -> PERCENTILE's list as (values float64, counts int64);
+    stored_type: _abi.PG_TYPE_*.  Two LONGs that land on one double are one run."""
+    import numpy as np
+    lib = _lib()
+    bits = np.ascontiguousarray(value_bits, dtype=np.int64)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert bits.shape == cnt.shape
+    out_v, out_c = np.zeros(max(len(bits), 1), dtype=np.float64), np.zeros(max(len(bits), 1), dtype=np.int64)
+    lib.ph_value_counts_from_device.restype = C.c_int32
+    lib.ph_value_counts_from_device.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    n = lib.ph_value_counts_from_device(int(stored_type), bits.ctypes.data, cnt.ctypes.data, len(bits), out_v.ctypes.data, out_c.ctypes.data)
+    return out_v[:n], out_c[:n]
+
+
+def value_set_from_device(stored_type, value_bits):
+    """ValueSet::fromDeviceValues: the run values of a raw column -> DISTINCTCOUNT's set as ascending int64 images of the stored type."""
+    import numpy as np
+    lib = _lib()
+    bits = np.ascontiguousarray(value_bits, dtype=np.int64)
+    out = np.zeros(max(len(bits), 1), dtype=np.int64)
+    lib.ph_value_set_from_device.restype = C.c_int32
+    lib.ph_value_set_from_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    n = lib.ph_value_set_from_device(int(stored_type), bits.ctypes.data, len(bits), out.ctypes.data)
+    return out[:n]
+
+
 def execute_sql_datatable(segments, sql, max_execution_threads=0):
     """The DataTable V4 bytes a server would send the broker for `sql` over these segments (combine, then
     InstanceResponseBlock.toDataTable().toBytes(); pinot_amd/csrc/host/datatable_v4.cpp)."""

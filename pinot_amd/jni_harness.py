@@ -192,6 +192,19 @@ class FakeJvm:
         finally:
             self.release(*arrays)
 
+    def execute_with_value_lists(self, handle, spec):
+        """PinotGpuNative.executeWithValueLists: [the Object[PGM_RESULT_ARRAYS] as numpy arrays, the raw columns' run values (int64 value bits), their counts
+        (int32): aggregation * rows + row -> array or None]."""
+        arrays, limit, flags = self.query_arrays(spec)
+        try:
+            out = self.call("executeWithValueLists", C.c_void_p, C.c_int64(handle), *arrays, C.c_int32(limit), C.c_int32(flags))
+            try:
+                return self.to_python(out)
+            finally:
+                self.release(C.c_void_p(out))
+        finally:
+            self.release(*arrays)
+
     def query_check(self, handle, spec):
         arrays, limit, flags = self.query_arrays(spec)
         try:

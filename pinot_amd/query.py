@@ -116,8 +116,8 @@ def not_(child):
 
 
 COUNT, SUM, MIN, MAX, AVG = _abi.PG_AGG_COUNT, _abi.PG_AGG_SUM, _abi.PG_AGG_MIN, _abi.PG_AGG_MAX, _abi.PG_AGG_AVG
-DISTINCTCOUNT = _abi.PG_AGG_DISTINCTCOUNT      # on a dictionary-encoded column: the set of dictIds (AggValue.dict_ids)
-PERCENTILE = _abi.PG_AGG_PERCENTILE            # on a dictionary-encoded column: the value list as (dictIds, counts) (AggValue.dict_id_counts)
+DISTINCTCOUNT = _abi.PG_AGG_DISTINCTCOUNT      # on a dictionary-encoded column: the set of dictIds (AggValue.dict_ids); on a raw column: AggValue.value_counts
+PERCENTILE = _abi.PG_AGG_PERCENTILE            # on a dictionary-encoded column: the value list as (dictIds, counts) (AggValue.dict_id_counts); raw: AggValue.value_counts
 
 
 class QuerySpec:
@@ -187,21 +187,23 @@ class QuerySpec:
 
 
 class AggValue:
-    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max", "dict_ids", "dict_id_counts")
+    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max", "dict_ids", "dict_id_counts", "value_counts")
 
-    def __init__(self, v, dict_ids=None, dict_id_counts=None):
+    def __init__(self, v, dict_ids=None, dict_id_counts=None, value_counts=None):
         self.count, self.sum, self.sum_i64, self.sum_exact, self.min, self.max = (
             int(v.count), float(v.sum), int(v.sum_i64), bool(v.sum_exact), float(v.min), float(v.max))
         self.dict_ids = dict_ids      # DISTINCTCOUNT: the sorted dictIds of the set (numpy int32); None for every other function
         self.dict_id_counts = dict_id_counts      # PERCENTILE: (ascending dictIds int32, their non-zero counts uint32); None for every other function
+        # PERCENTILE / DISTINCTCOUNT on a RAW column: (ascending value bits int64, their non-zero counts uint32) -- pg_result_value_counts; None otherwise
+        self.value_counts = value_counts
 
     def intermediate(self, function):
         """The reference's intermediate result type: COUNT -> Long, SUM/MIN/MAX -> Double, AVG -> (sum, count), DISTINCTCOUNT -> the
         segment's dictId set (the values behind it are what segments merge: dictIds differ from segment to segment)."""
         if function == DISTINCTCOUNT:
-            return self.dict_ids
+            return self.dict_ids if self.value_counts is None else self.value_counts[0]
         if function == PERCENTILE:
-            return self.dict_id_counts
+            return self.dict_id_counts if self.value_counts is None else self.value_counts
         if function == COUNT:
             return self.count
         if function == SUM:
@@ -230,8 +232,23 @@ class Result:
         self.dominant_kernel = _abi.KERNEL_NAMES.get(int(getattr(res, "dominant_kernel", -1)), "")
         self.filter_entries_exact = bool(res.filter_entries_exact)      # stats[1] is the reference's count, not an upper bound
         na = int(res.num_aggregations)
+        def value_counts(a, row):
+            """The sorted runs of a PERCENTILE / DISTINCTCOUNT on a raw column; None when the aggregation is anything else (a dictionary column's
+            forms answer through their own functions: the library says PG_ERR_INVALID_ARGUMENT here)."""
+            if self.functions[a] not in (DISTINCTCOUNT, PERCENTILE):
+                return None
+            the_lib = lib if lib is not None else _abi.load_gpu_library()
+            bits, counts, n = C.POINTER(C.c_int64)(), C.POINTER(C.c_uint32)(), C.c_int32()
+            status = the_lib.pg_result_value_counts(C.byref(res), a, row, C.byref(bits), C.byref(counts), C.byref(n))
+            if status == _abi.PG_ERR_INVALID_ARGUMENT:
+                return None
+            _abi.check(the_lib, status)
+            if not n.value:
+                return np.zeros(0, np.int64), np.zeros(0, np.uint32)
+            return np.ctypeslib.as_array(bits, shape=(n.value,)).copy(), np.ctypeslib.as_array(counts, shape=(n.value,)).copy()
+
         def dict_ids(a, row):
-            if self.functions[a] != DISTINCTCOUNT:
+            if self.functions[a] != DISTINCTCOUNT or raw_lists[(a, row)] is not None:
                 return None
             the_lib = lib if lib is not None else _abi.load_gpu_library()
             words, n = C.POINTER(C.c_uint32)(), C.c_int32()
@@ -240,7 +257,7 @@ class Result:
             return np.flatnonzero(bits).astype(np.int32)
 
         def dict_id_counts(a, row):
-            if self.functions[a] != PERCENTILE:
+            if self.functions[a] != PERCENTILE or raw_lists[(a, row)] is not None:
                 return None
             the_lib = lib if lib is not None else _abi.load_gpu_library()
             ids, counts, n = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint32)(), C.c_int32()
@@ -249,7 +266,12 @@ class Result:
                 return np.zeros(0, np.int32), np.zeros(0, np.uint32)
             return np.ctypeslib.as_array(ids, shape=(n.value,)).copy(), np.ctypeslib.as_array(counts, shape=(n.value,)).copy()
 
-        self.aggregations = [AggValue(res.aggregations[a], dict_ids(a, -1), dict_id_counts(a, -1)) for a in range(na)] if res.aggregations else []
+        class _Lists(dict):
+            def __missing__(self, key):
+                self[key] = value_counts(*key)
+                return self[key]
+        raw_lists = _Lists()
+        self.aggregations = [AggValue(res.aggregations[a], dict_ids(a, -1), dict_id_counts(a, -1), raw_lists[(a, -1)]) for a in range(na)] if res.aggregations else []
         self.groups = {}
         self.group_id_upper_bound = int(res.group_id_upper_bound)
         self.num_groups_limit_reached = bool(res.num_groups_limit_reached)
@@ -262,7 +284,7 @@ class Result:
             tup = tuple(int(res.group_key_dict_ids[g * ng + j]) for j in range(ng)) if res.group_key_dict_ids else None
             self.group_keys.append(tup)
             gid = int(res.group_ids[g]) if self.group_key_kind == 0 else tup
-            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a], dict_ids(a, g), dict_id_counts(a, g)) for a in range(na)]
+            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a], dict_ids(a, g), dict_id_counts(a, g), raw_lists[(a, g)]) for a in range(na)]
         self.group_ids64 = [int(res.group_ids64[g]) for g in range(int(res.num_groups))] if (self.group_key_kind == 1 and res.group_ids64) else None
 
     def intermediates(self):

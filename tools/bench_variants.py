@@ -512,4 +512,53 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                             "note": "frac / achieved_GBps are on the HOST clock around the whole call (lowering, launch, completion of all 64 segments)"})
         finally:
             [g.close() for g in opened]
+    # ---- PERCENTILE / DISTINCTCOUNT on a RAW column (pg_scan_collect.h) beside the dictionary forms, on the same docs, values and filter ----
+    # 20 M docs (the lists are priced with the docs: 16 bytes each, PG_COLLECT_MAX_BYTES = 1 GiB): `r` is a raw INT column, `d` the same values
+    # dictionary-encoded, f the headline's filter column cut to the same docs.  The sort and the run-length encoding follow the scan kernel on the
+    # stream BEHIND the events that bracket all_kernels_ms: step_ms_host_clock is the figure that holds the whole query.
+    collect_ids = ("collect-percentile", "collect-distinct", "collect-percentile-dictionary", "collect-distinct-dictionary")
+    if any(want(x) for x in collect_ids):
+        import sys
+        tests_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+        if tests_dir not in sys.path:
+            sys.path.insert(0, tests_dir)
+        import raw_value_cases as RC      # the exact numpy model the tests hold the lists to
+        m = int(min(n, 20_000_000))
+        ids = S.synthetic_dict_ids(4242, 0, m, 100000)
+        values = (ids.astype(np.int64) * 5 + 1).astype(np.int32)
+        fm = S.Column.synthetic_uniform("f", m, np.arange(1000, dtype=np.int32), seed=2)
+        cseg = S.SegmentData("variants_collect", m, [S.Column.raw("r", values), S.Column.from_dict_ids("d", (np.arange(100000, dtype=np.int64) * 5 + 1).astype(np.int32), ids), fm])
+        cflt = Q.leaf(Q.Pred.dict_range(2, 0, 100))
+        engine.reinit(PINOT_GPU_COLLECT="1")          # (the pass is opt-in)
+        with engine.open(cseg) as g:
+            match_docs = RC.matching_docs(cseg, Q.QuerySpec([], filter=cflt)) if check else None
+            want_runs = RC.runs_of(values[match_docs]) if check else None
+
+            def raw_model(function):
+                def ok(got):
+                    bits, counts = got.aggregations[0].value_counts
+                    length = int(want_runs[1].astype(np.int64).sum())
+                    return (np.array_equal(bits, want_runs[0]) and np.array_equal(counts, want_runs[1]) and got.stats[0] == length and
+                            got.aggregations[0].count == (length if function == Q.PERCENTILE else len(want_runs[0])))
+                return ok
+
+            def dict_model(function):
+                def ok(got):
+                    want_ids = ((want_runs[0] - 1) // 5).astype(np.int32)
+                    if function == Q.PERCENTILE:
+                        return np.array_equal(got.aggregations[0].dict_id_counts[0], want_ids) and np.array_equal(got.aggregations[0].dict_id_counts[1], want_runs[1])
+                    return np.array_equal(got.aggregations[0].dict_ids, want_ids)
+                return ok
+
+            for vid, function, column, model_of, what in (
+                    ("collect-percentile", Q.PERCENTILE, 0, raw_model, "raw INT column: the matching docs' values collected, sorted (rocPRIM radix sort) and run-length encoded"),
+                    ("collect-distinct", Q.DISTINCTCOUNT, 0, raw_model, "raw INT column: the same list, its run values are the set"),
+                    ("collect-percentile-dictionary", Q.PERCENTILE, 1, dict_model, "the same values dictionary-encoded (100 000 dictIds: scan_counts_kernel's HBM tier)"),
+                    ("collect-distinct-dictionary", Q.DISTINCTCOUNT, 1, dict_model, "the same values dictionary-encoded (scan_distinct_kernel)")):
+                if want(vid):
+                    col = cseg.columns[column]
+                    report(vid, "PERCENTILE / DISTINCTCOUNT on a raw column beside the dictionary form, same docs and filter; " + what,
+                           "SELECT %s(%s) WHERE f < 100 (10%%) over %d docs" % ("PERCENTILE50" if function == Q.PERCENTILE else "DISTINCTCOUNT", col.name, m), m, B(col) + B(fm), g, cseg,
+                           Q.QuerySpec([(function, column)], filter=cflt), model_check=model_of(function) if check else None)
+        engine.reinit(PINOT_GPU_COLLECT=None)
     return out

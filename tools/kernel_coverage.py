@@ -440,6 +440,41 @@ def main():
                         ran += 1
             finally:
                 engine.reinit(**{k: flipped.get(k) for k in env})
+    # ---- PERCENTILE / DISTINCTCOUNT on raw columns (pg_scan_collect.h): scan_collect_kernel, group_collect_kernel behind an ordinary group-by, and the
+    # two run kernels behind either (collect_run_heads_kernel, collect_run_compact_kernel).  The oracle has neither function: the runs are held against
+    # the numpy model of tests/raw_value_cases.py (np.unique(..., return_counts=True) over the docs oracle.filter_bitmap matches, in the order image's
+    # order), every other function against the oracle.  The raw columns' values are build_segment's, made again from the same generator.
+    if only is None or only.search("collect"):
+        import raw_value_cases as RC
+        ids = lambda s, card: S.synthetic_dict_ids(1000 + s, 0, n, card)
+        seg.raw_values = {RI: (ids(10, 1_000_000) - 500_000).astype(np.int32), RL: (ids(11, 1 << 20).astype(np.int64) - (1 << 19)) * ((1 << 20) + 3),
+                          RD: (ids(12, 1 << 20).astype(np.float64) - (1 << 19)) * 0.37}
+        f100 = Q.leaf(Q.Pred.dict_range(F, 0, 100))
+        shapes = (("scan", Q.QuerySpec([(Q.PERCENTILE, RL), (Q.PERCENTILE, RI), (Q.COUNT, -1)], filter=f100), "scan_collect_kernel"),
+                  ("scan-distinct", Q.QuerySpec([(Q.DISTINCTCOUNT, RD), (Q.DISTINCTCOUNT, RI), (Q.DISTINCTCOUNT, RL)], filter=Q.leaf(Q.Pred.dict_set(F, list(range(0, 300, 3)), 1000))), "scan_collect_kernel"),
+                  ("group", Q.QuerySpec([(Q.PERCENTILE, RD), (Q.SUM, V), (Q.PERCENTILE, RI)], filter=Q.leaf(Q.Pred.dict_range(F, 0, 500)), group_by=[B]), "group_collect_kernel"),
+                  ("group-distinct", Q.QuerySpec([(Q.DISTINCTCOUNT, RL), (Q.COUNT, -1)], filter=f100, group_by=[B, C2]), "group_collect_kernel"))
+        engine.reinit(PINOT_GPU_COLLECT="1")          # (the pass is opt-in)
+        try:
+            with engine.open(seg) as g:
+                for sid, spec, family in shapes:
+                    eid = "collect-%s" % sid
+                    if g.check(spec) != 0:
+                        failed.append({"id": eid, "error": "pg_query_check declined"})
+                        continue
+                    want_lists = RC.model(seg, spec)
+                    for rep in range(2):
+                        got = g.execute(spec)
+                        try:
+                            RC.assert_lists_equal(got, spec, want_lists, eid)
+                            RC.assert_other_functions_equal(got, seg, spec)
+                            if not flipped and not spec.group_by:
+                                assert got.dominant_kernel == family, "dominant kernel %s, expected %s" % (got.dominant_kernel, family)
+                        except AssertionError as e:
+                            failed.append({"id": eid, "error": str(e)[:300]})
+                    ran += 1
+        finally:
+            engine.reinit(PINOT_GPU_COLLECT=flipped.get("PINOT_GPU_COLLECT"))
     # ---- the transducer's kernels: byte-function walks, then table walks of the same machines ----
     if only is None or only.search("fsm"):
         count = args.fsm_trees if args.fsm_trees >= 0 else (400 if args.regime == "tiny" else 40)
