@@ -54,7 +54,8 @@ extern "C" {
                             * 5: pg_doc_set_create / release / cardinality, PG_PRED_DOC_SET (upsert / dedup valid-doc sets); no struct layout changed;
                             *    (still 5) PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids: no struct layout changed, one enumerator and one function added;
                             *    (still 5) PG_AGG_PERCENTILE, pg_result_percentile_counts: no struct layout changed, one enumerator and one function added;
-                            *    (still 5) PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns, pg_result_value_counts: no struct layout changed, one function added */
+                            *    (still 5) PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns, pg_result_value_counts: no struct layout changed, one function added;
+                            *    (still 5) PG_DISTINCT_LDS_MAX_DICT_IDS: a diagnostic constant beside PG_PERCENTILE_LDS_MAX_COUNTERS, nothing else */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -254,6 +255,10 @@ typedef enum pg_agg_function {
 /* Diagnostics: the 32-bit counters of all PERCENTILE columns of a query that scan_counts_kernel keeps in LDS when the filter stages no dictId
  * set there (with one: 2048 fewer); above it, or with PINOT_GPU_PERCENTILE_LDS=0, the counters live in HBM. */
 #define PG_PERCENTILE_LDS_MAX_COUNTERS 39036
+/* Diagnostics: the dictIds of all DISTINCTCOUNT columns of a query (every column's bitset rounded up to whole 32-bit words) that
+ * scan_distinct_kernel keeps in LDS when the filter stages no dictId set there (with one: 2048 words = 65536 dictIds fewer); above it, or with
+ * PINOT_GPU_DISTINCT_LDS=0, the bitsets live in HBM. */
+#define PG_DISTINCT_LDS_MAX_DICT_IDS 1277952
 
 typedef struct pg_aggregation {
   int32_t function;            /* pg_agg_function */

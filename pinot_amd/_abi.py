@@ -33,6 +33,7 @@ PG_DISTINCT_GROUP_MAX_BYTES = 1 << 30
 PG_PERCENTILE_GROUP_MAX_BYTES = 1 << 30
 PG_COLLECT_MAX_BYTES = 1 << 30               # PERCENTILE / DISTINCTCOUNT on raw columns: numDocs x (16 x columns + 8 under GROUP BY) bytes
 PG_PERCENTILE_LDS_MAX_COUNTERS = 39036      # scan_counts_kernel's LDS tier without a staged filter set (with one: kSetLdsWords = 2048 fewer)
+PG_DISTINCT_LDS_MAX_DICT_IDS = 1277952      # scan_distinct_kernel's LDS tier without a staged filter set (with one: 65536 dictIds fewer)
 PG_CFG_TIME_KERNELS = 1
 PG_CFG_PROFILE_WAVES = 2
 

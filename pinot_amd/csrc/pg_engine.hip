@@ -3116,6 +3116,8 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
 // scan_counts_kernel's LDS tier: the reduction records of a workgroup of kHistBlockThreads, and the counters that fit beside them without a staged set
 constexpr size_t kCountsRecordBytes = sizeof(BlockPartial) * (kHistBlockThreads / 64) + 16;
 static_assert((kLdsBudget - kCountsRecordBytes) / 4 == PG_PERCENTILE_LDS_MAX_COUNTERS, "include/pinot_gpu.h states the LDS tier's reach");
+// scan_distinct_kernel's LDS tier: the reduction records overlay the bitsets' start (the maximum, not the sum, is the rule), so the whole budget holds bits
+static_assert(kLdsBudget * 8 == PG_DISTINCT_LDS_MAX_DICT_IDS, "include/pinot_gpu.h states the LDS tier's reach");
 struct ScanGrid { int blocks = 1, threads = kBlockThreads; size_t lds = 0, hist_set_off = 0; bool wide = false, distinct_lds = false; };
 // A segment whose tiles all fit the chip at once (one tile per wave: a 10 M-row segment at five waves per SIMD) is latency from end
 // to end -- launch, one round of loads, the hand-off of the workgroups' records to the fold.  Ten waves per workgroup there: 2.5x
@@ -4523,7 +4525,9 @@ static pg_status run_group_by(QueryRun& r) {
     fprintf(stderr, "group-by plan: product %lld, fine partitions %lld (shift %d), 2^%d per coarse -> %lld scatter partitions; partition %d (hash %d typed_direct %d map_based %d "
                     "private_leaves %d dense_ok %d aggs %d docs %d)\n", product, fine_partitions, partition_shift, log2_fine_per_coarse, num_partitions, (int)use_partition,
             hash_plan.kind, (int)typed_direct, (int)map_based, (int)private_leaves, gp.dense_ok, gp.num_group_aggs, seg->num_docs);
-  if (use_partition || !(use_private || typed_direct)) { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
+  // (group_typed_direct_kernel walks EVERY tile and reads the index AND's bitmap there: the tiles the AND did not list must be zero, not what an
+  //  earlier query of this context left in them -- only group_private_kernel goes by the tile list)
+  if (use_partition || typed_direct || !use_private) { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
   if (lw.side != nullptr) {
     const bool wrote = ((use_private && !use_partition) || typed_direct) && gp.scan.tile_list == nullptr;
     for (int l = 0; l < kMaxLeaves; ++l) gp.scan.leaf_out[l] = wrote ? lw.sp_leaf_out[l] : nullptr;
@@ -4766,7 +4770,9 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
     if (prepare_fsm_side(seg, ctx, *side->fsm, side) == PG_OK) lw.side = side;
     else (void)hipGetLastError();
   }
-  lw.raw_set_lean_hint = lw.side == nullptr && raw_set_lean_shape(seg, q, na, ng, want_bitmap, out != nullptr);
+  // (never a value pass: PERCENTILE / DISTINCTCOUNT of ONE raw INT column behind ONE IN list has that shape too, and scan_raw_set_kernel collects nothing --
+  //  the pass's kernels evaluate the lane-private filter, where a raw-set leaf is a pre-pass bitmap)
+  lw.raw_set_lean_hint = lw.side == nullptr && (q->flags & kQuerySetPass) == 0 && raw_set_lean_shape(seg, q, na, ng, want_bitmap, out != nullptr);
   st = lower_filter(seg, ctx, q, &lw); if (st != PG_OK) return st;
   exec_mark(2);
   if (out) memset(out, 0, sizeof(*out));
@@ -5453,7 +5459,11 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
     if (ag.function == PG_AGG_COUNT) {
-      if (null_handling && ag.column >= 0) { project(ag.column); only_distinct_and_count = false; }
+      if (null_handling && ag.column >= 0) {
+        project(ag.column); only_distinct_and_count = false;
+        // (AggregationPlanNode.hasNullValues :130-153 looks at COUNT's argument too: a nullable one keeps the scan)
+        if (ag.column < num_cols_total) nullable_input |= seg->cols[(size_t)ag.column].d_null_bitmap != nullptr;
+      }
       continue;
     }
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);

@@ -55,6 +55,8 @@ def test_the_header_and_its_mirror_agree_on_the_additions():
     assert re.search(r"\bPG_KERNEL_SCAN_DISTINCT\s*=\s*14\b", header) and _abi.KERNEL_NAMES[14] == "scan_distinct_kernel"
     assert re.search(r"\bPG_KERNEL_GROUP_DISTINCT\s*=\s*15\b", header) and _abi.KERNEL_NAMES[15] == "group_distinct_kernel"
     assert re.search(r"#define\s+PG_DISTINCT_GROUP_MAX_BYTES\s+\(1ull << 30\)", header) and _abi.PG_DISTINCT_GROUP_MAX_BYTES == 1 << 30
+    m = re.search(r"#define\s+PG_DISTINCT_LDS_MAX_DICT_IDS\s+(\d+)\b", header)
+    assert m and int(m.group(1)) == _abi.PG_DISTINCT_LDS_MAX_DICT_IDS
     assert "pg_result_distinct_dict_ids" in header and any(name == "pg_result_distinct_dict_ids" for name, _, _ in _abi.ABI_SYMBOLS)
     assert "no struct layout changed, one enumerator and one function added" in header
 

@@ -283,6 +283,69 @@ def test_a_dictionary_beyond_the_lds_tier(engine):
         D.assert_sets_equal(got, seg, spec)
 
 
+# ---- 5b. the tier boundary and the set area beside the bitsets: both sides of every edge of scan_grid's arithmetic (include/pinot_gpu.h
+# PG_DISTINCT_LDS_MAX_DICT_IDS = B, tied to kLdsBudget by a static_assert in pg_engine.hip).  bitsets (whole words, rounded up to 16 bytes) + the
+# staged set area (2048 words = 65536 bits, when the filter has a dictId-set leaf and PINOT_GPU_SET_LDS is on) <= kLdsBudget:
+#   B - 65536      the set is staged behind the bitset and the two add up to the budget exactly;
+#   B - 65536 + 1  the set no longer fits beside the bitset: it stays in memory, the bitset stays in LDS;
+#   B              the bitset alone fits exactly;      B + 1  the HBM tier.
+# Which branch ran is not visible from outside (one kernel id): the test holds the answer on both sides of every edge, with the HIGHEST dictId
+# of the column among the matching docs -- an area that overlaps the last words of the bitset shows there and nowhere else.
+EDGE_SET_BITS = 65536
+EDGE_SET_CARDS = [13, 65536, 65537]          # an ordinary staged set; the set fills the area (the area's own fit edge); 17 bits: never staged
+
+
+@pytest.fixture(scope="module")
+def tier_edge_segment():
+    b, n = _abi.PG_DISTINCT_LDS_MAX_DICT_IDS, 100003
+    rng = np.random.default_rng(43)
+    # columns 0-3: the DISTINCTCOUNT columns; 4-6: the set-leaf columns (5, of exactly 65536, is also the second column of the two-column case)
+    cards = [b - EDGE_SET_BITS, b - EDGE_SET_BITS + 1, b, b + 1] + EDGE_SET_CARDS
+    ids = [rng.integers(0, card, n).astype(np.int32) for card in cards]
+    members = {c: (0, cards[c] // 2, cards[c] - 1) for c in (4, 5, 6)}
+    # docs that carry the highest dictId of DISTINCTCOUNT column j (and of column 5 beside it) AND a member of every IN list: in the first tile, in a
+    # middle tile and in the last, partial, tile
+    for j in range(4):
+        for t, doc in enumerate((7 + 64 * j, 2048 * 23 + 100 + j, n - 1 - j)):
+            ids[j][doc] = cards[j] - 1
+            for c in (4, 5, 6):
+                ids[c][doc] = members[c][(j + t) % 3]
+            if t == 0:
+                ids[5][doc] = cards[5] - 1
+    cols = [S.Column.from_dict_ids("c%d" % i, np.arange(card, dtype=np.int32), ids[i]) for i, card in enumerate(cards)]
+    seg = S.SegmentData("distinct_tier_edges", n, cols)
+    seg.members = members
+    return seg
+
+
+@pytest.mark.parametrize("set_lds", [None, "0"], ids=["sets-staged", "PINOT_GPU_SET_LDS=0"])
+def test_the_tier_boundary_and_the_set_area_beside_the_bitsets(engine, tier_edge_segment, set_lds):
+    seg = tier_edge_segment
+    b = _abi.PG_DISTINCT_LDS_MAX_DICT_IDS
+    assert [seg.columns[c].cardinality for c in range(4)] == [b - EDGE_SET_BITS, b - EDGE_SET_BITS + 1, b, b + 1]
+    words = lambda c: (seg.columns[c].cardinality + 31) // 32
+    assert (words(0) + words(5)) * 32 == b          # the two-column case: word counts that sum to exactly the budget
+    leaf = lambda c: Q.leaf(Q.Pred.dict_set(c, list(seg.members[c]), seg.columns[c].cardinality))
+    engine.reinit(PINOT_GPU_SET_LDS=set_lds)
+    try:
+        with engine.open(seg) as g:
+            cases = [((c,), leaf(s)) for c in range(4) for s in (4, 5, 6)]
+            # two columns that fill the budget: without a set leaf (an exact fit), and with one (the set stays in memory)
+            cases += [((0, 5), Q.leaf(Q.Pred.dict_range(4, 0, 1))), ((5, 0), Q.not_(Q.leaf(Q.Pred.dict_range(4, 1, 13)))), ((0, 5), leaf(4)), ((0, 5), leaf(5))]
+            for cols, flt in cases:
+                spec = Q.QuerySpec([(DC, c) for c in cols] + [(Q.COUNT, -1)], filter=flt)
+                where = "columns %r (%r dictIds)" % (cols, [seg.columns[c].cardinality for c in cols])
+                got = g.execute(spec)
+                assert got.dominant_kernel == SCAN, where
+                D.assert_sets_equal(got, seg, spec, where=where)
+                for a, c in enumerate(cols):
+                    assert seg.columns[c].cardinality - 1 in got.aggregations[a].dict_ids, where
+                assert got.aggregations[len(cols)].count == got.stats[0] > 0
+                D.assert_other_functions_equal(got, seg, spec)
+    finally:
+        engine.reinit(PINOT_GPU_SET_LDS=None)
+
+
 # ---- 6. mixes ----
 def check_mix(g, seg, spec, key_values=None):
     got = g.execute(spec)
@@ -411,6 +474,70 @@ def test_a_nullable_column_is_declined_under_null_handling_only(engine):
         for spec in (Q.QuerySpec([(DC, 0)], filter=flt), Q.QuerySpec([(DC, 1), (Q.COUNT, -1)], filter=flt, null_handling=True)):
             got = g.execute(spec)
             D.assert_sets_equal(got, seg, spec)
+
+
+def test_a_nullable_count_argument_keeps_the_scan_under_null_handling(engine):
+    """AggregationPlanNode.java:98-115: hasNullValues (:130-153) looks at the argument of EVERY aggregation function, COUNT(column)'s included, so
+    `DISTINCTCOUNT(v), COUNT(vn)` without a filter under null handling is scanned -- statistics (docs, 0, docs x 2, docs), the set of the dictIds
+    that occur -- where the same query without null handling is answered from the dictionary (the whole dictionary, (docs, 0, 0, docs)).
+    Found while the model of tests/fuzz_value_cases.py was written against the reference's rule; this is its smallest case."""
+    n = 4099
+    rng = np.random.default_rng(19)
+    nulls = rng.random(n) < 0.1
+    ids = rng.integers(0, 40, n).astype(np.int32) * 2          # the odd dictIds never occur
+    seg = S.SegmentData("distinct_count_nulls", n, [S.Column.dict_encoded("vn", rng.integers(0, 30, n).astype(np.int32)).with_nulls(nulls),
+                                                    S.Column.from_dict_ids("v", np.arange(80, dtype=np.int32), ids)])
+    with engine.open(seg) as g:
+        got = g.execute(Q.QuerySpec([(DC, 1), (Q.COUNT, 0)], null_handling=True))
+        assert got.stats == (n, 0, 2 * n, n), got.stats
+        assert np.array_equal(got.aggregations[0].dict_ids, np.unique(ids)) and got.aggregations[0].count == 40
+        assert got.aggregations[1].count == n - int(nulls.sum())
+        got = g.execute(Q.QuerySpec([(DC, 1), (Q.COUNT, 0)]))
+        assert got.stats == (n, 0, 0, n), got.stats
+        assert np.array_equal(got.aggregations[0].dict_ids, np.arange(80)) and got.aggregations[1].count == n
+
+
+def test_a_typed_group_by_behind_an_index_leaf_sees_no_tiles_of_an_earlier_query(engine):
+    """A GROUP BY that aggregates a raw DOUBLE column runs in group_typed_direct_kernel, which walks every tile and reads the index AND's bitmap
+    there; the AND stores only the tiles that hold a match, so the others must be zeroed first -- they held what an earlier query of the same
+    context had left, and numDocsScanned and the groups counted those docs too.  The smallest case of what tests/test_gpu_fuzz_values.py found
+    (the ordinary query that brings a grouped DISTINCTCOUNT's statistics): query A's postings cover every tile, query B's only the first; B
+    alone, after A, and A and B side by side in one pg_execute_batch."""
+    n = 3 * 2048 + 5
+    rng = np.random.default_rng(29)
+    x = np.ones(n, dtype=np.int32)
+    x[rng.permutation(2048)[:300]] = 0                      # dictId 0: 300 docs, all in the first tile
+    k = rng.integers(0, 5, n).astype(np.int32)
+    rd = rng.integers(-50, 50, n).astype(np.float64) * 0.25
+    seg = S.SegmentData("distinct_index_tiles", n, [S.Column.from_dict_ids("x", np.arange(2, dtype=np.int32), x, with_inverted=True),
+                                                    S.Column.from_dict_ids("k", np.arange(5, dtype=np.int32), k),
+                                                    S.Column.raw_typed("rd", rd),
+                                                    S.Column.from_dict_ids("v", np.arange(200, dtype=np.int32), rng.integers(0, 200, n).astype(np.int32))])
+    leaf = lambda d: Q.leaf(Q.Pred.dict_range(0, d, d + 1, inverted=True))
+    specs = {name: [Q.QuerySpec([(Q.COUNT, -1), (Q.MAX, 2)], filter=leaf(d), group_by=[1]), Q.QuerySpec([(DC, 3), (Q.MAX, 2)], filter=leaf(d), group_by=[1])]
+             for name, d in (("a", 1), ("b", 0))}
+    want = {name: oracle.execute(seg, pair[0]) for name, pair in specs.items()}
+    assert want["a"].stats[0] == n - 300 and want["b"].stats[0] == 300
+
+    def check(got, name, distinct):
+        assert got.stats[0] == want[name].stats[0], (name, got.stats, want[name].stats)
+        if distinct:
+            D.assert_sets_equal(got, seg, specs[name][1])
+            D.assert_other_functions_equal(got, seg, specs[name][1])
+        else:
+            H.assert_results_equal(got, want[name], check_stats=True)
+
+    with engine.open(seg) as g:
+        for _ in range(3):
+            for name in ("a", "b"):
+                for distinct in (0, 1):
+                    check(g.execute(specs[name][distinct]), name, distinct)
+        order = [("a", 0), ("b", 0), ("a", 1), ("b", 1)] * 6
+        for _ in range(2):
+            out = engine.execute_batch([g] * len(order), [specs[name][distinct] for name, distinct in order])
+            for (status, got), (name, distinct) in zip(out, order):
+                assert status == _abi.PG_OK
+                check(got, name, distinct)
 
 
 # ---- 9. the accessor ----

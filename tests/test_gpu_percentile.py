@@ -199,6 +199,70 @@ def test_the_tier_boundary_follows_the_lds_budget(engine, boundary_segment):
             P.assert_counts_equal(g.execute(spec), seg, spec)
 
 
+# ---- 3b. the set area beside the counters: both sides of every edge of scan_grid's arithmetic.  counters (rounded up to 16 bytes) + the staged
+# set area (kSetLdsWords = 2048 words, when the filter has a dictId-set leaf and PINOT_GPU_SET_LDS is on) + the reduction records <= kLdsBudget:
+#   R - K      the set is staged behind the counters and the three add up to the budget exactly;
+#   R - K + 1  the set no longer fits beside the counters: it stays in memory, the counters stay in LDS;
+#   R          the counters alone fit exactly;      R + 1  the HBM tier.
+# Which branch ran is not visible from outside (one kernel id): the test holds the answer on both sides of every edge, with the HIGHEST dictId of
+# every PERCENTILE column among the matching docs -- an area that overlaps the last counters shows there and nowhere else.
+EDGE_K = 2048
+EDGE_A = 20000
+EDGE_SET_CARDS = {"13 values": 13, "65536: the set fills the area": 65536, "65537: 17 bits, never staged": 65537}
+
+
+@pytest.fixture(scope="module")
+def set_edge_segment():
+    r, n = _abi.PG_PERCENTILE_LDS_MAX_COUNTERS, 100003
+    rng = np.random.default_rng(41)
+    # columns 0-4: PERCENTILE columns; 0 + 1 = R - K, 0 + 2 = R - K + 1, 0 + 3 = R, 0 + 4 = R + 1.  columns 5-7: the set-leaf columns.
+    cards = [EDGE_A, r - EDGE_K - EDGE_A, r - EDGE_K - EDGE_A + 1, r - EDGE_A, r - EDGE_A + 1] + list(EDGE_SET_CARDS.values())
+    ids = [rng.integers(0, card, n).astype(np.int32) for card in cards]
+    members = {c: (0, cards[c] // 2, cards[c] - 1) for c in (5, 6, 7)}
+    # docs that carry the highest dictId of PERCENTILE column j AND a member of every IN list (lowest, middle, highest in turn): in the first tile,
+    # in a middle tile and in the last, partial, tile
+    for j in range(5):
+        for t, doc in enumerate((7 + 64 * j, 2048 * 23 + 100 + j, n - 1 - j)):
+            ids[j][doc] = cards[j] - 1
+            for c in (5, 6, 7):
+                ids[c][doc] = members[c][(j + t) % 3]
+    cols = [S.Column.from_dict_ids("c%d" % i, (np.arange(card, dtype=np.int64) * 3 - card).astype(np.int32), ids[i]) for i, card in enumerate(cards)]
+    seg = S.SegmentData("percentile_set_edges", n, cols)
+    seg.members = members
+    return seg
+
+
+@pytest.mark.parametrize("set_lds", [None, "0"], ids=["sets-staged", "PINOT_GPU_SET_LDS=0"])
+def test_the_set_area_beside_the_counters_on_both_sides_of_every_edge(engine, set_edge_segment, set_lds):
+    from oracle import oracle
+    seg = set_edge_segment
+    r = _abi.PG_PERCENTILE_LDS_MAX_COUNTERS
+    totals = {1: r - EDGE_K, 2: r - EDGE_K + 1, 3: r, 4: r + 1}
+    engine.reinit(PINOT_GPU_SET_LDS=set_lds)
+    try:
+        with engine.open(seg) as g:
+            for other, total in totals.items():
+                assert seg.columns[0].cardinality + seg.columns[other].cardinality == total
+                for set_col in (5, 6, 7):
+                    card = seg.columns[set_col].cardinality
+                    assert seg.columns[set_col].bits == (4 if card == 13 else (16 if card == 65536 else 17))
+                    # the IN list leads a small tree once (a second node beside it: the staged set of a tree, not of a single leaf)
+                    leaf = Q.leaf(Q.Pred.dict_set(set_col, list(seg.members[set_col]), card))
+                    for flt in (leaf, Q.or_(leaf, Q.leaf(Q.Pred.dict_range(0, EDGE_A - 1, EDGE_A)))):
+                        spec = Q.QuerySpec([(PCT, 0), (PCT, other), (Q.COUNT, -1)], filter=flt)
+                        where = "total %d, set column of %d" % (total, card)
+                        got = g.execute(spec)
+                        assert got.dominant_kernel == SCAN, where
+                        P.assert_counts_equal(got, seg, spec, where=where)
+                        for a, c in enumerate((0, other)):
+                            assert int(got.aggregations[a].dict_id_counts[0][-1]) == seg.columns[c].cardinality - 1, where
+                        want = oracle.execute(seg, P.without_percentile(spec))
+                        assert got.aggregations[2].count == want.aggregations[2].count == got.stats[0] == got.aggregations[0].count > 0, where
+                        P.assert_other_functions_equal(got, seg, spec)
+    finally:
+        engine.reinit(PINOT_GPU_SET_LDS=None)
+
+
 # ---- 4. skew ----
 @pytest.mark.parametrize("lds", REGIMES)
 def test_every_doc_on_one_dict_id_and_a_filter_that_matches_nothing(engine, lds):

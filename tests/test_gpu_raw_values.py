@@ -323,6 +323,25 @@ def test_mixes_with_other_functions_without_group_by(engine, group_segment):
                 check_others(got, seg, spec)
 
 
+@pytest.mark.parametrize("function", [PCT, DC])
+def test_one_raw_int_column_behind_one_in_list_is_still_collected(engine, group_segment, function):
+    """ONE raw INT value column behind a filter that is ONE raw IN list is the shape scan_raw_set_kernel takes for SUM / MIN / MAX: the value pass
+    must not be lowered for that kernel (it collects nothing: the query failed with "the DISTINCTCOUNT pass returned no sets").  The smallest
+    case of what tests/test_gpu_fuzz_values.py found: alone, beside COUNT(*), under GROUP BY, the IN list on the collected column and on another."""
+    seg = group_segment
+    members = [int(x) for x in np.unique(seg.raw_values[0])[::7]] + [100000]          # present values and an absent one
+    keys = [int(x) for x in np.unique(seg.key_raw)[::3]]
+    with engine.open(seg) as g:
+        for flt in (Q.leaf(Q.Pred.raw_set(0, members)), Q.leaf(Q.Pred.raw_set(9, keys)), Q.leaf(Q.Pred.raw_set(0, members, exclusive=True))):
+            for spec in (Q.QuerySpec([(function, 0)], filter=flt), Q.QuerySpec([(function, 0), (Q.COUNT, -1)], filter=flt),
+                         Q.QuerySpec([(function, 0)], filter=flt, group_by=[5]), Q.QuerySpec([(function, 0), (Q.MAX, 0)], filter=flt)):
+                got = run_twice(g, spec)
+                R.assert_lists_equal(got, spec, R.model(seg, spec))
+                check_others(got, seg, spec)
+                if not spec.group_by and len(spec.aggregations) == 1:
+                    assert got.aggregations[0].count > 0
+
+
 # ---- 5. declines: pg_query_check and pg_execute agree ----
 def declined(g, spec, pattern, status_want=_abi.PG_ERR_UNSUPPORTED):
     for call in (lambda: g.lib.pg_query_check(g.handle, C.byref(spec.c)), None):
