@@ -55,7 +55,8 @@ extern "C" {
                             *    (still 5) PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids: no struct layout changed, one enumerator and one function added;
                             *    (still 5) PG_AGG_PERCENTILE, pg_result_percentile_counts: no struct layout changed, one enumerator and one function added;
                             *    (still 5) PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns, pg_result_value_counts: no struct layout changed, one function added;
-                            *    (still 5) PG_DISTINCT_LDS_MAX_DICT_IDS: a diagnostic constant beside PG_PERCENTILE_LDS_MAX_COUNTERS, nothing else */
+                            *    (still 5) PG_DISTINCT_LDS_MAX_DICT_IDS: a diagnostic constant beside PG_PERCENTILE_LDS_MAX_COUNTERS, nothing else;
+                            *    (still 5) PG_AGG_DISTINCTCOUNTHLL / PG_AGG_HLL(log2m), pg_result_hll_registers: no struct layout changed, one enumerator and one function added */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -225,7 +226,7 @@ typedef enum pg_agg_function {
                                 * unless group_key_kind is 0, group_id_upper_bound <= numGroupsLimit (the limit can never bind), the keys are
                                 * dictionary columns or raw INT / LONG columns keyed by offset, without null docs under PG_QUERY_NULL_HANDLING,
                                 * at most four of them, and the bit matrices fit PG_DISTINCT_GROUP_MAX_BYTES. */
-  PG_AGG_PERCENTILE = 6        /* PercentileAggregationFunction.java (the exact PERCENTILE<p>(col) / PERCENTILE(col, p)) on a dictionary-encoded column of any
+  PG_AGG_PERCENTILE = 6,       /* PercentileAggregationFunction.java (the exact PERCENTILE<p>(col) / PERCENTILE(col, p)) on a dictionary-encoded column of any
                                 * stored type: the list of the matching docs' values (:77-100) as "how many matching docs carry each dictId" -- the
                                 * dictionary is sorted.  The percentile does not cross the ABI: the list is the intermediate result whatever p is.
                                 * pg_agg_value.count = the docs aggregated (the list's length), sum = 0, sum_exact = 0, min = +inf, max = -inf; the list
@@ -240,7 +241,30 @@ typedef enum pg_agg_function {
                                 * compressed raw columns are never resident: pg_segment_open declines them); a
                                 * PG_AGG_DISTINCTCOUNT in the same query; GROUP BY outside the conditions PG_AGG_DISTINCTCOUNT sets, or counter
                                 * matrices above PG_PERCENTILE_GROUP_MAX_BYTES. */
+  PG_AGG_DISTINCTCOUNTHLL = 7  /* DistinctCountHLLAggregationFunction.java: the HyperLogLog sketch of the matching docs' values -- 2^log2m registers of one
+                                * rank each (DESIGN.md section 4.1s states the hash, the rank rule and the estimator).  log2m travels in the function word:
+                                * PG_AGG_HLL(log2m); the plain enumerator means log2m 8 (CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M).  log2m outside
+                                * [PG_HLL_MIN_LOG2M, PG_HLL_MAX_LOG2M], or bits above the low byte on any other function: PG_ERR_INVALID_ARGUMENT.
+                                * pg_agg_value.count = the number of non-zero registers, sum = 0, sum_exact = 0, min = +inf, max = -inf; the registers come
+                                * from pg_result_hll_registers.  The cardinality is computed where sketches are merged, not here.
+                                * On a dictionary-encoded column of any stored type: the dictId bitset of PG_AGG_DISTINCTCOUNT (one bitset per column,
+                                * shared with a DISTINCTCOUNT and with HLLs of other log2m on the same column), folded into registers on the device
+                                * (hll_fold_kernel: the reference's convertToHyperLogLog); only the register rows are copied.  No filter (or one that
+                                * matches everything), no GROUP BY, every function answerable from metadata: the whole dictionary is folded, nothing scanned.
+                                * On a raw (PG_FWD_RAW_FIXED_BYTE, uncompressed) INT / LONG / FLOAT / DOUBLE column: one pass of scan_hll_kernel /
+                                * group_hll_kernel, always scanned, no PINOT_GPU_COLLECT and no sort.  Hashed is the value as stored: FLOAT by its 32 bits.
+                                * PG_ERR_UNSUPPORTED at plan time: everything PG_AGG_DISTINCTCOUNT names; raw and dictionary HLL columns in one query; a raw
+                                * HLL beside any DISTINCTCOUNT (it would need a second pass); any HLL beside a PERCENTILE; more than four (column, log2m) pairs; registers of the raw form beyond the LDS
+                                * budget; GROUP BY register matrices above PG_HLL_GROUP_MAX_BYTES. */
 } pg_agg_function;
+
+#define PG_AGG_HLL(log2m) (PG_AGG_DISTINCTCOUNTHLL | ((log2m) << 8))
+#define PG_HLL_MIN_LOG2M 4
+#define PG_HLL_MAX_LOG2M 14
+#define PG_HLL_DEFAULT_LOG2M 8
+/* GROUP BY with PG_AGG_DISTINCTCOUNTHLL: group_id_upper_bound x 2^log2m x 4 bytes (the registers are staged as 32-bit words), summed over the query's
+ * HLL aggregations (dictionary form) or columns (raw form), may not exceed this; PINOT_GPU_GROUP_TABLE_BYTES bounds it too. */
+#define PG_HLL_GROUP_MAX_BYTES (1ull << 30)
 
 /* GROUP BY with PG_AGG_DISTINCTCOUNT: group_id_upper_bound x ceil(cardinality / 32) x 4 bytes, summed over the query's DISTINCTCOUNT columns,
  * may not exceed this (a capacity limit: it bounds the host copy of the result; PINOT_GPU_GROUP_TABLE_BYTES bounds the device's). */
@@ -351,6 +375,8 @@ typedef enum pg_kernel_id {
   PG_KERNEL_GROUP_COUNTS = 17,     /* group_counts_kernel: the same under GROUP BY, one counter row per raw group id in HBM */
   PG_KERNEL_SCAN_COLLECT = 18,     /* scan_collect_kernel: PERCENTILE / DISTINCTCOUNT of raw columns, the matching docs' order images compacted into lists (sorted and run-length encoded behind it) */
   PG_KERNEL_GROUP_COLLECT = 19,    /* group_collect_kernel: the same under GROUP BY, every doc's raw group id beside its images */
+  PG_KERNEL_SCAN_HLL = 20,         /* scan_hll_kernel: DISTINCTCOUNTHLL of raw columns, 2^log2m 32-bit registers per column in LDS, max-merged into the query's row in HBM */
+  PG_KERNEL_GROUP_HLL = 21,        /* group_hll_kernel: the same under GROUP BY, one register row per raw group id in HBM */
   PG_KERNEL_SCAN_HIST = 6          /* scan_hist_kernel: lane-private scan, SUM = sum_d matches[d] * dictionary[d] through an LDS histogram */
 } pg_kernel_id;
 
@@ -470,6 +496,12 @@ pg_status pg_result_percentile_counts(const pg_result* result, int32_t aggregati
  * PG_ERR_INVALID_ARGUMENT. */
 pg_status pg_result_value_counts(const pg_result* result, int32_t aggregation, int32_t group_row,
                                  const int64_t** out_value_bits, const uint32_t** out_counts, int32_t* out_num);
+
+/* The registers behind a PG_AGG_DISTINCTCOUNTHLL aggregation: *out_num_registers = 2^log2m bytes, one rank (0 .. 32 - log2m + 1) per register.
+ * group_row = -1 for an aggregation-only query, else a row of group_aggregations.  Engine-owned, valid until pg_result_free.  Any other
+ * aggregation index or row: PG_ERR_INVALID_ARGUMENT.  (Registers of equal log2m merge by the register-wise maximum, across segments too.) */
+pg_status pg_result_hll_registers(const pg_result* result, int32_t aggregation, int32_t group_row,
+                                  const uint8_t** out_registers, int32_t* out_num_registers);
 
 /* How a group-by column's entries of pg_result.group_key_dict_ids turn into key values.  A dictionary column: *out_is_offset = 0, the
  * entry is a dictId (GroupKeyGenerator.getGroupKeys looks it up, DictionaryBasedGroupKeyGenerator.java:260-290).  A raw (no-dictionary)

@@ -90,6 +90,19 @@ char* ph_combine_counts(const char* sql, int32_t num_blocks, const int64_t* bloc
                         const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
                         const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* run_offsets, const double* run_values,
                         const int64_t* run_counts, int32_t* status);
+/* The combine of DISTINCTCOUNTHLL sketches: cell (row, function) of a DISTINCTCOUNTHLL function holds the registers registers[register_offsets[row *
+ * functions + function] .. register_offsets[.. + 1]) -- 2^log2m bytes, one rank each (pg_result_hll_registers' format), or none for an empty sketch;
+ * the combine merges them by the register-wise max, the final result is the estimate (a LONG).  GROUP BY: as ph_group_by_combine; aggregation
+ * only: one row per block, {"combined": <block>}. */
+char* ph_combine_hll(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                     const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                     const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* register_offsets, const uint8_t* registers, int32_t* status);
+/* HyperLogLog.cardinality() of num_registers = 2^log2m registers; -1 when num_registers is not such a count. */
+int64_t ph_hll_cardinality(const uint8_t* registers, int32_t num_registers);
+/* The registers (2^log2m bytes) after offering `num` longs to an empty sketch, computed with the header the kernels include; 0, or 1 for a bad log2m. */
+int32_t ph_hll_offer_longs(const int64_t* longs, int64_t num, int32_t log2m, uint8_t* out_registers);
+/* The 32 stored bits of a FLOAT dictionary entry from the bits of the double it was widened to (a NaN keeps its payload). */
+uint32_t ph_hll_float_bits_of_widened(uint64_t double_bits);
 /* The sorted runs of a raw column (pg_result_value_counts: value bits, counts) as the intermediate results that segments merge, without a device.
  * stored_type: 0 INT, 1 LONG, 2 FLOAT, 3 DOUBLE.  PERCENTILE's list: runs of (double, count) as getDoubleValuesSV gives the values -- two LONGs on one
  * double merge into one run; DISTINCTCOUNT's set: the stored type's 64-bit images, ascending as longs.  The out arrays hold `num` entries; returns

@@ -14,6 +14,8 @@
  */
 package org.apache.pinot.gpu;
 
+import com.clearspring.analytics.stream.cardinality.HyperLogLog;
+import com.clearspring.analytics.stream.cardinality.RegisterSet;
 import it.unimi.dsi.fastutil.doubles.DoubleArrayList;
 import java.util.ArrayList;
 import java.util.Arrays;
@@ -37,6 +39,7 @@ import org.apache.pinot.core.operator.blocks.results.GroupByResultsBlock;
 import org.apache.pinot.core.plan.PlanNode;
 import org.apache.pinot.core.query.aggregation.function.AggregationFunction;
 import org.apache.pinot.core.query.aggregation.function.AggregationFunctionUtils;
+import org.apache.pinot.core.query.aggregation.function.DistinctCountHLLAggregationFunction;
 import org.apache.pinot.core.query.aggregation.groupby.AggregationGroupByResult;
 import org.apache.pinot.core.query.aggregation.groupby.DoubleGroupByResultHolder;
 import org.apache.pinot.core.query.aggregation.groupby.GroupByResultHolder;
@@ -82,6 +85,7 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     Object[] _percentileCounts;   // ... and the int[] of how many matching docs carry each
     Object[] _valueBits;          // DISTINCTCOUNT / PERCENTILE lanes over RAW columns: long[] ascending value bits of aggregation a, row r at a * rows + r; else null
     Object[] _valueCounts;        // ... and the int[] of how many matching docs carry each
+    Object[] _hllRegisters;       // DISTINCTCOUNTHLL lanes: byte[] registers of aggregation a, row r at a * rows + r (null for other functions); else null
   }
 
   private final GpuSegment _segment;
@@ -173,7 +177,10 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       throw new UnsupportedOperationException("segment " + _segment.getSegmentName() + " is no longer resident on the device");
     }
     try {
-      Object[] raw = q._rawValueLists
+      Object[] raw = q._hasHll
+          ? PinotGpuNative.executeWithHllRegisters(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
+              q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
+          : q._rawValueLists
           ? PinotGpuNative.executeWithValueLists(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
               q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
           : q._hasPercentile
@@ -204,6 +211,14 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       valueBits = (Object[]) raw[PinotGpuNative.PGM_VALUES_BITS];
       valueCounts = (Object[]) raw[PinotGpuNative.PGM_VALUES_COUNTS];
       raw = (Object[]) raw[PinotGpuNative.PGM_VALUES_RESULT];
+    }
+    Object[] hllRegisters = null;
+    if (q._hasHll) {
+      if (raw == null || raw.length != PinotGpuNative.PGM_HLL_SLOTS) {
+        throw new IllegalStateException("native DISTINCTCOUNTHLL result does not match jni/pinot_gpu_jni.c");
+      }
+      hllRegisters = (Object[]) raw[PinotGpuNative.PGM_HLL_REGISTERS];
+      raw = (Object[]) raw[PinotGpuNative.PGM_HLL_RESULT];
     }
     Object[] distinctSets = null;
     if (q._hasDistinctCount && !q._rawValueLists) {
@@ -240,6 +255,7 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     result._percentileCounts = percentileCounts;
     result._valueBits = valueBits;
     result._valueCounts = valueCounts;
+    result._hllRegisters = hllRegisters;
     result._rows = _queryContext.getGroupByExpressions() == null ? 1 : result._groupIds.length;
     if (result._header.length != PinotGpuNative.PGM_HEADER_LEN) {
       throw new IllegalStateException("native result header does not match jni/pg_marshal.h");
@@ -256,10 +272,30 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       for (int i = 0; i < positions.length; i++) {
         AggregationFunctionType type = _functions[positions[i]].getType();
         out[positions[i]] = type == AggregationFunctionType.DISTINCTCOUNT ? valueSet(positions[i], result, i, 0)
+            : type == AggregationFunctionType.DISTINCTCOUNTHLL ? sketch(positions[i], result, i, 0)
             : type == AggregationFunctionType.PERCENTILE ? valueList(positions[i], result, i, 0, nullHandling) : intermediate(type, result, i, nullHandling);
       }
     }
     return new AggregationResultsBlock(_functions, Arrays.asList(out), _queryContext);
+  }
+
+  /**
+   * DISTINCTCOUNTHLL: the registers of aggregation {@code at}, row {@code row} of the lane -> the HyperLogLog the reference's function hands on
+   * (extractAggregationResult / extractGroupByResult :315-330): a sketch of the function's log2m whose register j holds the rank the device found.
+   */
+  private HyperLogLog sketch(int function, LaneResult result, int at, int row) {
+    int log2m = ((DistinctCountHLLAggregationFunction) _functions[function]).getLog2m();
+    byte[] registers = result._hllRegisters == null ? null : (byte[]) result._hllRegisters[at * result._rows + row];
+    if (registers == null || registers.length != 1 << log2m) {
+      throw new IllegalStateException("native DISTINCTCOUNTHLL registers do not match log2m " + log2m);
+    }
+    RegisterSet registerSet = new RegisterSet(registers.length);
+    for (int j = 0; j < registers.length; j++) {
+      if (registers[j] != 0) {
+        registerSet.set(j, registers[j]);
+      }
+    }
+    return new HyperLogLog(log2m, registerSet);
   }
 
   /**
@@ -434,6 +470,13 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
           ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);
           for (int g = 0; g < rowOf.length; g++) {
             holder.setValueForKey(rowOf[g], valueList(positions[i], r, i, g, nullHandling));
+          }
+          holders[positions[i]] = holder;
+        } else if (type == AggregationFunctionType.DISTINCTCOUNTHLL) {
+          // one sketch per group (aggregateGroupBySV keeps a HyperLogLog, or a dictId bitmap that turns into one, per group key)
+          ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);
+          for (int g = 0; g < rowOf.length; g++) {
+            holder.setValueForKey(rowOf[g], sketch(positions[i], r, i, g));
           }
           holders[positions[i]] = holder;
         } else if (type == AggregationFunctionType.DISTINCTCOUNT) {

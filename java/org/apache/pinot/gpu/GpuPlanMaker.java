@@ -192,19 +192,22 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
     GpuBatch planningBatch = _planningBatch.get();
     boolean distinctCount = false;
     boolean percentile = false;
+    boolean hll = false;
     for (GpuAggregationOperator.Lane lane : lanes) {
+      hll |= lane._query._hasHll;
       distinctCount |= lane._query._hasDistinctCount;
       percentile |= lane._query._hasPercentile;
     }
-    if ((distinctCount || percentile) && queryContext.hasFilteredAggregations()) {
-      return cpuPlan;      // DISTINCTCOUNT / PERCENTILE beside FILTER (WHERE ...) lanes keeps the CPU plan
+    if ((distinctCount || percentile || hll) && queryContext.hasFilteredAggregations()) {
+      return cpuPlan;      // DISTINCTCOUNT / PERCENTILE / DISTINCTCOUNTHLL beside FILTER (WHERE ...) lanes keeps the CPU plan
     }
     if (distinctCount && percentile) {
       return cpuPlan;      // the engine declines the two in one query
     }
     // (a DISTINCTCOUNT lane reads its sets before the native result is released: one call of its own, PinotGpuNative.executeWithDistinctSets)
     // (a PERCENTILE lane likewise: PinotGpuNative.executeWithPercentileCounts; either function on raw columns: PinotGpuNative.executeWithValueLists)
-    final GpuBatch batch = (distinctCount || percentile) ? null : planningBatch;
+    // (a DISTINCTCOUNTHLL lane likewise: PinotGpuNative.executeWithHllRegisters)
+    final GpuBatch batch = (distinctCount || percentile || hll) ? null : planningBatch;
     int[] batchSlots = null;
     if (batch != null) {
       batchSlots = new int[lanes.size()];

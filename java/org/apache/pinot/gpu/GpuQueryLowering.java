@@ -30,6 +30,7 @@ import org.apache.pinot.core.operator.filter.predicate.PredicateEvaluator;
 import org.apache.pinot.core.operator.filter.predicate.PredicateEvaluatorProvider;
 import org.apache.pinot.core.operator.filter.predicate.RangePredicateEvaluatorFactory.SortedDictionaryBasedRangePredicateEvaluator;
 import org.apache.pinot.core.query.aggregation.function.AggregationFunction;
+import org.apache.pinot.core.query.aggregation.function.DistinctCountHLLAggregationFunction;
 import org.apache.pinot.core.query.request.context.QueryContext;
 import org.apache.pinot.segment.spi.IndexSegment;
 import org.apache.pinot.segment.spi.datasource.DataSource;
@@ -64,6 +65,7 @@ final class GpuQueryLowering {
   static final int AGG_AVG = PinotGpuNative.PG_AGG_AVG;
   static final int AGG_DISTINCTCOUNT = PinotGpuNative.PG_AGG_DISTINCTCOUNT;
   static final int AGG_PERCENTILE = PinotGpuNative.PG_AGG_PERCENTILE;
+  static final int AGG_DISTINCTCOUNTHLL = PinotGpuNative.PG_AGG_DISTINCTCOUNTHLL;
   private static final int NODE_INTS = PinotGpuNative.PGM_FILTER_NODE_INTS;
   private static final int PRED_INTS = PinotGpuNative.PGM_PRED_INTS;
   private static final int PRED_LONGS = PinotGpuNative.PGM_PRED_LONGS;
@@ -90,6 +92,7 @@ final class GpuQueryLowering {
     int _flags;
     boolean _hasDistinctCount;      // a DISTINCTCOUNT among the aggregations: executed alone through executeWithDistinctSets, never in a batch
     boolean _hasPercentile;         // a PERCENTILE among the aggregations: executed alone through executeWithPercentileCounts, never in a batch
+    boolean _hasHll;                // a DISTINCTCOUNTHLL among the aggregations: executed alone through executeWithHllRegisters, never in a batch
     boolean _rawValueLists;         // those DISTINCTCOUNT / PERCENTILE columns are RAW (no dictionary): executed through executeWithValueLists instead
   }
 
@@ -210,6 +213,16 @@ final class GpuQueryLowering {
         case DISTINCTCOUNT:
           code = AGG_DISTINCTCOUNT;
           break;
+        case DISTINCTCOUNTHLL: {
+          // the HyperLogLog registers are built on the device, whichever way the column is stored; log2m travels in the function word
+          int log2m = ((DistinctCountHLLAggregationFunction) function).getLog2m();
+          if (log2m < PinotGpuNative.PG_HLL_MIN_LOG2M || log2m > PinotGpuNative.PG_HLL_MAX_LOG2M) {
+            throw new NotOffloadable("DISTINCTCOUNTHLL with log2m " + log2m);
+          }
+          code = PinotGpuNative.hllFunctionWord(log2m);
+          out._hasHll = true;
+          break;
+        }
         case PERCENTILE:
           // the exact PercentileAggregationFunction (PERCENTILE50(col) / PERCENTILE(col, 50)); the percentile itself stays with the function object:
           // the device returns the whole value list whatever it is
@@ -252,6 +265,10 @@ final class GpuQueryLowering {
       }
       out._aggregations[AGG_INTS * i] = code;
       out._aggregations[AGG_INTS * i + 1] = column;
+    }
+    if (out._hasHll && (out._hasDistinctCount || out._hasPercentile)) {
+      // one native call returns one kind of intermediate result (and the engine declines most of these mixes itself)
+      throw new NotOffloadable("DISTINCTCOUNTHLL beside DISTINCTCOUNT / PERCENTILE in one query");
     }
     // ---- group-by keys: dictionary-encoded identifiers ----
     List<ExpressionContext> groupBy = _queryContext.getGroupByExpressions();

@@ -85,6 +85,19 @@ public final class PinotGpuNative {
   public static final int PG_AGG_DISTINCTCOUNT = 5;
   /** PercentileAggregationFunction on a dictionary column: the value list comes back as (dictId, count) pairs through executeWithPercentileCounts. */
   public static final int PG_AGG_PERCENTILE = 6;
+  /**
+   * DistinctCountHLLAggregationFunction: the low byte of the function word; log2m travels in the bits above it (include/pinot_gpu.h PG_AGG_HLL), the plain
+   * value means log2m 8.  The registers come back through executeWithHllRegisters.
+   */
+  public static final int PG_AGG_DISTINCTCOUNTHLL = 7;
+  /** PG_AGG_HLL(log2m) of include/pinot_gpu.h: the function word of DISTINCTCOUNTHLL with its log2m; PG_HLL_MIN_LOG2M .. PG_HLL_MAX_LOG2M are offloaded. */
+  public static final int PG_HLL_MIN_LOG2M = 4;
+  public static final int PG_HLL_MAX_LOG2M = 14;
+  public static final int PG_HLL_DEFAULT_LOG2M = 8;
+
+  static int hllFunctionWord(int log2m) {
+    return PG_AGG_DISTINCTCOUNTHLL | (log2m << Byte.SIZE);
+  }
 
   /** pg_query.flags */
   public static final int PG_QUERY_NULL_HANDLING = 1;
@@ -219,6 +232,19 @@ public final class PinotGpuNative {
    * (bit d &amp; 31 of word d &gt;&gt; 5) for a DISTINCTCOUNT aggregation and null for every other function; rows = 1 without GROUP BY, else the groups.
    */
   static native Object[] executeWithDistinctSets(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
+      int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
+
+  /** Slots of executeWithHllRegisters' Object[]: the Object[PGM_RESULT_ARRAYS] of execute(), then the sketches' registers. */
+  public static final int PGM_HLL_SLOTS = 2;
+  public static final int PGM_HLL_RESULT = 0;
+  public static final int PGM_HLL_REGISTERS = 1;
+
+  /**
+   * pg_execute of a query with PG_AGG_DISTINCTCOUNTHLL aggregations plus pg_result_hll_registers over its result.  Returns Object[PGM_HLL_SLOTS]:
+   * what execute() returns, and Object[aggregations * rows] whose element {@code aggregation * rows + row} is the byte[] of the sketch's 2^log2m
+   * registers (one rank each) for a DISTINCTCOUNTHLL aggregation and null for every other function; rows = 1 without GROUP BY, else the groups.
+   */
+  static native Object[] executeWithHllRegisters(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
       int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
 
   /** Slots of executeWithPercentileCounts' Object[]: the Object[PGM_RESULT_ARRAYS] of execute(), then the lists' dictIds and their counts. */

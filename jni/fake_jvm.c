@@ -15,7 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-enum { FJ_INT_ARRAY = 1, FJ_LONG_ARRAY = 2, FJ_DOUBLE_ARRAY = 3, FJ_OBJECT_ARRAY = 4, FJ_STRING = 5, FJ_CLASS = 6, FJ_BUFFER = 7 };
+enum { FJ_INT_ARRAY = 1, FJ_LONG_ARRAY = 2, FJ_DOUBLE_ARRAY = 3, FJ_OBJECT_ARRAY = 4, FJ_STRING = 5, FJ_CLASS = 6, FJ_BUFFER = 7, FJ_BYTE_ARRAY = 8 };
 
 typedef struct fj_object {
   int kind;
@@ -139,12 +139,17 @@ static void fj_SetLongArrayRegion(JNIEnv* env, jlongArray a, jsize start, jsize 
   (void)env;
   if (start >= 0 && len >= 0 && start + len <= obj(a)->len) memcpy((jlong*)obj(a)->data + start, buf, (size_t)len * sizeof(jlong));
 }
+static jbyteArray fj_NewByteArray(JNIEnv* env, jsize len) { (void)env; return ref(new_object(FJ_BYTE_ARRAY, len, sizeof(jbyte))); }
+static void fj_SetByteArrayRegion(JNIEnv* env, jbyteArray a, jsize start, jsize len, const jbyte* buf) {
+  (void)env;
+  if (start >= 0 && len >= 0 && start + len <= obj(a)->len) memcpy((jbyte*)obj(a)->data + start, buf, (size_t)len);
+}
 
 static const struct JNINativeInterface_ g_table = {
   fj_FindClass, fj_ThrowNew, fj_ExceptionCheck, fj_DeleteLocalRef, fj_NewStringUTF, fj_GetStringUTFChars, fj_ReleaseStringUTFChars,
   fj_GetArrayLength, fj_NewObjectArray, fj_GetObjectArrayElement, fj_SetObjectArrayElement, fj_NewIntArray, fj_NewLongArray,
   fj_NewDoubleArray, fj_GetIntArrayElements, fj_GetLongArrayElements, fj_GetDoubleArrayElements, fj_ReleaseIntArrayElements,
-  fj_ReleaseLongArrayElements, fj_ReleaseDoubleArrayElements, fj_GetDirectBufferAddress, fj_SetLongArrayRegion};
+  fj_ReleaseLongArrayElements, fj_ReleaseDoubleArrayElements, fj_GetDirectBufferAddress, fj_SetLongArrayRegion, fj_NewByteArray, fj_SetByteArrayRegion};
 static JNIEnv g_env = &g_table;
 
 /* ---- what the harness (ctypes) calls ---- */

@@ -407,6 +407,50 @@ JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeW
   return out;
 }
 
+/* pg_execute of a query with PG_AGG_DISTINCTCOUNTHLL aggregations, and pg_result_hll_registers over its result before that is released.
+ * Returns Object[PGM_HLL_SLOTS]: {the Object[PGM_RESULT_ARRAYS] execute() returns, Object[aggregations * rows]} -- element (aggregation * rows + row) of the
+ * second array is the byte[] of the sketch's 2^log2m registers (one rank each) for a DISTINCTCOUNTHLL aggregation, null for every other function;
+ * rows = 1 for an aggregation-only query, else the number of groups. */
+JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeWithHllRegisters(JNIEnv* env, jclass cls, jlong handle, jintArray filterNodes,
+    jintArray predInts, jlongArray predLongs, jintArray setOffsets, jintArray setWords, jintArray aggregations, jintArray groupBy,
+    jint numGroupsLimit, jint flags) {
+  (void)cls;
+  pinned_query p;
+  if (!pin_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy, numGroupsLimit, flags)) return NULL;
+  const int32_t num_group_by = pgm_query_get(p.built)->num_group_by;
+  pg_result result;
+  const pg_status status = pg_execute((pg_segment*)(intptr_t)handle, pgm_query_get(p.built), &result);
+  release_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy);
+  if (status != PG_OK) { throw_status(env, status); return NULL; }     /* pg_execute freed the result */
+  const jsize rows = num_group_by > 0 ? (jsize)result.num_groups : 1;
+  const jsize na = (jsize)result.num_aggregations;
+  jclass object_class = (*env)->FindClass(env, "java/lang/Object");
+  jobjectArray sketches = object_class ? (*env)->NewObjectArray(env, na * rows, object_class, NULL) : NULL;
+  int ok = sketches != NULL;
+  for (jsize a = 0; ok && a < na; ++a) {
+    for (jsize r = 0; ok && r < rows; ++r) {
+      const uint8_t* registers = NULL;
+      int32_t num_registers = 0;
+      if (pg_result_hll_registers(&result, (int32_t)a, num_group_by > 0 ? (int32_t)r : -1, &registers, &num_registers) != PG_OK) break;      /* not a DISTINCTCOUNTHLL: the row of nulls stays */
+      jbyteArray b = (*env)->NewByteArray(env, (jsize)num_registers);
+      if (b == NULL) { ok = 0; break; }
+      (*env)->SetByteArrayRegion(env, b, 0, (jsize)num_registers, (const jbyte*)registers);
+      (*env)->SetObjectArrayElement(env, sketches, a * rows + r, b);
+      (*env)->DeleteLocalRef(env, b);
+    }
+  }
+  jobjectArray converted = result_to_java(env, &result, num_group_by);      /* releases the result */
+  if (!ok || converted == NULL) {
+    if (!(*env)->ExceptionCheck(env)) throw_new(env, "java/lang/OutOfMemoryError", "allocating the DISTINCTCOUNTHLL registers failed");
+    return NULL;
+  }
+  jobjectArray out = (*env)->NewObjectArray(env, PGM_HLL_SLOTS, object_class, NULL);
+  if (out == NULL) return NULL;
+  (*env)->SetObjectArrayElement(env, out, PGM_HLL_RESULT, converted);
+  (*env)->SetObjectArrayElement(env, out, PGM_HLL_REGISTERS, sketches);
+  return out;
+}
+
 /* pg_execute of a query with PG_AGG_PERCENTILE aggregations, and pg_result_percentile_counts over its result before that is released.
  * Returns Object[PGM_PERCENTILE_SLOTS]: {the Object[PGM_RESULT_ARRAYS] execute() returns, Object[aggregations * rows], Object[aggregations * rows]} -- element
  * (aggregation * rows + row) of the second array is the int[] of the list's ascending dictIds, of the third the int[] of their counts (non-zero;

@@ -16,6 +16,7 @@
 #define JNICALL
 #define JNI_ABORT 2
 
+typedef int8_t jbyte;
 typedef int32_t jint;
 typedef int64_t jlong;
 typedef double jdouble;
@@ -28,6 +29,7 @@ typedef jobject jclass;
 typedef jobject jstring;
 typedef jobject jarray;
 typedef jarray jobjectArray;
+typedef jarray jbyteArray;
 typedef jarray jintArray;
 typedef jarray jlongArray;
 typedef jarray jdoubleArray;
@@ -58,6 +60,8 @@ struct JNINativeInterface_ {
   void (*ReleaseDoubleArrayElements)(JNIEnv* env, jdoubleArray array, jdouble* elems, jint mode);
   void* (*GetDirectBufferAddress)(JNIEnv* env, jobject buffer);
   void (*SetLongArrayRegion)(JNIEnv* env, jlongArray array, jsize start, jsize len, const jlong* buf);
+  jbyteArray (*NewByteArray)(JNIEnv* env, jsize len);
+  void (*SetByteArrayRegion)(JNIEnv* env, jbyteArray array, jsize start, jsize len, const jbyte* buf);
 };
 
 #endif

@@ -15,7 +15,7 @@ PG_OK, PG_ERR_INVALID_ARGUMENT, PG_ERR_UNSUPPORTED, PG_ERR_DEVICE, PG_ERR_OUT_OF
 KERNEL_NAMES = {0: "scan_agg_kernel", 1: "scan_private_kernel", 2: "scan_group_kernel", 3: "group_private_kernel",
                 4: "group_partition_scatter_kernel", 5: "scan_private_typed_kernel", 6: "scan_hist_kernel", 7: "index_and_kernel", 8: "scan_narrow_kernel", 9: "scan_sparse_kernel", 10: "scan_simple_kernel", 11: "scan_raw_kernel", 12: "scan_raw_set_kernel", 13: "scan_simple_valid_kernel",
                 14: "scan_distinct_kernel", 15: "group_distinct_kernel", 16: "scan_counts_kernel", 17: "group_counts_kernel",
-                18: "scan_collect_kernel", 19: "group_collect_kernel"}
+                18: "scan_collect_kernel", 19: "group_collect_kernel", 20: "scan_hll_kernel", 21: "group_hll_kernel"}
 PG_TYPE_INT, PG_TYPE_LONG, PG_TYPE_FLOAT, PG_TYPE_DOUBLE = range(4)
 PG_FWD_FIXED_BIT_DICT, PG_FWD_RAW_FIXED_BYTE = 0, 1
 # pg_predicate_kind / pg_leaf_eval
@@ -29,6 +29,16 @@ PG_EVAL_SCAN, PG_EVAL_INVERTED = 0, 1
 PG_FILTER_LEAF, PG_FILTER_AND, PG_FILTER_OR, PG_FILTER_NOT = range(4)
 # pg_agg_function
 PG_AGG_COUNT, PG_AGG_SUM, PG_AGG_MIN, PG_AGG_MAX, PG_AGG_AVG, PG_AGG_DISTINCTCOUNT, PG_AGG_PERCENTILE = range(7)
+PG_AGG_DISTINCTCOUNTHLL = 7                  # the low byte of the function word; log2m travels above it: PG_AGG_HLL(log2m)
+PG_HLL_MIN_LOG2M, PG_HLL_MAX_LOG2M, PG_HLL_DEFAULT_LOG2M = 4, 14, 8
+PG_HLL_GROUP_MAX_BYTES = 1 << 30             # GROUP BY with DISTINCTCOUNTHLL: group_id_upper_bound x 2^log2m x 4 bytes over the query's HLL aggregations
+
+
+def PG_AGG_HLL(log2m):
+    """The function word of DISTINCTCOUNTHLL with an explicit log2m (plain PG_AGG_DISTINCTCOUNTHLL means log2m 8)."""
+    return PG_AGG_DISTINCTCOUNTHLL | (int(log2m) << 8)
+
+
 PG_DISTINCT_GROUP_MAX_BYTES = 1 << 30
 PG_PERCENTILE_GROUP_MAX_BYTES = 1 << 30
 PG_COLLECT_MAX_BYTES = 1 << 30               # PERCENTILE / DISTINCTCOUNT on raw columns: numDocs x (16 x columns + 8 under GROUP BY) bytes
@@ -123,6 +133,7 @@ ABI_SYMBOLS = [
     ("pg_result_distinct_dict_ids", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(_P(C.c_uint32)), _P(C.c_int32)]),
     ("pg_result_percentile_counts", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(_P(C.c_int32)), _P(_P(C.c_uint32)), _P(C.c_int32)]),
     ("pg_result_value_counts", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(_P(C.c_int64)), _P(_P(C.c_uint32)), _P(C.c_int32)]),
+    ("pg_result_hll_registers", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(_P(C.c_uint8)), _P(C.c_int32)]),
     ("pg_group_key_info", C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
     ("pg_group_key_values", C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64), C.c_int32, _P(C.c_int32)]),
     ("pg_execute_batch", C.c_int, [_P(C.c_void_p), _P(_P(pg_query)), C.c_int32, _P(pg_result), _P(C.c_int)]),

@@ -44,6 +44,7 @@ std::vector<OrderByValue> TableResizer::orderByValues(const Record& r) const {
       if (isNullResult(v)) out.emplace_back(std::monostate{});
       else if (f.getType() == AggregationFunctionType::COUNT) out.emplace_back(std::get<int64_t>(v));
       else if (f.getType() == AggregationFunctionType::DISTINCTCOUNT) out.emplace_back((int64_t)std::get<ValueSet>(v).values.size());      // an INT final result
+      else if (f.getType() == AggregationFunctionType::DISTINCTCOUNTHLL) out.emplace_back(std::get<HllRegisters>(v).cardinality());      // a LONG final result
       else out.emplace_back(f.extractFinalResult(v));
     }
   }
@@ -204,6 +205,7 @@ std::vector<ReducedRow> reduceGroupBy(const ResultsBlock& combined, const QueryC
       if (isNullResult(r.values[a])) row.finals.emplace_back(std::monostate{});
       else if (g.functions[a].getType() == AggregationFunctionType::COUNT) row.finals.emplace_back(std::get<int64_t>(r.values[a]));
       else if (g.functions[a].getType() == AggregationFunctionType::DISTINCTCOUNT) row.finals.emplace_back((int64_t)std::get<ValueSet>(r.values[a]).values.size());
+      else if (g.functions[a].getType() == AggregationFunctionType::DISTINCTCOUNTHLL) row.finals.emplace_back(std::get<HllRegisters>(r.values[a]).cardinality());
       else row.finals.emplace_back(g.functions[a].extractFinalResult(r.values[a]));
     }
     rows.push_back(std::move(row));

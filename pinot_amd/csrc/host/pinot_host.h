@@ -206,7 +206,7 @@ struct FilterContext {                               // common/request/context/F
   Predicate predicate;
 };
 
-enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE };   // sspi/AggregationFunctionType.java (ordinals = pg_agg_function)
+enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE, DISTINCTCOUNTHLL };   // sspi/AggregationFunctionType.java (ordinals = pg_agg_function)
 // DISTINCTCOUNT(col) / DISTINCT_COUNT(col) (the reference canonicalises function names by dropping underscores): the engine returns a segment's
 // dictId set (PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids), the mirror turns it into the value set that segments merge (ValueSet below).
 
@@ -214,11 +214,15 @@ enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, P
 // form, :133-141): the exact PercentileAggregationFunction.  The engine returns how many matching docs carry each dictId (PG_AGG_PERCENTILE,
 // pg_result_percentile_counts), the mirror turns that into the value list that segments merge (ValueCounts below).
 
+// DISTINCTCOUNTHLL(col) / DISTINCTCOUNTHLL(col, log2m) (and the underscore spellings): DistinctCountHLLAggregationFunction.  The engine returns a
+// segment's 2^log2m registers (PG_AGG_HLL(log2m), pg_result_hll_registers); the mirror merges them by the register-wise max (HllRegisters below).
+
 struct AggregationExpression {
   AggregationFunctionType function;
   std::string column;                                // "*" for COUNT(*)
   double percentile = 0.0;                           // PERCENTILE: p in [0, 100]
   bool percentileIntForm = false;                    // PERCENTILE50(col) -> "percentile50(col)"; PERCENTILE(col, 50) -> "percentile(col, 50.0)"
+  int hllLog2m = 8;                                  // DISTINCTCOUNTHLL: CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M unless the second argument gives it
   // SUM(x) FILTER (WHERE ...): FilteredAggregationFunction (core/query/aggregation/function/FilterableAggregationFunction / QueryContext
   // filtered aggregations); evaluated as one "swim lane" per distinct filter like FilteredAggregationOperator
   bool hasFilter = false;
@@ -309,7 +313,17 @@ struct ValueCounts {
   // one run (they are neighbours: the conversion is monotone).
   static ValueCounts fromDeviceValues(DataType storedType, const int64_t* valueBits, const uint32_t* counts, int32_t num);
 };
-using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet, ValueCounts>;   // Long / Double / AvgPair / null (null handling only) / value set / value list
+// DISTINCTCOUNTHLL's intermediate result: the HyperLogLog as its registers, one rank per byte, 2^log2m of them (pinot_amd/csrc/pg_hll.h states the
+// sketch).  merge = the register-wise max; sketches of different sizes follow DistinctCountHLLAggregationFunction.merge :333-350 -- the one whose
+// cardinality is 0 gives way, two non-empty ones of different sizes cannot be merged.  The final result is the estimate, a LONG.
+struct HllRegisters {
+  std::vector<uint8_t> registers;
+  static HllRegisters fromDeviceRegisters(const uint8_t* registers, int32_t num);      // pg_result_hll_registers' bytes (num = 2^log2m)
+  static HllRegisters empty(int log2m) { HllRegisters h; h.registers.assign((size_t)1 << log2m, 0); return h; }
+  int log2m() const { int l = 0; while (((size_t)1 << l) < registers.size()) ++l; return l; }
+  int64_t cardinality() const;
+};
+using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet, ValueCounts, HllRegisters>;   // Long / Double / AvgPair / null (null handling only) / value set / value list / HLL registers
 inline bool isNullResult(const IntermediateResult& r) { return std::holds_alternative<std::monostate>(r); }
 
 class AggregationFunction {                         // query/aggregation/function/AggregationFunction.java:42-145
@@ -317,7 +331,8 @@ class AggregationFunction {                         // query/aggregation/functio
   AggregationFunction(AggregationFunctionType type, std::string column, bool nullHandlingEnabled = false)
       : _type(type), _column(std::move(column)), _nullHandlingEnabled(nullHandlingEnabled) {}
   AggregationFunction(const AggregationExpression& e, bool nullHandlingEnabled = false)
-      : _type(e.function), _column(e.column), _nullHandlingEnabled(nullHandlingEnabled), _percentile(e.percentile), _percentileIntForm(e.percentileIntForm) {}
+      : _type(e.function), _column(e.column), _nullHandlingEnabled(nullHandlingEnabled), _percentile(e.percentile), _percentileIntForm(e.percentileIntForm), _hllLog2m(e.hllLog2m) {}
+  int getHllLog2m() const { return _hllLog2m; }
   double getPercentile() const { return _percentile; }
   AggregationFunctionType getType() const { return _type; }
   const std::string& getColumn() const { return _column; }
@@ -336,6 +351,7 @@ class AggregationFunction {                         // query/aggregation/functio
   bool _nullHandlingEnabled;                          // NullableSingleInputAggregationFunction._nullHandlingEnabled
   double _percentile = 0.0;                           // PERCENTILE only
   bool _percentileIntForm = false;
+  int _hllLog2m = 8;                                  // DISTINCTCOUNTHLL only
 };
 
 // ---- operator/ExecutionStatistics.java:25-64 ---------------------------------------------------------------------
@@ -533,6 +549,7 @@ struct GpuAbi {
   decltype(&pg_execute_batch) execute_batch;
   decltype(&pg_result_free) result_free;
   decltype(&pg_result_distinct_dict_ids) result_distinct_dict_ids;
+  decltype(&pg_result_hll_registers) result_hll_registers;
   decltype(&pg_result_percentile_counts) result_percentile_counts;
   decltype(&pg_result_value_counts) result_value_counts;
   decltype(&pg_filter_bitmap) filter_bitmap;

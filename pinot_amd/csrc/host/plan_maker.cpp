@@ -17,6 +17,7 @@
 #include <thread>
 
 #include "pinot_host.h"
+#include "../pg_hll.h"
 
 namespace pinot {
 
@@ -48,6 +49,7 @@ const GpuAbi& gpuAbi() {
     abi.execute_batch = (decltype(abi.execute_batch))sym("pg_execute_batch");
     abi.result_free = (decltype(abi.result_free))sym("pg_result_free");
     abi.result_distinct_dict_ids = (decltype(abi.result_distinct_dict_ids))sym("pg_result_distinct_dict_ids");
+    abi.result_hll_registers = (decltype(abi.result_hll_registers))sym("pg_result_hll_registers");
     abi.result_percentile_counts = (decltype(abi.result_percentile_counts))sym("pg_result_percentile_counts");
     abi.result_value_counts = (decltype(abi.result_value_counts))sym("pg_result_value_counts");
     abi.filter_bitmap = (decltype(abi.filter_bitmap))sym("pg_filter_bitmap");
@@ -164,7 +166,7 @@ void ImmutableSegment::setQueryableDocIds(const void* roaringBytes, uint64_t siz
 // AggregationFunction
 // ---------------------------------------------------------------------------------------------------------------
 std::string AggregationFunction::getResultColumnName() const {
-  static const char* names[] = {"count", "sum", "min", "max", "avg", "distinctcount", "percentile"};
+  static const char* names[] = {"count", "sum", "min", "max", "avg", "distinctcount", "percentile", "distinctcounthll"};
   if (_type == AggregationFunctionType::PERCENTILE) {
     // PercentileAggregationFunction.getResultColumnName :63-66: version 0 "percentile50(col)", version 1 "percentile(col, 50.0)" (Double.toString)
     if (_percentileIntForm) return "percentile" + std::to_string((int)_percentile) + "(" + _column + ")";
@@ -188,6 +190,7 @@ IntermediateResult AggregationFunction::fromDevice(const pg_agg_value& v) const 
     case AggregationFunctionType::AVG: return AvgPair{v.sum, v.count};     // AvgPair(sum, count)
     case AggregationFunctionType::DISTINCTCOUNT: return ValueSet{};         // (no doc reached the holder: the empty set; a set comes through fromDeviceSet)
     case AggregationFunctionType::PERCENTILE: return ValueCounts{};         // (the empty list; a list comes through fromDeviceCounts)
+    case AggregationFunctionType::DISTINCTCOUNTHLL: return HllRegisters::empty(_hllLog2m);      // (an empty sketch; registers come through fromDeviceRegisters)
   }
   return 0.0;
 }
@@ -219,6 +222,17 @@ IntermediateResult AggregationFunction::fromDeviceCounts(const int32_t* dictIds,
   }
   return list;
 }
+
+HllRegisters HllRegisters::fromDeviceRegisters(const uint8_t* registers, int32_t num) {
+  HllRegisters h;
+  if (num < (1 << PG_HLL_MIN_LOG2M) || num > (1 << PG_HLL_MAX_LOG2M) || (num & (num - 1)) != 0) throw QueryException("an HLL of " + std::to_string(num) + " registers");
+  h.registers.assign(registers, registers + num);
+  // a rank is at most 32 - log2m + 1: anything above it is not a register of this sketch (and would shift past a word in the estimator)
+  const int maxRank = 32 - h.log2m() + 1;
+  for (uint8_t r : h.registers) if (r > maxRank) throw QueryException("an HLL register of rank " + std::to_string((int)r) + " at log2m " + std::to_string(h.log2m()) + " (at most " + std::to_string(maxRank) + ")");
+  return h;
+}
+int64_t HllRegisters::cardinality() const { return pg::hll_cardinality(registers.data(), log2m()); }
 
 ValueSet ValueSet::fromDeviceValues(DataType storedType, const int64_t* valueBits, int32_t num) {
   ValueSet set;
@@ -254,6 +268,19 @@ IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const
       r.storedType = x.values.empty() ? y.storedType : x.storedType;
       r.values.reserve(x.values.size() + y.values.size());
       std::set_union(x.values.begin(), x.values.end(), y.values.begin(), y.values.end(), std::back_inserter(r.values));
+      return r;
+    }
+    case AggregationFunctionType::DISTINCTCOUNTHLL: {                                          // DistinctCountHLLAggregationFunction.merge :333-350
+      const HllRegisters& x = std::get<HllRegisters>(a);
+      const HllRegisters& y = std::get<HllRegisters>(b);
+      if (x.registers.size() != y.registers.size()) {
+        // "Can happen when aggregating serialized HyperLogLog with non-default log2m": the empty side gives way
+        if (x.cardinality() == 0) return y;
+        if (y.cardinality() != 0) throw QueryException("Cannot merge HyperLogLogs of different sizes");
+        return x;
+      }
+      HllRegisters r = x;
+      for (size_t j = 0; j < r.registers.size(); ++j) r.registers[j] = std::max(r.registers[j], y.registers[j]);      // addAll: the register-wise max
       return r;
     }
     case AggregationFunctionType::PERCENTILE: {                                                // PercentileAggregationFunction.merge :143-147: addAll, up to order
@@ -297,6 +324,7 @@ double AggregationFunction::extractFinalResult(const IntermediateResult& r) cons
   switch (_type) {
     case AggregationFunctionType::COUNT: return (double)std::get<int64_t>(r);
     case AggregationFunctionType::DISTINCTCOUNT: return (double)std::get<ValueSet>(r).values.size();   // extractFinalResult :66-68: the set's size (an INT)
+    case AggregationFunctionType::DISTINCTCOUNTHLL: return (double)std::get<HllRegisters>(r).cardinality();   // extractFinalResult: hyperLogLog.cardinality() (a LONG)
     case AggregationFunctionType::PERCENTILE: {
       // PercentileAggregationFunction.extractFinalResult :155-172: empty -> DEFAULT_FINAL_RESULT = -inf; else sort and take
       // values[(int) ((long) size * percentile / 100)] (long x double / 100, truncated), the last value when percentile == 100
@@ -593,8 +621,12 @@ std::unique_ptr<LoweredQuery> lowerQuery(const ImmutableSegment& seg, const Quer
       if (a.column == "*") throw QueryException("'*' is only valid in COUNT(*)");
       if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException("DISTINCTCOUNT(" + a.column + ") on a STRING column keeps the CPU plan");
     }
+    if (a.function == AggregationFunctionType::DISTINCTCOUNTHLL) {
+      if (a.column == "*") throw QueryException("'*' is only valid in COUNT(*)");
+      if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException("DISTINCTCOUNTHLL(" + a.column + ") on a STRING column keeps the CPU plan");
+    }
     pg_aggregation pa;
-    pa.function = (int32_t)a.function;
+    pa.function = a.function == AggregationFunctionType::DISTINCTCOUNTHLL ? PG_AGG_HLL(a.hllLog2m) : (int32_t)a.function;
     pa.column = a.column == "*" ? -1 : seg.getColumnIndex(a.column);
     if (pa.column >= 0) {
       const DataSource& ds = seg.getDataSource(a.column);
@@ -800,6 +832,13 @@ class GpuAggregationOperator : public Operator {
 
   // one function's holder out of the device result: DISTINCTCOUNT through the set accessor and the column's dictionary (before the result is freed)
   IntermediateResult fromResult(const AggregationFunction& f, const pg_result& res, int aggregation, int groupRow, const pg_agg_value& v) const {
+    if (f.getType() == AggregationFunctionType::DISTINCTCOUNTHLL) {
+      // the registers, whichever way the column is stored
+      const uint8_t* registers = nullptr;
+      int32_t num = 0;
+      checkStatus(gpuAbi().result_hll_registers(&res, aggregation, groupRow, &registers, &num), "reading DISTINCTCOUNTHLL registers");
+      return HllRegisters::fromDeviceRegisters(registers, num);
+    }
     // a raw (no-dictionary) column: the sorted runs of pg_result_value_counts, for either function
     const bool collected = f.getType() == AggregationFunctionType::PERCENTILE || f.getType() == AggregationFunctionType::DISTINCTCOUNT;
     if (collected && _segment->getDataSource(f.getColumn()).dictionary == nullptr) {
@@ -1065,6 +1104,8 @@ std::unique_ptr<PlanNode> GpuPlanMaker::makeSegmentPlanNode(const SegmentContext
     if (a.function == AggregationFunctionType::DISTINCTCOUNT) throw UnsupportedOperationException("DISTINCTCOUNT in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
   for (const auto& a : qc.aggregations)
     if (a.function == AggregationFunctionType::PERCENTILE) throw UnsupportedOperationException("PERCENTILE in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
+  for (const auto& a : qc.aggregations)
+    if (a.function == AggregationFunctionType::DISTINCTCOUNTHLL) throw UnsupportedOperationException("DISTINCTCOUNTHLL in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
   std::vector<std::string> keys;                       // lane order = first appearance, the unfiltered lane keyed ""
   std::vector<QueryContext> laneQueries;
   std::vector<std::vector<int>> positions;

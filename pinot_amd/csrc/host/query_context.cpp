@@ -392,6 +392,7 @@ QueryContext getQueryContext(const std::string& sql) {
     else if (u == "MAX") e.function = AggregationFunctionType::MAX;
     else if (u == "AVG") e.function = AggregationFunctionType::AVG;
     else if (u == "DISTINCTCOUNT") e.function = AggregationFunctionType::DISTINCTCOUNT;
+    else if (u == "DISTINCTCOUNTHLL") e.function = AggregationFunctionType::DISTINCTCOUNTHLL;
     else if (u.rfind("PERCENTILE", 0) == 0) {
       // AggregationFunctionFactory.java:68-140: PERCENTILE<digits>(col) is the exact function with an int percentile, PERCENTILE(col, p) the same
       // with a double; every other PERCENTILE... spelling (EST, TDIGEST, KLL, RAW..., ...MV, SMARTTDIGEST) is another function
@@ -405,7 +406,7 @@ QueryContext getQueryContext(const std::string& sql) {
         e.percentile = (double)atoi(rest.c_str());
       }
     }
-    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT/PERCENTILE are offloaded, got " + fn.text);
+    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT/DISTINCTCOUNTHLL/PERCENTILE are offloaded, got " + fn.text);
     lx.expectSymbol("(");
     if (lx.acceptSymbol("*")) e.column = "*";
     else {
@@ -427,6 +428,16 @@ QueryContext getQueryContext(const std::string& sql) {
         if ((p.kind != Token::NUMBER && p.kind != Token::STRING) || p.text.empty() || end == p.text.c_str() || *end != '\0') throw QueryException("Invalid percentile: " + p.text);
         if (!(v >= 0.0 && v <= 100.0)) throw QueryException("Invalid percentile: " + p.text);
         e.percentile = v;
+      }
+      if (e.function == AggregationFunctionType::DISTINCTCOUNTHLL && lx.acceptSymbol(",")) {
+        // the optional second argument: log2m, an integer literal (DistinctCountHLLAggregationFunction's constructor); the engine takes [PG_HLL_MIN_LOG2M, PG_HLL_MAX_LOG2M]
+        const Token p = lx.next();
+        char* end = nullptr;
+        const long v = strtol(p.text.c_str(), &end, 10);
+        if ((p.kind != Token::NUMBER && p.kind != Token::STRING) || p.text.empty() || end == p.text.c_str() || *end != '\0') throw QueryException("Invalid log2m: " + p.text);
+        if (v < PG_HLL_MIN_LOG2M || v > PG_HLL_MAX_LOG2M)
+          throw UnsupportedOperationException("DISTINCTCOUNTHLL with log2m " + p.text + " is not offloaded (" + std::to_string(PG_HLL_MIN_LOG2M) + " to " + std::to_string(PG_HLL_MAX_LOG2M) + " are)");
+        e.hllLog2m = (int)v;
       }
       if (!(lx.peek().kind == Token::SYMBOL && lx.peek().text == ")"))
         throw UnsupportedOperationException("only identifier arguments are offloaded (transform expressions keep the CPU plan, ProjectPlanNode.java:85-86)");
@@ -497,7 +508,7 @@ QueryContext getQueryContext(const std::string& sql) {
         int found = -1;
         for (size_t a = 0; a < q.aggregations.size() && found < 0; ++a) {
           const AggregationExpression& e = q.aggregations[a];
-          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "PERCENTILE()"};      // (a PERCENTILE is ordered by through its alias)
+          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "PERCENTILE()", "DISTINCTCOUNTHLL"};      // (a PERCENTILE is ordered by through its alias)
           if (!e.hasFilter && u == names[(int)e.function] && (e.column == column || (e.function == AggregationFunctionType::COUNT && (column == "*" || e.column == "*")))) found = (int)a;
         }
         if (found < 0) {
@@ -508,7 +519,7 @@ QueryContext getQueryContext(const std::string& sql) {
           static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG"};      // (a DISTINCTCOUNT that is only ordered by keeps the CPU plan)
           for (int k = 0; k < 5; ++k) if (u == names[k]) kind = k;
           if (u.rfind("PERCENTILE", 0) == 0) throw UnsupportedOperationException("ORDER BY a PERCENTILE expression keeps the CPU plan (select it with an alias and order by the alias on this path)");
-          if (u == "DISTINCTCOUNT") throw UnsupportedOperationException("a DISTINCTCOUNT that appears only in ORDER BY keeps the CPU plan (select it to order by it on this path)");
+          if (u == "DISTINCTCOUNT" || u == "DISTINCTCOUNTHLL") throw UnsupportedOperationException("a " + u + " that appears only in ORDER BY keeps the CPU plan (select it to order by it on this path)");
           if (kind < 0) throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT are offloaded, got " + first.text);
           e.function = (AggregationFunctionType)kind;
           e.column = column;

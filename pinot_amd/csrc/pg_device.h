@@ -274,6 +274,31 @@ struct CollectParams {
 };
 constexpr uint32_t kCollectOverflow = 1u;
 
+// ---- DISTINCTCOUNTHLL (pg_scan_hll.h): HyperLogLog registers, staged as 32-bit words so that the max is one native atomic ----
+// Raw columns: scan_hll_kernel keeps every slot's 2^log2m registers in the workgroup's dynamic LDS and max-merges them into the query's row in HBM;
+// group_hll_kernel updates row g of a [num_rows x 2^log2m] matrix in HBM.  A slot is a (column, log2m) pair.
+struct HllParams {
+  DistinctParams d;                               // scan: the filter and the record; num_cols: slots (cols[] unused); num_keys / keys: group_hll_kernel's raw group ids
+  const uint8_t* fwd[kMaxAggCols];                // the raw columns' first value byte (big-endian 4- or 8-byte values, padded to whole 2048-doc tiles)
+  uint32_t* regs[kMaxAggCols];                    // HBM, zero before the launch: [2^log2m] words, GROUP BY: row g starts at word g << log2m
+  int32_t wide[kMaxAggCols];                      // 1: 8-byte values (LONG / DOUBLE), 0: 4-byte values (INT / FLOAT) -- the stored bits are what is hashed
+  int32_t log2m[kMaxAggCols];
+  int32_t lds_off[kMaxAggCols];                   // scan_hll_kernel: first word of the slot's registers in the workgroup's dynamic LDS
+  int32_t lds_words;                              // scan_hll_kernel: words of all slots together (side by side from word 0)
+  uint32_t num_rows;                              // group_hll_kernel: rows of every matrix (a raw group id at or above it updates nothing)
+};
+// Dictionary columns: hll_fold_kernel turns rows of the bitset pass's dictId bitsets into register rows (the reference's convertToHyperLogLog).
+enum HllDictKind : int32_t { kHllDictI32 = 0, kHllDictI64 = 1, kHllDictFloat = 2, kHllDictDouble = 3 };
+struct HllFoldParams {
+  const uint32_t* bits;                 // [rows x words] the bitsets of the pass
+  uint32_t* regs;                       // [rows << log2m] words, zero before the launch
+  const int32_t* dict32;                // kHllDictI32: value = base + entry
+  const unsigned long long* dict64;     // kHllDictI64: the long; kHllDictFloat: the float widened to a double; kHllDictDouble: the double
+  long long base;
+  int32_t words, cardinality, log2m, dict_kind;
+  int32_t chunks, words_per_chunk;      // workgroup b folds words [chunk * words_per_chunk, ...) of row b / chunks, chunk = b % chunks
+};
+
 // raw_set_bitmap_kernel (pg_scan_raw_set.h): the match bitmap of one PG_PRED_RAW_SET leaf
 struct RawSetBitmapParams {
   const uint8_t* fwd;                   // the raw column's first value byte (padded to whole 2048-doc tiles)

@@ -30,6 +30,7 @@
 #include "pg_launch.h"
 #include "pg_rank_image.h"
 #include "pg_raw_set_table.h"
+#include "pg_hll.h"
 
 namespace {
 
@@ -1036,6 +1037,8 @@ struct Lowered {
   uint32_t* sp_leaf_out[kMaxLeaves] = {};      // out: ScanParams.leaf_out, by LEAF node ordinal
   // the bitset pass of a DISTINCTCOUNT query (kQueryDistinctPass): plan slots of its DISTINCTCOUNT columns and of group_distinct_kernel's keys
   std::vector<int> distinct_slots, distinct_key_slots;
+  bool hll_pass = false;                       // kQueryHllPass: the slots are RAW columns with a log2m each (hll_slot_log2m), the kernels scan_hll_kernel / group_hll_kernel (pg_scan_hll.h)
+  std::vector<int> hll_slot_log2m;
   bool counts_pass = false;                    // kQueryCountsPass: the slots are PERCENTILE columns, the kernels scan_counts_kernel / group_counts_kernel (32-bit counters per dictId)
   bool collect_pass = false;                   // kQueryCollectPass: the slots are RAW columns, the kernels scan_collect_kernel / group_collect_kernel (pg_scan_collect.h)
 };
@@ -2570,7 +2573,14 @@ struct ValueList {
   std::vector<uint32_t> run_rows;       // in transit only: the raw group id of every run
   bool grouped_in_transit = false;
 };
-struct ResultInternal { std::vector<DistinctSet> distinct; std::vector<CountList> counts; std::vector<ValueList> values; };
+// The registers behind a PG_AGG_DISTINCTCOUNTHLL aggregation (pg_result_hll_registers): one rank per byte, 2^log2m bytes per row.
+struct HllSet {
+  int aggregation = 0;
+  int log2m = 0;
+  int rows = 1;                         // one (aggregation only), or one per row of group_aggregations (in transit from the pass: one per raw group id)
+  std::vector<uint8_t> registers;       // [rows << log2m]
+};
+struct ResultInternal { std::vector<DistinctSet> distinct; std::vector<CountList> counts; std::vector<ValueList> values; std::vector<HllSet> hll; };
 
 void pg_result_free(pg_result* r) {
   if (!r) return;
@@ -2598,7 +2608,11 @@ constexpr int32_t kQueryCountsPass = 1 << 27;
 // internal pg_query.flags bit, set beside one of the two above: the pass's columns are RAW columns -- their values are collected into lists, sorted
 // and run-length encoded (scan_collect_kernel / group_collect_kernel, pg_scan_collect.h) instead of counted per dictId.
 constexpr int32_t kQueryCollectPass = 1 << 26;
+// internal pg_query.flags bit, set beside kQueryDistinctPass: the pass's aggregations are DISTINCTCOUNTHLLs on RAW columns -- one launch of scan_hll_kernel /
+// group_hll_kernel (pg_scan_hll.h) builds their registers.  (HLLs on dictionary columns ride the bitset pass itself: hll_fold_kernel behind its kernel.)
+constexpr int32_t kQueryHllPass = 1 << 25;
 constexpr int32_t kQuerySetPass = kQueryDistinctPass | kQueryCountsPass;
+static inline bool is_hll_function(int32_t function) { return (function & 0xFF) == PG_AGG_DISTINCTCOUNTHLL; }
 // the one function besides COUNT(*) a pass query carries, -1: not a pass
 static inline int set_pass_function(int32_t flags) { return (flags & kQueryCountsPass) ? PG_AGG_PERCENTILE : ((flags & kQueryDistinctPass) ? PG_AGG_DISTINCTCOUNT : -1); }
 
@@ -2755,7 +2769,7 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
   std::vector<std::pair<int, int>> group_aggs;     // distinct (column, SUM | MIN | MAX)
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    if (distinct_pass ? (ag.function != PG_AGG_COUNT && ag.function != pass_function) : (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG))
+    if (distinct_pass ? (ag.function != PG_AGG_COUNT && ag.function != pass_function && !(pass_function == PG_AGG_DISTINCTCOUNT && is_hll_function(ag.function))) : (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG))
       return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.function == PG_AGG_COUNT) continue;
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
@@ -2983,14 +2997,14 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
 // ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
 // preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
-enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Counts, GroupCounts, Collect, GroupCollect, Agg };
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Counts, GroupCounts, Collect, GroupCollect, Hll, GroupHll, Agg };
 // per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
 // leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
 static const struct { int id; bool writes_leaves; } kScanKernels[] = {
   {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
   {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_SIMPLE_VALID, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
   {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_DISTINCT, true}, {PG_KERNEL_GROUP_DISTINCT, true}, {PG_KERNEL_SCAN_COUNTS, true}, {PG_KERNEL_GROUP_COUNTS, true},
-  {PG_KERNEL_SCAN_COLLECT, true}, {PG_KERNEL_GROUP_COLLECT, true}, {PG_KERNEL_SCAN_AGG, false}};
+  {PG_KERNEL_SCAN_COLLECT, true}, {PG_KERNEL_GROUP_COLLECT, true}, {PG_KERNEL_SCAN_HLL, true}, {PG_KERNEL_GROUP_HLL, true}, {PG_KERNEL_SCAN_AGG, false}};
 static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
 // general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
 // specialised kernel that won keeps it: the index handling, the leap-frog count and the batch's fallbacks go by the family.
@@ -3015,6 +3029,7 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
   // The bitset pass of a DISTINCTCOUNT query: kernels of their own (pg_scan_distinct.h) with the lane-private filter -- check_distinct_plan
   // declined the leaves that filter does not evaluate.  Everything that goes by the family (tile lists, the entry counts) is Private's.
   // On raw columns both passes collect the values (pg_scan_collect.h).
+  if (!lw.distinct_slots.empty() && lw.hll_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Hll : ScanKernel::GroupHll); }      // DISTINCTCOUNTHLL on raw columns (pg_scan_hll.h)
   if (!lw.distinct_slots.empty() && lw.collect_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Collect : ScanKernel::GroupCollect); }
   if (!lw.distinct_slots.empty() && !lw.counts_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Distinct : ScanKernel::GroupDistinct); }
   // The counts pass of a PERCENTILE query: the same, with 32-bit counters per dictId (pg_scan_counts.h).
@@ -3214,6 +3229,29 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Lowe
       g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, (k.kernel == ScanKernel::Collect ? waves_scan_collect() : waves_group_collect()) / wpb));
       break;
     }
+    case ScanKernel::Hll: {
+      // every slot's registers side by side, the filter's set area behind them, the reduction records over their start at the end -- one register set
+      // per workgroup of 16 wavefronts (the Distinct case's LDS tier; plan_distinct priced registers + set area against kLdsBudget and declined
+      // what does not fit: there is no HBM tier and no fallback here)
+      bool has_set = false;
+      if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) has_set |= sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet;
+      size_t reg_bytes = 0;
+      for (int log2m : lw.hll_slot_log2m) reg_bytes += (size_t)4 << log2m;
+      g.hist_set_off = has_set ? reg_bytes : 0;
+      g.lds = std::max(reg_bytes + (has_set ? (size_t)kSetLdsWords * 4 : 0), kCountsRecordBytes);
+      g.threads = kHistBlockThreads;
+      g.blocks = grid_blocks(seg, tiles, hist_waves, std::max(1, std::min(waves_scan_hll() / hist_waves, (int)((160 * 1024 - 2048) / (g.lds + 256)))));
+      break;
+    }
+    case ScanKernel::GroupHll: {
+      // the matrices live in HBM: workgroups of four wavefronts, the filter's set area (if any) 16 bytes in, the reduction records over the start
+      bool has_set = false;
+      if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) has_set |= sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet;
+      g.hist_set_off = has_set ? 16 : 0;
+      g.lds = std::max((size_t)(has_set ? 16 + kSetLdsWords * 4 : 0), sizeof(BlockPartial) * (size_t)wpb + 16);
+      g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, waves_group_hll() / wpb));
+      break;
+    }
     case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
     case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
@@ -3269,7 +3307,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::Agg: launch_scan_agg(g_engine.use_dma, one, typed, g.blocks, g.threads, g.lds, stream, sp); break;
     case ScanKernel::Distinct: case ScanKernel::GroupDistinct: case ScanKernel::Counts: case ScanKernel::GroupCounts:
-    case ScanKernel::Collect: case ScanKernel::GroupCollect: break;      // (launched with their own parameter block: run_aggregation)
+    case ScanKernel::Collect: case ScanKernel::GroupCollect: case ScanKernel::Hll: case ScanKernel::GroupHll: break;      // (launched with their own parameter block: run_aggregation)
   }
 }
 // What the phases of execute_impl share about one query
@@ -3411,6 +3449,22 @@ static pg_status count_from_index(QueryRun& r, int64_t* out_cardinality) {
   if (out_cardinality) *out_cardinality = (int64_t)*h_card;
   return timed ? time_index_and(ctx, out) : PG_OK;
 }
+// ---- DISTINCTCOUNTHLL (pg_scan_hll.h): helpers of the two passes ----
+static int64_t hll_nonzero(const uint8_t* registers, size_t n) { int64_t c = 0; for (size_t j = 0; j < n; ++j) c += registers[j] != 0; return c; }
+// rows << log2m packed registers, from byte `first` of the pass's host copy
+static HllSet hll_set_of(const std::vector<uint8_t>& host, size_t first, int aggregation, int log2m, long long rows) {
+  HllSet hs;
+  hs.aggregation = aggregation; hs.log2m = log2m; hs.rows = (int)rows;
+  hs.registers.assign(host.begin() + (ptrdiff_t)first, host.begin() + (ptrdiff_t)(first + ((size_t)rows << log2m)));
+  return hs;
+}
+// where hll_fold_kernel finds the long of a dictId: the device copy of the dictionary in the kernels' domain (ColumnDev)
+static void fill_hll_dictionary(const ColumnDev& col, HllFoldParams* fp) {
+  fp->dict32 = col.d_dict; fp->dict64 = col.d_dict64; fp->base = col.value_base;
+  if (col.vkind == kValI32) fp->dict_kind = kHllDictI32;
+  else if (col.vkind == kValI64) fp->dict_kind = kHllDictI64;
+  else fp->dict_kind = col.stored_type == PG_TYPE_FLOAT ? kHllDictFloat : kHllDictDouble;
+}
 // ---------------- aggregation only ----------------
 static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_request, uint64_t* host_bitmap, int64_t host_bitmap_words, int64_t* out_cardinality) {
   pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; ScanParams& sp = lw.sp;
@@ -3422,6 +3476,8 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   const char* const pass_name = pass_function == PG_AGG_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT";
   lw.counts_pass = distinct_pass && pass_function == PG_AGG_PERCENTILE;
   lw.collect_pass = distinct_pass && (q->flags & kQueryCollectPass) != 0;
+  lw.hll_pass = distinct_pass && (q->flags & kQueryHllPass) != 0;
+  std::vector<int> hll_log2m_of((size_t)std::max(na, 1), 0);      // per aggregation: the log2m of a DISTINCTCOUNTHLL (0: another function)
   std::vector<int> distinct_of((size_t)std::max(na, 1), -1);      // per aggregation: its bitset (index into lw.distinct_slots)
   std::vector<int> distinct_key_cards;
   for (int a = 0; a < na; ++a) {
@@ -3430,20 +3486,26 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       if ((q->flags & kQueryCountReadsColumn) && ag.column >= 0 && ag.column < num_cols_total) r.add_projected(ag.column);
       continue;
     }
-    if (distinct_pass && ag.function == pass_function) {
-      // a column of the bitset / counts pass: its dictId stream, one bitset / counter vector per distinct column (the same column twice shares it)
+    const bool hll_agg = distinct_pass && pass_function == PG_AGG_DISTINCTCOUNT && is_hll_function(ag.function);
+    if (hll_agg || (distinct_pass && ag.function == pass_function && !lw.hll_pass)) {
+      // a column of the bitset / counts pass: its dictId stream, one bitset / counter vector per distinct column (the same column twice shares it;
+      // a DISTINCTCOUNTHLL on a dictionary column shares the bitset too and is folded into registers behind the kernel)
       if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
-      // (the collect pass: a raw column's value bytes, one list per distinct column)
-      if (lw.collect_pass ? seg->cols[(size_t)ag.column].encoding != PG_FWD_RAW_FIXED_BYTE : seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT)
-        return fail(PG_ERR_UNSUPPORTED, "%s on %s column %s", pass_name, lw.collect_pass ? "dictionary" : "raw", seg->cols[(size_t)ag.column].name.c_str());
+      if (hll_agg) hll_log2m_of[(size_t)a] = pg::hll_log2m_of(ag.function);
+      // (the collect pass: a raw column's value bytes, one list per distinct column; the HLL pass: one register set per raw column and log2m)
+      if ((lw.collect_pass || lw.hll_pass) ? seg->cols[(size_t)ag.column].encoding != PG_FWD_RAW_FIXED_BYTE : seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT)
+        return fail(PG_ERR_UNSUPPORTED, "%s on %s column %s", pass_name, (lw.collect_pass || lw.hll_pass) ? "dictionary" : "raw", seg->cols[(size_t)ag.column].name.c_str());
       r.add_projected(ag.column);
       const int s = slot_for(&lw, seg, ag.column, false);
       if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
       pl.cols[s].in_agg = 1;
-      size_t dc = std::find(lw.distinct_slots.begin(), lw.distinct_slots.end(), s) - lw.distinct_slots.begin();
+      size_t dc = 0;
+      if (lw.hll_pass) { while (dc < lw.distinct_slots.size() && !(lw.distinct_slots[dc] == s && lw.hll_slot_log2m[dc] == hll_log2m_of[(size_t)a])) ++dc; }
+      else dc = std::find(lw.distinct_slots.begin(), lw.distinct_slots.end(), s) - lw.distinct_slots.begin();
       if (dc == lw.distinct_slots.size()) {
         if (dc >= (size_t)kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d %s columns", kMaxAggCols, pass_name);
         lw.distinct_slots.push_back(s);
+        if (lw.hll_pass) lw.hll_slot_log2m.push_back(hll_log2m_of[(size_t)a]);
       }
       distinct_of[(size_t)a] = (int)dc;
       continue;
@@ -3592,7 +3654,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       const pg_aggregation& ag = q->aggregations[a];
       pg_agg_value& v = out->aggregations[a];
       empty_agg_value(&v, (int64_t)fp.count);
-      if (ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT || ag.function == PG_AGG_PERCENTILE) continue;      // (a DISTINCTCOUNT's count is its bitset's: filled in behind the copy; a PERCENTILE's is the docs aggregated)
+      if (ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT || ag.function == PG_AGG_PERCENTILE || is_hll_function(ag.function)) continue;      // (a DISTINCTCOUNT's count is its bitset's: filled in behind the copy; a PERCENTILE's is the docs aggregated)
       const int ac = agg_slot_of[(size_t)a];
       const ColumnDev& col = seg->cols[(size_t)ag.column];
       const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
@@ -3659,7 +3721,8 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   const bool is_counts = k.kernel == ScanKernel::Counts || k.kernel == ScanKernel::GroupCounts;      // 32-bit counters: a row is `cardinality` words
   const bool is_distinct = k.kernel == ScanKernel::Distinct || k.kernel == ScanKernel::GroupDistinct || is_counts;
   const bool is_collect = k.kernel == ScanKernel::Collect || k.kernel == ScanKernel::GroupCollect;      // raw columns: lists of order images, sorted behind the kernel
-  if (k.kernel == ScanKernel::Hist || is_distinct || is_collect) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / bitset kernels keep the area in their dynamic LDS, behind the counters / bitsets)
+  const bool is_hll = k.kernel == ScanKernel::Hll || k.kernel == ScanKernel::GroupHll;      // raw columns: HyperLogLog registers, packed to bytes behind the kernel
+  if (k.kernel == ScanKernel::Hist || is_distinct || is_collect || is_hll) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / bitset kernels keep the area in their dynamic LDS, behind the counters / bitsets)
   // The bitset pass: one zeroed bitset per DISTINCTCOUNT column in the context's scratch -- under GROUP BY a matrix of one row per raw group id --
   // and one copy of all of them behind the kernel.  Behind the last row: room for the dictIds the column's WIDTH admits beyond its cardinality,
   // so that a forward index that breaks the dictionary's bound cannot make the kernel write outside the allocation.
@@ -3667,6 +3730,12 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   std::vector<std::vector<uint32_t>> distinct_host;      // per bitset: where its copy lands -- the vector that becomes the result's DistinctSet, no second host copy
   std::vector<size_t> distinct_first;      // per bitset: its first word in the scratch
   long long distinct_rows = 1;
+  // DISTINCTCOUNTHLL: per aggregation (dictionary form) / per slot (raw form) the first staged register word in the scratch; the staged words are
+  // packed to bytes behind them and land in hll_host in the same order
+  std::vector<size_t> hll_first((size_t)std::max(na, 1), 0), hll_slot_first;
+  std::vector<int> hll_same_as((size_t)std::max(na, 1), -1);      // dictionary form: an earlier aggregation on the same column and log2m, whose registers this one shares
+  size_t hll_staged_words = 0, hll_staged_first = 0;
+  std::vector<uint8_t> hll_host;
   struct SyncOnExit { hipStream_t stream; bool armed; ~SyncOnExit() { if (armed) (void)hipStreamSynchronize(stream); } } distinct_copy{ctx->stream, false};      // (nothing frees distinct_host under the copy)
   if (is_distinct) {
     memset(&dp, 0, sizeof(dp));
@@ -3692,13 +3761,64 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       dp.keys[g].fwd = kc.fwd; dp.keys[g].bits = kc.bits; dp.keys[g].mult = mult;
       mult *= (uint32_t)distinct_key_cards[g];
     }
-    st = ensure_distinct(seg, ctx, total + slack); if (st != PG_OK) return st;
+    // DISTINCTCOUNTHLLs on these columns: behind the bitsets one zeroed register matrix of 32-bit words per such aggregation (hll_fold_kernel's
+    // target), and behind those the same registers packed to bytes (hll_pack_kernel's) -- the only part of them that is copied
+    size_t hll_words = 0;
+    const size_t hll_base = (total + slack + 3) & ~(size_t)3;      // (sixteen-byte aligned: hll_pack_kernel reads four registers per load)
+    for (int a = 0; a < na; ++a) {
+      if (hll_log2m_of[(size_t)a] == 0) continue;
+      // (the same column at the same log2m twice: one register matrix, one fold)
+      hll_same_as[(size_t)a] = -1;
+      for (int b = 0; b < a && hll_same_as[(size_t)a] < 0; ++b)
+        if (hll_log2m_of[(size_t)b] == hll_log2m_of[(size_t)a] && distinct_of[(size_t)b] == distinct_of[(size_t)a]) hll_same_as[(size_t)a] = b;
+      if (hll_same_as[(size_t)a] >= 0) { hll_first[(size_t)a] = hll_first[(size_t)hll_same_as[(size_t)a]]; continue; }
+      hll_first[(size_t)a] = hll_base + hll_words;
+      hll_words += (size_t)distinct_rows << hll_log2m_of[(size_t)a];
+    }
+    st = ensure_distinct(seg, ctx, hll_base + hll_words + hll_words / 4); if (st != PG_OK) return st;
     for (size_t c = 0; c < lw.distinct_slots.size(); ++c) dp.cols[c].set_bits = ctx->d_distinct + distinct_first[c];
-    HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, (total + slack) * 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, (hll_base + hll_words) * 4, ctx->stream));
+    hll_staged_words = hll_words; hll_staged_first = hll_base;
     if (out) {
       distinct_host.resize(lw.distinct_slots.size());
-      for (size_t c = 0; c < lw.distinct_slots.size(); ++c) distinct_host[c].resize((size_t)distinct_rows * (size_t)dp.cols[c].words);
+      // (a bitset that only HLLs use stays on the device)
+      for (int a = 0; a < na; ++a)
+        if (distinct_of[(size_t)a] >= 0 && hll_log2m_of[(size_t)a] == 0) distinct_host[(size_t)distinct_of[(size_t)a]].resize((size_t)distinct_rows * (size_t)dp.cols[distinct_of[(size_t)a]].words);
+      hll_host.resize(hll_words);
     }
+  }
+  // The HLL pass on raw columns: one zeroed register row per slot in the same scratch -- under GROUP BY a matrix of one row per raw group id -- and
+  // the packed bytes behind them.
+  HllParams hp;
+  if (is_hll) {
+    memset(&hp, 0, sizeof(hp));
+    for (int card : distinct_key_cards) distinct_rows *= card;
+    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "%s GROUP BY over %lld raw keys", pass_name, distinct_rows);
+    size_t hll_words = 0;
+    int lds_off = 0;
+    hp.d.num_cols = (int32_t)lw.distinct_slots.size();
+    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+      const DevColumn& dc = pl.cols[lw.distinct_slots[c]];
+      hp.fwd[c] = dc.fwd; hp.wide[c] = (dc.vkind == kValI64 || dc.vkind == kValF64) ? 1 : 0;
+      hp.log2m[c] = lw.hll_slot_log2m[c]; hp.lds_off[c] = lds_off;
+      lds_off += 1 << hp.log2m[c];
+      hll_slot_first.push_back(hll_words);
+      hll_words += (size_t)distinct_rows << hp.log2m[c];
+    }
+    hp.lds_words = k.kernel == ScanKernel::Hll ? lds_off : 0;
+    hp.num_rows = (uint32_t)distinct_rows;
+    hp.d.num_keys = (int32_t)lw.distinct_key_slots.size();
+    uint32_t mult = 1;
+    for (size_t g = 0; g < lw.distinct_key_slots.size(); ++g) {
+      const DevColumn& kc = pl.cols[lw.distinct_key_slots[g]];
+      hp.d.keys[g].fwd = kc.fwd; hp.d.keys[g].bits = kc.bits; hp.d.keys[g].mult = mult;
+      mult *= (uint32_t)distinct_key_cards[g];
+    }
+    st = ensure_distinct(seg, ctx, hll_words + hll_words / 4); if (st != PG_OK) return st;
+    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) hp.regs[c] = ctx->d_distinct + hll_slot_first[c];
+    HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, hll_words * 4, ctx->stream));
+    hll_staged_words = hll_words; hll_staged_first = 0;
+    if (out) hll_host.resize(hll_words);
   }
   // The collect pass: one list of `capacity` 64-bit images per raw column in the same scratch (GROUP BY: the docs' raw group ids beside them),
   // the sort's second buffers, the run arrays and rocPRIM's scratch behind them.  The capacity is the segment's docs -- what the plan-time
@@ -3787,9 +3907,13 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     *ctx->h_partial = g;
   } else {
     // (the bitsets' copy follows the kernel on the stream: the polled record does not cover it)
-    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm || is_distinct || is_collect;
+    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm || is_distinct || is_collect || is_hll;
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    if (is_collect) {
+    if (is_hll) {
+      hp.d.scan = sp;
+      if (k.kernel == ScanKernel::Hll) launch_scan_hll(grid.blocks, grid.lds, ctx->stream, hp);
+      else launch_group_hll(grid.blocks, grid.lds, ctx->stream, hp);
+    } else if (is_collect) {
       cp.d.scan = sp;
       if (k.kernel == ScanKernel::Collect) launch_scan_collect(grid.blocks, grid.lds, ctx->stream, cp);
       else launch_group_collect(grid.blocks, grid.lds, ctx->stream, cp);
@@ -3810,6 +3934,27 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     if (is_collect) {
       distinct_copy.armed = true;
       HIP_TRY(hipMemcpyAsync(collect_head, ctx->d_distinct, 16, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (is_distinct && hll_staged_words != 0) {
+      // the bitsets' rows -> register rows, one fold per DISTINCTCOUNTHLL aggregation over its column's bitset
+      for (int a = 0; a < na; ++a) {
+        if (hll_log2m_of[(size_t)a] == 0 || hll_same_as[(size_t)a] >= 0) continue;
+        const ColumnDev& col = seg->cols[(size_t)q->aggregations[a].column];
+        const DistinctCol& bits = dp.cols[distinct_of[(size_t)a]];
+        HllFoldParams fp;
+        memset(&fp, 0, sizeof(fp));
+        fp.bits = bits.set_bits; fp.regs = ctx->d_distinct + hll_first[(size_t)a];
+        fp.words = bits.words; fp.cardinality = col.cardinality; fp.log2m = hll_log2m_of[(size_t)a];
+        fill_hll_dictionary(col, &fp);
+        launch_hll_fold(distinct_rows, ctx->stream, fp);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    if ((is_hll || is_distinct) && hll_staged_words != 0) {
+      uint8_t* const packed = reinterpret_cast<uint8_t*>(ctx->d_distinct + hll_staged_first + hll_staged_words);
+      launch_hll_pack(ctx->d_distinct + hll_staged_first, packed, hll_staged_words, seg->num_cus, ctx->stream);
+      HIP_TRY(hipGetLastError());
+      if (!hll_host.empty()) { distinct_copy.armed = true; HIP_TRY(hipMemcpyAsync(hll_host.data(), packed, hll_host.size(), hipMemcpyDeviceToHost, ctx->stream)); }
     }
     if (!folded) {
       finalize_partials_kernel<<<dim3(1), dim3(kBlockThreads), 0, ctx->stream>>>(ctx->d_partials, blocks, g_engine.direct_result ? ctx->h_record_dev : nullptr, seq,
@@ -3874,10 +4019,15 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     for (int a = na - 1; a >= 0; --a) {      // (the last aggregation on a column takes the copy itself, earlier ones on the same column a copy of it)
       const int dc = distinct_of[(size_t)a];
       if (dc < 0) continue;
+      if (hll_log2m_of[(size_t)a] != 0) {
+        sets->hll.push_back(hll_set_of(hll_host, hll_first[(size_t)a] - hll_staged_first, a, hll_log2m_of[(size_t)a], distinct_rows));
+        if (lw.distinct_key_slots.empty()) out->aggregations[a].count = hll_nonzero(sets->hll.back().registers.data(), sets->hll.back().registers.size());
+        continue;
+      }
       DistinctSet ds;
       ds.aggregation = a; ds.num_words = dp.cols[dc].words; ds.rows = (int)distinct_rows;
       bool again = false;
-      for (int b = 0; b < a; ++b) again |= distinct_of[(size_t)b] == dc;
+      for (int b = 0; b < a; ++b) again |= distinct_of[(size_t)b] == dc && hll_log2m_of[(size_t)b] == 0;
       if (again) ds.words = distinct_host[(size_t)dc]; else ds.words = std::move(distinct_host[(size_t)dc]);
       if (lw.distinct_key_slots.empty() && !is_counts) {      // (PERCENTILE: count stays the docs aggregated, the list's length)
         int64_t card = 0;
@@ -3949,7 +4099,19 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       out->internal = lists.release();
     }
   }
-  if (is_distinct) trim_distinct(seg, ctx);
+  if (out && is_hll) {
+    // (the stream was synchronised: the packed registers are in hll_host)  One set per aggregation; aggregation only: its count is the non-zero registers
+    distinct_copy.armed = false;
+    std::unique_ptr<ResultInternal> sets(new ResultInternal());
+    for (int a = 0; a < na; ++a) {
+      const int dc = distinct_of[(size_t)a];
+      if (dc < 0) continue;
+      sets->hll.push_back(hll_set_of(hll_host, hll_slot_first[(size_t)dc], a, hp.log2m[dc], distinct_rows));
+      if (lw.distinct_key_slots.empty()) out->aggregations[a].count = hll_nonzero(sets->hll.back().registers.data(), sets->hll.back().registers.size());
+    }
+    out->internal = sets.release();
+  }
+  if (is_distinct || is_hll) trim_distinct(seg, ctx);
   if (out && k.kernel == ScanKernel::PrivateFsm) {
     // (the stream was synchronised: the walk's count is in the pinned counter)
     out->stats.num_entries_scanned_in_filter = (int64_t)*ctx->h_filter_entries;
@@ -5375,10 +5537,24 @@ static pg_status execute_one(pg_segment* segment, const pg_query* query, pg_resu
 constexpr int32_t kQueryPublicFlags = PG_QUERY_NULL_HANDLING | PG_QUERY_STATS_UPPER_BOUND_OK;
 static bool reserved_flags(const pg_query* q) { return q != nullptr && (q->flags & ~kQueryPublicFlags) != 0; }
 static pg_status fail_reserved_flags(const pg_query* q) { return fail(PG_ERR_INVALID_ARGUMENT, "pg_query.flags 0x%x sets reserved bits", (unsigned)q->flags); }
-static bool has_distinct(const pg_query* q) {
+static bool has_distinct(const pg_query* q) {      // (a DISTINCTCOUNTHLL is planned and executed with the DISTINCTCOUNTs: plan_distinct / execute_distinct)
   if (!q || !q->aggregations) return false;
-  for (int a = 0; a < q->num_aggregations; ++a) if (q->aggregations[a].function == PG_AGG_DISTINCTCOUNT) return true;
+  for (int a = 0; a < q->num_aggregations; ++a) if (q->aggregations[a].function == PG_AGG_DISTINCTCOUNT || is_hll_function(q->aggregations[a].function)) return true;
   return false;
+}
+// The function words of a query: bits above the low byte belong to PG_AGG_HLL(log2m) alone, and its log2m lies in [PG_HLL_MIN_LOG2M, PG_HLL_MAX_LOG2M].
+static const pg_aggregation* bad_function_word(const pg_query* q) {
+  if (!q || !q->aggregations) return nullptr;
+  for (int a = 0; a < q->num_aggregations; ++a) {
+    const int32_t f = q->aggregations[a].function;
+    if ((f & ~0xFF) == 0) continue;
+    if (!is_hll_function(f) || (f >> 8) < PG_HLL_MIN_LOG2M || (f >> 8) > PG_HLL_MAX_LOG2M) return &q->aggregations[a];
+  }
+  return nullptr;
+}
+static pg_status fail_function_word(const pg_aggregation* ag) {
+  if (is_hll_function(ag->function)) return fail(PG_ERR_INVALID_ARGUMENT, "DISTINCTCOUNTHLL with log2m %d: outside [%d, %d]", (int)(ag->function >> 8), PG_HLL_MIN_LOG2M, PG_HLL_MAX_LOG2M);
+  return fail(PG_ERR_INVALID_ARGUMENT, "aggregation function word 0x%x sets bits above the function's byte", (unsigned)ag->function);
 }
 static pg_status check_ordinary_query(const pg_segment* segment, const pg_query* query);
 // ---- PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns: the collect pass (pg_scan_collect.h) ----
@@ -5453,7 +5629,14 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
   const bool null_handling = (q->flags & PG_QUERY_NULL_HANDLING) != 0;
   if (na < 0 || ng < 0 || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
   if (q->num_filter_nodes > 0 && (!q->filter || !q->predicates)) return fail(PG_ERR_INVALID_ARGUMENT, "filter nodes without predicates");
+  bool has_hll = false;
+  for (int a = 0; a < na; ++a) has_hll |= is_hll_function(q->aggregations[a].function);
+  const char* const who = has_hll ? "DISTINCTCOUNTHLL" : "DISTINCTCOUNT";      // (the messages of a query without an HLL read as they always have)
   std::vector<int> distinct_cols, raw_cols, projected;
+  std::vector<std::pair<int, int>> hll_raw_slots;      // DISTINCTCOUNTHLL on raw columns: distinct (column, log2m) pairs, one register set each
+  std::vector<std::pair<int, int>> hll_dict_slots;     // ... on dictionary columns: the same pairs, one fold and one register matrix each
+  std::vector<int> hll_dict_cols, hll_aggs_log2m;      // ... on dictionary columns: the columns (they share distinct_cols' bitsets); every HLL aggregation's log2m
+  bool plain_distinct = false;
   auto project = [&](int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); };
   bool only_distinct_and_count = true, nullable_input = false;
   for (int a = 0; a < na; ++a) {
@@ -5469,43 +5652,67 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
     project(ag.column);
     nullable_input |= seg->cols[(size_t)ag.column].d_null_bitmap != nullptr;
-    if (ag.function != PG_AGG_DISTINCTCOUNT) { only_distinct_and_count = false; continue; }
+    if (ag.function == PG_AGG_PERCENTILE) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE beside %s in one query -- CPU plan", has_hll ? "DISTINCTCOUNTHLL" : "DISTINCTCOUNT");
+    const bool hll = is_hll_function(ag.function);
+    if (ag.function != PG_AGG_DISTINCTCOUNT && !hll) { only_distinct_and_count = false; continue; }
     const ColumnDev& col = seg->cols[(size_t)ag.column];
     // a raw column: its values are collected, sorted and run-length encoded (the collect pass); a dictionary column: its dictId bitset
     const bool raw = col.encoding != PG_FWD_FIXED_BIT_DICT;
-    if (raw) { const pg_status cst = plan_collect_column(col, "DISTINCTCOUNT"); if (cst != PG_OK) return cst; }
+    if (!hll && raw) { const pg_status cst = plan_collect_column(col, "DISTINCTCOUNT"); if (cst != PG_OK) return cst; }
     if (null_handling && col.d_null_bitmap != nullptr)
-      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on column %s, which carries a null value vector, under null handling -- CPU plan", col.name.c_str());
+      return fail(PG_ERR_UNSUPPORTED, "%s on column %s, which carries a null value vector, under null handling -- CPU plan", hll ? "DISTINCTCOUNTHLL" : "DISTINCTCOUNT", col.name.c_str());
+    if (hll) {
+      // a raw column: one pass of scan_hll_kernel / group_hll_kernel (no switch, no sort); a dictionary column: one more user of the column's bitset
+      hll_aggs_log2m.push_back(pg::hll_log2m_of(ag.function));
+      if (raw) {
+        if (col.encoding != PG_FWD_RAW_FIXED_BYTE || col.stored_type < PG_TYPE_INT || col.stored_type > PG_TYPE_DOUBLE || col.d_fwd == nullptr)
+          return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on column %s: neither dictionary-encoded nor raw fixed-width INT / LONG / FLOAT / DOUBLE -- CPU plan", col.name.c_str());
+        const std::pair<int, int> slot(ag.column, hll_aggs_log2m.back());
+        if (std::find(hll_raw_slots.begin(), hll_raw_slots.end(), slot) == hll_raw_slots.end()) hll_raw_slots.push_back(slot);
+        continue;
+      }
+      if (std::find(hll_dict_cols.begin(), hll_dict_cols.end(), ag.column) == hll_dict_cols.end()) hll_dict_cols.push_back(ag.column);
+      const std::pair<int, int> slot(ag.column, hll_aggs_log2m.back());
+      if (std::find(hll_dict_slots.begin(), hll_dict_slots.end(), slot) == hll_dict_slots.end()) hll_dict_slots.push_back(slot);
+    } else {
+      plain_distinct = true;
+    }
     std::vector<int>& into = raw ? raw_cols : distinct_cols;
     if (std::find(into.begin(), into.end(), ag.column) == into.end()) into.push_back(ag.column);
   }
   if (!raw_cols.empty() && !distinct_cols.empty())
     return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT on raw column %s and dictionary column %s in one query -- CPU plan", seg->cols[(size_t)raw_cols[0]].name.c_str(), seg->cols[(size_t)distinct_cols[0]].name.c_str());
-  if ((int)(distinct_cols.size() + raw_cols.size()) > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d DISTINCTCOUNT columns", kMaxAggCols);
+  if (!hll_raw_slots.empty() && !hll_dict_cols.empty())
+    return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on raw column %s and dictionary column %s in one query -- CPU plan", seg->cols[(size_t)hll_raw_slots[0].first].name.c_str(), seg->cols[(size_t)hll_dict_cols[0]].name.c_str());
+  if (!hll_raw_slots.empty() && plain_distinct)
+    return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on raw column %s beside a DISTINCTCOUNT in one query -- CPU plan", seg->cols[(size_t)hll_raw_slots[0].first].name.c_str());
+  if ((int)(distinct_cols.size() + raw_cols.size()) > kMaxAggCols || (int)hll_raw_slots.size() > kMaxAggCols || (int)hll_dict_slots.size() > kMaxAggCols)
+    return fail(PG_ERR_UNSUPPORTED, has_hll ? "more than %d DISTINCTCOUNTHLL columns" : "more than %d DISTINCTCOUNT columns", kMaxAggCols);
   // the bitset kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it
-  bool match_all = q->num_filter_nodes == 0;
+  bool match_all = q->num_filter_nodes == 0, filter_stages_set = false;
   for (int n = 0; n < q->num_filter_nodes; ++n) {
     if (q->filter[n].op != PG_FILTER_LEAF) continue;
     if (q->filter[n].predicate < 0 || q->filter[n].predicate >= q->num_predicates) return fail(PG_ERR_INVALID_ARGUMENT, "filter node %d: bad predicate index", n);
     const pg_predicate& pr = q->predicates[q->filter[n].predicate];
     if (pr.kind == PG_PRED_RAW_RANGE && pr.column >= 0 && pr.column < num_cols_total && seg->cols[(size_t)pr.column].stored_type != PG_TYPE_INT)
-      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT beside a range predicate on raw LONG / FLOAT / DOUBLE column %s -- CPU plan", seg->cols[(size_t)pr.column].name.c_str());
+      return fail(PG_ERR_UNSUPPORTED, "%s beside a range predicate on raw LONG / FLOAT / DOUBLE column %s -- CPU plan", who, seg->cols[(size_t)pr.column].name.c_str());
+    if (pr.kind == PG_PRED_DICT_SET) filter_stages_set = true;
     if (q->num_filter_nodes == 1) match_all = (pr.kind == PG_PRED_MATCH_ALL && !pr.exclusive) || (pr.kind == PG_PRED_MATCH_NONE && pr.exclusive);
   }
   if (ng > 0) {
     // GROUP BY, first cut: an int key space that numGroupsLimit can never cut, keys the kernel decodes as dictIds, a bit matrix within the cap
-    if (ng > kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT with more than %d group-by columns -- CPU plan", kMaxDistinctKeys);
+    if (ng > kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "%s with more than %d group-by columns -- CPU plan", who, kMaxDistinctKeys);
     std::vector<int> cards;
     for (int g = 0; g < ng; ++g) {
       int c = q->group_by_columns[g];
       if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
       project(c);
       if (null_handling && seg->cols[(size_t)c].d_null_bitmap != nullptr)
-        return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped by nullable column %s under null handling -- CPU plan", seg->cols[(size_t)c].name.c_str());
+        return fail(PG_ERR_UNSUPPORTED, "%s grouped by nullable column %s under null handling -- CPU plan", who, seg->cols[(size_t)c].name.c_str());
       if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
         const int image = seg->cols[(size_t)c].keyimage_column;
         if (image < 0 || seg->cols[(size_t)image].rank_image)
-          return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped by raw column %s, which is not keyed by offset -- CPU plan", seg->cols[(size_t)c].name.c_str());
+          return fail(PG_ERR_UNSUPPORTED, "%s grouped by raw column %s, which is not keyed by offset -- CPU plan", who, seg->cols[(size_t)c].name.c_str());
         c = image;
       }
       cards.push_back(seg->cols[(size_t)c].cardinality);
@@ -5513,12 +5720,12 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
     HashPlan hash_plan;
     const pg_status hst = plan_hash_holder(seg, cards, &hash_plan);
     if (hst != PG_OK) return hst;
-    if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", hash_plan.kind);
+    if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "%s grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", who, hash_plan.kind);
     unsigned long long product = 1;
     for (int card : cards) product *= (unsigned long long)std::max(card, 1);
     const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
     if (product > (unsigned long long)limit)
-      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", product, limit);
+      return fail(PG_ERR_UNSUPPORTED, "%s grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", who, product, limit);
     unsigned long long matrix = 0, slack = 0;
     for (int c : distinct_cols) {
       matrix += product * (unsigned long long)((seg->cols[(size_t)c].cardinality + 31) / 32) * 4ull;
@@ -5529,12 +5736,27 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
       return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT bit matrices of %llu bytes exceed PG_DISTINCT_GROUP_MAX_BYTES (%llu) -- CPU plan", matrix, (unsigned long long)PG_DISTINCT_GROUP_MAX_BYTES);
     if (matrix > g_engine.group_table_bytes)
       return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT bit matrices of %llu bytes exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", matrix, (unsigned long long)g_engine.group_table_bytes);
+    // the register matrices: one row of 2^log2m staged 32-bit words per raw group id -- per HLL aggregation (dictionary form) or per slot (raw form)
+    unsigned long long registers = 0;
+    if (!hll_raw_slots.empty()) for (const auto& slot : hll_raw_slots) registers += product * (4ull << slot.second);
+    else for (const auto& slot : hll_dict_slots) registers += product * (4ull << slot.second);
+    if (registers > PG_HLL_GROUP_MAX_BYTES)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL register matrices of %llu bytes exceed PG_HLL_GROUP_MAX_BYTES (%llu) -- CPU plan", registers, (unsigned long long)PG_HLL_GROUP_MAX_BYTES);
+    if (registers > g_engine.group_table_bytes)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL register matrices of %llu bytes exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", registers, (unsigned long long)g_engine.group_table_bytes);
+  } else if (!hll_raw_slots.empty()) {
+    // scan_hll_kernel keeps every slot's registers in LDS beside the filter's staged set area and the reduction records: there is no HBM tier
+    size_t lds = 0;
+    for (const auto& slot : hll_raw_slots) lds += (size_t)4 << slot.second;
+    if (filter_stages_set && g_engine.set_lds) lds += (size_t)kSetLdsWords * 4;
+    if (std::max(lds, kCountsRecordBytes) > kLdsBudget)
+      return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL registers of %zu bytes (with the filter's set area) exceed the %zu bytes of LDS a workgroup has -- CPU plan", lds, kLdsBudget);
   }
   plan->num_projected = (int)projected.size();
   plan->base_aggs.assign(q->aggregations, q->aggregations + na);
   plan->pass_aggs.assign(q->aggregations, q->aggregations + na);
   for (int a = 0; a < na; ++a) {
-    if (q->aggregations[a].function == PG_AGG_DISTINCTCOUNT) plan->base_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+    if (q->aggregations[a].function == PG_AGG_DISTINCTCOUNT || is_hll_function(q->aggregations[a].function)) plan->base_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
     else plan->pass_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
   }
   plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
@@ -5545,12 +5767,13 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
     if (cst != PG_OK) return cst;
     plan->pass.flags |= kQueryCollectPass;
   }
+  if (!hll_raw_slots.empty()) plan->pass.flags |= kQueryHllPass;
   // the dictionary answers under the conditions of the MIN / MAX dictionary path (answer_from_metadata): every function of the query that way
   // (a raw column has no dictionary to read: it is always scanned)
-  plan->from_dictionary = ng == 0 && match_all && !(null_handling && nullable_input) && raw_cols.empty();
+  plan->from_dictionary = ng == 0 && match_all && !(null_handling && nullable_input) && raw_cols.empty() && hll_raw_slots.empty();
   for (int a = 0; a < na && plan->from_dictionary; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    plan->from_dictionary = ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT ||
+    plan->from_dictionary = ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT || is_hll_function(ag.function) ||
                             ((ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) && seg->cols[(size_t)ag.column].encoding == PG_FWD_FIXED_BIT_DICT);
   }
   plan->pass_alone = ng == 0 && !plan->from_dictionary && only_distinct_and_count;
@@ -5576,6 +5799,24 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
   std::unique_ptr<ResultInternal> sets(new ResultInternal());
   if (plan.from_dictionary) {
     for (int a = 0; a < na; ++a) {
+      if (is_hll_function(q->aggregations[a].function)) {
+        // the whole dictionary folded into registers (the reference converts the dictionary's values; nothing is scanned)
+        const ColumnDev& col = seg->cols[(size_t)q->aggregations[a].column];
+        HllSet hs;
+        hs.aggregation = a; hs.log2m = pg::hll_log2m_of(q->aggregations[a].function); hs.rows = 1;
+        hs.registers.assign((size_t)1 << hs.log2m, 0);
+        for (int d = 0; d < col.cardinality; ++d) {
+          uint64_t v;
+          if (col.vkind != kValF64) v = (uint64_t)col.h_dict_i64[(size_t)d];
+          else { memcpy(&v, &col.h_dict_f64[(size_t)d], 8); if (col.stored_type == PG_TYPE_FLOAT) v = pg::hll_long_of_bits32(pg::hll_float_bits_of_widened(v)); }
+          const uint32_t x = pg::hll_hash_long(v);
+          uint8_t& reg = hs.registers[pg::hll_index(x, hs.log2m)];
+          reg = std::max(reg, (uint8_t)pg::hll_rank(x, hs.log2m));
+        }
+        distinct_agg_value(&out->aggregations[a], hll_nonzero(hs.registers.data(), hs.registers.size()));
+        sets->hll.push_back(std::move(hs));
+        continue;
+      }
       if (q->aggregations[a].function != PG_AGG_DISTINCTCOUNT) continue;
       const int card = seg->cols[(size_t)q->aggregations[a].column].cardinality;
       DistinctSet ds;
@@ -5607,6 +5848,7 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
   }
   if (q->num_group_by == 0) {
     for (const DistinctSet& ds : got->distinct) out->aggregations[ds.aggregation] = pass.aggregations[ds.aggregation];
+    for (const HllSet& hs : got->hll) out->aggregations[hs.aggregation] = pass.aggregations[hs.aggregation];
     out->internal = got.release();
     pg_result_free(&pass);
     return PG_OK;
@@ -5631,6 +5873,23 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
     m.words.resize((size_t)num_groups * (size_t)m.num_words);
     m.words.shrink_to_fit();
     sets->distinct.push_back(std::move(m));
+  }
+  for (HllSet& m : got->hll) {
+    const size_t m_regs = (size_t)1 << m.log2m;
+    int64_t previous = -1;
+    for (int k = 0; k < num_groups; ++k) {
+      const int64_t row = out->group_ids[k];
+      if (row <= previous || row >= m.rows) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the DISTINCTCOUNTHLL matrix of %d rows, or out of order", (long long)row, m.rows); }
+      previous = row;
+      const uint8_t* src = m.registers.data() + (size_t)row * m_regs;
+      const int64_t nonzero = hll_nonzero(src, m_regs);
+      if (row != k) memmove(m.registers.data() + (size_t)k * m_regs, src, m_regs);
+      distinct_agg_value(&out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation], nonzero);
+    }
+    m.rows = num_groups;
+    m.registers.resize((size_t)num_groups * m_regs);
+    m.registers.shrink_to_fit();
+    sets->hll.push_back(std::move(m));
   }
   out->internal = sets.release();
   return PG_OK;
@@ -5669,6 +5928,7 @@ static pg_status plan_percentile(const pg_segment* seg, const pg_query* q, Perce
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
     if (ag.function == PG_AGG_DISTINCTCOUNT) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE beside DISTINCTCOUNT in one query -- CPU plan");
+    if (is_hll_function(ag.function)) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE beside DISTINCTCOUNTHLL in one query -- CPU plan");
     if (ag.function == PG_AGG_COUNT) {
       if (null_handling && ag.column >= 0) { project(ag.column); only_percentile_and_count = false; }
       continue;
@@ -6473,6 +6733,7 @@ pg_status finish_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_res
 // segment's plan cache like a batch item's.  Everything else takes execute_one as before.  PINOT_GPU_GROUP_ONE_LAUNCH=0: never.
 pg_status pg_execute(pg_segment* segment, const pg_query* query, pg_result* out_result) {
   if (reserved_flags(query)) { if (out_result) memset(out_result, 0, sizeof(*out_result)); return fail_reserved_flags(query); }
+  if (const pg_aggregation* bad = bad_function_word(query)) { if (out_result) memset(out_result, 0, sizeof(*out_result)); return fail_function_word(bad); }
   if (has_percentile(query)) return execute_percentile(segment, query, out_result);
   if (has_distinct(query)) return execute_distinct(segment, query, out_result);
   // (PG_CFG_PROFILE_WAVES: the per-wave phase counters live in the kernels execute_one launches itself, and its HIP events bracket ALL of a
@@ -6552,6 +6813,7 @@ pg_status pg_execute_batch(pg_segment* const* segments, const pg_query* const* q
     const int i = todo[(size_t)t];
     if (!segments[i] || !queries[i]) { statuses[i] = PG_ERR_INVALID_ARGUMENT; errors[(size_t)i] = "null segment or query"; return; }
     if (reserved_flags(queries[i])) { statuses[i] = fail_reserved_flags(queries[i]); errors[(size_t)i] = g_error; return; }
+    if (const pg_aggregation* bad = bad_function_word(queries[i])) { statuses[i] = fail_function_word(bad); errors[(size_t)i] = g_error; return; }
     const auto t_item = trace ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
     // (a query that may enter the plan cache is lowered from a copy of its own: the item's conversion reads the query after this call has returned)
     const pg_query* q = queries[i];
@@ -6724,6 +6986,7 @@ pg_status pg_query_check(const pg_segment* segment, const pg_query* query) {
   if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
   if (!segment || !query) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
   if (reserved_flags(query)) return fail_reserved_flags(query);
+  if (const pg_aggregation* bad = bad_function_word(query)) return fail_function_word(bad);
   if (has_percentile(query)) { PercentilePlan plan; return plan_percentile(segment, query, &plan); }
   if (has_distinct(query)) { DistinctPlan plan; return plan_distinct(segment, query, &plan); }
   return check_ordinary_query(segment, query);
@@ -6742,6 +7005,22 @@ pg_status pg_result_distinct_dict_ids(const pg_result* result, int32_t aggregati
     return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
   *out_words = ds->words.data() + (size_t)(grouped ? group_row : 0) * (size_t)ds->num_words;
   *out_num_words = ds->num_words;
+  return PG_OK;
+}
+
+pg_status pg_result_hll_registers(const pg_result* result, int32_t aggregation, int32_t group_row, const uint8_t** out_registers, int32_t* out_num_registers) {
+  if (!result || !out_registers || !out_num_registers) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  *out_registers = nullptr; *out_num_registers = 0;
+  const ResultInternal* sets = static_cast<const ResultInternal*>(result->internal);
+  if (aggregation < 0 || aggregation >= result->num_aggregations) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d out of range", aggregation);
+  const HllSet* hs = nullptr;
+  if (sets) for (const HllSet& s : sets->hll) if (s.aggregation == aggregation) hs = &s;
+  if (!hs) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d is not a PG_AGG_DISTINCTCOUNTHLL", aggregation);
+  const bool grouped = result->group_aggregations != nullptr;
+  if (grouped ? (group_row < 0 || group_row >= result->num_groups || group_row >= hs->rows) : group_row != -1)
+    return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
+  *out_registers = hs->registers.data() + ((size_t)(grouped ? group_row : 0) << hs->log2m);
+  *out_num_registers = 1 << hs->log2m;
   return PG_OK;
 }
 

@@ -146,6 +146,18 @@ struct CollectRuns {                 // where the runs are, device pointers into
 hipError_t collect_sort_temp_bytes(size_t n, bool grouped, size_t* out_bytes);
 hipError_t collect_sort_runs(const CollectSort& s, size_t n, int num_cus, hipStream_t stream, CollectRuns* out);
 
+// scan_hll_kernel: DISTINCTCOUNTHLL of up to kMaxAggCols raw (column, log2m) slots, their registers in `lds` bytes of dynamic LDS (workgroups of
+// kHistBlockThreads), max-merged into the query's rows in HBM -- pg_scan_hll.h
+void launch_scan_hll(int blocks, size_t lds, hipStream_t stream, const HllParams& hp);
+int waves_scan_hll();
+// group_hll_kernel: the same under GROUP BY, one register row per raw group id in HBM (workgroups of 256; `lds`: the filter's set area + the reduction scratch)
+void launch_group_hll(int blocks, size_t lds, hipStream_t stream, const HllParams& hp);
+int waves_group_hll();
+// hll_fold_kernel: `rows` rows of a dictionary column's dictId bitsets -> register rows (chunks / words_per_chunk are set here); rows x chunks workgroups
+void launch_hll_fold(long long rows, hipStream_t stream, HllFoldParams fp);
+// hll_pack_kernel: n staged 32-bit registers (a multiple of four) -> n bytes
+void launch_hll_pack(const uint32_t* words, uint8_t* bytes, unsigned long long n, int num_cus, hipStream_t stream);
+
 // scan_private_typed_kernel: lane-private scan for raw / 8-byte aggregated columns (pg_scan_typed.h)
 void launch_scan_private_typed(int agg_cols, int blocks, hipStream_t stream, const ScanParams& p);      // instantiated for 1, 2 and kMaxAggCols slots
 int waves_scan_private_typed(int agg_cols);

@@ -308,6 +308,85 @@ def combine_counts(sql, blocks, key_types=()):
                                                  rc.ctypes.data, C.byref(st)), st)
 
 
+def combine_hll(sql, blocks, key_types=()):
+    """The combine of DISTINCTCOUNTHLL sketches built on the host (no device): ph_combine_hll.  `blocks` as for combine_counts; the cell of a
+    DISTINCTCOUNTHLL function carries a sixth element, the segment's registers (2^log2m uint8 ranks; an empty sequence: an empty sketch)."""
+    import numpy as np
+    lib = _lib()
+    P = C.POINTER
+    lib.ph_combine_hll.restype = C.c_void_p
+    lib.ph_combine_hll.argtypes = [C.c_char_p, C.c_int32, P(C.c_int64), P(C.c_int32), P(C.c_int64), P(C.c_double), P(C.c_char_p), P(C.c_uint8), P(C.c_int64),
+                                   P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_uint8), C.c_void_p, C.c_void_p, P(C.c_int32)]
+    rows = [r for b in blocks for r in b]
+    nk = len(key_types)
+    nf = len(rows[0][1]) if rows else 1
+    nr = len(rows)
+    br = (C.c_int64 * max(len(blocks), 1))(*[len(b) for b in blocks])
+    kt = (C.c_int32 * max(nk, 1))(*key_types)
+    kl, kd, ks, kn = (C.c_int64 * max(nr * nk, 1))(), (C.c_double * max(nr * nk, 1))(), (C.c_char_p * max(nr * nk, 1))(), (C.c_uint8 * max(nr * nk, 1))()
+    counts, sums = (C.c_int64 * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))()
+    mins, maxs, nulls = (C.c_double * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))(), (C.c_uint8 * max(nr * nf, 1))()
+    offsets, registers = [0], []
+    for r, (key_values, cells) in enumerate(rows):
+        for k, v in enumerate(key_values):
+            at = r * nk + k
+            if v is None:
+                kn[at] = 1
+                ks[at] = b""
+            elif key_types[k] in (KEY_INT, KEY_LONG):
+                kl[at] = int(v)
+            elif key_types[k] == KEY_STRING:
+                ks[at] = str(v).encode()
+            else:
+                kd[at] = float(v)
+        for f, cell in enumerate(cells):
+            c, s, mn, mx, is_null = cell[:5]
+            at = r * nf + f
+            counts[at], sums[at], mins[at], maxs[at], nulls[at] = int(c), float(s), float(mn), float(mx), int(bool(is_null))
+            regs = np.asarray(cell[5], dtype=np.uint8) if len(cell) > 5 else np.zeros(0, np.uint8)
+            registers.append(regs)
+            offsets.append(offsets[-1] + int(regs.shape[0]))
+    ro = np.asarray(offsets, dtype=np.int64)
+    rb = np.ascontiguousarray(np.concatenate(registers + [np.zeros(1, np.uint8)]), dtype=np.uint8)
+    st = C.c_int32()
+    return _take_json(lib, lib.ph_combine_hll(sql.encode(), len(blocks), br, kt, kl, kd, ks, kn, counts, sums, mins, maxs, nulls, ro.ctypes.data, rb.ctypes.data, C.byref(st)), st)
+
+
+def hll_cardinality(registers):
+    """HyperLogLog.cardinality() of 2^log2m registers, computed by the host mirror (pinot_amd/csrc/pg_hll.h)."""
+    import numpy as np
+    lib = _lib()
+    lib.ph_hll_cardinality.restype = C.c_int64
+    lib.ph_hll_cardinality.argtypes = [C.c_void_p, C.c_int32]
+    regs = np.ascontiguousarray(registers, dtype=np.uint8)
+    out = int(lib.ph_hll_cardinality(regs.ctypes.data, int(regs.shape[0])))
+    if out < 0:
+        raise ValueError("%d registers are not a HyperLogLog" % regs.shape[0])
+    return out
+
+
+def hll_offer_longs(longs, log2m=8):
+    """The registers (uint8, 2^log2m) after offering the int64 `longs` to an empty sketch, computed with pinot_amd/csrc/pg_hll.h -- the header the
+    kernels include (ph_hll_offer_longs)."""
+    import numpy as np
+    lib = _lib()
+    lib.ph_hll_offer_longs.restype = C.c_int32
+    lib.ph_hll_offer_longs.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    longs = np.ascontiguousarray(longs, dtype=np.int64)
+    out = np.zeros(1 << max(int(log2m), 0) if 0 <= int(log2m) <= 20 else 1, dtype=np.uint8)
+    if lib.ph_hll_offer_longs(longs.ctypes.data, int(longs.shape[0]), int(log2m), out.ctypes.data) != 0:
+        raise ValueError("log2m %d is not offloaded" % log2m)
+    return out
+
+
+def hll_float_bits_of_widened(double_bits):
+    """pg_hll.h's hll_float_bits_of_widened: the 32 stored bits of a FLOAT dictionary entry from the bits of the double it was widened to."""
+    lib = _lib()
+    lib.ph_hll_float_bits_of_widened.restype = C.c_uint32
+    lib.ph_hll_float_bits_of_widened.argtypes = [C.c_uint64]
+    return int(lib.ph_hll_float_bits_of_widened(int(double_bits) & (2 ** 64 - 1)))
+
+
 def value_counts_from_device(stored_type, value_bits, counts):
     """ValueCounts::fromDeviceValues: the runs of a raw column (pg_result_value_counts) -> PERCENTILE's list as (values float64, counts int64);
     stored_type: _abi.PG_TYPE_*.  Two LONGs that land on one double are one run."""

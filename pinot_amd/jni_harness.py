@@ -12,7 +12,7 @@ from . import marshal as M
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(ROOT, "jni", "libpinot_gpu_jni_fake.so")
 PREFIX = "Java_org_apache_pinot_gpu_PinotGpuNative_"
-FJ_INT_ARRAY, FJ_LONG_ARRAY, FJ_DOUBLE_ARRAY, FJ_OBJECT_ARRAY, FJ_STRING = 1, 2, 3, 4, 5
+FJ_INT_ARRAY, FJ_LONG_ARRAY, FJ_DOUBLE_ARRAY, FJ_OBJECT_ARRAY, FJ_STRING, FJ_BYTE_ARRAY = 1, 2, 3, 4, 5, 8
 
 
 def _header_constants():
@@ -89,6 +89,8 @@ class FakeJvm:
             return np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, np.int64)
         if kind == FJ_DOUBLE_ARRAY:
             return np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_double)), (n,)).copy() if n else np.zeros(0, np.float64)
+        if kind == FJ_BYTE_ARRAY:
+            return np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_uint8)), (n,)).copy() if n else np.zeros(0, np.uint8)
         if kind == FJ_STRING:
             return C.string_at(data).decode("utf-8", "replace")
         if kind == FJ_OBJECT_ARRAY:
@@ -172,6 +174,18 @@ class FakeJvm:
         arrays, limit, flags = self.query_arrays(spec)
         try:
             out = self.call("executeWithDistinctSets", C.c_void_p, C.c_int64(handle), *arrays, C.c_int32(limit), C.c_int32(flags))
+            try:
+                return self.to_python(out)
+            finally:
+                self.release(C.c_void_p(out))
+        finally:
+            self.release(*arrays)
+
+    def execute_with_hll_registers(self, handle, spec):
+        """PinotGpuNative.executeWithHllRegisters: [the Object[PGM_RESULT_ARRAYS] as numpy arrays, the sketches: aggregation * rows + row -> uint8 registers or None]."""
+        arrays, limit, flags = self.query_arrays(spec)
+        try:
+            out = self.call("executeWithHllRegisters", C.c_void_p, C.c_int64(handle), *arrays, C.c_int32(limit), C.c_int32(flags))
             try:
                 return self.to_python(out)
             finally:

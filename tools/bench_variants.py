@@ -82,7 +82,7 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
         return lambda matched: B(col) if matched * 16 >= rows else min(B(col), matched * 64)
 
     # ---- C2 / C3 on 1 B rows: the headline's v and f, v under two dictionaries without structure, and the C3 columns ----
-    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list", "C2b-valid-docs", "C2b-valid-docs-5pct", "C2b-distinct", "C3-distinct", "C2b-percentile", "C3-percentile")):
+    if any(want(x) for x in ("C2b-irregular", "C2b-window", "C2a-affine", "C2a-irregular", "C3", "C3-filter", "C3-irregular", "COUNT-filter", "C2b-1pct", "C2b-50pct", "AND3-scan", "AND-OR-scan", "AND-NOT-scan", "NOT-NOT-scan", "AND-NOT-OR-scan", "AND-NOT-OR-scan-bound", "AND3-scan-bound", "AND-OR-scan-bound", "AND-NOT-scan-bound", "NOT-NOT-scan-bound", "C2b-in-list", "C2b-irregular-in-list", "C3-in-list", "C2b-valid-docs", "C2b-valid-docs-5pct", "C2b-distinct", "C2b-hll", "C3-distinct", "C2b-percentile", "C3-percentile")):
         t0 = time.time()
         v_irr = _shared(S, v, "v_irr", v_dictionary("irregular"))
         v_win = _shared(S, v, "v_win", v_dictionary("window"))
@@ -165,6 +165,24 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                     return np.array_equal(got.aggregations[0].dict_ids, np.flatnonzero(seen)) and got.aggregations[0].count == int(seen.sum()) and got.stats[0] == docs
                 report("C2b-distinct", "BASELINE.json configs[1] with DISTINCTCOUNT for SUM: C2b-irregular's two dictId streams, an OR per matching doc where the histogram has an add",
                        "SELECT DISTINCTCOUNT(v_irr) WHERE f < 100 (10%)", n, B(v) + B(f), g, seg, Q.QuerySpec([(Q.DISTINCTCOUNT, 2)], filter=flt), model_check=c2b_model)
+            if want("C2b-hll"):
+                # DISTINCTCOUNTHLL on the same streams (pg_scan_hll.h): the bitset pass, then hll_fold_kernel; the model offers the values of the dictIds seen
+                def c2b_hll_model(got):
+                    import sys
+                    tests_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+                    if tests_dir not in sys.path:
+                        sys.path.insert(0, tests_dir)
+                    import hll_cases as HL
+                    seen = np.zeros(seg.columns[2].cardinality, dtype=bool)
+                    docs = 0
+                    for _, (ids, fids) in dict_id_chunks(2, 1):
+                        hit = fids < 100
+                        docs += int(hit.sum())
+                        seen[ids[hit]] = True
+                    regs = HL.registers(np.asarray(seg.columns[2].dict_values)[seen], np.int32)
+                    return np.array_equal(got.aggregations[0].hll_registers, regs) and got.aggregations[0].count == int(np.count_nonzero(regs)) and got.stats[0] == docs
+                report("C2b-hll", "C2b-distinct with DISTINCTCOUNTHLL for DISTINCTCOUNT: the same bitset pass, the bitset folded into 256 registers on the device (hll_fold_kernel), 256 bytes copied",
+                       "SELECT DISTINCTCOUNTHLL(v_irr) WHERE f < 100 (10%)", n, B(v) + B(f), g, seg, Q.QuerySpec([(Q.hll(), 2)], filter=flt), model_check=c2b_hll_model)
             if want("C3-distinct"):
                 def c3_model(got):
                     ka, kk = seg.columns[5].cardinality, seg.columns[4].cardinality
@@ -516,7 +534,7 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
     # 20 M docs (the lists are priced with the docs: 16 bytes each, PG_COLLECT_MAX_BYTES = 1 GiB): `r` is a raw INT column, `d` the same values
     # dictionary-encoded, f the headline's filter column cut to the same docs.  The sort and the run-length encoding follow the scan kernel on the
     # stream BEHIND the events that bracket all_kernels_ms: step_ms_host_clock is the figure that holds the whole query.
-    collect_ids = ("collect-percentile", "collect-distinct", "collect-percentile-dictionary", "collect-distinct-dictionary")
+    collect_ids = ("collect-percentile", "collect-distinct", "collect-percentile-dictionary", "collect-distinct-dictionary", "C2b-hll-raw")
     if any(want(x) for x in collect_ids):
         import sys
         tests_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
@@ -560,5 +578,15 @@ def run(engine, gseg0, seg0, n, n_c5, match, check=True, steps=10, warmup=40):
                     report(vid, "PERCENTILE / DISTINCTCOUNT on a raw column beside the dictionary form, same docs and filter; " + what,
                            "SELECT %s(%s) WHERE f < 100 (10%%) over %d docs" % ("PERCENTILE50" if function == Q.PERCENTILE else "DISTINCTCOUNT", col.name, m), m, B(col) + B(fm), g, cseg,
                            Q.QuerySpec([(function, column)], filter=cflt), model_check=model_of(function) if check else None)
+            if want("C2b-hll-raw"):
+                # DISTINCTCOUNTHLL on the raw column (scan_hll_kernel: one pass, no sort), beside collect-distinct on the same docs, values and filter
+                import hll_cases as HL
+
+                def hll_raw_model(got):
+                    regs = HL.registers(want_runs[0], np.int32)
+                    return np.array_equal(got.aggregations[0].hll_registers, regs) and got.aggregations[0].count == int(np.count_nonzero(regs))
+                report("C2b-hll-raw", "DISTINCTCOUNTHLL on a raw INT column: scan_hll_kernel, 256 registers in LDS, one pass and no sort -- beside collect-distinct",
+                       "SELECT DISTINCTCOUNTHLL(r) WHERE f < 100 (10%%) over %d docs" % m, m, B(cseg.columns[0]) + B(fm), g, cseg,
+                       Q.QuerySpec([(Q.hll(), 0)], filter=cflt), model_check=hll_raw_model if check else None)
         engine.reinit(PINOT_GPU_COLLECT=None)
     return out

@@ -475,6 +475,53 @@ def main():
                     ran += 1
         finally:
             engine.reinit(PINOT_GPU_COLLECT=flipped.get("PINOT_GPU_COLLECT"))
+    # ---- DISTINCTCOUNTHLL (pg_scan_hll.h): scan_hll_kernel and group_hll_kernel over raw columns, hll_fold_kernel (and hll_pack_kernel behind all three)
+    # over the bitsets of dictionary columns, aggregation only and grouped.  The oracle has no such function: the registers are held byte for byte
+    # against the numpy model of tests/hll_cases.py over the docs oracle.filter_bitmap matches, every other function against the oracle.
+    if only is None or only.search("hll"):
+        import distinct_cases as DC
+        import hll_cases as HL
+        ids = lambda s, card: S.synthetic_dict_ids(1000 + s, 0, n, card)
+        HL.set_values(seg, RI, (ids(10, 1_000_000) - 500_000).astype(np.int32))
+        HL.set_values(seg, RL, (ids(11, 1 << 20).astype(np.int64) - (1 << 19)) * ((1 << 20) + 3))
+        HL.set_values(seg, RD, (ids(12, 1 << 20).astype(np.float64) - (1 << 19)) * 0.37)
+        f100 = Q.leaf(Q.Pred.dict_range(F, 0, 100))
+        shapes = (("scan-raw", Q.QuerySpec([(Q.hll(), RL), (Q.hll(12), RI), (Q.hll(4), RD), (Q.COUNT, -1)], filter=Q.leaf(Q.Pred.dict_set(F, list(range(0, 300, 3)), 1000))), "scan_hll_kernel"),
+                  ("group-raw", Q.QuerySpec([(Q.hll(), RD), (Q.SUM, V), (Q.hll(10), RI)], filter=Q.leaf(Q.Pred.dict_range(F, 0, 500)), group_by=[B, C2]), "group_hll_kernel"),
+                  ("scan-dict", Q.QuerySpec([(Q.hll(), W8), (Q.hll(14), DL), (Q.DISTINCTCOUNT, W8), (Q.COUNT, -1)], filter=f100), "scan_distinct_kernel"),
+                  ("group-dict", Q.QuerySpec([(Q.hll(), A), (Q.SUM, V), (Q.hll(6), W32)], filter=Q.leaf(Q.Pred.dict_range(F, 0, 500)), group_by=[B]), "group_distinct_kernel"))
+        with engine.open(seg) as g:
+            for sid, spec, family in shapes:
+                eid = "hll-%s" % sid
+                if g.check(spec) != 0:
+                    failed.append({"id": eid, "error": "pg_query_check declined"})
+                    continue
+                want_registers = HL.model(seg, spec)
+                oracle_spec = HL.without_hll(DC.without_distinct(spec))
+                for rep in range(2):
+                    got = g.execute(spec)
+                    try:
+                        HL.assert_registers_equal(got, seg, spec, want=want_registers, where=eid)
+                        want = want_of(eid, oracle_spec)
+                        for a, (fn, _) in enumerate(spec.aggregations):
+                            if Q.is_hll(fn) or fn == Q.DISTINCTCOUNT:
+                                continue
+                            if spec.group_by:
+                                assert sorted(got.groups) == sorted(want.groups), "group ids differ"
+                                for gid in want.groups:
+                                    H.assert_agg_equal(got.groups[gid][a], want.groups[gid][a], fn, "group %r agg %d" % (gid, a))
+                            else:
+                                H.assert_agg_equal(got.aggregations[a], want.aggregations[a], fn, "agg %d" % a)
+                        assert got.stats[0] == want.stats[0] and got.stats[3] == want.stats[3], (got.stats, want.stats)
+                        if not flipped and not spec.group_by:
+                            assert got.dominant_kernel == family, "dominant kernel %s, expected %s" % (got.dominant_kernel, family)
+                        elif not flipped:
+                            # the ordinary group-by runs too: dominant_kernel is the pass's kernel or the ordinary query's own, whichever took longer
+                            ordinary = g.execute(oracle_spec).dominant_kernel
+                            assert got.dominant_kernel in (family, ordinary), "dominant kernel %s, expected %s or %s" % (got.dominant_kernel, family, ordinary)
+                    except AssertionError as e:
+                        failed.append({"id": eid, "error": str(e)[:300]})
+                ran += 1
     # ---- the transducer's kernels: byte-function walks, then table walks of the same machines ----
     if only is None or only.search("fsm"):
         count = args.fsm_trees if args.fsm_trees >= 0 else (400 if args.regime == "tiny" else 40)
