@@ -56,7 +56,8 @@ extern "C" {
                             *    (still 5) PG_AGG_PERCENTILE, pg_result_percentile_counts: no struct layout changed, one enumerator and one function added;
                             *    (still 5) PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns, pg_result_value_counts: no struct layout changed, one function added;
                             *    (still 5) PG_DISTINCT_LDS_MAX_DICT_IDS: a diagnostic constant beside PG_PERCENTILE_LDS_MAX_COUNTERS, nothing else;
-                            *    (still 5) PG_AGG_DISTINCTCOUNTHLL / PG_AGG_HLL(log2m), pg_result_hll_registers: no struct layout changed, one enumerator and one function added */
+                            *    (still 5) PG_AGG_DISTINCTCOUNTHLL / PG_AGG_HLL(log2m), pg_result_hll_registers: no struct layout changed, one enumerator and one function added;
+                            *    (still 5) PG_STAGED_SET_LDS_WORDS: a diagnostic constant beside PG_DISTINCT_LDS_MAX_DICT_IDS, nothing else */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -283,6 +284,9 @@ typedef enum pg_agg_function {
  * scan_distinct_kernel keeps in LDS when the filter stages no dictId set there (with one: 2048 words = 65536 dictIds fewer); above it, or with
  * PINOT_GPU_DISTINCT_LDS=0, the bitsets live in HBM. */
 #define PG_DISTINCT_LDS_MAX_DICT_IDS 1277952
+/* Diagnostics: the 32-bit words of a workgroup's LDS that hold the dictId sets of a filter's IN / NOT IN leaves when they are staged there
+ * (PINOT_GPU_SET_LDS, on by default): the "2048 fewer" above, and the room scan_hll_kernel needs beside its registers behind such a leaf. */
+#define PG_STAGED_SET_LDS_WORDS 2048
 
 typedef struct pg_aggregation {
   int32_t function;            /* pg_agg_function */

@@ -3133,6 +3133,7 @@ constexpr size_t kCountsRecordBytes = sizeof(BlockPartial) * (kHistBlockThreads 
 static_assert((kLdsBudget - kCountsRecordBytes) / 4 == PG_PERCENTILE_LDS_MAX_COUNTERS, "include/pinot_gpu.h states the LDS tier's reach");
 // scan_distinct_kernel's LDS tier: the reduction records overlay the bitsets' start (the maximum, not the sum, is the rule), so the whole budget holds bits
 static_assert(kLdsBudget * 8 == PG_DISTINCT_LDS_MAX_DICT_IDS, "include/pinot_gpu.h states the LDS tier's reach");
+static_assert(kSetLdsWords == PG_STAGED_SET_LDS_WORDS, "include/pinot_gpu.h states the staged set area");
 struct ScanGrid { int blocks = 1, threads = kBlockThreads; size_t lds = 0, hist_set_off = 0; bool wide = false, distinct_lds = false; };
 // A segment whose tiles all fit the chip at once (one tile per wave: a 10 M-row segment at five waves per SIMD) is latency from end
 // to end -- launch, one round of loads, the hand-off of the workgroups' records to the fold.  Ten waves per workgroup there: 2.5x

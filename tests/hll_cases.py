@@ -150,17 +150,20 @@ def without_hll(spec):
                        stats_upper_bound_ok=spec.stats_upper_bound_ok)
 
 
+def assert_one_register_set(v, regs, where=""):
+    """One AggValue of an HLL aggregation: the registers byte for byte, count = the non-zero registers, sum 0, min +inf, max -inf."""
+    assert v.hll_registers is not None, "%s: no registers came back" % where
+    got_regs = np.frombuffer(bytes(v.hll_registers), dtype=np.uint8)
+    assert got_regs.shape == regs.shape, "%s: %d registers, model %d" % (where, got_regs.shape[0], regs.shape[0])
+    bad = np.flatnonzero(got_regs != regs)
+    assert bad.size == 0, "%s: %d registers differ, first %d: %d, model %d" % (where, bad.size, bad[0], got_regs[bad[0]], regs[bad[0]])
+    assert v.count == int(np.count_nonzero(regs)) and v.sum == 0.0 and v.sum_i64 == 0 and not v.sum_exact and v.min == float("inf") and v.max == float("-inf"), (where, v)
+
+
 def assert_registers_equal(got, seg, spec, want=None, key_values=None, where="", match=None):
     """The result's HLL fields against the model: the registers byte for byte, count = the non-zero registers, sum 0, min +inf, max -inf."""
     want = model(seg, spec, key_values, match) if want is None else want
-
-    def one(v, regs, at):
-        assert v.hll_registers is not None, "%s %s: no registers came back" % (where, at)
-        got_regs = np.frombuffer(bytes(v.hll_registers), dtype=np.uint8)
-        assert got_regs.shape == regs.shape, "%s %s: %d registers, model %d" % (where, at, got_regs.shape[0], regs.shape[0])
-        bad = np.flatnonzero(got_regs != regs)
-        assert bad.size == 0, "%s %s: %d registers differ, first %d: %d, model %d" % (where, at, bad.size, bad[0], got_regs[bad[0]], regs[bad[0]])
-        assert v.count == int(np.count_nonzero(regs)) and v.sum == 0.0 and v.sum_i64 == 0 and not v.sum_exact and v.min == float("inf") and v.max == float("-inf"), (where, at, v)
+    one = lambda v, regs, at: assert_one_register_set(v, regs, "%s %s" % (where, at))
 
     if not spec.group_by:
         for a, regs in want.items():
@@ -258,3 +261,198 @@ def edge_segment(S, num_docs, raw, seed=11):
     for c, v in zip((E_INT, E_LONG, E_FLOAT, E_DOUBLE, E_ONE), values + [one]):
         set_values(seg, c, v)
     return seg
+
+
+# ---- constructed register corpus: values whose hash is chosen ----
+M_INVERSE = np.uint32(pow(0x5BD1E995, -1, 1 << 32))                     # the constant is odd: multiplication by it is a bijection mod 2^32
+CORPUS_LOG2M = (4, 8, 14)
+CORPUS_SIZES = (2049, 6145)
+C_INT, C_LONG, C_FLOAT, C_DOUBLE, C_FILTER, C_KEY = range(6)
+CORPUS_RUN = 64                                                         # consecutive docs of one value: a whole wavefront offers one register at once
+
+
+def _undo_xor_shift(y, s):
+    """x of y = x ^ (x >> s), 32 bits: the top s bits of x are y's, every pass restores s more."""
+    x = int(y)
+    for _ in range(32 // s + 1):
+        x = int(y) ^ (x >> s)
+    return x & 0xFFFFFFFF
+
+
+def long_with_hash(x, hi):
+    """The long with high word `hi` whose hash_long is x: every Murmur2 step undone, last to first."""
+    m, inv, mask = int(M), int(M_INVERSE), 0xFFFFFFFF
+    h = _undo_xor_shift(int(x) & mask, 15)
+    h = (h * inv) & mask
+    h = _undo_xor_shift(h, 13)
+    k = ((int(hi) & mask) * m) & mask
+    k ^= k >> 24
+    h ^= (k * m) & mask
+    h = (h * inv) & mask                                                # = (k_low * M): the first word's contribution
+    k = (h * inv) & mask
+    k = _undo_xor_shift(k, 24)
+    lo = (k * inv) & mask
+    v = ((int(hi) & mask) << 32) | lo
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def int_with_hash(x):
+    """The int (as a Python integer) whose sign-extended long hashes to x, or None: the high word of a sign-extended int is 0 or -1, and the
+    low word that solves the hash for it must carry the same sign."""
+    for hi in (0, -1):
+        v = long_with_hash(x, hi)
+        if -2 ** 31 <= v < 2 ** 31:
+            return v
+    return None
+
+
+def hash_of_target(log2m, index, rank):
+    """The hash that lands in register `index` with rank `rank`, its remainder all zero below the leading one (rank max: all zero, so that
+    only the sentinel bit ends the count)."""
+    rest = 32 - log2m
+    assert 0 <= index < 1 << log2m and 1 <= rank <= rest + 1
+    return (index << rest) | (0 if rank == rest + 1 else 1 << (rest - rank))
+
+
+def corpus_targets(log2m):
+    """[(index, rank)]: the first, one middle and the last register, each with rank 1, 2, max - 1 and max = 32 - log2m + 1."""
+    m, top = 1 << log2m, 32 - log2m + 1
+    return [(j, r) for j in (0, (m // 2) | 5 if m > 16 else 5, m - 1) for r in (1, 2, top - 1, top)]
+
+
+def corpus_values(width):
+    """{(log2m, index, rank): value} -- 64-bit longs (width 64: the index is always reached) or ints (width 32: where an index has no 32-bit
+    solution, the nearest index that has one).  `index` is the one reached."""
+    out = {}
+    for log2m in CORPUS_LOG2M:
+        m = 1 << log2m
+        for j, r in corpus_targets(log2m):
+            if width == 64:
+                # a high word of every shape, fixed per target
+                out[(log2m, j, r)] = long_with_hash(hash_of_target(log2m, j, r), (0x9E3779B9 * (j + 3 * r + log2m)) & 0xFFFFFFFF)
+                continue
+            for d in sorted(range(m), key=lambda d: (abs(d - j), d)):
+                v = int_with_hash(hash_of_target(log2m, d, r))
+                if v is not None:
+                    out[(log2m, d, r)] = v
+                    break
+    return out
+
+
+def corpus_order(n, targets):
+    """Doc -> position in `targets`.  Per register the entries go [largest rank, smaller ranks ..., largest rank], so the largest rank is
+    offered both before and after the smaller ones (the plain read before the atomic max must survive both orders); the registers' entries
+    are cycled in short runs over the docs.  Three runs of CORPUS_RUN consecutive docs carry a largest-rank value: at doc 0, across the
+    middle of tile 1, and ending in the last doc.  A lane holds 32 consecutive docs, so in the third tile (when there is a whole one) the
+    cycle has a period of 32 docs instead: all 64 lanes of the wavefront then offer the same register in the same step."""
+    per_register = {}
+    for i, (log2m, j, r) in enumerate(targets):
+        per_register.setdefault((log2m, j), []).append((r, i))
+    groups, largest = [], []
+    for entries in per_register.values():
+        entries = sorted(entries, reverse=True)
+        groups.append([entries[0][1]] + [i for _, i in entries[1:]] + [entries[0][1]])
+        largest.append(entries[0][1])
+
+    def whole_groups(room, repeat):
+        """Whole groups (never one cut short) in cycle, every entry `repeat` docs long, padded to `room` docs with the last group's largest rank."""
+        out, k = [], 0
+        while len(out) + len(groups[k % len(groups)]) * repeat <= room:
+            out += [i for i in groups[k % len(groups)] for _ in range(repeat)]
+            k += 1
+        return np.array(out + [out[-1]] * (room - len(out)), dtype=np.int64)
+
+    docs = np.empty(n, dtype=np.int64)
+    docs[:CORPUS_RUN] = largest[0]
+    body_end = 2 * 2048 if n >= 3 * 2048 else n - CORPUS_RUN
+    docs[CORPUS_RUN: body_end] = whole_groups(body_end - CORPUS_RUN, 5)
+    if n >= 3 * 2048:
+        docs[2 * 2048: n] = np.tile(whole_groups(32, 1), -(-(n - 2 * 2048) // 32))[: n - 2 * 2048]
+    mid = 2048 + 1024 if n > 2048 + 1024 + CORPUS_RUN else n // 2
+    docs[mid - CORPUS_RUN // 2: mid + CORPUS_RUN // 2] = largest[len(largest) // 2]
+    docs[n - CORPUS_RUN:] = largest[-1]
+    return docs
+
+
+def corpus_segment(S, num_docs, raw):
+    """INT / LONG / FLOAT (the constructed 32 bits as float bits) / DOUBLE (the constructed 64 bits) columns over the constructed values, a
+    filter column and a 5-value key.  NaN bit patterns stay in raw columns only (a widened FLOAT dictionary quiets a signalling NaN and a
+    sorted dictionary holds one NaN): the dictionary form replaces them by the column's first non-NaN value."""
+    n = num_docs
+    rng = np.random.default_rng(41 + n)
+    wide, narrow = corpus_values(64), corpus_values(32)
+    columns, stored = [], []
+    for name, width, dtype in (("i", 32, np.int32), ("l", 64, np.int64), ("f", 32, np.float32), ("d", 64, np.float64)):
+        table = narrow if width == 32 else wide
+        targets = list(table)
+        ints = np.array([table[t] for t in targets], dtype=np.int32 if width == 32 else np.int64)
+        values = ints[corpus_order(n, targets)].view(dtype)
+        if dtype in (np.float32, np.float64) and not raw:
+            nan = np.isnan(values)
+            values = np.where(nan, values[~nan][0], values).astype(dtype)
+        stored.append(np.ascontiguousarray(values))
+    for name, v in zip("ilfd", stored):
+        if raw:
+            columns.append(S.Column.raw_typed(name, v))
+        else:
+            dict_values = _sorted_like_java(v)
+            bits_of = lambda a: a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+            order = np.argsort(bits_of(dict_values), kind="stable")
+            ids = order[np.searchsorted(bits_of(dict_values)[order], bits_of(v))].astype(np.int32)
+            columns.append(typed_dict_column(S, name, dict_values, ids))
+    columns.append(S.Column.from_dict_ids("flt", np.arange(1000, dtype=np.int32), rng.integers(0, 1000, n).astype(np.int32)))
+    columns.append(S.Column.from_dict_ids("k", np.arange(5, dtype=np.int32) * 2 - 3, rng.integers(0, 5, n).astype(np.int32)))
+    seg = S.SegmentData("hll_corpus_%d_%s" % (n, "raw" if raw else "dict"), n, columns)
+    for c, v in zip((C_INT, C_LONG, C_FLOAT, C_DOUBLE), stored):
+        set_values(seg, c, v)
+    return seg
+
+
+# ---- fold edges: chosen dictIds around hll_fold_kernel's chunks ----
+FOLD_CARDINALITIES = (8191, 8192, 8193, 8225, 16385, 524288, 524289)
+FOLD_DOCS = 4097
+F_INT, F_LONG, F_FILTER, F_KEY = range(4)
+
+
+def fold_chunks(cardinality):
+    """[(first word, end word)] of the chunks launch_hll_fold forms (restated, not called): one workgroup per 256 words of a bitset row, at
+    most 64, then the words per chunk by ceiling division."""
+    words = (cardinality + 31) // 32
+    chunks = max(1, min(64, (words + 255) // 256))
+    per = (words + chunks - 1) // chunks
+    return [(c * per, min(words, (c + 1) * per)) for c in range(chunks) if c * per < words]
+
+
+def fold_dict_ids(cardinality):
+    """(dictIds, chunk of each): the first and last dictId of EVERY chunk, two interior ones per chunk, and cardinality - 1 (the last
+    chunk's last: a cardinality that is no multiple of 32 has it in a partial word)."""
+    ids = {}
+    for c, (first, end) in enumerate(fold_chunks(cardinality)):
+        lo, hi = first * 32, min(cardinality, end * 32) - 1
+        for d in (lo, hi, lo + (hi - lo) // 2, min(hi, lo + 33)):
+            ids[d] = c
+    assert cardinality - 1 in ids
+    order = sorted(ids)
+    return np.array(order, dtype=np.int32), np.array([ids[d] for d in order], dtype=np.int32)
+
+
+FOLD_ALL, FOLD_ODD, FOLD_EVEN = (1, 3), (2, 3), (1, 2)                  # dictId ranges [lo, hi) of the filter column, below
+
+
+def fold_segment(S, cardinality):
+    """Dictionary INT and LONG columns of the given cardinality whose docs carry exactly fold_dict_ids (in a fixed shuffled order); a filter
+    column whose dictId is 1 for a doc of an even chunk, 2 for a doc of an odd chunk and 9 for the last doc -- so a range leaf can keep every
+    chunk (FOLD_ALL), or leave the even / the odd chunks wholly without a bit (FOLD_ODD / FOLD_EVEN); a 5-value key."""
+    n = FOLD_DOCS
+    rng = np.random.default_rng(cardinality)
+    chosen, chunk_of = fold_dict_ids(cardinality)
+    pick = rng.permutation(n) % len(chosen)
+    ids = chosen[pick].astype(np.int32)
+    flt = (1 + chunk_of[pick] % 2).astype(np.int32)
+    flt[-1] = 9
+    ints = (np.arange(cardinality, dtype=np.int64) * 3 - 700000).astype(np.int32)
+    longs = np.arange(cardinality, dtype=np.int64) * 0x100000003 - 2 ** 50
+    cols = [S.Column.from_dict_ids("i", ints, ids), typed_dict_column(S, "l", longs, ids),
+            S.Column.from_dict_ids("flt", np.arange(10, dtype=np.int32), flt),
+            S.Column.from_dict_ids("k", np.arange(5, dtype=np.int32), rng.integers(0, 5, n).astype(np.int32))]
+    return S.SegmentData("hll_fold_%d" % cardinality, n, cols)

@@ -258,3 +258,94 @@ def test_rounding_is_floor_of_x_plus_a_half():
             closest = min(closest, abs(estimate - math.floor(estimate) - 0.5))
             assert host.hll_cardinality(regs) == int(math.floor(estimate + 0.5)) == HL.cardinality(regs)
     assert closest > 1e-9 and searched + linear == 300 and searched >= 200, (closest, searched, linear)
+
+
+# ---- the constructed register corpus: values whose hash is chosen (hll_cases.long_with_hash) ----
+def test_the_hash_is_inverted_for_every_high_word():
+    rng = np.random.default_rng(31)
+    hashes = [int(x) for x in rng.integers(0, 2 ** 32, 1000)] + [0, 1, 2 ** 32 - 1, 2 ** 31]
+    hashes += [HL.hash_of_target(log2m, j, r) for log2m in HL.CORPUS_LOG2M for j, r in HL.corpus_targets(log2m)]
+    his = [int(x) for x in rng.integers(0, 2 ** 32, len(hashes))]
+    his[:4] = [0, 0xFFFFFFFF, 0x80000000, 1]
+    longs = np.array([HL.long_with_hash(x, hi) for x, hi in zip(hashes, his)], dtype=np.int64)
+    assert np.array_equal((longs.view(np.uint64) >> np.uint64(32)).astype(np.int64), np.array(his, dtype=np.int64))
+    assert np.array_equal(HL.hash_long(longs).astype(np.int64), np.array(hashes, dtype=np.int64))
+    # through the header the kernels include: one long at a time, the register and the rank its hash was built for
+    for log2m in HL.CORPUS_LOG2M:
+        for j, r in HL.corpus_targets(log2m):
+            for hi in (0, 0xFFFFFFFF, 0x12345678):
+                one = np.array([HL.long_with_hash(HL.hash_of_target(log2m, j, r), hi)], dtype=np.int64)
+                regs = host.hll_offer_longs(one, log2m)
+                assert regs[j] == r and np.count_nonzero(regs) == 1, (log2m, j, r, hi)
+                assert np.array_equal(regs, HL.registers_of_longs(one, log2m))
+    # ints: the candidate whose sign agrees with its high word, or none
+    found = 0
+    for x in hashes:
+        v = HL.int_with_hash(x)
+        if v is not None:
+            found += 1
+            assert -2 ** 31 <= v < 2 ** 31 and int(HL.hash_long(np.array([v], dtype=np.int64))[0]) == x
+            assert int(HL.hash_long(HL.longs_of(np.array([v], dtype=np.int32), np.int32))[0]) == x
+        else:
+            assert all(not -2 ** 31 <= HL.long_with_hash(x, hi) < 2 ** 31 for hi in (0, -1))
+    assert found >= len(hashes) // 4                                     # (each of the two candidates agrees half the time)
+    assert HL.int_with_hash(HL.hash_of_target(8, 255, 25)) is None       # index 255 at log2m 8 with the largest rank: no int hashes there
+
+
+def test_the_corpus_reaches_its_targets():
+    """Every target (index 0 / a middle index / the last index) x (rank 1, 2, max - 1, max) at log2m 4, 8, 14: LONG and DOUBLE reach each
+    one exactly; INT and FLOAT the nearest index a 32-bit value can reach, with the rank wanted."""
+    wide, narrow = HL.corpus_values(64), HL.corpus_values(32)
+    for log2m in HL.CORPUS_LOG2M:
+        m, top = 1 << log2m, 32 - log2m + 1
+        assert {(j, r) for (l, j, r) in wide if l == log2m} == set(HL.corpus_targets(log2m))
+        assert (log2m, 0, top) in wide and (log2m, m - 1, top) in wide    # the first and the last register hold the largest rank
+        assert sorted(r for (l, j, r) in narrow if l == log2m) == sorted(r for _, r in HL.corpus_targets(log2m))
+        for table, dtype in ((wide, np.int64), (narrow, np.int32)):
+            for (l, j, r), v in table.items():
+                if l != log2m:
+                    continue
+                regs = HL.registers(np.array([v], dtype=dtype), dtype, log2m)
+                assert regs[j] == r and np.count_nonzero(regs) == 1, (log2m, j, r, v)
+                assert np.array_equal(host.hll_offer_longs(HL.longs_of(np.array([v], dtype=dtype), dtype), log2m), regs)
+
+
+@pytest.mark.parametrize("num_docs", HL.CORPUS_SIZES)
+def test_the_corpus_orders_the_largest_rank_before_and_after_the_smaller_ones(num_docs):
+    wide = HL.corpus_values(64)
+    targets = list(wide)
+    order = HL.corpus_order(num_docs, targets)
+    assert order.shape == (num_docs,)
+    ranks = {}
+    for i, (log2m, j, r) in enumerate(targets):
+        ranks.setdefault((log2m, j), {})[i] = r
+    for register, entries in ranks.items():
+        big = max(entries, key=entries.get)
+        at_big = np.flatnonzero(order == big)
+        for i in entries:
+            if i != big:
+                at = np.flatnonzero(order == i)
+                assert at.size and at_big.min() < at.min() and at_big.max() > at.max(), (register, entries[i])
+    # three runs of 64 consecutive docs of a largest-rank value: at doc 0, inside a tile, ending in the last doc
+    is_big = lambda i: targets[i][2] == 32 - targets[i][0] + 1
+    for first in (0, (2048 + 1024 if num_docs > 4096 else num_docs // 2) - 32, num_docs - 64):
+        run = order[first: first + 64]
+        assert len(set(run.tolist())) == 1 and is_big(int(run[0])), first
+    if num_docs >= 3 * 2048:
+        tile = order[2 * 2048: 3 * 2048 - 64].reshape(-1, 32)
+        assert np.all(tile == tile[0])                                   # the same position of every lane offers the same register
+
+
+# ---- the fold segments of tests/test_gpu_hll_edges.py ----
+def test_the_fold_segments_set_the_edges_of_every_chunk():
+    """launch_hll_fold's arithmetic restated: 256 words per workgroup, at most 64 workgroups per row, then the words per chunk by ceiling
+    division.  8192 dictIds are one chunk, 8193 two; above 524288 dictIds the cap of 64 makes chunks of more than 256 words."""
+    assert [len(HL.fold_chunks(c)) for c in HL.FOLD_CARDINALITIES] == [1, 1, 2, 2, 3, 64, 64]
+    assert HL.fold_chunks(524288)[0] == (0, 256) and HL.fold_chunks(524289)[0] == (0, 257) and HL.fold_chunks(524289)[-1] == (63 * 257, 16385)
+    for card in HL.FOLD_CARDINALITIES:
+        ids, chunk_of = HL.fold_dict_ids(card)
+        chunks = HL.fold_chunks(card)
+        assert chunks[0][0] == 0 and chunks[-1][1] == (card + 31) // 32 and all(a[1] == b[0] for a, b in zip(chunks, chunks[1:]))
+        for c, (first, end) in enumerate(chunks):
+            assert first * 32 in ids and min(card, end * 32) - 1 in ids
+        assert ids[-1] == card - 1 and len(ids) <= HL.FOLD_DOCS
