@@ -4185,6 +4185,16 @@ static pg_status defer_group_item(QueryRun& r, const GroupParams& gp, int pblock
   };
   return defer_item(r, std::move(item));
 }
+// One packed dword per doc when the only aggregation input is an unsigned field that fits beside the slot (pg_group_partition.h):
+// the width of that field, 1 for COUNT alone, 0 for separate key / value record columns.
+static int partition_packed_bits(const GroupParams& gp, int scatter_shift) {
+  if (!g_engine.partition_packed) return 0;
+  if (gp.num_group_aggs == 0) return 1;
+  if (gp.num_group_aggs != 1) return 0;
+  const DevGroupAgg& ga = gp.group_aggs[0];
+  const bool unsigned_field = !ga.is_raw && ga.vkind == kValI32 && (ga.kind != kGroupSum || ga.is_plane);
+  return unsigned_field && ga.bits + scatter_shift <= 32 ? ga.bits : 0;
+}
 // Key spaces above the LDS table: the docs are partitioned by key range first, then every partition is aggregated in LDS
 // (pg_group_partition.h) instead of one global atomic per doc and aggregation.  P partitions of 2^partition_shift keys each; two
 // levels when log2_fine_per_coarse > 0 (pass A scatters by coarse partition, group_repartition_*_kernel by fine partition).
@@ -4198,16 +4208,7 @@ static pg_status run_partitioned_group_by(QueryRun& r, const GroupParams& gp, in
   auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t off_upper = 0, off_cursor = align(off_upper + (size_t)P * 4), off_offsets = align(off_cursor + (size_t)P * 4);
   const size_t off_work = align(off_offsets + (size_t)(P + 1) * 4), off_key = align(off_work + max_work * sizeof(PartitionWork));
-  // one packed dword per doc when the only aggregation input is an unsigned field that fits beside the slot (pg_group_partition.h)
-  int packed_bits = 0;
-  if (g_engine.partition_packed) {
-    if (gp.num_group_aggs == 0) packed_bits = 1;
-    else if (gp.num_group_aggs == 1) {
-      const DevGroupAgg& ga = gp.group_aggs[0];
-      const bool unsigned_field = !ga.is_raw && ga.vkind == kValI32 && (ga.kind != kGroupSum || ga.is_plane);
-      if (unsigned_field && ga.bits + scatter_shift <= 32) packed_bits = ga.bits;
-    }
-  }
+  const int packed_bits = partition_packed_bits(gp, scatter_shift);
   const size_t off_val = align(off_key + N * 4), level1_bytes = off_val + (packed_bits > 0 ? 0 : (size_t)gp.num_group_aggs * align(N * 4));
   // two levels: the second record buffer(s), the fine partitions' count / offset / cursor arrays, pass B's device-built work list and its
   // length, and the re-scatter's own chunk list
@@ -4686,8 +4687,9 @@ static pg_status run_group_by(QueryRun& r) {
   static const bool partition_trace = getenv("PINOT_GPU_PARTITION_TRACE") != nullptr;
   if (partition_trace)
     fprintf(stderr, "group-by plan: product %lld, fine partitions %lld (shift %d), 2^%d per coarse -> %lld scatter partitions; partition %d (hash %d typed_direct %d map_based %d "
-                    "private_leaves %d dense_ok %d aggs %d docs %d)\n", product, fine_partitions, partition_shift, log2_fine_per_coarse, num_partitions, (int)use_partition,
-            hash_plan.kind, (int)typed_direct, (int)map_based, (int)private_leaves, gp.dense_ok, gp.num_group_aggs, seg->num_docs);
+                    "private_leaves %d dense_ok %d aggs %d docs %d packed_bits %d)\n", product, fine_partitions, partition_shift, log2_fine_per_coarse, num_partitions, (int)use_partition,
+            hash_plan.kind, (int)typed_direct, (int)map_based, (int)private_leaves, gp.dense_ok, gp.num_group_aggs, seg->num_docs,
+            use_partition ? partition_packed_bits(gp, partition_shift + log2_fine_per_coarse) : 0);
   // (group_typed_direct_kernel walks EVERY tile and reads the index AND's bitmap there: the tiles the AND did not list must be zero, not what an
   //  earlier query of this context left in them -- only group_private_kernel goes by the tile list)
   if (use_partition || typed_direct || !use_private) { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }

@@ -15,7 +15,6 @@ Per generated query, through the C ABI:
   * declines: PG_ERR_UNSUPPORTED only, with a message of fuzz_cases.DECLINE_ALLOW_LIST; at most 10 % of the seed set's queries.
 The seed set must reach the kernels of REQUIRED_KERNELS, each from two segments, and runs twice: on the whole device and with
 PINOT_GPU_TEST_CUS=1 (more tiles than waves)."""
-import math
 import re
 
 import numpy as np
@@ -23,6 +22,7 @@ import pytest
 
 import fuzz_cases as F
 import helpers as H
+from device_results import same_results
 from oracle import oracle
 from pinot_amd import _abi
 from pinot_amd import query as Q
@@ -33,24 +33,6 @@ pytestmark = pytest.mark.gpu
 REQUIRED_KERNELS = ["scan_raw_set_kernel", "scan_raw_kernel", "scan_simple_kernel", "scan_narrow_kernel", "scan_hist_kernel", "scan_private_kernel",
                     "scan_private_typed_kernel", "group_private_kernel", "scan_group_kernel"]
 MAX_DECLINED = 0.10
-
-
-def same_value(a, b):
-    return a == b or (math.isnan(a) and math.isnan(b))
-
-
-def same_results(a, b):
-    """Two device Results of one query (the batch against the single execution): statistics, keys and everything exact field for field.
-    (FLOAT / DOUBLE sums may be added in another order by a shared launch: both are held to the model's bound instead.)"""
-    assert a.stats == b.stats and a.filter_entries_exact == b.filter_entries_exact
-    assert a.group_keys == b.group_keys and a.num_groups_limit_reached == b.num_groups_limit_reached
-    rows = [(a.aggregations, b.aggregations)] + [(a.groups[g], b.groups[g]) for g in a.groups]
-    for va, vb in rows:
-        assert len(va) == len(vb)
-        for x, y in zip(va, vb):
-            assert x.count == y.count and x.sum_i64 == y.sum_i64 and x.sum_exact == y.sum_exact
-            assert same_value(x.min, y.min) and same_value(x.max, y.max)
-            assert not x.sum_exact or x.sum == y.sum
 
 
 def check_query(seg, fq, got, want, exp):
