@@ -31,6 +31,7 @@
 #include "pg_rank_image.h"
 #include "pg_raw_set_table.h"
 #include "pg_hll.h"
+#include "pg_set_pass_layout.h"
 
 namespace {
 
@@ -428,17 +429,7 @@ pg_status ensure_bitmap(pg_segment* seg, ExecCtx* c, size_t index) {
   return PG_OK;
 }
 
-// Words behind the last bitset row: the dictIds a column's WIDTH admits beyond its cardinality (a forward index that breaks the dictionary's
-// bound then still writes inside the allocation).  Counted in the plan-time byte checks (plan_distinct).
-inline size_t distinct_slack_words(int bits, int cardinality) {
-  const size_t by_width = (((size_t)1 << bits) + 31) / 32, by_card = ((size_t)std::max(cardinality, 0) + 31) / 32;
-  return (by_width > by_card ? by_width - by_card : 0) + 1;
-}
-// The same for the 32-bit counters of PERCENTILE (pg_scan_counts.h): 2^bits - cardinality counters behind the last one (plan_percentile counts them).
-inline size_t counts_slack_words(int bits, int cardinality) {
-  const size_t by_width = (size_t)1 << bits, by_card = (size_t)std::max(cardinality, 0);
-  return (by_width > by_card ? by_width - by_card : 0) + 1;
-}
+// (the sizes of what the set passes keep in this scratch: pg_set_pass_layout.h)
 constexpr size_t kDistinctKeepWords = (size_t)64 << 20;      // a bit matrix above 256 MB is freed after the query instead of staying with the context
 pg_status ensure_distinct(pg_segment* seg, ExecCtx* c, size_t words) {
   if (c->distinct_capacity >= words) return PG_OK;
@@ -2558,10 +2549,10 @@ struct CountList {
   std::vector<int32_t> dict_ids;
   std::vector<uint32_t> counts;
 };
-// `distinct` also carries the counts pass's dense counter rows (num_words = the cardinality) from run_aggregation to execute_percentile, which
+// `distinct` also carries the counts pass's dense counter rows (num_words = the cardinality) from harvest_sets to execute_percentile, which
 // compacts them into `counts`: the dense matrix does not outlive pg_execute.
 // The values behind a PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT aggregation on a raw column, as sorted runs (pg_result_value_counts): row r holds
-// the runs [offsets[r], offsets[r + 1]) of (value_bits, counts).  From run_aggregation to execute_percentile / execute_distinct under GROUP BY the
+// the runs [offsets[r], offsets[r + 1]) of (value_bits, counts).  From harvest_collect to execute_percentile / execute_distinct under GROUP BY the
 // runs of ALL raw group ids travel in one row with run_rows beside them (ascending raw group id, then ascending value): finish_value_lists cuts
 // them into the rows of the groups that exist.
 struct ValueList {
@@ -3134,6 +3125,7 @@ static_assert((kLdsBudget - kCountsRecordBytes) / 4 == PG_PERCENTILE_LDS_MAX_COU
 // scan_distinct_kernel's LDS tier: the reduction records overlay the bitsets' start (the maximum, not the sum, is the rule), so the whole budget holds bits
 static_assert(kLdsBudget * 8 == PG_DISTINCT_LDS_MAX_DICT_IDS, "include/pinot_gpu.h states the LDS tier's reach");
 static_assert(kSetLdsWords == PG_STAGED_SET_LDS_WORDS, "include/pinot_gpu.h states the staged set area");
+// distinct_lds: scan_distinct_kernel / scan_counts_kernel keep their bitsets / counters in LDS (the set passes' parameter blocks and launches: SetPass, below)
 struct ScanGrid { int blocks = 1, threads = kBlockThreads; size_t lds = 0, hist_set_off = 0; bool wide = false, distinct_lds = false; };
 // A segment whose tiles all fit the chip at once (one tile per wave: a 10 M-row segment at five waves per SIMD) is latency from end
 // to end -- launch, one round of loads, the hand-off of the workgroups' records to the fold.  Ten waves per workgroup there: 2.5x
@@ -3308,7 +3300,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::Agg: launch_scan_agg(g_engine.use_dma, one, typed, g.blocks, g.threads, g.lds, stream, sp); break;
     case ScanKernel::Distinct: case ScanKernel::GroupDistinct: case ScanKernel::Counts: case ScanKernel::GroupCounts:
-    case ScanKernel::Collect: case ScanKernel::GroupCollect: case ScanKernel::Hll: case ScanKernel::GroupHll: break;      // (launched with their own parameter block: run_aggregation)
+    case ScanKernel::Collect: case ScanKernel::GroupCollect: case ScanKernel::Hll: case ScanKernel::GroupHll: break;      // (launched with their own parameter block: launch_set_pass)
   }
 }
 // What the phases of execute_impl share about one query
@@ -3466,52 +3458,388 @@ static void fill_hll_dictionary(const ColumnDev& col, HllFoldParams* fp) {
   else if (col.vkind == kValI64) fp->dict_kind = kHllDictI64;
   else fp->dict_kind = col.stored_type == PG_TYPE_FLOAT ? kHllDictFloat : kHllDictDouble;
 }
+// ---- the set passes: what a pass query (kQueryDistinctPass / kQueryCountsPass) adds to the aggregation-only scan ----
+// Four forms, each with kernels and a parameter block of its own, all keeping their device state in the context's d_distinct scratch (GROUP BY: one
+// row per raw group id).  run_aggregation calls the stages below where a scalar query has nothing to do: bind (the columns and keys), arm (keys,
+// layout, scratch, host buffers), launch, enqueue_post (what follows the kernel on the stream), harvest.
+struct CollectLayout { size_t images[kMaxAggCols], work, heads, position, rows, rows_a, rows_b, temp, temp_bytes, total; };
+constexpr size_t kCollectHeadBytes = 256;      // the scratch's first line: the cursor, the flag word, (later) a column's runs
+struct SetPass {
+  // Bitsets: DISTINCTCOUNT (and DISTINCTCOUNTHLL, folded behind the kernel) on dictionary columns; Counts: PERCENTILE on dictionary columns;
+  // Collect: either function on raw columns; HllRaw: DISTINCTCOUNTHLL on raw columns
+  enum Form { None, Bitsets, Counts, Collect, HllRaw } form = None;
+  int function = -1;                       // the one function besides COUNT(*) the pass query carries (set_pass_function)
+  const char* name = "DISTINCTCOUNT";      // ... as the messages spell it
+  std::vector<int> distinct_of;            // per aggregation: its bitset / counter row / list / register set (index into lw.distinct_slots), -1: none
+  std::vector<int> hll_log2m_of;           // per aggregation: the log2m of a DISTINCTCOUNTHLL (0: another function)
+  std::vector<int> key_cards;              // the key columns' cardinalities
+  long long rows = 1;                      // raw group ids: their product
+  DistinctParams dp; HllParams hp; CollectParams cp;      // the form's parameter block (Bitsets and Counts: dp)
+  std::vector<std::vector<uint32_t>> distinct_host;      // Bitsets / Counts: per bitset where its copy lands -- the vector that becomes the result's DistinctSet, no second host copy
+  // DISTINCTCOUNTHLL: per aggregation the first staged register word in the scratch (Bitsets: its own matrix's; HllRaw: its slot's); the staged
+  // words are packed to bytes behind them and land in hll_host in the same order
+  std::vector<size_t> hll_first;
+  std::vector<int> hll_same_as;            // Bitsets: an earlier aggregation on the same column and log2m, whose registers this one shares
+  size_t hll_staged_words = 0, hll_staged_first = 0;
+  std::vector<uint8_t> hll_host;
+  CollectLayout cl{};                                            // Collect: where everything lies in the scratch, ...
+  unsigned long long collect_head[3] = {0ull, 0ull, 0ull};      // ... what the kernel leaves in its first line, and the lists' capacity in docs
+  size_t collect_capacity = 0;
+  // (declared last, destroyed first: nothing frees the host buffers above under a copy that is still on the stream)
+  struct SyncOnExit { hipStream_t stream = nullptr; bool armed = false; ~SyncOnExit() { if (armed) (void)hipStreamSynchronize(stream); } } copy;
+  bool grouped(const Lowered& lw) const { return !lw.distinct_key_slots.empty(); }
+};
+// bind, 1: which pass the query is.  (choose_scan_kernel and scan_grid go by the Lowered's flags and slots.)
+static void open_set_pass(QueryRun& r, SetPass* p) {
+  Lowered& lw = r.lw;
+  const bool on = (r.q->flags & kQuerySetPass) != 0 && !r.want_bitmap;
+  p->function = set_pass_function(r.q->flags);
+  p->name = p->function == PG_AGG_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT";
+  lw.counts_pass = on && p->function == PG_AGG_PERCENTILE;
+  lw.collect_pass = on && (r.q->flags & kQueryCollectPass) != 0;
+  lw.hll_pass = on && (r.q->flags & kQueryHllPass) != 0;
+  if (!on) return;
+  p->form = lw.hll_pass ? SetPass::HllRaw : (lw.collect_pass ? SetPass::Collect : (lw.counts_pass ? SetPass::Counts : SetPass::Bitsets));
+  p->copy.stream = r.ctx->stream;
+  p->distinct_of.assign((size_t)std::max(r.na, 1), -1);
+  p->hll_log2m_of.assign((size_t)std::max(r.na, 1), 0);
+}
+// bind, 2: aggregation `a`, if it is the pass's (*bound) -- its column's dictId stream (Bitsets / Counts) or value bytes (Collect / HllRaw).  One slot
+// per distinct column (the same column twice shares it; a DISTINCTCOUNTHLL on a dictionary column shares the bitset too); HllRaw: per column and log2m.
+static pg_status bind_set_pass_column(QueryRun& r, SetPass* p, int a, bool* bound) {
+  const pg_segment* seg = r.seg; Lowered& lw = r.lw;
+  const pg_aggregation& ag = r.q->aggregations[a];
+  const bool hll_agg = p->function == PG_AGG_DISTINCTCOUNT && is_hll_function(ag.function);
+  *bound = p->form != SetPass::None && (hll_agg || (ag.function == p->function && !lw.hll_pass));
+  if (!*bound) return PG_OK;
+  if (ag.column < 0 || ag.column >= (int)seg->cols.size()) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
+  if (hll_agg) p->hll_log2m_of[(size_t)a] = pg::hll_log2m_of(ag.function);
+  const bool raw_form = lw.collect_pass || lw.hll_pass;
+  if (seg->cols[(size_t)ag.column].encoding != (raw_form ? PG_FWD_RAW_FIXED_BYTE : PG_FWD_FIXED_BIT_DICT))
+    return fail(PG_ERR_UNSUPPORTED, "%s on %s column %s", p->name, raw_form ? "dictionary" : "raw", seg->cols[(size_t)ag.column].name.c_str());
+  r.add_projected(ag.column);
+  const int s = slot_for(&lw, seg, ag.column, false);
+  if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+  lw.plan.cols[s].in_agg = 1;
+  size_t dc = 0;
+  if (lw.hll_pass) { while (dc < lw.distinct_slots.size() && !(lw.distinct_slots[dc] == s && lw.hll_slot_log2m[dc] == p->hll_log2m_of[(size_t)a])) ++dc; }
+  else dc = std::find(lw.distinct_slots.begin(), lw.distinct_slots.end(), s) - lw.distinct_slots.begin();
+  if (dc == lw.distinct_slots.size()) {
+    if (dc >= (size_t)kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d %s columns", kMaxAggCols, p->name);
+    lw.distinct_slots.push_back(s);
+    if (lw.hll_pass) lw.hll_slot_log2m.push_back(p->hll_log2m_of[(size_t)a]);
+  }
+  p->distinct_of[(size_t)a] = (int)dc;
+  return PG_OK;
+}
+// bind, 3: the grouped kernels' keys -- dictionary columns, raw INT / LONG columns through their key images (built by the ordinary query before this pass)
+static pg_status bind_set_pass_keys(QueryRun& r, SetPass* p) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; Lowered& lw = r.lw;
+  if (lw.distinct_slots.empty()) return fail(PG_ERR_INTERNAL, "a %s pass without a %s column", p->name, p->name);
+  for (int g = 0; g < q->num_group_by; ++g) {
+    int c = q->group_by_columns[g];
+    if (c < 0 || c >= (int)seg->cols.size()) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
+    r.add_projected(c);
+    if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) { const pg_status st = ensure_key_image(seg, c, &c); if (st != PG_OK) return st; }
+    if ((int)lw.distinct_key_slots.size() >= kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "%s with more than %d group-by columns", p->name, kMaxDistinctKeys);
+    const int s = slot_for(&lw, seg, c, false);
+    if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
+    lw.plan.cols[s].in_agg = 1;
+    lw.distinct_key_slots.push_back(s);
+    p->key_cards.push_back(std::max(seg->cols[(size_t)c].cardinality, 1));
+  }
+  return PG_OK;
+}
+// keys: the rows of every form's matrices -- one per raw group id -- and the kernels' mixed-radix decode of it
+static pg_status set_pass_keys(const Lowered& lw, SetPass* p, DistinctParams* d) {
+  for (int card : p->key_cards) p->rows *= card;
+  if (p->rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "%s GROUP BY over %lld raw keys", p->name, p->rows);
+  d->num_cols = (int32_t)lw.distinct_slots.size();
+  d->num_keys = (int32_t)lw.distinct_key_slots.size();
+  uint32_t mult = 1;
+  for (size_t g = 0; g < lw.distinct_key_slots.size(); ++g) {
+    const DevColumn& kc = lw.plan.cols[lw.distinct_key_slots[g]];
+    d->keys[g].fwd = kc.fwd; d->keys[g].bits = kc.bits; d->keys[g].mult = mult;
+    mult *= (uint32_t)p->key_cards[g];
+  }
+  return PG_OK;
+}
+// arm, Bitsets / Counts: one zeroed bitset (counter vector) per column in the context's scratch -- under GROUP BY a matrix of one row per raw group
+// id -- and behind the last row the slack of pg_set_pass_layout.h, so that a forward index that breaks the dictionary's bound cannot make the kernel
+// write outside the allocation.  DISTINCTCOUNTHLLs on these columns: behind the bitsets one zeroed register matrix of 32-bit words per such
+// aggregation (hll_fold_kernel's target), and behind those the same registers packed to bytes (hll_pack_kernel's) -- the only part of them that is copied.
+static pg_status arm_bitsets(QueryRun& r, SetPass* p, const ScanGrid& grid) {
+  ExecCtx* ctx = r.ctx; const Lowered& lw = r.lw; const int na = r.na;
+  const bool counters = p->form == SetPass::Counts;
+  DistinctParams& dp = p->dp;
+  memset(&dp, 0, sizeof(dp));
+  pg_status st = set_pass_keys(lw, p, &dp); if (st != PG_OK) return st;
+  SetMatrixLayout matrices;
+  size_t first[kMaxAggCols] = {};
+  int lds_off = 0;
+  for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+    const DevColumn& dc = lw.plan.cols[lw.distinct_slots[c]];
+    DistinctCol& col = dp.cols[c];
+    col.fwd = dc.fwd; col.bits = dc.bits; col.words = set_row_words(counters, dc.cardinality); col.lds_off = lds_off;
+    lds_off += col.words;
+    first[c] = (size_t)matrices.add(counters, (uint64_t)p->rows, dc.bits, dc.cardinality);
+  }
+  dp.lds_words = grid.distinct_lds ? lds_off : 0;
+  p->hll_first.assign((size_t)std::max(na, 1), 0);
+  p->hll_same_as.assign((size_t)std::max(na, 1), -1);
+  size_t hll_words = 0;
+  const size_t hll_base = (size_t)hll_staged_base(matrices.total_words());
+  for (int a = 0; a < na; ++a) {
+    if (p->hll_log2m_of[(size_t)a] == 0) continue;
+    // (the same column at the same log2m twice: one register matrix, one fold)
+    for (int b = 0; b < a && p->hll_same_as[(size_t)a] < 0; ++b)
+      if (p->hll_log2m_of[(size_t)b] == p->hll_log2m_of[(size_t)a] && p->distinct_of[(size_t)b] == p->distinct_of[(size_t)a]) p->hll_same_as[(size_t)a] = b;
+    if (p->hll_same_as[(size_t)a] >= 0) { p->hll_first[(size_t)a] = p->hll_first[(size_t)p->hll_same_as[(size_t)a]]; continue; }
+    p->hll_first[(size_t)a] = hll_base + hll_words;
+    hll_words += (size_t)hll_staged_words((uint64_t)p->rows, p->hll_log2m_of[(size_t)a]);
+  }
+  st = ensure_distinct(r.seg, ctx, (size_t)hll_scratch_words(hll_base, hll_words)); if (st != PG_OK) return st;
+  for (size_t c = 0; c < lw.distinct_slots.size(); ++c) dp.cols[c].set_bits = ctx->d_distinct + first[c];
+  HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, (hll_base + hll_words) * 4, ctx->stream));
+  p->hll_staged_words = hll_words; p->hll_staged_first = hll_base;
+  if (r.out) {
+    p->distinct_host.resize(lw.distinct_slots.size());
+    // (a bitset that only HLLs use stays on the device)
+    for (int a = 0; a < na; ++a) {
+      const int dc = p->distinct_of[(size_t)a];
+      if (dc >= 0 && p->hll_log2m_of[(size_t)a] == 0) p->distinct_host[(size_t)dc].resize((size_t)p->rows * (size_t)dp.cols[dc].words);
+    }
+    p->hll_host.resize(hll_words);
+  }
+  return PG_OK;
+}
+// arm, HllRaw: one zeroed register row per slot in the same scratch -- under GROUP BY a matrix of one row per raw group id -- and the packed bytes behind them
+static pg_status arm_hll_raw(QueryRun& r, SetPass* p) {
+  ExecCtx* ctx = r.ctx; const Lowered& lw = r.lw;
+  HllParams& hp = p->hp;
+  memset(&hp, 0, sizeof(hp));
+  pg_status st = set_pass_keys(lw, p, &hp.d); if (st != PG_OK) return st;
+  size_t hll_words = 0, slot_first[kMaxAggCols] = {};
+  int lds_off = 0;
+  for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+    const DevColumn& dc = lw.plan.cols[lw.distinct_slots[c]];
+    hp.fwd[c] = dc.fwd; hp.wide[c] = (dc.vkind == kValI64 || dc.vkind == kValF64) ? 1 : 0;
+    hp.log2m[c] = lw.hll_slot_log2m[c]; hp.lds_off[c] = lds_off;
+    lds_off += 1 << hp.log2m[c];
+    slot_first[c] = hll_words;
+    hll_words += (size_t)hll_staged_words((uint64_t)p->rows, hp.log2m[c]);
+  }
+  hp.lds_words = p->grouped(lw) ? 0 : lds_off;      // (scan_hll_kernel keeps the registers in LDS; group_hll_kernel's matrices live in HBM)
+  hp.num_rows = (uint32_t)p->rows;
+  st = ensure_distinct(r.seg, ctx, (size_t)hll_scratch_words(0, hll_words)); if (st != PG_OK) return st;
+  for (size_t c = 0; c < lw.distinct_slots.size(); ++c) hp.regs[c] = ctx->d_distinct + slot_first[c];
+  p->hll_first.assign((size_t)std::max(r.na, 1), 0);
+  for (int a = 0; a < r.na; ++a) if (p->distinct_of[(size_t)a] >= 0) p->hll_first[(size_t)a] = slot_first[p->distinct_of[(size_t)a]];
+  HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, hll_words * 4, ctx->stream));
+  p->hll_staged_words = hll_words; p->hll_staged_first = 0;
+  if (r.out) p->hll_host.resize(hll_words);
+  return PG_OK;
+}
+// arm, Collect: one list of `capacity` 64-bit images per raw column in the same scratch (GROUP BY: the docs' raw group ids beside them), the sort's
+// second buffers, the run arrays and rocPRIM's scratch behind them.  The capacity is the segment's docs -- what the plan-time bound was priced
+// with (plan_collect_bytes) -- so no reservation of a matching doc can fail; the kernel checks every one all the same.
+static pg_status arm_collect(QueryRun& r, SetPass* p) {
+  ExecCtx* ctx = r.ctx; const Lowered& lw = r.lw;
+  CollectParams& cp = p->cp; CollectLayout& cl = p->cl;
+  memset(&cp, 0, sizeof(cp));
+  pg_status st = set_pass_keys(lw, p, &cp.d); if (st != PG_OK) return st;
+  const bool grouped = p->grouped(lw);
+  const size_t capacity = p->collect_capacity = (size_t)std::max<long long>((long long)r.seg->num_docs, 1);
+  HIP_TRY(collect_sort_temp_bytes(capacity, grouped, &cl.temp_bytes));
+  auto take = [&cl](size_t bytes) { const size_t at = cl.total; cl.total += (bytes + 255) & ~(size_t)255; return at; };
+  (void)take(kCollectHeadBytes);
+  for (size_t c = 0; c < lw.distinct_slots.size(); ++c) cl.images[c] = take(capacity * 8);
+  cl.work = take(capacity * 8);
+  cl.heads = take(capacity * 4);
+  cl.position = take(capacity * 4);
+  if (grouped) { cl.rows = take(capacity * 4); cl.rows_a = take(capacity * 4); cl.rows_b = take(capacity * 4); }
+  cl.temp = take(std::max<size_t>(cl.temp_bytes, 256));
+  st = ensure_distinct(r.seg, ctx, cl.total / 4); if (st != PG_OK) return st;
+  uint8_t* const base = reinterpret_cast<uint8_t*>(ctx->d_distinct);
+  for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+    const DevColumn& dc = lw.plan.cols[lw.distinct_slots[c]];
+    cp.fwd[c] = dc.fwd; cp.vkind[c] = dc.vkind;
+    cp.out_images[c] = reinterpret_cast<unsigned long long*>(base + cl.images[c]);
+  }
+  cp.out_rows = grouped ? reinterpret_cast<uint32_t*>(base + cl.rows) : nullptr;
+  cp.cursor = reinterpret_cast<unsigned long long*>(base);
+  cp.flags = reinterpret_cast<uint32_t*>(base + 8);
+  cp.capacity = (unsigned long long)capacity;
+  HIP_TRY(hipMemsetAsync(base, 0, kCollectHeadBytes, ctx->stream));
+  return PG_OK;
+}
+static pg_status arm_set_pass(QueryRun& r, SetPass* p, const ScanGrid& grid) {
+  switch (p->form) {
+    case SetPass::Bitsets: case SetPass::Counts: return arm_bitsets(r, p, grid);
+    case SetPass::Collect: return arm_collect(r, p);
+    case SetPass::HllRaw: return arm_hll_raw(r, p);
+    default: return PG_OK;
+  }
+}
+// launch: the form's kernel behind the lowered filter -- the scan form without GROUP BY, the group form with it
+static void launch_set_pass(const QueryRun& r, SetPass* p, const ScanGrid& grid) {
+  const ScanParams& sp = r.lw.sp; hipStream_t stream = r.ctx->stream;
+  const bool grouped = p->grouped(r.lw); const int blocks = grid.blocks; const size_t lds = grid.lds;
+  switch (p->form) {
+    case SetPass::Bitsets: p->dp.scan = sp; grouped ? launch_group_distinct(blocks, lds, stream, p->dp) : launch_scan_distinct(grid.distinct_lds, blocks, lds, stream, p->dp); break;
+    case SetPass::Counts: p->dp.scan = sp; grouped ? launch_group_counts(blocks, lds, stream, p->dp) : launch_scan_counts(grid.distinct_lds, blocks, lds, stream, p->dp); break;
+    case SetPass::Collect: p->cp.d.scan = sp; grouped ? launch_group_collect(blocks, lds, stream, p->cp) : launch_scan_collect(blocks, lds, stream, p->cp); break;
+    case SetPass::HllRaw: p->hp.d.scan = sp; grouped ? launch_group_hll(blocks, lds, stream, p->hp) : launch_scan_hll(blocks, lds, stream, p->hp); break;
+    default: break;
+  }
+}
+// enqueue_post: what follows the kernel on the stream -- the bitsets' / counters' copies; the collect pass's cursor and flag word; one hll_fold_kernel
+// per DISTINCTCOUNTHLL aggregation over its column's bitset rows, then hll_pack_kernel over all staged registers and the copy of the packed bytes
+static pg_status enqueue_set_pass_post(QueryRun& r, SetPass* p) {
+  const pg_segment* seg = r.seg; ExecCtx* ctx = r.ctx;
+  const bool bitsets = p->form == SetPass::Bitsets || p->form == SetPass::Counts;
+  if (bitsets && !p->distinct_host.empty()) {
+    p->copy.armed = true;
+    for (size_t c = 0; c < p->distinct_host.size(); ++c)
+      if (!p->distinct_host[c].empty()) HIP_TRY(hipMemcpyAsync(p->distinct_host[c].data(), p->dp.cols[c].set_bits, p->distinct_host[c].size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (p->form == SetPass::Collect) { p->copy.armed = true; HIP_TRY(hipMemcpyAsync(p->collect_head, ctx->d_distinct, 16, hipMemcpyDeviceToHost, ctx->stream)); }
+  if (p->hll_staged_words == 0) return PG_OK;
+  for (int a = 0; a < (bitsets ? r.na : 0); ++a) {      // the bitsets' rows -> register rows, one fold per DISTINCTCOUNTHLL aggregation over its column's bitset
+    if (p->hll_log2m_of[(size_t)a] == 0 || p->hll_same_as[(size_t)a] >= 0) continue;
+    const ColumnDev& col = seg->cols[(size_t)r.q->aggregations[a].column];
+    const DistinctCol& bits = p->dp.cols[p->distinct_of[(size_t)a]];
+    HllFoldParams fp;
+    memset(&fp, 0, sizeof(fp));
+    fp.bits = bits.set_bits; fp.regs = ctx->d_distinct + p->hll_first[(size_t)a];
+    fp.words = bits.words; fp.cardinality = col.cardinality; fp.log2m = p->hll_log2m_of[(size_t)a];
+    fill_hll_dictionary(col, &fp);
+    launch_hll_fold(p->rows, ctx->stream, fp);
+    HIP_TRY(hipGetLastError());
+  }
+  uint8_t* const packed = reinterpret_cast<uint8_t*>(ctx->d_distinct + p->hll_staged_first + p->hll_staged_words);
+  launch_hll_pack(ctx->d_distinct + p->hll_staged_first, packed, p->hll_staged_words, seg->num_cus, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  if (!p->hll_host.empty()) { p->copy.armed = true; HIP_TRY(hipMemcpyAsync(p->hll_host.data(), packed, p->hll_host.size(), hipMemcpyDeviceToHost, ctx->stream)); }
+  return PG_OK;
+}
+// harvest, Bitsets / Counts / HllRaw: one set per DISTINCTCOUNT / PERCENTILE aggregation, one register set per DISTINCTCOUNTHLL.  Aggregation only: a
+// DISTINCTCOUNT's count is its set's cardinality, an HLL's its non-zero registers.  Under GROUP BY the rows are raw group ids: execute_distinct /
+// execute_percentile keep the rows of the groups that exist.
+static void harvest_sets(QueryRun& r, SetPass* p) {
+  pg_result* out = r.out; const bool grouped = p->grouped(r.lw);
+  std::unique_ptr<ResultInternal> sets(new ResultInternal());
+  for (int a = r.na - 1; a >= 0; --a) {      // (the last aggregation on a column takes the copy itself, earlier ones on the same column a copy of it)
+    const int dc = p->distinct_of[(size_t)a];
+    if (dc < 0) continue;
+    if (p->hll_log2m_of[(size_t)a] != 0) {
+      sets->hll.push_back(hll_set_of(p->hll_host, p->hll_first[(size_t)a] - p->hll_staged_first, a, p->hll_log2m_of[(size_t)a], p->rows));
+      if (!grouped) out->aggregations[a].count = hll_nonzero(sets->hll.back().registers.data(), sets->hll.back().registers.size());
+      continue;
+    }
+    DistinctSet ds;
+    ds.aggregation = a; ds.num_words = p->dp.cols[dc].words; ds.rows = (int)p->rows;
+    bool again = false;
+    for (int b = 0; b < a; ++b) again |= p->distinct_of[(size_t)b] == dc && p->hll_log2m_of[(size_t)b] == 0;
+    if (again) ds.words = p->distinct_host[(size_t)dc]; else ds.words = std::move(p->distinct_host[(size_t)dc]);
+    if (!grouped && p->form == SetPass::Bitsets) {      // (PERCENTILE: count stays the docs aggregated, the list's length)
+      int64_t card = 0;
+      for (uint32_t w : ds.words) card += __builtin_popcount(w);
+      out->aggregations[a].count = card;
+    }
+    sets->distinct.push_back(std::move(ds));
+  }
+  out->internal = sets.release();
+}
+// harvest, Collect: the cursor's final value is the filter's match count (`matched`: the scan record's).  Every column's list is sorted and
+// run-length encoded on the device; only the runs cross the bus.
+static pg_status harvest_collect(QueryRun& r, SetPass* p, unsigned long long matched) {
+  pg_segment* seg = r.seg; ExecCtx* ctx = r.ctx; const Lowered& lw = r.lw; pg_result* out = r.out;
+  const CollectLayout& cl = p->cl;
+  struct Trim { pg_segment* seg; ExecCtx* ctx; ~Trim() { trim_distinct(seg, ctx); } } trim_on_exit{seg, ctx};
+  const unsigned long long n = p->collect_head[0];
+  if ((uint32_t)p->collect_head[1] & kCollectOverflow) return fail(PG_ERR_INTERNAL, "%s: the value lists overflowed their capacity of %zu docs (cursor %llu)", p->name, p->collect_capacity, n);
+  if (n != matched) return fail(PG_ERR_INTERNAL, "%s: %llu values were collected for %llu matching docs", p->name, n, matched);
+  if (!out) return PG_OK;
+  const bool grouped = p->grouped(lw);
+  uint8_t* const base = reinterpret_cast<uint8_t*>(ctx->d_distinct);
+  int row_bits = 1;
+  while (row_bits < 32 && (1ll << row_bits) < p->rows) ++row_bits;
+  std::vector<ValueList> per_col(lw.distinct_slots.size());
+  std::vector<uint32_t> first;
+  for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
+    ValueList& vl = per_col[c];
+    vl.grouped_in_transit = grouped;
+    if (n == 0) continue;
+    CollectSort cs;
+    cs.images = p->cp.out_images[c]; cs.images_work = reinterpret_cast<unsigned long long*>(base + cl.work);
+    cs.rows = p->cp.out_rows; cs.rows_a = reinterpret_cast<uint32_t*>(base + cl.rows_a); cs.rows_b = reinterpret_cast<uint32_t*>(base + cl.rows_b);
+    cs.row_bits = row_bits;
+    cs.heads = reinterpret_cast<uint32_t*>(base + cl.heads); cs.position = reinterpret_cast<uint32_t*>(base + cl.position);
+    cs.num_runs = reinterpret_cast<uint32_t*>(base + 16);
+    cs.temp = base + cl.temp; cs.temp_bytes = std::max<size_t>(cl.temp_bytes, 256);
+    CollectRuns runs;
+    HIP_TRY(collect_sort_runs(cs, (size_t)n, seg->num_cus, ctx->stream, &runs));
+    uint32_t num_runs = 0;
+    HIP_TRY(hipMemcpyAsync(&num_runs, cs.num_runs, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (num_runs == 0u || (unsigned long long)num_runs > n) return fail(PG_ERR_INTERNAL, "%s: %u runs in a list of %llu values", p->name, num_runs, n);
+    // only the runs cross the bus: their images, the index of their first entry and (GROUP BY) their raw group ids
+    vl.value_bits.resize(num_runs); first.resize(num_runs);
+    HIP_TRY(hipMemcpyAsync(vl.value_bits.data(), runs.images, (size_t)num_runs * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(first.data(), runs.first, (size_t)num_runs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (grouped) { vl.run_rows.resize(num_runs); HIP_TRY(hipMemcpyAsync(vl.run_rows.data(), runs.rows, (size_t)num_runs * 4, hipMemcpyDeviceToHost, ctx->stream)); }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const bool floating = p->cp.vkind[c] == kValF64 || p->cp.vkind[c] == kValF32;
+    vl.counts.resize(num_runs);
+    for (uint32_t j = 0; j < num_runs; ++j) {
+      vl.value_bits[j] = (int64_t)rank_image_value_bits((unsigned long long)vl.value_bits[j], floating);
+      vl.counts[j] = (j + 1 < num_runs ? first[j + 1] : (uint32_t)n) - first[j];
+    }
+  }
+  std::unique_ptr<ResultInternal> lists(new ResultInternal());
+  for (int a = r.na - 1; a >= 0; --a) {      // (the last aggregation on a column takes the runs themselves, earlier ones on the same column a copy)
+    const int dc = p->distinct_of[(size_t)a];
+    if (dc < 0) continue;
+    bool again = false;
+    for (int b = 0; b < a; ++b) again |= p->distinct_of[(size_t)b] == dc;
+    ValueList vl;
+    if (again) vl = per_col[(size_t)dc]; else vl = std::move(per_col[(size_t)dc]);
+    vl.aggregation = a;
+    vl.offsets = {0, vl.value_bits.size()};
+    // aggregation only: PERCENTILE's count is the list's length (the docs aggregated: convert put it there), DISTINCTCOUNT's the number of runs
+    if (!grouped && p->function == PG_AGG_DISTINCTCOUNT) out->aggregations[a].count = (int64_t)vl.value_bits.size();
+    lists->values.push_back(std::move(vl));
+  }
+  out->internal = lists.release();
+  return PG_OK;
+}
+// harvest: the stream was synchronised -- the copies of enqueue_post have landed.  The sets go to out->internal for execute_distinct / execute_percentile.
+static pg_status harvest_set_pass(QueryRun& r, SetPass* p, const BlockPartial& fp) {
+  p->copy.armed = false;
+  if (p->form == SetPass::Collect) return harvest_collect(r, p, (unsigned long long)fp.count);
+  if (r.out) harvest_sets(r, p);
+  trim_distinct(r.seg, r.ctx);
+  return PG_OK;
+}
 // ---------------- aggregation only ----------------
 static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_request, uint64_t* host_bitmap, int64_t host_bitmap_words, int64_t* out_cardinality) {
   pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; ScanParams& sp = lw.sp;
   PlanParams& pl = lw.plan; const int na = r.na, num_cols_total = (int)seg->cols.size(); const bool want_bitmap = r.want_bitmap, timed = r.timed;
   pg_status st = PG_OK;
   std::vector<int> agg_slot_of((size_t)std::max(na, 1), -1);
-  const bool distinct_pass = (q->flags & kQuerySetPass) != 0 && !want_bitmap;      // the bitset pass (DISTINCTCOUNT) or the counts pass (PERCENTILE)
-  const int pass_function = set_pass_function(q->flags);
-  const char* const pass_name = pass_function == PG_AGG_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT";
-  lw.counts_pass = distinct_pass && pass_function == PG_AGG_PERCENTILE;
-  lw.collect_pass = distinct_pass && (q->flags & kQueryCollectPass) != 0;
-  lw.hll_pass = distinct_pass && (q->flags & kQueryHllPass) != 0;
-  std::vector<int> hll_log2m_of((size_t)std::max(na, 1), 0);      // per aggregation: the log2m of a DISTINCTCOUNTHLL (0: another function)
-  std::vector<int> distinct_of((size_t)std::max(na, 1), -1);      // per aggregation: its bitset (index into lw.distinct_slots)
-  std::vector<int> distinct_key_cards;
+  SetPass pass;      // (form None: an ordinary query -- every stage below is skipped)
+  open_set_pass(r, &pass);
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
     if (ag.function == PG_AGG_COUNT) {
       if ((q->flags & kQueryCountReadsColumn) && ag.column >= 0 && ag.column < num_cols_total) r.add_projected(ag.column);
       continue;
     }
-    const bool hll_agg = distinct_pass && pass_function == PG_AGG_DISTINCTCOUNT && is_hll_function(ag.function);
-    if (hll_agg || (distinct_pass && ag.function == pass_function && !lw.hll_pass)) {
-      // a column of the bitset / counts pass: its dictId stream, one bitset / counter vector per distinct column (the same column twice shares it;
-      // a DISTINCTCOUNTHLL on a dictionary column shares the bitset too and is folded into registers behind the kernel)
-      if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
-      if (hll_agg) hll_log2m_of[(size_t)a] = pg::hll_log2m_of(ag.function);
-      // (the collect pass: a raw column's value bytes, one list per distinct column; the HLL pass: one register set per raw column and log2m)
-      if ((lw.collect_pass || lw.hll_pass) ? seg->cols[(size_t)ag.column].encoding != PG_FWD_RAW_FIXED_BYTE : seg->cols[(size_t)ag.column].encoding != PG_FWD_FIXED_BIT_DICT)
-        return fail(PG_ERR_UNSUPPORTED, "%s on %s column %s", pass_name, (lw.collect_pass || lw.hll_pass) ? "dictionary" : "raw", seg->cols[(size_t)ag.column].name.c_str());
-      r.add_projected(ag.column);
-      const int s = slot_for(&lw, seg, ag.column, false);
-      if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
-      pl.cols[s].in_agg = 1;
-      size_t dc = 0;
-      if (lw.hll_pass) { while (dc < lw.distinct_slots.size() && !(lw.distinct_slots[dc] == s && lw.hll_slot_log2m[dc] == hll_log2m_of[(size_t)a])) ++dc; }
-      else dc = std::find(lw.distinct_slots.begin(), lw.distinct_slots.end(), s) - lw.distinct_slots.begin();
-      if (dc == lw.distinct_slots.size()) {
-        if (dc >= (size_t)kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d %s columns", kMaxAggCols, pass_name);
-        lw.distinct_slots.push_back(s);
-        if (lw.hll_pass) lw.hll_slot_log2m.push_back(hll_log2m_of[(size_t)a]);
-      }
-      distinct_of[(size_t)a] = (int)dc;
-      continue;
-    }
-    if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG || distinct_pass) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
+    bool bound = false;
+    st = bind_set_pass_column(r, &pass, a, &bound); if (st != PG_OK) return st;
+    if (bound) continue;
+    if (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG || pass.form != SetPass::None) return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
     r.add_projected(ag.column);
     int s = slot_for(&lw, seg, ag.column, lw.plane_cols[(size_t)ag.column] != 0);
@@ -3528,22 +3856,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     if (ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) pl.agg_cols[ac].need_minmax = 1;
     agg_slot_of[(size_t)a] = ac;
   }
-  if (distinct_pass) {
-    if (lw.distinct_slots.empty()) return fail(PG_ERR_INTERNAL, "a %s pass without a %s column", pass_name, pass_name);
-    // group_distinct_kernel's keys: dictionary columns, raw INT / LONG columns through their key images (built by the ordinary query before this pass)
-    for (int g = 0; g < q->num_group_by; ++g) {
-      int c = q->group_by_columns[g];
-      if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
-      r.add_projected(c);
-      if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) { st = ensure_key_image(seg, c, &c); if (st != PG_OK) return st; }
-      if ((int)lw.distinct_key_slots.size() >= kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "%s with more than %d group-by columns", pass_name, kMaxDistinctKeys);
-      const int s = slot_for(&lw, seg, c, false);
-      if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
-      pl.cols[s].in_agg = 1;
-      lw.distinct_key_slots.push_back(s);
-      distinct_key_cards.push_back(std::max(seg->cols[(size_t)c].cardinality, 1));
-    }
-  }
+  if (pass.form != SetPass::None) { st = bind_set_pass_keys(r, &pass); if (st != PG_OK) return st; }
   bool need_queue = false, typed = false;
   for (int i = 0; i < pl.num_agg_cols; ++i) {
     const DevColumn& c = pl.cols[pl.agg_cols[i].col];
@@ -3719,152 +4032,8 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   sp.lane_skip = g_engine.lane_skip ? 1 : 0;
   sp.set_leaves_in_lds = 0;
   if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) if (sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet) sp.set_leaves_in_lds = 1;
-  const bool is_counts = k.kernel == ScanKernel::Counts || k.kernel == ScanKernel::GroupCounts;      // 32-bit counters: a row is `cardinality` words
-  const bool is_distinct = k.kernel == ScanKernel::Distinct || k.kernel == ScanKernel::GroupDistinct || is_counts;
-  const bool is_collect = k.kernel == ScanKernel::Collect || k.kernel == ScanKernel::GroupCollect;      // raw columns: lists of order images, sorted behind the kernel
-  const bool is_hll = k.kernel == ScanKernel::Hll || k.kernel == ScanKernel::GroupHll;      // raw columns: HyperLogLog registers, packed to bytes behind the kernel
-  if (k.kernel == ScanKernel::Hist || is_distinct || is_collect || is_hll) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / bitset kernels keep the area in their dynamic LDS, behind the counters / bitsets)
-  // The bitset pass: one zeroed bitset per DISTINCTCOUNT column in the context's scratch -- under GROUP BY a matrix of one row per raw group id --
-  // and one copy of all of them behind the kernel.  Behind the last row: room for the dictIds the column's WIDTH admits beyond its cardinality,
-  // so that a forward index that breaks the dictionary's bound cannot make the kernel write outside the allocation.
-  DistinctParams dp;
-  std::vector<std::vector<uint32_t>> distinct_host;      // per bitset: where its copy lands -- the vector that becomes the result's DistinctSet, no second host copy
-  std::vector<size_t> distinct_first;      // per bitset: its first word in the scratch
-  long long distinct_rows = 1;
-  // DISTINCTCOUNTHLL: per aggregation (dictionary form) / per slot (raw form) the first staged register word in the scratch; the staged words are
-  // packed to bytes behind them and land in hll_host in the same order
-  std::vector<size_t> hll_first((size_t)std::max(na, 1), 0), hll_slot_first;
-  std::vector<int> hll_same_as((size_t)std::max(na, 1), -1);      // dictionary form: an earlier aggregation on the same column and log2m, whose registers this one shares
-  size_t hll_staged_words = 0, hll_staged_first = 0;
-  std::vector<uint8_t> hll_host;
-  struct SyncOnExit { hipStream_t stream; bool armed; ~SyncOnExit() { if (armed) (void)hipStreamSynchronize(stream); } } distinct_copy{ctx->stream, false};      // (nothing frees distinct_host under the copy)
-  if (is_distinct) {
-    memset(&dp, 0, sizeof(dp));
-    for (int card : distinct_key_cards) distinct_rows *= card;
-    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "%s GROUP BY over %lld raw keys", pass_name, distinct_rows);
-    size_t total = 0, slack = 0;
-    int lds_off = 0;
-    dp.num_cols = (int32_t)lw.distinct_slots.size();
-    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
-      const DevColumn& dc = pl.cols[lw.distinct_slots[c]];
-      DistinctCol& col = dp.cols[c];
-      col.fwd = dc.fwd; col.bits = dc.bits; col.words = is_counts ? std::max(dc.cardinality, 0) : (dc.cardinality + 31) / 32; col.lds_off = lds_off;
-      lds_off += col.words;
-      distinct_first.push_back(total);
-      total += (size_t)distinct_rows * (size_t)col.words;
-      slack = std::max(slack, is_counts ? counts_slack_words(dc.bits, dc.cardinality) : distinct_slack_words(dc.bits, dc.cardinality));
-    }
-    dp.lds_words = grid.distinct_lds ? lds_off : 0;
-    dp.num_keys = (int32_t)lw.distinct_key_slots.size();
-    uint32_t mult = 1;
-    for (size_t g = 0; g < lw.distinct_key_slots.size(); ++g) {
-      const DevColumn& kc = pl.cols[lw.distinct_key_slots[g]];
-      dp.keys[g].fwd = kc.fwd; dp.keys[g].bits = kc.bits; dp.keys[g].mult = mult;
-      mult *= (uint32_t)distinct_key_cards[g];
-    }
-    // DISTINCTCOUNTHLLs on these columns: behind the bitsets one zeroed register matrix of 32-bit words per such aggregation (hll_fold_kernel's
-    // target), and behind those the same registers packed to bytes (hll_pack_kernel's) -- the only part of them that is copied
-    size_t hll_words = 0;
-    const size_t hll_base = (total + slack + 3) & ~(size_t)3;      // (sixteen-byte aligned: hll_pack_kernel reads four registers per load)
-    for (int a = 0; a < na; ++a) {
-      if (hll_log2m_of[(size_t)a] == 0) continue;
-      // (the same column at the same log2m twice: one register matrix, one fold)
-      hll_same_as[(size_t)a] = -1;
-      for (int b = 0; b < a && hll_same_as[(size_t)a] < 0; ++b)
-        if (hll_log2m_of[(size_t)b] == hll_log2m_of[(size_t)a] && distinct_of[(size_t)b] == distinct_of[(size_t)a]) hll_same_as[(size_t)a] = b;
-      if (hll_same_as[(size_t)a] >= 0) { hll_first[(size_t)a] = hll_first[(size_t)hll_same_as[(size_t)a]]; continue; }
-      hll_first[(size_t)a] = hll_base + hll_words;
-      hll_words += (size_t)distinct_rows << hll_log2m_of[(size_t)a];
-    }
-    st = ensure_distinct(seg, ctx, hll_base + hll_words + hll_words / 4); if (st != PG_OK) return st;
-    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) dp.cols[c].set_bits = ctx->d_distinct + distinct_first[c];
-    HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, (hll_base + hll_words) * 4, ctx->stream));
-    hll_staged_words = hll_words; hll_staged_first = hll_base;
-    if (out) {
-      distinct_host.resize(lw.distinct_slots.size());
-      // (a bitset that only HLLs use stays on the device)
-      for (int a = 0; a < na; ++a)
-        if (distinct_of[(size_t)a] >= 0 && hll_log2m_of[(size_t)a] == 0) distinct_host[(size_t)distinct_of[(size_t)a]].resize((size_t)distinct_rows * (size_t)dp.cols[distinct_of[(size_t)a]].words);
-      hll_host.resize(hll_words);
-    }
-  }
-  // The HLL pass on raw columns: one zeroed register row per slot in the same scratch -- under GROUP BY a matrix of one row per raw group id -- and
-  // the packed bytes behind them.
-  HllParams hp;
-  if (is_hll) {
-    memset(&hp, 0, sizeof(hp));
-    for (int card : distinct_key_cards) distinct_rows *= card;
-    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "%s GROUP BY over %lld raw keys", pass_name, distinct_rows);
-    size_t hll_words = 0;
-    int lds_off = 0;
-    hp.d.num_cols = (int32_t)lw.distinct_slots.size();
-    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
-      const DevColumn& dc = pl.cols[lw.distinct_slots[c]];
-      hp.fwd[c] = dc.fwd; hp.wide[c] = (dc.vkind == kValI64 || dc.vkind == kValF64) ? 1 : 0;
-      hp.log2m[c] = lw.hll_slot_log2m[c]; hp.lds_off[c] = lds_off;
-      lds_off += 1 << hp.log2m[c];
-      hll_slot_first.push_back(hll_words);
-      hll_words += (size_t)distinct_rows << hp.log2m[c];
-    }
-    hp.lds_words = k.kernel == ScanKernel::Hll ? lds_off : 0;
-    hp.num_rows = (uint32_t)distinct_rows;
-    hp.d.num_keys = (int32_t)lw.distinct_key_slots.size();
-    uint32_t mult = 1;
-    for (size_t g = 0; g < lw.distinct_key_slots.size(); ++g) {
-      const DevColumn& kc = pl.cols[lw.distinct_key_slots[g]];
-      hp.d.keys[g].fwd = kc.fwd; hp.d.keys[g].bits = kc.bits; hp.d.keys[g].mult = mult;
-      mult *= (uint32_t)distinct_key_cards[g];
-    }
-    st = ensure_distinct(seg, ctx, hll_words + hll_words / 4); if (st != PG_OK) return st;
-    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) hp.regs[c] = ctx->d_distinct + hll_slot_first[c];
-    HIP_TRY(hipMemsetAsync(ctx->d_distinct, 0, hll_words * 4, ctx->stream));
-    hll_staged_words = hll_words; hll_staged_first = 0;
-    if (out) hll_host.resize(hll_words);
-  }
-  // The collect pass: one list of `capacity` 64-bit images per raw column in the same scratch (GROUP BY: the docs' raw group ids beside them),
-  // the sort's second buffers, the run arrays and rocPRIM's scratch behind them.  The capacity is the segment's docs -- what the plan-time
-  // bound was priced with (plan_collect_bytes) -- so no reservation of a matching doc can fail; the kernel checks every one all the same.
-  CollectParams cp;
-  struct CollectLayout { size_t images[kMaxAggCols], work, heads, position, rows, rows_a, rows_b, temp, temp_bytes, total; } cl{};
-  unsigned long long collect_head[3] = {0ull, 0ull, 0ull};      // what the kernel leaves in the scratch's first line: the cursor, the flag word, (later) a column's runs
-  constexpr size_t kCollectHeadBytes = 256;
-  size_t collect_capacity = 0;
-  if (is_collect) {
-    memset(&cp, 0, sizeof(cp));
-    for (int card : distinct_key_cards) distinct_rows *= card;
-    if (distinct_rows > (long long)kMaxGroupSlots) return fail(PG_ERR_UNSUPPORTED, "%s GROUP BY over %lld raw keys", pass_name, distinct_rows);
-    const bool grouped = !lw.distinct_key_slots.empty();
-    collect_capacity = (size_t)std::max<long long>((long long)seg->num_docs, 1);
-    HIP_TRY(collect_sort_temp_bytes(collect_capacity, grouped, &cl.temp_bytes));
-    auto take = [&cl](size_t bytes) { const size_t at = cl.total; cl.total += (bytes + 255) & ~(size_t)255; return at; };
-    (void)take(kCollectHeadBytes);
-    cp.d.num_cols = (int32_t)lw.distinct_slots.size();
-    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) cl.images[c] = take(collect_capacity * 8);
-    cl.work = take(collect_capacity * 8);
-    cl.heads = take(collect_capacity * 4);
-    cl.position = take(collect_capacity * 4);
-    if (grouped) { cl.rows = take(collect_capacity * 4); cl.rows_a = take(collect_capacity * 4); cl.rows_b = take(collect_capacity * 4); }
-    cl.temp = take(std::max<size_t>(cl.temp_bytes, 256));
-    st = ensure_distinct(seg, ctx, cl.total / 4); if (st != PG_OK) return st;
-    uint8_t* const base = reinterpret_cast<uint8_t*>(ctx->d_distinct);
-    for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
-      const DevColumn& dc = pl.cols[lw.distinct_slots[c]];
-      cp.fwd[c] = dc.fwd; cp.vkind[c] = dc.vkind;
-      cp.out_images[c] = reinterpret_cast<unsigned long long*>(base + cl.images[c]);
-    }
-    cp.out_rows = grouped ? reinterpret_cast<uint32_t*>(base + cl.rows) : nullptr;
-    cp.cursor = reinterpret_cast<unsigned long long*>(base);
-    cp.flags = reinterpret_cast<uint32_t*>(base + 8);
-    cp.capacity = (unsigned long long)collect_capacity;
-    cp.d.num_keys = (int32_t)lw.distinct_key_slots.size();
-    uint32_t mult = 1;
-    for (size_t g = 0; g < lw.distinct_key_slots.size(); ++g) {
-      const DevColumn& kc = pl.cols[lw.distinct_key_slots[g]];
-      cp.d.keys[g].fwd = kc.fwd; cp.d.keys[g].bits = kc.bits; cp.d.keys[g].mult = mult;
-      mult *= (uint32_t)distinct_key_cards[g];
-    }
-    HIP_TRY(hipMemsetAsync(base, 0, kCollectHeadBytes, ctx->stream));
-  }
+  if (k.kernel == ScanKernel::Hist || pass.form != SetPass::None) sp.set_leaves_in_lds = grid.hist_set_off != 0 ? 1 + (int32_t)grid.hist_set_off : 0;      // (the histogram / set-pass kernels keep the area in their dynamic LDS, behind the counters / bitsets)
+  if (pass.form != SetPass::None) { st = arm_set_pass(r, &pass, grid); if (st != PG_OK) return st; }
   sp.sparse_lanes = g_engine.sparse_lanes;
   sp.fold_one_counter = g_engine.fold_one_counter;
   if (defer_index_and) {
@@ -3908,55 +4077,13 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
     *ctx->h_partial = g;
   } else {
     // (the bitsets' copy follows the kernel on the stream: the polled record does not cover it)
-    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm || is_distinct || is_collect || is_hll;
+    const bool post_work = !g_engine.direct_result || count_leap2 || want_bitmap || sp.leaf_out_enabled || k.kernel == ScanKernel::PrivateFsm || pass.form != SetPass::None;
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    if (is_hll) {
-      hp.d.scan = sp;
-      if (k.kernel == ScanKernel::Hll) launch_scan_hll(grid.blocks, grid.lds, ctx->stream, hp);
-      else launch_group_hll(grid.blocks, grid.lds, ctx->stream, hp);
-    } else if (is_collect) {
-      cp.d.scan = sp;
-      if (k.kernel == ScanKernel::Collect) launch_scan_collect(grid.blocks, grid.lds, ctx->stream, cp);
-      else launch_group_collect(grid.blocks, grid.lds, ctx->stream, cp);
-    } else if (is_distinct) {
-      dp.scan = sp;
-      if (k.kernel == ScanKernel::Distinct) launch_scan_distinct(grid.distinct_lds, grid.blocks, grid.lds, ctx->stream, dp);
-      else if (k.kernel == ScanKernel::GroupDistinct) launch_group_distinct(grid.blocks, grid.lds, ctx->stream, dp);
-      else if (k.kernel == ScanKernel::Counts) launch_scan_counts(grid.distinct_lds, grid.blocks, grid.lds, ctx->stream, dp);
-      else launch_group_counts(grid.blocks, grid.lds, ctx->stream, dp);
-    } else launch_scan_kernel(k, grid, pl.num_agg_cols, typed, ctx->stream, sp);
+    if (pass.form != SetPass::None) launch_set_pass(r, &pass, grid);
+    else launch_scan_kernel(k, grid, pl.num_agg_cols, typed, ctx->stream, sp);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    if (is_distinct && !distinct_host.empty()) {
-      distinct_copy.armed = true;
-      for (size_t c = 0; c < distinct_host.size(); ++c)
-        if (!distinct_host[c].empty()) HIP_TRY(hipMemcpyAsync(distinct_host[c].data(), ctx->d_distinct + distinct_first[c], distinct_host[c].size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (is_collect) {
-      distinct_copy.armed = true;
-      HIP_TRY(hipMemcpyAsync(collect_head, ctx->d_distinct, 16, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (is_distinct && hll_staged_words != 0) {
-      // the bitsets' rows -> register rows, one fold per DISTINCTCOUNTHLL aggregation over its column's bitset
-      for (int a = 0; a < na; ++a) {
-        if (hll_log2m_of[(size_t)a] == 0 || hll_same_as[(size_t)a] >= 0) continue;
-        const ColumnDev& col = seg->cols[(size_t)q->aggregations[a].column];
-        const DistinctCol& bits = dp.cols[distinct_of[(size_t)a]];
-        HllFoldParams fp;
-        memset(&fp, 0, sizeof(fp));
-        fp.bits = bits.set_bits; fp.regs = ctx->d_distinct + hll_first[(size_t)a];
-        fp.words = bits.words; fp.cardinality = col.cardinality; fp.log2m = hll_log2m_of[(size_t)a];
-        fill_hll_dictionary(col, &fp);
-        launch_hll_fold(distinct_rows, ctx->stream, fp);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    if ((is_hll || is_distinct) && hll_staged_words != 0) {
-      uint8_t* const packed = reinterpret_cast<uint8_t*>(ctx->d_distinct + hll_staged_first + hll_staged_words);
-      launch_hll_pack(ctx->d_distinct + hll_staged_first, packed, hll_staged_words, seg->num_cus, ctx->stream);
-      HIP_TRY(hipGetLastError());
-      if (!hll_host.empty()) { distinct_copy.armed = true; HIP_TRY(hipMemcpyAsync(hll_host.data(), packed, hll_host.size(), hipMemcpyDeviceToHost, ctx->stream)); }
-    }
+    if (pass.form != SetPass::None) { st = enqueue_set_pass_post(r, &pass); if (st != PG_OK) return st; }
     if (!folded) {
       finalize_partials_kernel<<<dim3(1), dim3(kBlockThreads), 0, ctx->stream>>>(ctx->d_partials, blocks, g_engine.direct_result ? ctx->h_record_dev : nullptr, seq,
                                                                                   sp.fold_slots, sp.fold_typed, sp.profile);
@@ -4012,107 +4139,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   }
   if (out_cardinality) *out_cardinality = (int64_t)fp.count;
   if (out) convert(fp, out);
-  if (out && is_distinct) {
-    // (the stream was synchronised: the bitsets are in distinct_host)  One set per DISTINCTCOUNT aggregation; aggregation only: its count is
-    // the set's cardinality.  Under GROUP BY the rows are raw group ids: execute_distinct keeps the rows of the groups that exist.
-    distinct_copy.armed = false;
-    std::unique_ptr<ResultInternal> sets(new ResultInternal());
-    for (int a = na - 1; a >= 0; --a) {      // (the last aggregation on a column takes the copy itself, earlier ones on the same column a copy of it)
-      const int dc = distinct_of[(size_t)a];
-      if (dc < 0) continue;
-      if (hll_log2m_of[(size_t)a] != 0) {
-        sets->hll.push_back(hll_set_of(hll_host, hll_first[(size_t)a] - hll_staged_first, a, hll_log2m_of[(size_t)a], distinct_rows));
-        if (lw.distinct_key_slots.empty()) out->aggregations[a].count = hll_nonzero(sets->hll.back().registers.data(), sets->hll.back().registers.size());
-        continue;
-      }
-      DistinctSet ds;
-      ds.aggregation = a; ds.num_words = dp.cols[dc].words; ds.rows = (int)distinct_rows;
-      bool again = false;
-      for (int b = 0; b < a; ++b) again |= distinct_of[(size_t)b] == dc && hll_log2m_of[(size_t)b] == 0;
-      if (again) ds.words = distinct_host[(size_t)dc]; else ds.words = std::move(distinct_host[(size_t)dc]);
-      if (lw.distinct_key_slots.empty() && !is_counts) {      // (PERCENTILE: count stays the docs aggregated, the list's length)
-        int64_t card = 0;
-        for (uint32_t w : ds.words) card += __builtin_popcount(w);
-        out->aggregations[a].count = card;
-      }
-      sets->distinct.push_back(std::move(ds));
-    }
-    out->internal = sets.release();
-  }
-  if (is_collect) {
-    // (the stream was synchronised: the cursor and the flag word are in collect_head)  The cursor's final value is the filter's match count.
-    distinct_copy.armed = false;
-    struct Trim { pg_segment* seg; ExecCtx* ctx; ~Trim() { trim_distinct(seg, ctx); } } trim_on_exit{seg, ctx};
-    const unsigned long long n = collect_head[0];
-    if ((uint32_t)collect_head[1] & kCollectOverflow) return fail(PG_ERR_INTERNAL, "%s: the value lists overflowed their capacity of %zu docs (cursor %llu)", pass_name, collect_capacity, n);
-    if (n != fp.count) return fail(PG_ERR_INTERNAL, "%s: %llu values were collected for %llu matching docs", pass_name, n, (unsigned long long)fp.count);
-    if (out) {
-      const bool grouped = !lw.distinct_key_slots.empty();
-      uint8_t* const base = reinterpret_cast<uint8_t*>(ctx->d_distinct);
-      int row_bits = 1;
-      while (row_bits < 32 && (1ll << row_bits) < distinct_rows) ++row_bits;
-      std::vector<ValueList> per_col(lw.distinct_slots.size());
-      std::vector<uint32_t> first;
-      for (size_t c = 0; c < lw.distinct_slots.size(); ++c) {
-        ValueList& vl = per_col[c];
-        vl.grouped_in_transit = grouped;
-        if (n == 0) continue;
-        CollectSort cs;
-        cs.images = cp.out_images[c]; cs.images_work = reinterpret_cast<unsigned long long*>(base + cl.work);
-        cs.rows = cp.out_rows; cs.rows_a = reinterpret_cast<uint32_t*>(base + cl.rows_a); cs.rows_b = reinterpret_cast<uint32_t*>(base + cl.rows_b);
-        cs.row_bits = row_bits;
-        cs.heads = reinterpret_cast<uint32_t*>(base + cl.heads); cs.position = reinterpret_cast<uint32_t*>(base + cl.position);
-        cs.num_runs = reinterpret_cast<uint32_t*>(base + 16);
-        cs.temp = base + cl.temp; cs.temp_bytes = std::max<size_t>(cl.temp_bytes, 256);
-        CollectRuns runs;
-        HIP_TRY(collect_sort_runs(cs, (size_t)n, seg->num_cus, ctx->stream, &runs));
-        uint32_t num_runs = 0;
-        HIP_TRY(hipMemcpyAsync(&num_runs, cs.num_runs, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (num_runs == 0u || (unsigned long long)num_runs > n) return fail(PG_ERR_INTERNAL, "%s: %u runs in a list of %llu values", pass_name, num_runs, n);
-        // only the runs cross the bus: their images, the index of their first entry and (GROUP BY) their raw group ids
-        vl.value_bits.resize(num_runs); first.resize(num_runs);
-        HIP_TRY(hipMemcpyAsync(vl.value_bits.data(), runs.images, (size_t)num_runs * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(first.data(), runs.first, (size_t)num_runs * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (grouped) { vl.run_rows.resize(num_runs); HIP_TRY(hipMemcpyAsync(vl.run_rows.data(), runs.rows, (size_t)num_runs * 4, hipMemcpyDeviceToHost, ctx->stream)); }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        const bool floating = cp.vkind[c] == kValF64 || cp.vkind[c] == kValF32;
-        vl.counts.resize(num_runs);
-        for (uint32_t j = 0; j < num_runs; ++j) {
-          vl.value_bits[j] = (int64_t)rank_image_value_bits((unsigned long long)vl.value_bits[j], floating);
-          vl.counts[j] = (j + 1 < num_runs ? first[j + 1] : (uint32_t)n) - first[j];
-        }
-      }
-      std::unique_ptr<ResultInternal> lists(new ResultInternal());
-      for (int a = na - 1; a >= 0; --a) {      // (the last aggregation on a column takes the runs themselves, earlier ones on the same column a copy)
-        const int dc = distinct_of[(size_t)a];
-        if (dc < 0) continue;
-        bool again = false;
-        for (int b = 0; b < a; ++b) again |= distinct_of[(size_t)b] == dc;
-        ValueList vl;
-        if (again) vl = per_col[(size_t)dc]; else vl = std::move(per_col[(size_t)dc]);
-        vl.aggregation = a;
-        vl.offsets = {0, vl.value_bits.size()};
-        // aggregation only: PERCENTILE's count is the list's length (the docs aggregated: convert put it there), DISTINCTCOUNT's the number of runs
-        if (!grouped && pass_function == PG_AGG_DISTINCTCOUNT) out->aggregations[a].count = (int64_t)vl.value_bits.size();
-        lists->values.push_back(std::move(vl));
-      }
-      out->internal = lists.release();
-    }
-  }
-  if (out && is_hll) {
-    // (the stream was synchronised: the packed registers are in hll_host)  One set per aggregation; aggregation only: its count is the non-zero registers
-    distinct_copy.armed = false;
-    std::unique_ptr<ResultInternal> sets(new ResultInternal());
-    for (int a = 0; a < na; ++a) {
-      const int dc = distinct_of[(size_t)a];
-      if (dc < 0) continue;
-      sets->hll.push_back(hll_set_of(hll_host, hll_slot_first[(size_t)dc], a, hp.log2m[dc], distinct_rows));
-      if (lw.distinct_key_slots.empty()) out->aggregations[a].count = hll_nonzero(sets->hll.back().registers.data(), sets->hll.back().registers.size());
-    }
-    out->internal = sets.release();
-  }
-  if (is_distinct || is_hll) trim_distinct(seg, ctx);
+  if (pass.form != SetPass::None) { st = harvest_set_pass(r, &pass, fp); if (st != PG_OK) return st; }
   if (out && k.kernel == ScanKernel::PrivateFsm) {
     // (the stream was synchronised: the walk's count is in the pinned counter)
     out->stats.num_entries_scanned_in_filter = (int64_t)*ctx->h_filter_entries;
@@ -5562,7 +5589,7 @@ static pg_status fail_function_word(const pg_aggregation* ag) {
 static pg_status check_ordinary_query(const pg_segment* segment, const pg_query* query);
 // ---- PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns: the collect pass (pg_scan_collect.h) ----
 // A raw (no-dictionary) column has no dictId to count or to set a bit for: the pass writes the order image of every matching doc's value into a
-// list per column, sorts it and run-length encodes it (run_aggregation); the runs are pg_result_value_counts' answer.  The query runs exactly as
+// list per column, sorts it and run-length encodes it (arm_collect / harvest_collect); the runs are pg_result_value_counts' answer.  The query runs exactly as
 // the dictionary forms do -- the ordinary query, then the pass behind the same filter, or the pass alone -- with kQueryCollectPass set beside the
 // pass's own flag.  A query's PERCENTILE / DISTINCTCOUNT columns are all raw or all dictionary-encoded.
 // The plan-time bound of the lists: every doc could match (pg_query_check knows no better, and pg_execute must agree with it).
@@ -5616,13 +5643,116 @@ static pg_status finish_value_lists(const pg_query* q, pg_result* out, ResultInt
   }
   return PG_OK;
 }
-struct DistinctPlan {
+// ---- what plan_distinct / plan_percentile and execute_distinct / execute_percentile share (`who`: the function's name in the messages) ----
+struct PassPlan {
   std::vector<pg_aggregation> base_aggs, pass_aggs;
-  pg_query base, pass;
-  bool from_dictionary = false;      // NonScanBasedAggregationOperator: the whole dictionary
-  bool pass_alone = false;           // DISTINCTCOUNT(..) [, COUNT(*)] without GROUP BY: one launch
+  pg_query base, pass;               // the ordinary query; the pass
+  bool pass_alone = false;           // FUNCTION(..) [, COUNT(*)] without GROUP BY: one launch
   int num_projected = 0;             // distinct columns the whole query projects (numEntriesScannedPostFilter = numDocsScanned x this)
 };
+// The pass kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it.  match_all: the filter is absent or
+// matches every doc; filter_stages_set: a dictId-set leaf (an IN list) wants its staged area in LDS.
+static pg_status plan_pass_filter(const pg_segment* seg, const pg_query* q, const char* who, bool* match_all, bool* filter_stages_set) {
+  *match_all = q->num_filter_nodes == 0; *filter_stages_set = false;
+  for (int n = 0; n < q->num_filter_nodes; ++n) {
+    if (q->filter[n].op != PG_FILTER_LEAF) continue;
+    if (q->filter[n].predicate < 0 || q->filter[n].predicate >= q->num_predicates) return fail(PG_ERR_INVALID_ARGUMENT, "filter node %d: bad predicate index", n);
+    const pg_predicate& pr = q->predicates[q->filter[n].predicate];
+    if (pr.kind == PG_PRED_RAW_RANGE && pr.column >= 0 && pr.column < (int)seg->cols.size() && seg->cols[(size_t)pr.column].stored_type != PG_TYPE_INT)
+      return fail(PG_ERR_UNSUPPORTED, "%s beside a range predicate on raw LONG / FLOAT / DOUBLE column %s -- CPU plan", who, seg->cols[(size_t)pr.column].name.c_str());
+    if (pr.kind == PG_PRED_DICT_SET) *filter_stages_set = true;
+    if (q->num_filter_nodes == 1) *match_all = (pr.kind == PG_PRED_MATCH_ALL && !pr.exclusive) || (pr.kind == PG_PRED_MATCH_NONE && pr.exclusive);
+  }
+  return PG_OK;
+}
+// GROUP BY of a pass query: an int key space that numGroupsLimit can never cut, keys the kernel decodes as dictIds (dictionary columns, raw
+// columns through their offset key images).  Projects the key columns; *product: the raw group ids, the rows of the pass's matrices.
+static pg_status plan_pass_keys(const pg_segment* seg, const pg_query* q, const char* who, std::vector<int>* projected, unsigned long long* product) {
+  const int ng = q->num_group_by, num_cols_total = (int)seg->cols.size();
+  const bool null_handling = (q->flags & PG_QUERY_NULL_HANDLING) != 0;
+  if (ng > kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "%s with more than %d group-by columns -- CPU plan", who, kMaxDistinctKeys);
+  std::vector<int> cards;
+  for (int g = 0; g < ng; ++g) {
+    int c = q->group_by_columns[g];
+    if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
+    if (std::find(projected->begin(), projected->end(), c) == projected->end()) projected->push_back(c);
+    if (null_handling && seg->cols[(size_t)c].d_null_bitmap != nullptr)
+      return fail(PG_ERR_UNSUPPORTED, "%s grouped by nullable column %s under null handling -- CPU plan", who, seg->cols[(size_t)c].name.c_str());
+    if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
+      const int image = seg->cols[(size_t)c].keyimage_column;
+      if (image < 0 || seg->cols[(size_t)image].rank_image)
+        return fail(PG_ERR_UNSUPPORTED, "%s grouped by raw column %s, which is not keyed by offset -- CPU plan", who, seg->cols[(size_t)c].name.c_str());
+      c = image;
+    }
+    cards.push_back(seg->cols[(size_t)c].cardinality);
+  }
+  HashPlan hash_plan;
+  const pg_status hst = plan_hash_holder(seg, cards, &hash_plan); if (hst != PG_OK) return hst;
+  if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "%s grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", who, hash_plan.kind);
+  *product = 1;
+  for (int card : cards) *product *= (unsigned long long)std::max(card, 1);
+  const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
+  if (*product > (unsigned long long)limit)
+    return fail(PG_ERR_UNSUPPORTED, "%s grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", who, *product, limit);
+  return PG_OK;
+}
+// The two queries that answer the caller's: the ordinary query -- every aggregation of the pass (is_pass) turned into COUNT(*) -- and the pass, with
+// everything BUT those turned into COUNT(*) and pass_flags set.  Ends with the plan-time checks of both (check_pass false: only the ordinary one runs).
+static pg_status split_pass_query(const pg_segment* seg, const pg_query* q, PassPlan* plan, bool (*is_pass)(int32_t function), int32_t pass_flags, bool check_pass = true) {
+  const int na = q->num_aggregations;
+  plan->base_aggs.assign(q->aggregations, q->aggregations + na);
+  plan->pass_aggs.assign(q->aggregations, q->aggregations + na);
+  for (int a = 0; a < na; ++a) (is_pass(q->aggregations[a].function) ? plan->base_aggs : plan->pass_aggs)[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+  plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
+  plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
+  plan->pass.flags |= pass_flags;
+  if (!plan->pass_alone) plan->pass.flags |= PG_QUERY_STATS_UPPER_BOUND_OK;      // (the ordinary query brings the statistics)
+  pg_status st = plan->pass_alone ? PG_OK : check_ordinary_query(seg, &plan->base);
+  if (st == PG_OK && check_pass) st = check_ordinary_query(seg, &plan->pass);
+  return st;
+}
+// The ordinary query into `out` and the pass behind it on the same stream into `pass` -- or the pass alone into `out`.  The pass's device time joins
+// the result's, its sets come back in *got (null: it left none); the caller frees `pass`.  A failure of the pass leaves `out` released and zeroed.
+static pg_status execute_base_and_pass(pg_segment* seg, const PassPlan& plan, pg_result* out, pg_result* pass, std::unique_ptr<ResultInternal>* got) {
+  memset(pass, 0, sizeof(*pass));
+  pg_result* from = plan.pass_alone ? out : pass;
+  pg_status st = execute_one(seg, plan.pass_alone ? &plan.pass : &plan.base, out, nullptr);
+  if (st != PG_OK) return st;
+  if (!plan.pass_alone) {
+    out->stats.num_entries_scanned_post_filter = out->stats.num_docs_scanned * (int64_t)plan.num_projected;
+    st = execute_one(seg, &plan.pass, pass, nullptr);
+    if (st != PG_OK) { pg_result_free(out); return st; }
+    out->device_ms += pass->device_ms;
+    if (pass->dominant_kernel_ms >= out->dominant_kernel_ms) { out->dominant_kernel_ms = pass->dominant_kernel_ms; out->dominant_kernel = pass->dominant_kernel; }
+  }
+  got->reset(static_cast<ResultInternal*>(from->internal));
+  from->internal = nullptr;
+  return PG_OK;
+}
+// GROUP BY: the rows of the groups the ordinary query reports (group_ids: ascending raw ids, key kind 0) out of a matrix of `rows` rows of row_len
+// elements, compacted in place -- group ids ascend, so row k of the result never lies behind the matrix row it is taken from: no second buffer.
+// per_row(k, row's elements) sees every kept row before it moves.  false: *bad_row is a group id outside the matrix, or out of order.
+extern "C++" {      // (a template inside the C ABI's linkage block)
+template <typename T, typename PerRow>
+static bool keep_group_rows(const pg_result* out, std::vector<T>* matrix, int rows, size_t row_len, int64_t* bad_row, PerRow&& per_row) {
+  int64_t previous = -1;
+  for (int k = 0; k < out->num_groups; ++k) {
+    const int64_t row = out->group_ids[k];
+    if (row <= previous || row >= rows) { *bad_row = row; return false; }
+    previous = row;
+    const T* src = matrix->data() + (size_t)row * row_len;
+    per_row(k, src);
+    if (row != k) memmove(matrix->data() + (size_t)k * row_len, src, row_len * sizeof(T));
+  }
+  matrix->resize((size_t)out->num_groups * row_len);
+  matrix->shrink_to_fit();
+  return true;
+}
+}
+struct DistinctPlan : PassPlan {
+  bool from_dictionary = false;      // NonScanBasedAggregationOperator: the whole dictionary
+};
+static bool is_distinct_pass_function(int32_t function) { return function == PG_AGG_DISTINCTCOUNT || is_hll_function(function); }
 // Every reason a DISTINCTCOUNT query is declined for, from the query and the segment's metadata alone (pg_query_check and pg_execute both
 // come through here), and the two queries that answer it.
 static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, DistinctPlan* plan) {
@@ -5691,58 +5821,22 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
     return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on raw column %s beside a DISTINCTCOUNT in one query -- CPU plan", seg->cols[(size_t)hll_raw_slots[0].first].name.c_str());
   if ((int)(distinct_cols.size() + raw_cols.size()) > kMaxAggCols || (int)hll_raw_slots.size() > kMaxAggCols || (int)hll_dict_slots.size() > kMaxAggCols)
     return fail(PG_ERR_UNSUPPORTED, has_hll ? "more than %d DISTINCTCOUNTHLL columns" : "more than %d DISTINCTCOUNT columns", kMaxAggCols);
-  // the bitset kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it
-  bool match_all = q->num_filter_nodes == 0, filter_stages_set = false;
-  for (int n = 0; n < q->num_filter_nodes; ++n) {
-    if (q->filter[n].op != PG_FILTER_LEAF) continue;
-    if (q->filter[n].predicate < 0 || q->filter[n].predicate >= q->num_predicates) return fail(PG_ERR_INVALID_ARGUMENT, "filter node %d: bad predicate index", n);
-    const pg_predicate& pr = q->predicates[q->filter[n].predicate];
-    if (pr.kind == PG_PRED_RAW_RANGE && pr.column >= 0 && pr.column < num_cols_total && seg->cols[(size_t)pr.column].stored_type != PG_TYPE_INT)
-      return fail(PG_ERR_UNSUPPORTED, "%s beside a range predicate on raw LONG / FLOAT / DOUBLE column %s -- CPU plan", who, seg->cols[(size_t)pr.column].name.c_str());
-    if (pr.kind == PG_PRED_DICT_SET) filter_stages_set = true;
-    if (q->num_filter_nodes == 1) match_all = (pr.kind == PG_PRED_MATCH_ALL && !pr.exclusive) || (pr.kind == PG_PRED_MATCH_NONE && pr.exclusive);
-  }
+  bool match_all = false, filter_stages_set = false;
+  pg_status st = plan_pass_filter(seg, q, who, &match_all, &filter_stages_set); if (st != PG_OK) return st;
   if (ng > 0) {
-    // GROUP BY, first cut: an int key space that numGroupsLimit can never cut, keys the kernel decodes as dictIds, a bit matrix within the cap
-    if (ng > kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "%s with more than %d group-by columns -- CPU plan", who, kMaxDistinctKeys);
-    std::vector<int> cards;
-    for (int g = 0; g < ng; ++g) {
-      int c = q->group_by_columns[g];
-      if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
-      project(c);
-      if (null_handling && seg->cols[(size_t)c].d_null_bitmap != nullptr)
-        return fail(PG_ERR_UNSUPPORTED, "%s grouped by nullable column %s under null handling -- CPU plan", who, seg->cols[(size_t)c].name.c_str());
-      if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
-        const int image = seg->cols[(size_t)c].keyimage_column;
-        if (image < 0 || seg->cols[(size_t)image].rank_image)
-          return fail(PG_ERR_UNSUPPORTED, "%s grouped by raw column %s, which is not keyed by offset -- CPU plan", who, seg->cols[(size_t)c].name.c_str());
-        c = image;
-      }
-      cards.push_back(seg->cols[(size_t)c].cardinality);
-    }
-    HashPlan hash_plan;
-    const pg_status hst = plan_hash_holder(seg, cards, &hash_plan);
-    if (hst != PG_OK) return hst;
-    if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "%s grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", who, hash_plan.kind);
+    // GROUP BY, first cut: the key space, then the bit matrices within the cap -- priced with the functions the pass allocates by (pg_set_pass_layout.h)
     unsigned long long product = 1;
-    for (int card : cards) product *= (unsigned long long)std::max(card, 1);
-    const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
-    if (product > (unsigned long long)limit)
-      return fail(PG_ERR_UNSUPPORTED, "%s grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", who, product, limit);
-    unsigned long long matrix = 0, slack = 0;
-    for (int c : distinct_cols) {
-      matrix += product * (unsigned long long)((seg->cols[(size_t)c].cardinality + 31) / 32) * 4ull;
-      slack = std::max<unsigned long long>(slack, distinct_slack_words(seg->cols[(size_t)c].bits, seg->cols[(size_t)c].cardinality) * 4ull);
-    }
-    matrix += slack;      // (the room behind the last row is part of the device allocation)
+    st = plan_pass_keys(seg, q, who, &projected, &product); if (st != PG_OK) return st;
+    SetMatrixLayout bitsets;
+    for (int c : distinct_cols) bitsets.add(false, product, seg->cols[(size_t)c].bits, seg->cols[(size_t)c].cardinality);
+    const unsigned long long matrix = bitsets.total_words() * 4ull;      // (the room behind the last row is part of the device allocation)
     if (matrix > PG_DISTINCT_GROUP_MAX_BYTES)
       return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT bit matrices of %llu bytes exceed PG_DISTINCT_GROUP_MAX_BYTES (%llu) -- CPU plan", matrix, (unsigned long long)PG_DISTINCT_GROUP_MAX_BYTES);
     if (matrix > g_engine.group_table_bytes)
       return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNT bit matrices of %llu bytes exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", matrix, (unsigned long long)g_engine.group_table_bytes);
     // the register matrices: one row of 2^log2m staged 32-bit words per raw group id -- per HLL aggregation (dictionary form) or per slot (raw form)
     unsigned long long registers = 0;
-    if (!hll_raw_slots.empty()) for (const auto& slot : hll_raw_slots) registers += product * (4ull << slot.second);
-    else for (const auto& slot : hll_dict_slots) registers += product * (4ull << slot.second);
+    for (const auto& slot : !hll_raw_slots.empty() ? hll_raw_slots : hll_dict_slots) registers += hll_staged_words(product, slot.second) * 4ull;
     if (registers > PG_HLL_GROUP_MAX_BYTES)
       return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL register matrices of %llu bytes exceed PG_HLL_GROUP_MAX_BYTES (%llu) -- CPU plan", registers, (unsigned long long)PG_HLL_GROUP_MAX_BYTES);
     if (registers > g_engine.group_table_bytes)
@@ -5756,34 +5850,22 @@ static pg_status plan_distinct(const pg_segment* seg, const pg_query* q, Distinc
       return fail(PG_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL registers of %zu bytes (with the filter's set area) exceed the %zu bytes of LDS a workgroup has -- CPU plan", lds, kLdsBudget);
   }
   plan->num_projected = (int)projected.size();
-  plan->base_aggs.assign(q->aggregations, q->aggregations + na);
-  plan->pass_aggs.assign(q->aggregations, q->aggregations + na);
-  for (int a = 0; a < na; ++a) {
-    if (q->aggregations[a].function == PG_AGG_DISTINCTCOUNT || is_hll_function(q->aggregations[a].function)) plan->base_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
-    else plan->pass_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
-  }
-  plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
-  plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
-  plan->pass.flags |= kQueryDistinctPass;
+  int32_t pass_flags = kQueryDistinctPass;
   if (!raw_cols.empty()) {
-    const pg_status cst = plan_collect_bytes(seg, "DISTINCTCOUNT", raw_cols.size(), ng > 0);
-    if (cst != PG_OK) return cst;
-    plan->pass.flags |= kQueryCollectPass;
+    st = plan_collect_bytes(seg, "DISTINCTCOUNT", raw_cols.size(), ng > 0); if (st != PG_OK) return st;
+    pass_flags |= kQueryCollectPass;
   }
-  if (!hll_raw_slots.empty()) plan->pass.flags |= kQueryHllPass;
+  if (!hll_raw_slots.empty()) pass_flags |= kQueryHllPass;
   // the dictionary answers under the conditions of the MIN / MAX dictionary path (answer_from_metadata): every function of the query that way
   // (a raw column has no dictionary to read: it is always scanned)
   plan->from_dictionary = ng == 0 && match_all && !(null_handling && nullable_input) && raw_cols.empty() && hll_raw_slots.empty();
   for (int a = 0; a < na && plan->from_dictionary; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    plan->from_dictionary = ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT || is_hll_function(ag.function) ||
+    plan->from_dictionary = ag.function == PG_AGG_COUNT || is_distinct_pass_function(ag.function) ||
                             ((ag.function == PG_AGG_MIN || ag.function == PG_AGG_MAX) && seg->cols[(size_t)ag.column].encoding == PG_FWD_FIXED_BIT_DICT);
   }
   plan->pass_alone = ng == 0 && !plan->from_dictionary && only_distinct_and_count;
-  if (!plan->pass_alone) plan->pass.flags |= PG_QUERY_STATS_UPPER_BOUND_OK;      // (the ordinary query brings the statistics)
-  pg_status st = plan->pass_alone ? PG_OK : check_ordinary_query(seg, &plan->base);
-  if (st == PG_OK && !plan->from_dictionary) st = check_ordinary_query(seg, &plan->pass);
-  return st;
+  return split_pass_query(seg, q, plan, is_distinct_pass_function, pass_flags, !plan->from_dictionary);
 }
 static void distinct_agg_value(pg_agg_value* v, int64_t cardinality) { memset(v, 0, sizeof(*v)); empty_agg_value(v, cardinality); }
 
@@ -5796,11 +5878,10 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
   if (st != PG_OK) return st;
   const int na = q->num_aggregations;
   if (plan.pass_alone) return execute_one(seg, &plan.pass, out, nullptr);
-  st = execute_one(seg, &plan.base, out, nullptr);
-  if (st != PG_OK) return st;
-  out->stats.num_entries_scanned_post_filter = plan.from_dictionary ? 0 : out->stats.num_docs_scanned * (int64_t)plan.num_projected;
   std::unique_ptr<ResultInternal> sets(new ResultInternal());
   if (plan.from_dictionary) {
+    st = execute_one(seg, &plan.base, out, nullptr); if (st != PG_OK) return st;
+    out->stats.num_entries_scanned_post_filter = 0;
     for (int a = 0; a < na; ++a) {
       if (is_hll_function(q->aggregations[a].function)) {
         // the whole dictionary folded into registers (the reference converts the dictionary's values; nothing is scanned)
@@ -5833,12 +5914,8 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
     return PG_OK;
   }
   pg_result pass;
-  st = execute_one(seg, &plan.pass, &pass, nullptr);
-  if (st != PG_OK) { pg_result_free(out); return st; }
-  std::unique_ptr<ResultInternal> got(static_cast<ResultInternal*>(pass.internal));
-  pass.internal = nullptr;
-  out->device_ms += pass.device_ms;
-  if (pass.dominant_kernel_ms >= out->dominant_kernel_ms) { out->dominant_kernel_ms = pass.dominant_kernel_ms; out->dominant_kernel = pass.dominant_kernel; }
+  std::unique_ptr<ResultInternal> got;
+  st = execute_base_and_pass(seg, plan, out, &pass, &got); if (st != PG_OK) return st;
   if (!got) { pg_result_free(&pass); pg_result_free(out); return fail(PG_ERR_INTERNAL, "the DISTINCTCOUNT pass returned no sets"); }
   if (!got->values.empty()) {
     // raw columns: sorted runs instead of bitsets
@@ -5857,41 +5934,25 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
     return PG_OK;
   }
   pg_result_free(&pass);
-  // GROUP BY: the rows of the groups the ordinary query reports (group_ids: ascending raw ids, key kind 0) out of each matrix
-  const int num_groups = out->num_groups;
-  // (compacted in place: group_ids ascend, so row k of the result never lies behind the matrix row it is taken from -- no second buffer)
+  // GROUP BY: the rows of the groups the ordinary query reports out of each matrix
+  int64_t bad_row = 0;
   for (DistinctSet& m : got->distinct) {
-    int64_t previous = -1;
-    for (int k = 0; k < num_groups; ++k) {
-      const int64_t row = out->group_ids[k];
-      if (row <= previous || row >= m.rows) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the DISTINCTCOUNT matrix of %d rows, or out of order", (long long)row, m.rows); }
-      previous = row;
-      const uint32_t* src = m.words.data() + (size_t)row * (size_t)m.num_words;
+    const bool kept = keep_group_rows(out, &m.words, m.rows, (size_t)m.num_words, &bad_row, [&](int k, const uint32_t* row) {
       int64_t card = 0;
-      for (int w = 0; w < m.num_words; ++w) card += __builtin_popcount(src[w]);
-      if (row != k) memmove(m.words.data() + (size_t)k * (size_t)m.num_words, src, (size_t)m.num_words * 4);
+      for (int w = 0; w < m.num_words; ++w) card += __builtin_popcount(row[w]);
       distinct_agg_value(&out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation], card);
-    }
-    m.rows = num_groups;
-    m.words.resize((size_t)num_groups * (size_t)m.num_words);
-    m.words.shrink_to_fit();
+    });
+    if (!kept) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the DISTINCTCOUNT matrix of %d rows, or out of order", (long long)bad_row, m.rows); }
+    m.rows = out->num_groups;
     sets->distinct.push_back(std::move(m));
   }
   for (HllSet& m : got->hll) {
     const size_t m_regs = (size_t)1 << m.log2m;
-    int64_t previous = -1;
-    for (int k = 0; k < num_groups; ++k) {
-      const int64_t row = out->group_ids[k];
-      if (row <= previous || row >= m.rows) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the DISTINCTCOUNTHLL matrix of %d rows, or out of order", (long long)row, m.rows); }
-      previous = row;
-      const uint8_t* src = m.registers.data() + (size_t)row * m_regs;
-      const int64_t nonzero = hll_nonzero(src, m_regs);
-      if (row != k) memmove(m.registers.data() + (size_t)k * m_regs, src, m_regs);
-      distinct_agg_value(&out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation], nonzero);
-    }
-    m.rows = num_groups;
-    m.registers.resize((size_t)num_groups * m_regs);
-    m.registers.shrink_to_fit();
+    const bool kept = keep_group_rows(out, &m.registers, m.rows, m_regs, &bad_row, [&](int k, const uint8_t* row) {
+      distinct_agg_value(&out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation], hll_nonzero(row, m_regs));
+    });
+    if (!kept) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the DISTINCTCOUNTHLL matrix of %d rows, or out of order", (long long)bad_row, m.rows); }
+    m.rows = out->num_groups;
     sets->hll.push_back(std::move(m));
   }
   out->internal = sets.release();
@@ -5909,13 +5970,8 @@ static bool has_percentile(const pg_query* q) {
   for (int a = 0; a < q->num_aggregations; ++a) if (q->aggregations[a].function == PG_AGG_PERCENTILE) return true;
   return false;
 }
-struct PercentilePlan {
-  std::vector<pg_aggregation> base_aggs, pass_aggs;
-  pg_query base, pass;
-  bool pass_alone = false;           // PERCENTILE(..) [, COUNT(*)] without GROUP BY: one launch
-  int num_projected = 0;             // distinct columns the whole query projects (numEntriesScannedPostFilter = numDocsScanned x this)
-  unsigned long long scratch_bytes = 0;      // the counters (GROUP BY: the matrices) with the slack behind the last one: what the pass allocates
-};
+struct PercentilePlan : PassPlan {};
+static bool is_percentile_function(int32_t function) { return function == PG_AGG_PERCENTILE; }
 // Every reason a PERCENTILE query is declined for, from the query and the segment's metadata alone (pg_query_check and pg_execute both come
 // through here), and the two queries that answer it.
 static pg_status plan_percentile(const pg_segment* seg, const pg_query* q, PercentilePlan* plan) {
@@ -5951,77 +6007,30 @@ static pg_status plan_percentile(const pg_segment* seg, const pg_query* q, Perce
   if (!raw_cols.empty() && !pct_cols.empty())
     return fail(PG_ERR_UNSUPPORTED, "PERCENTILE on raw column %s and dictionary column %s in one query -- CPU plan", seg->cols[(size_t)raw_cols[0]].name.c_str(), seg->cols[(size_t)pct_cols[0]].name.c_str());
   if ((int)(pct_cols.size() + raw_cols.size()) > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d PERCENTILE columns", kMaxAggCols);
-  // the counts kernels evaluate the lane-private filter: range leaves on raw 8-byte / FLOAT columns are not in it
-  for (int n = 0; n < q->num_filter_nodes; ++n) {
-    if (q->filter[n].op != PG_FILTER_LEAF) continue;
-    if (q->filter[n].predicate < 0 || q->filter[n].predicate >= q->num_predicates) return fail(PG_ERR_INVALID_ARGUMENT, "filter node %d: bad predicate index", n);
-    const pg_predicate& pr = q->predicates[q->filter[n].predicate];
-    if (pr.kind == PG_PRED_RAW_RANGE && pr.column >= 0 && pr.column < num_cols_total && seg->cols[(size_t)pr.column].stored_type != PG_TYPE_INT)
-      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE beside a range predicate on raw LONG / FLOAT / DOUBLE column %s -- CPU plan", seg->cols[(size_t)pr.column].name.c_str());
-  }
-  unsigned long long product = 1;
+  bool match_all = false, filter_stages_set = false;      // (no metadata fast path and no LDS-only tier here: neither is read)
+  pg_status st = plan_pass_filter(seg, q, "PERCENTILE", &match_all, &filter_stages_set); if (st != PG_OK) return st;
   if (ng > 0) {
-    // GROUP BY under plan_distinct's conditions: an int key space that numGroupsLimit can never cut, keys the kernel decodes as dictIds
-    if (ng > kMaxDistinctKeys) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE with more than %d group-by columns -- CPU plan", kMaxDistinctKeys);
-    std::vector<int> cards;
-    for (int g = 0; g < ng; ++g) {
-      int c = q->group_by_columns[g];
-      if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
-      project(c);
-      if (null_handling && seg->cols[(size_t)c].d_null_bitmap != nullptr)
-        return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped by nullable column %s under null handling -- CPU plan", seg->cols[(size_t)c].name.c_str());
-      if (seg->cols[(size_t)c].encoding != PG_FWD_FIXED_BIT_DICT) {
-        const int image = seg->cols[(size_t)c].keyimage_column;
-        if (image < 0 || seg->cols[(size_t)image].rank_image)
-          return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped by raw column %s, which is not keyed by offset -- CPU plan", seg->cols[(size_t)c].name.c_str());
-        c = image;
-      }
-      cards.push_back(seg->cols[(size_t)c].cardinality);
-    }
-    HashPlan hash_plan;
-    const pg_status hst = plan_hash_holder(seg, cards, &hash_plan);
-    if (hst != PG_OK) return hst;
-    if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", hash_plan.kind);
-    for (int card : cards) product *= (unsigned long long)std::max(card, 1);
-    const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
-    if (product > (unsigned long long)limit)
-      return fail(PG_ERR_UNSUPPORTED, "PERCENTILE grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", product, limit);
-  }
-  // the scratch: group_id_upper_bound x cardinality x 4 bytes per column, and behind the last counter the 2^bits - cardinality counters a
-  // dictId beyond the dictionary's bound could reach (counts_slack_words)
-  unsigned long long matrix = 0, slack = 0;
-  for (int c : pct_cols) {
-    matrix += product * (unsigned long long)std::max(seg->cols[(size_t)c].cardinality, 0) * 4ull;
-    slack = std::max<unsigned long long>(slack, counts_slack_words(seg->cols[(size_t)c].bits, seg->cols[(size_t)c].cardinality) * 4ull);
-  }
-  matrix += slack;
-  plan->scratch_bytes = matrix;
-  if (ng > 0) {
+    // GROUP BY under plan_distinct's conditions.  The counter matrices: group_id_upper_bound x cardinality x 4 bytes per column, and behind the last
+    // counter the 2^bits - cardinality counters a dictId beyond the dictionary's bound could reach -- priced with the functions the pass allocates
+    // by (pg_set_pass_layout.h)
+    unsigned long long product = 1;
+    st = plan_pass_keys(seg, q, "PERCENTILE", &projected, &product); if (st != PG_OK) return st;
+    SetMatrixLayout counters;
+    for (int c : pct_cols) counters.add(true, product, seg->cols[(size_t)c].bits, seg->cols[(size_t)c].cardinality);
+    const unsigned long long matrix = counters.total_words() * 4ull;
     if (matrix > PG_PERCENTILE_GROUP_MAX_BYTES)
       return fail(PG_ERR_UNSUPPORTED, "PERCENTILE counter matrices of %llu bytes exceed PG_PERCENTILE_GROUP_MAX_BYTES (%llu) -- CPU plan", matrix, (unsigned long long)PG_PERCENTILE_GROUP_MAX_BYTES);
     if (matrix > g_engine.group_table_bytes)
       return fail(PG_ERR_UNSUPPORTED, "PERCENTILE counter matrices of %llu bytes exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", matrix, (unsigned long long)g_engine.group_table_bytes);
   }
   plan->num_projected = (int)projected.size();
-  plan->base_aggs.assign(q->aggregations, q->aggregations + na);
-  plan->pass_aggs.assign(q->aggregations, q->aggregations + na);
-  for (int a = 0; a < na; ++a) {
-    if (q->aggregations[a].function == PG_AGG_PERCENTILE) plan->base_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
-    else plan->pass_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
-  }
-  plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
-  plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
-  plan->pass.flags |= kQueryCountsPass;
+  int32_t pass_flags = kQueryCountsPass;
   if (!raw_cols.empty()) {
-    const pg_status cst = plan_collect_bytes(seg, "PERCENTILE", raw_cols.size(), ng > 0);
-    if (cst != PG_OK) return cst;
-    plan->pass.flags |= kQueryCollectPass;
+    st = plan_collect_bytes(seg, "PERCENTILE", raw_cols.size(), ng > 0); if (st != PG_OK) return st;
+    pass_flags |= kQueryCollectPass;
   }
   plan->pass_alone = ng == 0 && only_percentile_and_count;
-  if (!plan->pass_alone) plan->pass.flags |= PG_QUERY_STATS_UPPER_BOUND_OK;      // (the ordinary query brings the statistics)
-  pg_status st = plan->pass_alone ? PG_OK : check_ordinary_query(seg, &plan->base);
-  if (st == PG_OK) st = check_ordinary_query(seg, &plan->pass);
-  return st;
+  return split_pass_query(seg, q, plan, is_percentile_function, pass_flags);
 }
 
 // Row `row` of a dense counter matrix -> the pairs of a CountList; returns the docs counted.
@@ -6046,22 +6055,8 @@ static pg_status execute_percentile(pg_segment* seg, const pg_query* q, pg_resul
   if (st != PG_OK) return st;
   const int na = q->num_aggregations;
   pg_result pass;
-  memset(&pass, 0, sizeof(pass));
-  if (plan.pass_alone) {
-    st = execute_one(seg, &plan.pass, out, nullptr);
-    if (st != PG_OK) return st;
-  } else {
-    st = execute_one(seg, &plan.base, out, nullptr);
-    if (st != PG_OK) return st;
-    out->stats.num_entries_scanned_post_filter = out->stats.num_docs_scanned * (int64_t)plan.num_projected;
-    st = execute_one(seg, &plan.pass, &pass, nullptr);
-    if (st != PG_OK) { pg_result_free(out); memset(out, 0, sizeof(*out)); return st; }
-    out->device_ms += pass.device_ms;
-    if (pass.dominant_kernel_ms >= out->dominant_kernel_ms) { out->dominant_kernel_ms = pass.dominant_kernel_ms; out->dominant_kernel = pass.dominant_kernel; }
-  }
-  pg_result& from = plan.pass_alone ? *out : pass;
-  std::unique_ptr<ResultInternal> got(static_cast<ResultInternal*>(from.internal));
-  from.internal = nullptr;
+  std::unique_ptr<ResultInternal> got;
+  st = execute_base_and_pass(seg, plan, out, &pass, &got); if (st != PG_OK) return st;
   pg_result_free(&pass);
   auto give_up = [&](const char* what) { pg_result_free(out); memset(out, 0, sizeof(*out)); return fail(PG_ERR_INTERNAL, "%s", what); };
   if (!got) return give_up("the PERCENTILE pass returned no counters");

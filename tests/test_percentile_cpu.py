@@ -35,12 +35,17 @@ def test_the_slack_behind_the_last_counter_is_part_of_the_byte_arithmetic():
     """plan_percentile's sizing rule, from the source: group_id_upper_bound x cardinality x 4 bytes per column plus 2^bits - cardinality (+ 1)
     counters behind the last one -- what a dictId beyond the dictionary's bound could reach.  (tests/test_gpu_percentile.py holds the
     engine's message to this sum; no test provokes a stray write.)"""
-    engine = open(os.path.join(ROOT, "pinot_amd", "csrc", "pg_engine.hip")).read()
-    body = engine[engine.index("inline size_t counts_slack_words"):]
+    layout = open(os.path.join(ROOT, "pinot_amd", "csrc", "pg_set_pass_layout.h")).read()
+    body = layout[layout.index("inline size_t counts_slack_words"):]
     body = body[:body.index("}") + 1]
     assert "(size_t)1 << bits" in body and "by_width - by_card" in body and "+ 1" in body
+    # the matrix total is rows x row words + the largest slack, and a counter row's slack is counts_slack_words
+    total = layout[layout.index("struct SetMatrixLayout"):layout.index("// DISTINCTCOUNTHLL.")]
+    assert "set_slack_words(counters, bits, cardinality)" in total and "return row_words + slack_words;" in total
+    assert "counters ? counts_slack_words(bits, cardinality)" in layout
+    engine = open(os.path.join(ROOT, "pinot_amd", "csrc", "pg_engine.hip")).read()
     plan = engine[engine.index("static pg_status plan_percentile"):engine.index("static pg_status execute_percentile")]
-    assert "counts_slack_words(" in plan and "matrix += slack" in plan and "PG_PERCENTILE_GROUP_MAX_BYTES" in plan and "group_table_bytes" in plan
+    assert "counters.add(true, product," in plan and "counters.total_words() * 4ull" in plan and "PG_PERCENTILE_GROUP_MAX_BYTES" in plan and "group_table_bytes" in plan
 
 
 # ---- the SQL forms ----

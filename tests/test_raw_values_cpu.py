@@ -195,6 +195,9 @@ def test_the_planners_route_raw_columns_to_the_collect_pass_and_name_every_decli
     for function, begin, end in (("PERCENTILE", "static pg_status plan_percentile", "static int64_t append_count_row"),
                                  ("DISTINCTCOUNT", "static pg_status plan_distinct", "static void distinct_agg_value")):
         plan = engine[engine.index(begin):engine.index(end)]
+        # the filter walk and the GROUP BY key space are planned by helpers the two planners share: their text counts as the planner's
+        assert "plan_pass_filter(seg, q, " in plan and "plan_pass_keys(seg, q, " in plan
+        plan += engine[engine.index("static pg_status plan_pass_filter"):engine.index("static pg_status split_pass_query")]
         assert "raw (no-dictionary) column" not in plan                                        # the old decline is gone
         assert "plan_collect_column(col, \"%s\")" % function in plan and "plan_collect_bytes(seg, \"%s\", raw_cols.size(), ng > 0)" % function in plan
         assert "kQueryCollectPass" in plan
