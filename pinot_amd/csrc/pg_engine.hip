@@ -32,6 +32,7 @@
 #include "pg_raw_set_table.h"
 #include "pg_hll.h"
 #include "pg_set_pass_layout.h"
+#include "pg_group_plan.h"
 
 namespace {
 
@@ -2616,6 +2617,8 @@ static inline int set_pass_function(int32_t flags) { return (flags & kQueryCount
 // Group-by key spaces beyond an int: the reference's LongMapBasedHolder (the raw key fits a long) and ArrayMapBasedHolder (it does not)
 // -- DictionaryBasedGroupKeyGenerator.java:162-176.  Here: a hashed table in HBM (GroupParams.hash_*), sized at plan time to at least
 // twice the keys that can exist (min(numDocs, product)), so that it cannot fill up at run time.
+// numGroupsLimit, with the reference's default (InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT)
+static inline int groups_limit(const pg_query* q) { return q->num_groups_limit > 0 ? q->num_groups_limit : 100000; }
 struct HashPlan {
   int kind = 0;                    // 0: int raw keys (direct-indexed table); 1: long raw keys; 2: beyond a long (chained tables)
   int levels = 0;                  // first tables of a key beyond a long: table l takes over at column split[l]
@@ -4148,21 +4151,66 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
   }
   return PG_OK;
 }
+// ---------------- group-by ----------------
+// The kernel that aggregates a group-by, decided once (choose_group_route) and in this precedence: the partitioned passes
+// (run_partitioned_group_by), group_typed_direct_kernel, group_private_kernel, scan_group_kernel.  DESIGN.md has the table.
+enum class GroupRoute { Partition, TypedDirect, Private, Staged };
+// What run_group_by's stages settle about a query before its first launch, beside the QueryRun
+struct GroupPlan {
+  GroupParams gp;
+  std::vector<int> cards;                  // the key columns' cardinalities, in multiplier order
+  int group_slot[kMaxGroupCols] = {}, group_mult[kMaxGroupCols] = {};
+  PlanGroupAgg plan_aggs[kMaxGroupAggs];   // the distinct (column slot, SUM|MIN|MAX) pairs: the device's accumulators ...
+  std::vector<int> dev_agg_of;             // ... and per aggregation of the query which of them it reads (-1: COUNT)
+  HashPlan hash_plan; long long product = 1;      // product: raw keys (direct-indexed table), or the slots of a hashed one
+  bool no_dict_keys = false;               // a key is a raw column read through its key image, or the null-key image of one
+  bool first_appearance = false, map_based = false, private_leaves = true;      // private_leaves: every filter leaf is of a kind the lane-private filter implements
+  size_t table_words = 0, table_bytes = 0; Geometry geo;      // geo: the staged launch (scan_group_kernel)
+  int pblocks = 1, pthreads = kBlockThreads; size_t plds = 0;      // the private launch (group_private_kernel; also what the shared launch of a batch takes)
+  PartitionPlan part; int packed_bits = 0;      // pg_group_plan.h; packed_bits: Partition's partition_packed_bits, else 0
+  GroupRoute route = GroupRoute::Staged;
+  bool count_leap2 = false, count_entries = false;      // arm_group_stats: the kernel counts numEntriesScannedInFilter
+  GroupPlan() { memset(&gp, 0, sizeof(gp)); }
+  // The launch was sized for group_private_kernel: a partitioned query passes every test of the private one (its first-doc pass and a batch go by that geometry)
+  bool private_sized() const { return route == GroupRoute::Partition || route == GroupRoute::Private; }
+  // The kernel evaluates the filter leaf by leaf over every doc: it can leave the leaves' outputs and entry counts behind.  NOT the condition under
+  // which the index AND's bitmap must be complete: every route but Private reads that bitmap on every tile (arm_group_stats).
+  bool route_writes_leaf_outputs() const { return route == GroupRoute::Private || route == GroupRoute::TypedDirect; }
+  // pg_result.dominant_kernel.  group_typed_direct_kernel has no id of its own: such a query has always reported PG_KERNEL_SCAN_GROUP.
+  int kernel_id() const { return route == GroupRoute::Partition ? PG_KERNEL_GROUP_PARTITION : (route == GroupRoute::Private ? PG_KERNEL_GROUP_PRIVATE : PG_KERNEL_SCAN_GROUP); }
+};
+// A raw key of a direct-indexed holder -> the dictIds of its columns (the first column is the least significant digit)
+static inline void decode_mixed_radix(long long raw, const std::vector<int>& cards, int ng, int32_t* out) {
+  for (int g = 0; g < ng; ++g) { out[g] = (int32_t)(raw % cards[(size_t)g]); raw /= cards[(size_t)g]; }
+}
+// One accumulator of one group -> the reference's holder value for aggregation `ag` (not COUNT) in *v, which already carries the group's count.
+// `acc` is what the standalone kernels leave in the table; the shared launch of a batch removes its zero-identity bias first.  The floating-point and raw
+// 8-byte branches are not reached from there: the deferral requires private_sized(), which implies dense_ok != 0, i.e. 32-bit-domain accumulators only.
+static void group_agg_value(const pg_segment* seg, const pg_aggregation& ag, bool plane, long long acc, unsigned long long group_docs, pg_agg_value* v) {
+  const ColumnDev& col = seg->cols[(size_t)ag.column];
+  if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) {
+    if (col.vkind == kValF64 || col.vkind == kValF32) { memcpy(&v->sum, &acc, 8); v->sum_i64 = 0; v->sum_exact = 0; }      // the slot accumulated doubles (ds_add_f64 / global_atomic_add_f64)
+    else set_integer_sum(v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
+  }
+  else if (col.encoding == PG_FWD_RAW_FIXED_BYTE && col.vkind != kValI32) {      // raw LONG value, or the order key of a raw FLOAT / DOUBLE value
+    if (ag.function == PG_AGG_MIN) v->min = group_key64_to_double(col, acc, true); else v->max = group_key64_to_double(col, acc, false);
+  }
+  else if (ag.function == PG_AGG_MIN) v->min = group_dict_min_double(col, (int32_t)acc, plane);
+  else v->max = agg_value_double(col, (int32_t)acc, plane);
+}
 // pg_execute_batch: a group-by of the LDS-table form over a small segment shares ONE launch with the batch's other such items
 // (group_lds_batch_kernel; BatchKind::GroupLds) -- no table init, no compaction launches: the item's slice of the batch's table is
 // all-zero before the launch (zero-identity keys), comes back whole in the batch's one copy, and the host keeps the slots whose
 // count is not zero.  What GroupByCombineOperator.java:102-165 gets from one task per segment.
-static pg_status defer_group_item(QueryRun& r, const GroupParams& gp, int pblocks, int pthreads, size_t plds, const std::vector<int>& cards,
-                                  const std::vector<int>& dev_agg_of, bool no_dict_keys) {
+static pg_status defer_group_item(QueryRun& r, const GroupPlan& p) {
   pg_segment* seg = r.seg; const pg_query* q = r.q; const Lowered& lw = r.lw; const int na = r.na, ng = r.ng;
+  const GroupParams& gp = p.gp;
   auto item = std::make_shared<LoweredItem>();
   item->gp = std::make_shared<GroupParams>(gp);
   item->gp->zero_identity = 1;
   item->gp->scan.lean_kind = (int32_t)BatchKind::GroupLds;
   item->sp.lean_kind = (int32_t)BatchKind::GroupLds;
-  item->blocks = pblocks;
-  item->group_threads = pthreads;
-  item->group_lds = plds;
+  item->blocks = p.pblocks; item->group_threads = p.pthreads; item->group_lds = p.plds;
   item->group_table_words = ((size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs) + 31) & ~(size_t)31;      // (slices start on 256-byte boundaries)
   item->sets = lw.set_leaves;
   const int G = gp.num_groups, NA = gp.num_group_aggs;
@@ -4170,23 +4218,19 @@ static pg_status defer_group_item(QueryRun& r, const GroupParams& gp, int pblock
   for (int a = 0; a < NA; ++a) kinds[(size_t)a] = gp.group_aggs[a].kind;
   const size_t num_projected = r.projected.size();
   // (captured by value and kept with the cached item: what the conversion needs of the lowering -- the planes its aggregations read through
-  //  and the statistics plan -- not the whole Lowered with its index-AND parameter block: advisor, round 5)
-  const std::vector<char> plane_cols = lw.plane_cols;
-  const fstats::Plan stats_plan = lw.stats_plan;
-  const int stats_scan_leaves = lw.stats_scan_leaves;
+  //  and the statistics plan -- not the whole Lowered with its index-AND parameter block: advisor, round 5; and of the plan, never the plan itself)
+  const std::vector<char> plane_cols = lw.plane_cols; const fstats::Plan stats_plan = lw.stats_plan; const int stats_scan_leaves = lw.stats_scan_leaves;
+  const std::vector<int> cards = p.cards, dev_agg_of = p.dev_agg_of; const bool no_dict_keys = p.no_dict_keys;
   item->convert_group = [q, seg, na, ng, cards, dev_agg_of, plane_cols, stats_plan, stats_scan_leaves, G, kinds, num_projected, no_dict_keys](const unsigned long long* table, pg_result* out) {
-    int num_present = 0;
+    int num_present = 0, k = 0; long long docs = 0;
     for (int g = 0; g < G; ++g) num_present += table[g] != 0ull ? 1 : 0;
-    start_group_result(out, na, ng, num_present, PG_KERNEL_GROUP_PRIVATE, no_dict_keys ? (q->num_groups_limit > 0 ? q->num_groups_limit : 100000) : G, 0);
-    long long docs = 0;
-    int k = 0;
+    start_group_result(out, na, ng, num_present, PG_KERNEL_GROUP_PRIVATE, no_dict_keys ? groups_limit(q) : G, 0);
     for (int g = 0; g < G; ++g) {
       const unsigned long long group_docs = table[g];
       if (group_docs == 0ull) continue;
       docs += (long long)group_docs;
       out->group_ids[k] = g;
-      long long raw = g;
-      for (int c = 0; c < ng; ++c) { out->group_key_dict_ids[(size_t)k * (size_t)ng + (size_t)c] = (int32_t)(raw % cards[(size_t)c]); raw /= cards[(size_t)c]; }
+      decode_mixed_radix(g, cards, ng, out->group_key_dict_ids + (size_t)k * (size_t)ng);
       for (int a = 0; a < na; ++a) {
         const pg_aggregation& ag = q->aggregations[a];
         pg_agg_value& v = out->group_aggregations[(size_t)k * (size_t)na + (size_t)a];
@@ -4197,11 +4241,7 @@ static pg_status defer_group_item(QueryRun& r, const GroupParams& gp, int pblock
         // zero-identity keys of the shared launch (group_private_body's flush): MIN travelled as 2^31 - v, MAX as v + 2^31 + 1
         if (kinds[(size_t)da] == kGroupMin) acc = 0x80000000ll - acc;
         else if (kinds[(size_t)da] == kGroupMax) acc = acc - 0x80000001ll;
-        const ColumnDev& col = seg->cols[(size_t)ag.column];
-        const bool plane = plane_cols[(size_t)ag.column] != 0;
-        if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) set_integer_sum(&v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
-        else if (ag.function == PG_AGG_MIN) v.min = group_dict_min_double(col, (int32_t)acc, plane);
-        else v.max = agg_value_double(col, (int32_t)acc, plane);
+        group_agg_value(seg, ag, plane_cols[(size_t)ag.column] != 0, acc, group_docs, &v);
       }
       ++k;
     }
@@ -4212,41 +4252,18 @@ static pg_status defer_group_item(QueryRun& r, const GroupParams& gp, int pblock
   };
   return defer_item(r, std::move(item));
 }
-// One packed dword per doc when the only aggregation input is an unsigned field that fits beside the slot (pg_group_partition.h):
-// the width of that field, 1 for COUNT alone, 0 for separate key / value record columns.
-static int partition_packed_bits(const GroupParams& gp, int scatter_shift) {
-  if (!g_engine.partition_packed) return 0;
-  if (gp.num_group_aggs == 0) return 1;
-  if (gp.num_group_aggs != 1) return 0;
-  const DevGroupAgg& ga = gp.group_aggs[0];
-  const bool unsigned_field = !ga.is_raw && ga.vkind == kValI32 && (ga.kind != kGroupSum || ga.is_plane);
-  return unsigned_field && ga.bits + scatter_shift <= 32 ? ga.bits : 0;
-}
 // Key spaces above the LDS table: the docs are partitioned by key range first, then every partition is aggregated in LDS
-// (pg_group_partition.h) instead of one global atomic per doc and aggregation.  P partitions of 2^partition_shift keys each; two
-// levels when log2_fine_per_coarse > 0 (pass A scatters by coarse partition, group_repartition_*_kernel by fine partition).
-static pg_status run_partitioned_group_by(QueryRun& r, const GroupParams& gp, int P, int partition_shift, int log2_fine_per_coarse) {
+// (pg_group_partition.h) instead of one global atomic per doc and aggregation.  p.part: P scatter partitions, fine partitions of 2^shift
+// keys each; two levels when log2_fine_per_coarse > 0 (pass A scatters by coarse partition, group_repartition_*_kernel by fine partition).
+// Where everything lies in the record buffer: PartitionLayout (pg_group_plan.h).
+static pg_status run_partitioned_group_by(QueryRun& r, const GroupPlan& p) {
   pg_segment* seg = r.seg; const pg_query* q = r.q; ExecCtx* ctx = r.ctx; const int ng = r.ng;
-  const bool two_level = log2_fine_per_coarse > 0;
-  const int scatter_shift = partition_shift + log2_fine_per_coarse;
-  const int partition_entry_bytes = 4 + 8 * gp.num_group_aggs;
-  const size_t N = (size_t)std::max(seg->num_tiles, 1) * 2048;
-  const size_t max_work = N / (1u << 16) + (size_t)P + 1;
-  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t off_upper = 0, off_cursor = align(off_upper + (size_t)P * 4), off_offsets = align(off_cursor + (size_t)P * 4);
-  const size_t off_work = align(off_offsets + (size_t)(P + 1) * 4), off_key = align(off_work + max_work * sizeof(PartitionWork));
-  const int packed_bits = partition_packed_bits(gp, scatter_shift);
-  const size_t off_val = align(off_key + N * 4), level1_bytes = off_val + (packed_bits > 0 ? 0 : (size_t)gp.num_group_aggs * align(N * 4));
-  // two levels: the second record buffer(s), the fine partitions' count / offset / cursor arrays, pass B's device-built work list and its
-  // length, and the re-scatter's own chunk list
-  const int num_vals = packed_bits > 0 ? 0 : gp.num_group_aggs;
-  const size_t fine_slots = (size_t)P << log2_fine_per_coarse;
-  const size_t max_work2 = N / (1u << 16) + fine_slots + 1, max_chunks = N / kRepartitionChunk + (size_t)P + 1;
-  const size_t off_key2 = align(level1_bytes), off_val2 = align(off_key2 + N * 4);
-  const size_t off_fine = align(off_val2 + (size_t)num_vals * align(N * 4));                       // count | cursor | work_count (zeroed together), then offsets
-  const size_t off_fine_offsets = align(off_fine + 2 * fine_slots * 4 + 64);
-  const size_t off_work2 = align(off_fine_offsets + fine_slots * 4), off_chunks = align(off_work2 + max_work2 * sizeof(PartitionWork));
-  const size_t bytes = two_level ? align(off_chunks + max_chunks * sizeof(PartitionWork)) : level1_bytes;
+  const GroupParams& gp = p.gp; const int P = (int)p.part.scatter_partitions, partition_shift = p.part.shift, log2_fine_per_coarse = p.part.log2_fine_per_coarse;
+  const int scatter_shift = p.part.scatter_shift(), packed_bits = p.packed_bits;
+  const PartitionLayout lay(P, (size_t)std::max(seg->num_tiles, 1) * 2048, gp.num_group_aggs, packed_bits, log2_fine_per_coarse, sizeof(PartitionWork), kRepartitionChunk);
+  const int num_vals = lay.num_vals; const size_t fine_slots = lay.fine_slots, bytes = lay.bytes;
+  auto u32_at = [&](size_t off) { return reinterpret_cast<uint32_t*>(ctx->d_partition + off); };                       // (after the allocation below)
+  auto work_at = [&](size_t off) { return reinterpret_cast<PartitionWork*>(ctx->d_partition + off); };
   if (ctx->partition_capacity < bytes) {
     if (ctx->d_partition) (void)hipFree(ctx->d_partition);
     ctx->d_partition = nullptr; ctx->partition_capacity = 0;
@@ -4255,17 +4272,14 @@ static pg_status run_partitioned_group_by(QueryRun& r, const GroupParams& gp, in
   }
   PartitionParams pp;
   memset(&pp, 0, sizeof(pp));
-  pp.gp = gp;
-  pp.shift = scatter_shift;                     // (two levels: pass 0 and pass A work on coarse partitions)
-  pp.num_partitions = P;
-  pp.packed_bits = packed_bits;
-  pp.upper = reinterpret_cast<uint32_t*>(ctx->d_partition + off_upper);
-  pp.cursor = reinterpret_cast<uint32_t*>(ctx->d_partition + off_cursor);
-  pp.offsets = reinterpret_cast<const uint32_t*>(ctx->d_partition + off_offsets);
-  pp.work = reinterpret_cast<const PartitionWork*>(ctx->d_partition + off_work);
-  pp.part_key = reinterpret_cast<uint32_t*>(ctx->d_partition + off_key);
-  for (int a = 0; a < gp.num_group_aggs; ++a) pp.part_val[a] = reinterpret_cast<uint32_t*>(ctx->d_partition + off_val + (size_t)a * align(N * 4));
-  HIP_TRY(hipMemsetAsync(ctx->d_partition, 0, off_offsets, ctx->stream));          // upper and cursor
+  pp.gp = gp; pp.shift = scatter_shift; pp.num_partitions = P; pp.packed_bits = packed_bits;      // (two levels: pass 0 and pass A work on coarse partitions)
+  pp.upper = u32_at(lay.off_upper);
+  pp.cursor = u32_at(lay.off_cursor);
+  pp.offsets = u32_at(lay.off_offsets);
+  pp.work = work_at(lay.off_work);
+  pp.part_key = u32_at(lay.off_key);
+  for (int a = 0; a < gp.num_group_aggs; ++a) pp.part_val[a] = u32_at(lay.off_val + (size_t)a * lay.val_stride);
+  HIP_TRY(hipMemsetAsync(ctx->d_partition, 0, lay.off_offsets, ctx->stream));          // upper and cursor
   const long long tiles2k = doc_tiles(seg);
   const int hist_blocks = grid_blocks(seg, tiles2k, 4, 6, false);
   std::vector<int> stats_key{scatter_shift};
@@ -4288,42 +4302,33 @@ static pg_status run_partitioned_group_by(QueryRun& r, const GroupParams& gp, in
   }
   std::vector<uint32_t> offsets((size_t)P + 1, 0u);
   std::vector<PartitionWork> work;
-  // chunk size: about two rounds of resident pass-B workgroups over the whole input, so that the flush of the touched slots
-  // (one global atomic per slot, accumulator and chunk) stays small next to the records a chunk aggregates
   unsigned long long total_upper = 0;
-  for (int p = 0; p < P; ++p) total_upper += upper[(size_t)p];
-  const unsigned long long want_chunk = (total_upper + (unsigned long long)seg->num_cus * 6 - 1) / ((unsigned long long)seg->num_cus * 6);
-  const uint32_t chunk = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>((want_chunk + 1023) & ~1023ull, 1u << 16), (unsigned long long)kPartitionChunk);
-  for (int p = 0; p < P; ++p) {
-    offsets[(size_t)p + 1] = offsets[(size_t)p] + upper[(size_t)p];
-    for (uint32_t s0 = 0; s0 < upper[(size_t)p]; s0 += chunk) work.push_back(PartitionWork{p, s0, std::min<uint32_t>(chunk, upper[(size_t)p] - s0), 0u});
+  for (int i = 0; i < P; ++i) total_upper += upper[(size_t)i];
+  const uint32_t chunk = partition_chunk(total_upper, seg->num_cus, (unsigned long long)kPartitionChunk);
+  for (int i = 0; i < P; ++i) {
+    offsets[(size_t)i + 1] = offsets[(size_t)i] + upper[(size_t)i];
+    for (uint32_t s0 = 0; s0 < upper[(size_t)i]; s0 += chunk) work.push_back(PartitionWork{i, s0, std::min<uint32_t>(chunk, upper[(size_t)i] - s0), 0u});
   }
-  HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_offsets, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (!work.empty()) HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_work, work.data(), work.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->d_partition + lay.off_offsets, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (!work.empty()) HIP_TRY(hipMemcpyAsync(ctx->d_partition + lay.off_work, work.data(), work.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
   const int scatter_bpc = packed_bits > 0 ? blocks_per_cu_group_partition_scatter_packed(P) : std::max(1, waves_group_partition_scatter() / 4);
   const int scatter_blocks = grid_blocks(seg, tiles2k, 4, scatter_bpc, false);
   launch_group_partition_scatter(scatter_blocks, ctx->stream, pp);
   HIP_TRY(hipGetLastError());
   std::vector<PartitionWork> chunks;
-  if (two_level && !work.empty()) {
+  if (lay.two_level && !work.empty()) {
     RepartitionParams rp;
     memset(&rp, 0, sizeof(rp));
-    rp.src_key = pp.part_key;
-    rp.dst_key = reinterpret_cast<uint32_t*>(ctx->d_partition + off_key2);
-    for (int a = 0; a < num_vals; ++a) { rp.src_val[a] = pp.part_val[a]; rp.dst_val[a] = reinterpret_cast<uint32_t*>(ctx->d_partition + off_val2 + (size_t)a * align(N * 4)); }
+    rp.src_key = pp.part_key; rp.dst_key = u32_at(lay.off_key2);
+    for (int a = 0; a < num_vals; ++a) { rp.src_val[a] = pp.part_val[a]; rp.dst_val[a] = u32_at(lay.off_val2 + (size_t)a * lay.val_stride); }
     rp.coarse_offsets = pp.offsets; rp.coarse_cursor = pp.cursor;
-    rp.fine_count = reinterpret_cast<uint32_t*>(ctx->d_partition + off_fine);
-    rp.fine_cursor = rp.fine_count + fine_slots;
-    rp.work_count = rp.fine_cursor + fine_slots;
-    rp.fine_offsets = reinterpret_cast<uint32_t*>(ctx->d_partition + off_fine_offsets);
-    rp.work = reinterpret_cast<PartitionWork*>(ctx->d_partition + off_work2);
-    rp.chunks = reinterpret_cast<const PartitionWork*>(ctx->d_partition + off_chunks);
-    rp.num_coarse = P; rp.log2_fine_per_coarse = log2_fine_per_coarse; rp.fine_shift = partition_shift; rp.packed_bits = packed_bits; rp.num_vals = num_vals;
-    rp.aggregate_chunk = chunk;
-    for (int p = 0; p < P; ++p)
-      for (uint32_t s0 = 0; s0 < upper[(size_t)p]; s0 += kRepartitionChunk) chunks.push_back(PartitionWork{p, s0, std::min<uint32_t>(kRepartitionChunk, upper[(size_t)p] - s0), 0u});
-    HIP_TRY(hipMemsetAsync(ctx->d_partition + off_fine, 0, 2 * fine_slots * 4 + 64, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->d_partition + off_chunks, chunks.data(), chunks.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
+    rp.fine_count = u32_at(lay.off_fine); rp.fine_cursor = rp.fine_count + fine_slots; rp.work_count = rp.fine_cursor + fine_slots;      // count | cursor | work_count (zeroed together), then offsets
+    rp.fine_offsets = u32_at(lay.off_fine_offsets); rp.work = work_at(lay.off_work2); rp.chunks = work_at(lay.off_chunks);
+    rp.num_coarse = P; rp.log2_fine_per_coarse = log2_fine_per_coarse; rp.fine_shift = partition_shift; rp.packed_bits = packed_bits; rp.num_vals = num_vals; rp.aggregate_chunk = chunk;
+    for (int i = 0; i < P; ++i)
+      for (uint32_t s0 = 0; s0 < upper[(size_t)i]; s0 += kRepartitionChunk) chunks.push_back(PartitionWork{i, s0, std::min<uint32_t>(kRepartitionChunk, upper[(size_t)i] - s0), 0u});
+    HIP_TRY(hipMemsetAsync(ctx->d_partition + lay.off_fine, 0, lay.fine_zero_bytes, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_partition + lay.off_chunks, chunks.data(), chunks.size() * sizeof(PartitionWork), hipMemcpyHostToDevice, ctx->stream));
     launch_group_repartition((int)chunks.size(), ctx->stream, rp);
     HIP_TRY(hipGetLastError());
     // pass B over the fine partitions: the second buffer, the device-built work list (as many workgroups as it can have entries)
@@ -4334,9 +4339,9 @@ static pg_status run_partitioned_group_by(QueryRun& r, const GroupParams& gp, in
     fine.work = rp.work; fine.work_count = rp.work_count;
     fine.part_key = rp.dst_key;
     for (int a = 0; a < num_vals; ++a) fine.part_val[a] = rp.dst_val[a];
-    launch_group_partition_aggregate((int)max_work2, ((size_t)partition_entry_bytes) << partition_shift, ctx->stream, fine);
+    launch_group_partition_aggregate((int)lay.max_work2, ((size_t)p.part.entry_bytes) << partition_shift, ctx->stream, fine);
   } else if (!work.empty()) {
-    launch_group_partition_aggregate((int)work.size(), ((size_t)partition_entry_bytes) << partition_shift, ctx->stream, pp);
+    launch_group_partition_aggregate((int)work.size(), ((size_t)p.part.entry_bytes) << partition_shift, ctx->stream, pp);
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));      // `offsets` / `work` / `chunks` are pageable host vectors: keep them alive until the copies ran
   return PG_OK;
@@ -4353,12 +4358,11 @@ struct PresentGroups {
 
 // IntMapBasedHolder range: compact the HBM table on the device; honour numGroupsLimit the way the reference does
 // (_globalGroupIdUpperBound = min(product, numGroupsLimit), DictionaryBasedGroupKeyGenerator.java:176).
-static pg_status compact_map_groups(QueryRun& r, const GroupParams& gp, const HashPlan& hash_plan, long long product, bool use_private, int pblocks, int pthreads,
-                                    size_t plds, PresentGroups* found) {
-  pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; const bool timed = r.timed;
+static pg_status compact_map_groups(QueryRun& r, const GroupPlan& p, PresentGroups* found) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; const bool timed = r.timed; const GroupParams& gp = p.gp; const HashPlan& hash_plan = p.hash_plan;
   pg_status st = PG_OK;
-  const int limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
-  const long long bound = hash_plan.kind != 0 ? (long long)limit : std::min<long long>(product, limit);      // LongMap / ArrayMap holders: _globalGroupIdUpperBound = numGroupsLimit (:150-163)
+  const int limit = groups_limit(q);
+  const long long bound = hash_plan.kind != 0 ? (long long)limit : std::min<long long>(p.product, limit);      // LongMap / ArrayMap holders: _globalGroupIdUpperBound = numGroupsLimit (:150-163)
   const int num_chunks = (int)(((long long)gp.num_groups + kGroupChunk - 1) / kGroupChunk);
   DeviceScratch scratch(ctx);
   uint32_t* d_chunk_counts = (uint32_t*)scratch.alloc((size_t)num_chunks * 4);
@@ -4414,10 +4418,11 @@ static pg_status compact_map_groups(QueryRun& r, const GroupParams& gp, const Ha
       for (int n = 0; n < fg.scan.num_nodes; ++n) fg.scan.nodes[n].flags &= ~(kNodeLeapfrog2 | kNodeCountEntries);
       // (plds: the set area, when the filter has dictId sets.  A query whose aggregation runs in group_typed_direct_kernel never sized a
       //  group_private_kernel launch: the pass takes that kernel's own geometry then)
-      const int fd_threads = use_private ? pthreads : kBlockThreads;
-      const int fd_blocks = use_private ? pblocks : grid_blocks(seg, doc_tiles(seg), 4, 8, false);
+      const bool use_private = p.private_sized();
+      const int fd_threads = use_private ? p.pthreads : kBlockThreads;
+      const int fd_blocks = use_private ? p.pblocks : grid_blocks(seg, doc_tiles(seg), 4, 8, false);
       if (!use_private) fg.set_lds_off = -1;
-      launch_group_private(false, fd_blocks, fd_threads, use_private ? plds : 0, ctx->stream, fg);
+      launch_group_private(false, fd_blocks, fd_threads, use_private ? p.plds : 0, ctx->stream, fg);
       HIP_TRY(hipGetLastError());
       done_docs = seg->num_docs;
       max_first_doc = 0xFFFFFFFEu;
@@ -4487,19 +4492,12 @@ static pg_status compact_map_groups(QueryRun& r, const GroupParams& gp, const Ha
   }
   return PG_OK;
 }
-// ---------------- group-by (ArrayBasedHolder) ----------------
-static pg_status run_group_by(QueryRun& r) {
-  pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; ScanParams& sp = lw.sp;
-  PlanParams& pl = lw.plan; const int na = r.na, ng = r.ng, num_cols_total = (int)seg->cols.size();
-  const bool want_bitmap = r.want_bitmap, timed = r.timed;
+// The stages of run_group_by, in call order; their declines keep the order they had in one function (a query with two problems gets the first's message).
+// plan, 1: the key columns' streams, the holder (direct-indexed or hashed), the key space
+static pg_status bind_group_keys(QueryRun& r, GroupPlan* p) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; Lowered& lw = r.lw; PlanParams& pl = lw.plan; const int ng = r.ng, num_cols_total = (int)seg->cols.size();
+  const HashPlan& hash_plan = p->hash_plan;
   pg_status st = PG_OK;
-  GroupParams gp;
-  memset(&gp, 0, sizeof(gp));
-  int group_slot[kMaxGroupCols] = {}, group_mult[kMaxGroupCols] = {};
-  PlanGroupAgg plan_aggs[kMaxGroupAggs];
-  long long product = 1;
-  std::vector<int> cards;
-  bool no_dict_keys = false;            // a key is a raw column read through its key image, or the null-key image of one
   for (int g = 0; g < ng; ++g) {
     int c = q->group_by_columns[g];
     if (c < 0 || c >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "group-by column %d out of range", c);
@@ -4509,36 +4507,40 @@ static pg_status run_group_by(QueryRun& r) {
       st = ensure_key_image(seg, c, &c); if (st != PG_OK) return st;
     }
     const ColumnDev& col = seg->cols[(size_t)c];
-    no_dict_keys |= col.key_image_of >= 0;
+    p->no_dict_keys |= col.key_image_of >= 0;
     int s = slot_for(&lw, seg, c);
     if (s < 0) return fail(PG_ERR_UNSUPPORTED, "query references more than %d columns", kMaxCols);
     pl.cols[s].in_agg = 1;
-    group_slot[g] = s;
-    cards.push_back(col.cardinality);
+    p->group_slot[g] = s;
+    p->cards.push_back(col.cardinality);
   }
   // DictionaryBasedGroupKeyGenerator.java:164-184: up to arrayBasedThreshold (10 000) the raw key IS the group id (ArrayBasedHolder);
   // above it the reference hashes raw keys (IntMapBasedHolder) -- here the table stays direct-indexed, in HBM, one slot per raw
   // key, and only the groups that exist come back.  2^24 slots keep the 24-bit key multiplies exact and the table <= 1.2 GB.
   // Beyond an int (Long / ArrayMap holders) the table is hashed: `product` is then its number of slots (plan_hash_holder).
-  HashPlan hash_plan;
-  st = plan_hash_holder(seg, cards, &hash_plan); if (st != PG_OK) return st;
+  st = plan_hash_holder(seg, p->cards, &p->hash_plan); if (st != PG_OK) return st;
   if (hash_plan.kind == 0) {
-    for (int g = 0; g < ng; ++g) { group_mult[g] = (int32_t)product; product *= cards[(size_t)g]; }
+    for (int g = 0; g < ng; ++g) { p->group_mult[g] = (int32_t)p->product; p->product *= p->cards[(size_t)g]; }
   } else {
-    product = hash_plan.slots;
+    p->product = hash_plan.slots;
     if (q->flags & kQueryHashHolder) return fail(PG_ERR_UNSUPPORTED, "group-by with raw keys beyond an int under null handling (plan-time fallback)");
   }
   // (kQueryHashHolder: the no-dictionary key generators of null handling hand out group ids by first appearance up to numGroupsLimit
   //  whatever the key space: the compaction path below is the one that honours the limit)
   // A raw key column always runs the no-dictionary generators (DefaultGroupByExecutor.java:106-121): _globalGroupIdUpperBound =
   // numGroupsLimit whatever the key space (NoDictionarySingleColumnGroupKeyGenerator.java:73-79), ids by first appearance.
-  const bool first_appearance = (q->flags & kQueryHashHolder) != 0 || (no_dict_keys && hash_plan.kind == 0 && (long long)(q->num_groups_limit > 0 ? q->num_groups_limit : 100000) < product);
-  const bool map_based = product > 10000 || first_appearance || hash_plan.kind != 0;
-  bool typed_direct = false;            // an aggregation input is a raw LONG / FLOAT / DOUBLE column: group_typed_direct_kernel
-  gp.num_group_cols = ng;
-  gp.num_groups = (int32_t)product;
-  gp.dense_ok = 1;
-  std::vector<int> dev_agg_of((size_t)std::max(na, 1), -1);
+  p->first_appearance = (q->flags & kQueryHashHolder) != 0 || (p->no_dict_keys && hash_plan.kind == 0 && (long long)groups_limit(q) < p->product);
+  p->map_based = p->product > 10000 || p->first_appearance || hash_plan.kind != 0;
+  p->gp.num_group_cols = ng;
+  p->gp.num_groups = (int32_t)p->product;
+  p->gp.dense_ok = 1;
+  return PG_OK;
+}
+// plan, 2: the aggregations' columns, and the distinct accumulators the device keeps for them
+static pg_status bind_group_aggs(QueryRun& r, GroupPlan* p) {
+  pg_segment* seg = r.seg; const pg_query* q = r.q; Lowered& lw = r.lw; PlanParams& pl = lw.plan; const int na = r.na, num_cols_total = (int)seg->cols.size();
+  GroupParams& gp = p->gp; PlanGroupAgg* plan_aggs = p->plan_aggs; std::vector<int>& dev_agg_of = p->dev_agg_of;
+  dev_agg_of.assign((size_t)std::max(na, 1), -1);
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
     if (ag.function == PG_AGG_COUNT) {
@@ -4562,48 +4564,38 @@ static pg_status run_group_by(QueryRun& r) {
     }
     dev_agg_of[(size_t)a] = da;
   }
-  gp.wide_keys = product > (1ll << 24) ? 1 : 0;
+  gp.wide_keys = p->product > (1ll << 24) ? 1 : 0;
+  return PG_OK;
+}
+// plan, 3: the table -- count[G] | acc[num_group_aggs][G], behind them a hashed holder's keys and first tables -- in the context's d_table; the columns' place in a staged tile
+static pg_status lay_out_group_table(QueryRun& r, GroupPlan* p) {
+  pg_segment* seg = r.seg; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; ScanParams& sp = lw.sp; PlanParams& pl = lw.plan; const int ng = r.ng;
+  GroupParams& gp = p->gp; const HashPlan& hash_plan = p->hash_plan; const PlanGroupAgg* plan_aggs = p->plan_aggs; Geometry& geo = p->geo;
   // (hashed holders: one more word per slot for its key, and the first table of an ArrayMap-range key)
-  const size_t table_words = (size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs + (hash_plan.kind ? 1 : 0)) + (size_t)hash_plan.level_slots();
-  if ((unsigned long long)table_words * 8ull > g_engine.group_table_bytes)
-    return fail(PG_ERR_UNSUPPORTED, "group-by table of %lld slots x %d words exceeds the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", product, 1 + gp.num_group_aggs,
+  p->table_words = (size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs + (hash_plan.kind ? 1 : 0)) + (size_t)hash_plan.level_slots(); p->table_bytes = p->table_words * 8;
+  if ((unsigned long long)p->table_words * 8ull > g_engine.group_table_bytes)
+    return fail(PG_ERR_UNSUPPORTED, "group-by table of %lld slots x %d words exceeds the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", p->product, 1 + gp.num_group_aggs,
                 (unsigned long long)g_engine.group_table_bytes);
-  st = ensure_table(ctx, table_words, map_based ? 0 : table_words); if (st != PG_OK) return st;
-  struct TableTrim {            // a table of the upper IntMapBasedHolder range goes back to the allocator with the query
-    ExecCtx* c;
-    ~TableTrim() {
-      if (c->table_capacity * 8 > kGroupTableKeepBytes) { (void)hipFree(c->d_table); c->d_table = nullptr; c->table_capacity = 0; }
-    }
-  } table_trim{ctx};
-  gp.table_count = ctx->d_table;
-  gp.table_acc = reinterpret_cast<long long*>(ctx->d_table + gp.num_groups);
-  gp.hash_kind = hash_plan.kind;
-  gp.hash_levels = hash_plan.levels;
+  const pg_status st = ensure_table(ctx, p->table_words, p->map_based ? 0 : p->table_words); if (st != PG_OK) return st;
+  gp.table_count = ctx->d_table; gp.table_acc = reinterpret_cast<long long*>(ctx->d_table + gp.num_groups);
+  gp.hash_kind = hash_plan.kind; gp.hash_levels = hash_plan.levels;
   if (hash_plan.kind != 0) {
     gp.hash_mask = (unsigned long long)gp.num_groups - 1ull;
     gp.hash_keys = ctx->d_table + (size_t)gp.num_groups * (size_t)(1 + gp.num_group_aggs);
     unsigned long long* next_table = gp.hash_keys + gp.num_groups;
     for (int l = 0; l < hash_plan.levels; ++l) {
-      gp.hash_split[l] = hash_plan.split[l];
-      gp.hash_mask_lvl[l] = (unsigned long long)hash_plan.slots_lvl[l] - 1ull;
-      gp.hash_keys_lvl[l] = next_table;
-      next_table += hash_plan.slots_lvl[l];
+      gp.hash_split[l] = hash_plan.split[l]; gp.hash_mask_lvl[l] = (unsigned long long)hash_plan.slots_lvl[l] - 1ull;
+      gp.hash_keys_lvl[l] = next_table; next_table += hash_plan.slots_lvl[l];
     }
     for (int g = 0; g < ng; ++g) gp.key_mult[g] = hash_plan.mult[g];
   }
-  const size_t table_bytes = table_words * 8;
-  Geometry geo;
+  // the staged geometry (which places the column streams), then the keys and accumulators as the kernels read them
   const int group_wave_cap = waves_scan_group();
-  finish_geometry(seg, &lw, table_bytes, false, g_engine.group_waves > 0 ? std::min(g_engine.group_waves, kGroupBlockThreads / 64) : kGroupBlockThreads / 64, group_wave_cap, &geo);
+  finish_geometry(seg, &lw, p->table_bytes, false, g_engine.group_waves > 0 ? std::min(g_engine.group_waves, kGroupBlockThreads / 64) : kGroupBlockThreads / 64, group_wave_cap, &geo);
   if ((size_t)sp.wave_lds_bytes > kLdsBudget) return fail(PG_ERR_UNSUPPORTED, "query needs %d bytes of LDS per wavefront", sp.wave_lds_bytes);
   gp.use_lds_table = geo.table_in_lds ? 1 : 0;
-  const int blocks = geo.blocks;
-  const size_t lds = geo.lds;
   sp.speculate = 1;
-  for (int g = 0; g < ng; ++g) {
-    const DevColumn& c = pl.cols[group_slot[g]];
-    gp.group_keys[g] = DevGroupKey{c.bits, c.slot_off, group_mult[g], 0, c.fwd};
-  }
+  for (int g = 0; g < ng; ++g) { const DevColumn& c = pl.cols[p->group_slot[g]]; gp.group_keys[g] = DevGroupKey{c.bits, c.slot_off, p->group_mult[g], 0, c.fwd}; }
   for (int a = 0; a < gp.num_group_aggs; ++a) {
     const DevColumn& c = pl.cols[plan_aggs[a].col];
     DevGroupAgg& ga = gp.group_aggs[a];
@@ -4611,10 +4603,7 @@ static pg_status run_group_by(QueryRun& r) {
     ga.dict_bytes = c.dict_bytes; ga.fwd = c.fwd; ga.dict = c.dict;
     // MIN / MAX run on dictIds whatever the value type; only a SUM reads 8-byte / floating-point dictionary entries
     ga.vkind = (ga.kind == kGroupSum) ? c.vkind : kValI32;
-    if (c.is_raw && c.vkind != kValI32) { typed_direct = true; ga.vkind = c.vkind; }      // group_typed_direct_kernel: the value type decides the accumulator
-    // (the SUM of a dictionary column with 8-byte values under a Long / ArrayMap holder: the staged kernel that gathers such values has no
-    //  hashed table, group_typed_direct_kernel<.., kHash> gathers them too)
-    if (hash_plan.kind != 0 && ga.vkind != kValI32) typed_direct = true;
+    if (c.is_raw && c.vkind != kValI32) ga.vkind = c.vkind;      // group_typed_direct_kernel: the value type decides the accumulator
     if (ga.vkind != kValI32) gp.dense_ok = 0;
     if (ga.vkind == kValI64 && !c.is_raw) {
       // the table slot is one wrapping int64: refuse (plan-time fallback) when numDocs * max|value| could overflow it
@@ -4623,44 +4612,68 @@ static pg_status run_group_by(QueryRun& r) {
       if ((double)seg->num_docs * max_abs >= 9.2e18) return fail(PG_ERR_UNSUPPORTED, "group-by SUM of LONG column %s could overflow int64", sc.name.c_str());
     }
   }
+  return PG_OK;
+}
+// plan, 4: the route
+static pg_status choose_group_route(QueryRun& r, GroupPlan* p) {
+  const pg_segment* seg = r.seg; const PlanParams& pl = r.lw.plan; const bool want_bitmap = r.want_bitmap; const GroupParams& gp = p->gp; const HashPlan& hash_plan = p->hash_plan;
+  // An accumulator is a raw LONG / FLOAT / DOUBLE value: group_typed_direct_kernel.  So is the SUM of a dictionary column with 8-byte values under a Long /
+  // ArrayMap holder: the staged kernel that gathers such values has no hashed table, group_typed_direct_kernel<.., kHash> gathers them too.
+  bool typed_direct = false;
+  for (int a = 0; a < gp.num_group_aggs; ++a) typed_direct |= gp.group_aggs[a].vkind != kValI32 && (gp.group_aggs[a].is_raw || hash_plan.kind != 0);
   // Without a filter every tile is aggregated in full: the lane-private kernel decodes straight from HBM and needs LDS only
   // for the table (group_private_kernel).
   // every leaf kind the lane-private filter implements (scan / set / bitmap / docId-range leaves, raw INT ranges)
-  bool private_leaves = true;
+  bool& private_leaves = p->private_leaves;
   for (int l = 0; l < pl.num_leaves; ++l) private_leaves &= pl.leaves[l].kind <= kLeafBitmap || pl.leaves[l].kind == kLeafDocRange;
   if (typed_direct && !private_leaves) return fail(PG_ERR_UNSUPPORTED, "group-by aggregation of a raw 8-byte column under a raw 8-byte range predicate (plan-time fallback)");
   const bool use_private = (g_engine.group_private || hash_plan.kind != 0) && private_leaves && gp.dense_ok && !want_bitmap && !typed_direct;
   if (hash_plan.kind != 0 && !use_private && !typed_direct) return fail(PG_ERR_UNSUPPORTED, "group-by with raw keys beyond an int: only 32-bit-domain or raw 8-byte aggregations under lane-private filter leaves");
-  int pblocks = blocks, pthreads = geo.threads;
-  size_t plds = lds;
+  // Key spaces above the LDS table: partition the docs by key range first, then aggregate every partition in LDS (pg_group_partition.h) instead of one
+  // global atomic per doc and aggregation.  More fine partitions than one scatter pass can address (key spaces of 2 M .. 2^31 raw keys): two levels
+  // (partition_plan, pg_group_plan.h).  PINOT_GPU_PARTITION_TWO_LEVEL=0: such key spaces keep the direct HBM atomics.
+  p->part = partition_plan(p->product, gp.num_group_aggs, kMaxPartitions);
+  const bool use_partition = hash_plan.kind == 0 && !typed_direct && p->map_based && g_engine.group_partition && g_engine.group_private && private_leaves && gp.dense_ok && !want_bitmap &&
+                             gp.num_group_aggs <= kMaxPartitionAggs && (!p->part.two_level() || (g_engine.partition_two_level && (1 << p->part.log2_fine_per_coarse) <= kMaxFinePerCoarse)) &&
+                             (long long)seg->num_docs >= g_engine.partition_min_docs;
+  p->route = use_partition ? GroupRoute::Partition : (typed_direct ? GroupRoute::TypedDirect : (use_private ? GroupRoute::Private : GroupRoute::Staged));
+  const DevGroupAgg& ga = gp.group_aggs[0];
+  if (use_partition) p->packed_bits = partition_packed_bits(g_engine.partition_packed, gp.num_group_aggs, ga.kind == kGroupSum, ga.bits, ga.is_raw != 0, ga.is_plane != 0, ga.vkind == kValI32, p->part.scatter_shift());
+  return PG_OK;
+}
+// plan, 5: the private launch, count packing, the LDS table's replicas and the set area; the scan block the kernels get
+static pg_status size_group_launch(QueryRun& r, GroupPlan* p) {
+  pg_segment* seg = r.seg; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; ScanParams& sp = lw.sp; GroupParams& gp = p->gp; const Geometry& geo = p->geo;
+  const size_t table_bytes = p->table_bytes; const bool use_private = p->private_sized(); const int blocks = geo.blocks;
+  // the private launch: the staged geometry unless the route is sized for group_private_kernel
+  int& pblocks = p->pblocks; int& pthreads = p->pthreads; size_t& plds = p->plds;
+  pblocks = blocks;
+  pthreads = geo.threads;
+  plds = geo.lds;
   if (use_private) {
     const int private_wave_cap = waves_group_private();
-    const bool in_lds = table_bytes <= 96 * 1024;
-    gp.use_lds_table = in_lds ? 1 : 0;
+    const bool in_lds = table_bytes <= 96 * 1024; gp.use_lds_table = in_lds ? 1 : 0;
     int waves = in_lds ? kGroupBlockThreads / 64 : kBlockThreads / 64;
     if (g_engine.group_waves > 0) waves = std::min(waves, g_engine.group_waves);
     while (waves > private_wave_cap) waves >>= 1;
-    pthreads = waves * 64;
-    plds = in_lds ? table_bytes : 0;
+    pthreads = waves * 64; plds = in_lds ? table_bytes : 0;
     int bpc = std::max(1, private_wave_cap / waves);
     if (in_lds) bpc = std::max(1, std::min(bpc, (int)(kLdsBudget / std::max<size_t>(plds, 1))));
     pblocks = grid_blocks(seg, doc_tiles(seg), waves, bpc);
   }
-  // Count packing: when the first summed value plane is narrow enough, its 64-bit LDS slot carries (count << shift) | sum
-  // and the separate count atomic disappears.  Safe while a workgroup sees fewer than 2^cbits docs:
-  // sum < 2^cbits * 2^w = 2^shift and count < 2^cbits, so cbits + shift <= 64 never carries into or out of the count.
-  gp.packed_agg = -1;
-  gp.packed_shift = 0;
+  // Count packing (count_bits / count_packed_shift, pg_group_plan.h): the first summed value plane that is narrow enough for the docs a
+  // workgroup sees carries the count in its LDS slot.
+  gp.packed_agg = -1; gp.packed_shift = 0;
   if (gp.use_lds_table && g_engine.group_pack) {
     const long long waves_total = use_private ? (long long)pblocks * (pthreads / 64) : (long long)blocks * (geo.threads / 64);
     const long long tiles_total = use_private ? doc_tiles(seg) : (long long)sp.num_tiles;
     const long long tiles_per_wave = (tiles_total + waves_total - 1) / waves_total;
     const long long docs_per_block = use_private ? tiles_per_wave * (pthreads / 64) * 2048 : tiles_per_wave * (geo.threads / 64) * 64 * sp.tile_steps;
-    int cbits = 1;
-    while ((1ll << cbits) <= docs_per_block) ++cbits;
+    const int cbits = count_bits(docs_per_block);
     for (int a = 0; a < gp.num_group_aggs; ++a) {
       const DevGroupAgg& ga = gp.group_aggs[a];
-      if (ga.kind == kGroupSum && ga.is_plane && !ga.is_raw && 2 * cbits + ga.bits <= 64) { gp.packed_agg = a; gp.packed_shift = std::max(32, cbits + ga.bits); break; }
+      const int shift = (ga.kind == kGroupSum && ga.is_plane && !ga.is_raw) ? count_packed_shift(cbits, ga.bits) : 0;
+      if (shift != 0) { gp.packed_agg = a; gp.packed_shift = shift; break; }
     }
   }
   // group_private_kernel's LDS table in as many bank-interleaved copies as the workgroup's share of the CU's LDS holds (pg_kernels.h,
@@ -4675,82 +4688,78 @@ static pg_status run_group_by(QueryRun& r) {
     const size_t budget = kLdsBudget / (size_t)resident - set_area;
     int log_r = 0;
     while (log_r < g_engine.group_log_replicas && (size_t)lds_group_table_bytes(gp, log_r + 1) <= budget) ++log_r;
-    gp.lds_log_replicas = log_r;
-    plds = lds_group_table_bytes(gp, log_r);
+    gp.lds_log_replicas = log_r; plds = lds_group_table_bytes(gp, log_r);
   }
   gp.set_lds_off = -1;
   if (set_area != 0 && plds + set_area <= kLdsBudget) { gp.set_lds_off = (int32_t)((plds + 15) & ~(size_t)15); plds = (size_t)gp.set_lds_off + set_area; }
   gp.scan = sp;
   gp.scan.partials = nullptr;
   gp.scan.out_bitmap = nullptr;
-  if (lw.tile_list != nullptr) { st = complete_index_list(&lw, ctx); if (st != PG_OK) return st; }
-  gp.scan.tile_list = lw.tile_list;            // read by group_private_kernel only
-  gp.scan.tile_count = lw.tile_count;
+  if (lw.tile_list != nullptr) { const pg_status st = complete_index_list(&lw, ctx); if (st != PG_OK) return st; }
+  gp.scan.tile_list = lw.tile_list; gp.scan.tile_count = lw.tile_count;            // read by group_private_kernel only
   gp.scan.filter_entries = nullptr;
-  if (r.defer != nullptr && g_engine.batch_group && use_private && gp.use_lds_table && hash_plan.kind == 0 && !first_appearance && !typed_direct && !want_bitmap && out &&
-      lw.tile_list == nullptr && lw.side == nullptr && !lw.stats_leap2_flagged && !lw.stats_chain_flagged && !ctx->pre_enqueued && r.stats_is_final &&
-      (long long)(q->num_groups_limit > 0 ? q->num_groups_limit : 100000) >= product && (r.defer->single || doc_tiles(seg) <= kBatchMaxTiles))
-    return defer_group_item(r, gp, pblocks, pthreads, plds, cards, dev_agg_of, no_dict_keys);
+  return PG_OK;
+}
+// run, 1: the table's identities; PINOT_GPU_PARTITION_TRACE's line
+static pg_status init_group_table(QueryRun& r, const GroupPlan& p) {
+  const pg_segment* seg = r.seg; ExecCtx* ctx = r.ctx; const GroupParams& gp = p.gp;
   HIP_TRY(mark_pre_work(ctx));
-  init_group_table_kernel<<<dim3((unsigned)std::max<long long>(64, std::min<long long>(product >> 12, (long long)seg->num_cus * 16))), dim3(256), 0, ctx->stream>>>(gp);
+  init_group_table_kernel<<<dim3((unsigned)std::max<long long>(64, std::min<long long>(p.product >> 12, (long long)seg->num_cus * 16))), dim3(256), 0, ctx->stream>>>(gp);
   HIP_TRY(hipGetLastError());
-  if (timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-  // Key spaces above the LDS table: partition the docs by key range first, then aggregate every partition in LDS
-  // (pg_group_partition.h) instead of one global atomic per doc and aggregation.
-  const int partition_entry_bytes = 4 + 8 * gp.num_group_aggs;
-  const int partition_shift = partition_entry_bytes <= 20 ? 12 : 11;
-  const long long fine_partitions = (product + (1ll << partition_shift) - 1) >> partition_shift;
-  // More fine partitions than one scatter pass can address (key spaces of 2 M .. 2^31 raw keys): two levels -- pass A scatters by
-  // coarse partition (2^k fine ones each), group_repartition_*_kernel scatter every coarse partition's records by fine partition
-  // (pg_group_partition.h).  PINOT_GPU_PARTITION_TWO_LEVEL=0: such key spaces keep the direct HBM atomics.
-  const bool two_level_on = g_engine.partition_two_level;
-  int log2_fine_per_coarse = 0;
-  while (((fine_partitions + (1ll << log2_fine_per_coarse) - 1) >> log2_fine_per_coarse) > kMaxPartitions) ++log2_fine_per_coarse;
-  const bool two_level = log2_fine_per_coarse > 0;
-  const long long num_partitions = (fine_partitions + (1ll << log2_fine_per_coarse) - 1) >> log2_fine_per_coarse;       // what pass A scatters into
-  const bool use_partition = hash_plan.kind == 0 && !typed_direct && map_based && g_engine.group_partition && g_engine.group_private && private_leaves && gp.dense_ok && !want_bitmap &&
-                             gp.num_group_aggs <= kMaxPartitionAggs && (!two_level || (two_level_on && (1 << log2_fine_per_coarse) <= kMaxFinePerCoarse)) &&
-                             (long long)seg->num_docs >= g_engine.partition_min_docs;
+  if (r.timed) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
   static const bool partition_trace = getenv("PINOT_GPU_PARTITION_TRACE") != nullptr;
   if (partition_trace)
     fprintf(stderr, "group-by plan: product %lld, fine partitions %lld (shift %d), 2^%d per coarse -> %lld scatter partitions; partition %d (hash %d typed_direct %d map_based %d "
-                    "private_leaves %d dense_ok %d aggs %d docs %d packed_bits %d)\n", product, fine_partitions, partition_shift, log2_fine_per_coarse, num_partitions, (int)use_partition,
-            hash_plan.kind, (int)typed_direct, (int)map_based, (int)private_leaves, gp.dense_ok, gp.num_group_aggs, seg->num_docs,
-            use_partition ? partition_packed_bits(gp, partition_shift + log2_fine_per_coarse) : 0);
-  // (group_typed_direct_kernel walks EVERY tile and reads the index AND's bitmap there: the tiles the AND did not list must be zero, not what an
-  //  earlier query of this context left in them -- only group_private_kernel goes by the tile list)
-  if (use_partition || typed_direct || !use_private) { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
+                    "private_leaves %d dense_ok %d aggs %d docs %d packed_bits %d)\n", p.product, p.part.fine_partitions, p.part.shift, p.part.log2_fine_per_coarse, p.part.scatter_partitions,
+            (int)(p.route == GroupRoute::Partition), p.hash_plan.kind, (int)(p.route == GroupRoute::TypedDirect), (int)p.map_based, (int)p.private_leaves, gp.dense_ok, gp.num_group_aggs,
+            seg->num_docs, p.packed_bits);
+  return PG_OK;
+}
+// run, 2: what the filter statistics need of the kernel -- the leaves' outputs for the transducer pass, the leapfrog tables, the entry counter
+static pg_status arm_group_stats(QueryRun& r, GroupPlan* p) {
+  pg_segment* seg = r.seg; pg_result* out = r.out; ExecCtx* ctx = r.ctx; Lowered& lw = r.lw; GroupParams& gp = p->gp; pg_status st = PG_OK;
+  // (every kernel but group_private_kernel walks EVERY tile and reads the index AND's bitmap there: the tiles the AND did not list must be zero,
+  //  not what an earlier query of this context left in them -- only group_private_kernel goes by the tile list.  Not route_writes_leaf_outputs().)
+  if (p->route != GroupRoute::Private) { st = complete_index_and_bitmap(&lw, ctx); if (st != PG_OK) return st; }
   if (lw.side != nullptr) {
-    const bool wrote = ((use_private && !use_partition) || typed_direct) && gp.scan.tile_list == nullptr;
+    const bool wrote = p->route_writes_leaf_outputs() && gp.scan.tile_list == nullptr;
     for (int l = 0; l < kMaxLeaves; ++l) gp.scan.leaf_out[l] = wrote ? lw.sp_leaf_out[l] : nullptr;
     gp.scan.leaf_out_enabled = wrote ? 1 : 0;
     lw.side->kernel_wrote = wrote;
   }
-  const bool count_leap2 = out && lw.stats_leap2_flagged && ((use_private && !use_partition) || typed_direct);
-  const bool count_entries = (out && lw.stats_chain_flagged && ((use_private && !use_partition) || typed_direct)) || count_leap2;
+  const bool count_leap2 = p->count_leap2 = out && lw.stats_leap2_flagged && p->route_writes_leaf_outputs();
+  const bool count_entries = p->count_entries = (out && lw.stats_chain_flagged && p->route_writes_leaf_outputs()) || count_leap2;
   gp.scan.leap_tables = nullptr;
   if (count_leap2) { st = arm_leap_tables(seg, ctx, &gp.scan.leap_tables, &gp.scan.filter_entries); if (st != PG_OK) return st; }
   else if (lw.stats_leap2_flagged) for (int n = 0; n < gp.scan.num_nodes; ++n) gp.scan.nodes[n].flags &= ~kNodeLeapfrog2;
   if (count_entries && !count_leap2) { st = arm_filter_entries(ctx, &gp.scan.filter_entries); if (st != PG_OK) return st; }
-  if (use_partition) { st = run_partitioned_group_by(r, gp, (int)num_partitions, partition_shift, log2_fine_per_coarse); if (st != PG_OK) return st; }
-  else if (typed_direct) launch_group_typed_direct(grid_blocks(seg, doc_tiles(seg), 4, 8, false), ctx->stream, gp);
-  else if (use_private) launch_group_private(gp.use_lds_table != 0, pblocks, pthreads, plds, ctx->stream, gp);
-  else launch_scan_group(g_engine.use_dma, gp.use_lds_table != 0, blocks, geo.threads, lds, ctx->stream, gp);
+  return PG_OK;
+}
+// run, 3: the route's kernel(s), and behind them what the entry count needs on the stream
+static pg_status launch_group_route(QueryRun& r, const GroupPlan& p) {
+  pg_segment* seg = r.seg; ExecCtx* ctx = r.ctx; const GroupParams& gp = p.gp; pg_status st = PG_OK;
+  switch (p.route) {
+    case GroupRoute::Partition: st = run_partitioned_group_by(r, p); if (st != PG_OK) return st; break;
+    case GroupRoute::TypedDirect: launch_group_typed_direct(grid_blocks(seg, doc_tiles(seg), 4, 8, false), ctx->stream, gp); break;
+    case GroupRoute::Private: launch_group_private(gp.use_lds_table != 0, p.pblocks, p.pthreads, p.plds, ctx->stream, gp); break;
+    case GroupRoute::Staged: launch_scan_group(g_engine.use_dma, gp.use_lds_table != 0, p.geo.blocks, p.geo.threads, p.geo.lds, ctx->stream, gp); break;
+  }
   HIP_TRY(hipGetLastError());
-  if (timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-  if (count_leap2) { st = launch_leap_chain(seg, ctx, 0); if (st != PG_OK) return st; }
-  if (count_entries) HIP_TRY(hipMemcpyAsync(ctx->h_filter_entries, ctx->d_filter_entries, 8, hipMemcpyDeviceToHost, ctx->stream));
-  // The groups that exist, in ascending raw-key order
-  PresentGroups found;
-  if (!map_based) {
-    HIP_TRY(hipMemcpyAsync(ctx->h_table, ctx->d_table, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (r.timed) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+  if (p.count_leap2) { st = launch_leap_chain(seg, ctx, 0); if (st != PG_OK) return st; }
+  if (p.count_entries) HIP_TRY(hipMemcpyAsync(ctx->h_filter_entries, ctx->d_filter_entries, 8, hipMemcpyDeviceToHost, ctx->stream));
+  return PG_OK;
+}
+// run, 4: the groups that exist, in ascending raw-key order (hashed holders: in slot order)
+static pg_status harvest_groups(QueryRun& r, const GroupPlan& p, PresentGroups* found_out) {
+  ExecCtx* ctx = r.ctx; const bool timed = r.timed; const GroupParams& gp = p.gp; PresentGroups& found = *found_out;
+  if (!p.map_based) {
+    HIP_TRY(hipMemcpyAsync(ctx->h_table, ctx->d_table, p.table_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (timed) HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const unsigned long long* hc = ctx->h_table;
-    const long long* ha = reinterpret_cast<const long long*>(ctx->h_table + gp.num_groups);
+    const unsigned long long* hc = ctx->h_table; const long long* ha = reinterpret_cast<const long long*>(ctx->h_table + gp.num_groups);
     for (int g = 0; g < gp.num_groups; ++g) if (hc[g]) { found.num_present++; found.docs += (long long)hc[g]; }
-    found.ids.reserve((size_t)found.num_present); found.counts.reserve((size_t)found.num_present);
-    found.acc.resize((size_t)found.num_present * (size_t)gp.num_group_aggs);
+    found.ids.reserve((size_t)found.num_present); found.counts.reserve((size_t)found.num_present); found.acc.resize((size_t)found.num_present * (size_t)gp.num_group_aggs);
     int k = 0;
     for (int g = 0; g < gp.num_groups; ++g) {
       if (!hc[g]) continue;
@@ -4759,20 +4768,18 @@ static pg_status run_group_by(QueryRun& r) {
       k++;
     }
   } else {
-    st = compact_map_groups(r, gp, hash_plan, product, use_private, pblocks, pthreads, plds, &found); if (st != PG_OK) return st;
+    const pg_status st = compact_map_groups(r, p, &found); if (st != PG_OK) return st;
   }
   if (!found.ids_of) { found.ids_of = found.ids.data(); found.counts_of = found.counts.data(); found.acc_of = found.acc.data(); }
-  // hashed holders / no-dictionary generators: group_id_upper_bound = numGroupsLimit, like the reference (:150-163).  The keys come as dictId
-  // tuples for every kind of holder (what GroupKeyGenerator.getGroupKeys turns into values); rows in ascending raw-key order.  Hashed holders
-  // come out of the table in slot order: `perm` sorts them.
-  start_group_result(out, na, ng, found.num_present, use_partition ? PG_KERNEL_GROUP_PARTITION : (use_private ? PG_KERNEL_GROUP_PRIVATE : PG_KERNEL_SCAN_GROUP),
-                     (hash_plan.kind != 0 || no_dict_keys) ? (q->num_groups_limit > 0 ? q->num_groups_limit : 100000) : gp.num_groups, hash_plan.kind);
-  std::vector<int> perm;
+  return PG_OK;
+}
+// result, 1: the header, and the keys as dictId tuples for every kind of holder (what GroupKeyGenerator.getGroupKeys turns into values); rows in ascending raw-key order.
+// hashed holders / no-dictionary generators: group_id_upper_bound = numGroupsLimit, like the reference (:150-163); out of the table in slot order, `perm` sorts them.
+static void decode_group_keys(QueryRun& r, const GroupPlan& p, const PresentGroups& found, std::vector<int>* perm_out) {
+  pg_result* out = r.out; const int ng = r.ng; const HashPlan& hash_plan = p.hash_plan; const std::vector<int>& cards = p.cards; std::vector<int>& perm = *perm_out;
+  start_group_result(out, r.na, ng, found.num_present, p.kernel_id(), (hash_plan.kind != 0 || p.no_dict_keys) ? groups_limit(r.q) : p.gp.num_groups, hash_plan.kind);
   if (hash_plan.kind == 0) {
-    for (int k = 0; k < found.num_present; ++k) {
-      long long raw = found.ids_of[(size_t)k];
-      for (int g = 0; g < ng; ++g) { out->group_key_dict_ids[(size_t)k * (size_t)ng + (size_t)g] = (int32_t)(raw % cards[(size_t)g]); raw /= cards[(size_t)g]; }
-    }
+    for (int k = 0; k < found.num_present; ++k) decode_mixed_radix(found.ids_of[(size_t)k], cards, ng, out->group_key_dict_ids + (size_t)k * (size_t)ng);
   } else {
     std::vector<int32_t> tuples((size_t)found.num_present * (size_t)ng);
     for (int k = 0; k < found.num_present; ++k) {
@@ -4802,8 +4809,11 @@ static pg_status run_group_by(QueryRun& r) {
       if (hash_plan.kind == 1) out->group_ids64[k] = (int64_t)found.hash_keys[(size_t)src];
     }
   }
-  // Turning accumulators into the reference's holder values is independent per group: large results (the IntMapBasedHolder range
-  // returns up to numGroupsLimit rows) are converted by a few host threads, each touching its own pages of the result.
+}
+// result, 2: the rows' holder values, and the statistics.  Turning accumulators into the reference's holder values is independent per group: large results
+// (the IntMapBasedHolder range returns up to numGroupsLimit rows) are converted by a few host threads, each touching its own pages of the result.
+static void convert_group_rows(QueryRun& r, const GroupPlan& p, const PresentGroups& found, const std::vector<int>& perm) {
+  const pg_segment* seg = r.seg; const pg_query* q = r.q; pg_result* out = r.out; ExecCtx* ctx = r.ctx; const Lowered& lw = r.lw; const int na = r.na; const std::vector<int>& dev_agg_of = p.dev_agg_of;
   auto convert_groups = [&](int k_begin, int k_end) {
   for (int k = k_begin; k < k_end; ++k) {
     const int src = perm.empty() ? k : perm[(size_t)k];       // the row of the compacted table behind result row k
@@ -4815,22 +4825,7 @@ static pg_status run_group_by(QueryRun& r) {
       empty_agg_value(&v, (int64_t)group_docs);
       if (ag.function == PG_AGG_COUNT) continue;
       const long long acc = found.acc_of[(size_t)dev_agg_of[(size_t)a] * (size_t)found.num_present + (size_t)src];
-      const ColumnDev& col = seg->cols[(size_t)ag.column];
-      const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
-      if (ag.function == PG_AGG_SUM || ag.function == PG_AGG_AVG) {
-        if (col.vkind == kValF64 || col.vkind == kValF32) {
-          memcpy(&v.sum, &acc, 8);          // the slot accumulated doubles (ds_add_f64 / global_atomic_add_f64)
-          v.sum_i64 = 0;
-          v.sum_exact = 0;
-        } else {
-          set_integer_sum(&v, (__int128)acc * (__int128)sum_scale(col, plane) + (__int128)group_docs * (__int128)sum_base(col, plane));
-        }
-      }
-      else if (col.encoding == PG_FWD_RAW_FIXED_BYTE && col.vkind != kValI32) {      // raw LONG value, or the order key of a raw FLOAT / DOUBLE value
-        if (ag.function == PG_AGG_MIN) v.min = group_key64_to_double(col, acc, true); else v.max = group_key64_to_double(col, acc, false);
-      }
-      else if (ag.function == PG_AGG_MIN) v.min = group_dict_min_double(col, (int32_t)acc, plane);
-      else v.max = agg_value_double(col, (int32_t)acc, plane);
+      group_agg_value(seg, ag, lw.plane_cols[(size_t)ag.column] != 0, acc, group_docs, &v);
     }
   }
   };
@@ -4845,9 +4840,30 @@ static pg_status run_group_by(QueryRun& r) {
     for (auto& w : workers) w.join();
   }
   out->stats.num_docs_scanned = found.docs;
-  finish_filter_stats(lw, seg, count_entries ? (int64_t)*ctx->h_filter_entries : 0, count_entries, out);
+  finish_filter_stats(lw, seg, p.count_entries ? (int64_t)*ctx->h_filter_entries : 0, p.count_entries, out);
   out->stats.num_entries_scanned_post_filter = found.docs * (int64_t)r.projected.size();
   out->stats.num_total_docs = seg->num_docs;
+}
+// DictionaryBasedGroupKeyGenerator's holders: plan (GroupPlan), then either hand the query to a batch's shared launch or run its route and
+// turn the table into the result.
+static pg_status run_group_by(QueryRun& r) {
+  GroupPlan p; PresentGroups found; std::vector<int> perm; pg_status st = PG_OK;
+  // a table of the upper IntMapBasedHolder range goes back to the allocator with the query.  (Armed before lay_out_group_table, the only caller of
+  // ensure_table, so that every exit behind the allocation trims: no table above the bound outlives its query, and the guard finds none on entry.)
+  struct TableTrim {
+    ExecCtx* c;
+    ~TableTrim() { if (c->table_capacity * 8 > kGroupTableKeepBytes) { (void)hipFree(c->d_table); c->d_table = nullptr; c->table_capacity = 0; } }
+  } table_trim{r.ctx};
+  if ((st = bind_group_keys(r, &p)) != PG_OK || (st = bind_group_aggs(r, &p)) != PG_OK || (st = lay_out_group_table(r, &p)) != PG_OK ||
+      (st = choose_group_route(r, &p)) != PG_OK || (st = size_group_launch(r, &p)) != PG_OK) return st;
+  const Lowered& lw = r.lw;
+  if (r.defer != nullptr && g_engine.batch_group && p.private_sized() && p.gp.use_lds_table && p.hash_plan.kind == 0 && !p.first_appearance && !r.want_bitmap && r.out &&
+      lw.tile_list == nullptr && lw.side == nullptr && !lw.stats_leap2_flagged && !lw.stats_chain_flagged && !r.ctx->pre_enqueued && r.stats_is_final &&
+      (long long)groups_limit(r.q) >= p.product && (r.defer->single || doc_tiles(r.seg) <= kBatchMaxTiles))
+    return defer_group_item(r, p);
+  if ((st = init_group_table(r, p)) != PG_OK || (st = arm_group_stats(r, &p)) != PG_OK || (st = launch_group_route(r, p)) != PG_OK || (st = harvest_groups(r, p, &found)) != PG_OK) return st;
+  decode_group_keys(r, p, found, &perm);
+  convert_group_rows(r, p, found, perm);
   return PG_OK;
 }
 // The query's device time (PG_CFG_TIME_KERNELS) and the transducer pass behind its kernels
@@ -5130,7 +5146,7 @@ static pg_status execute_null_handling(pg_segment* seg, const pg_query* q, pg_re
       // numGroupsLimit binds at any key-space size here (NoDictionary*GroupKeyGenerator: _globalGroupIdUpperBound = numGroupsLimit)
       long long product = 1;
       for (int g = 0; g < ng; ++g) product *= std::max(seg->cols[(size_t)keys[(size_t)g]].cardinality, 1);
-      const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
+      const long long limit = groups_limit(q);
       if (limit < product) base.q.flags |= kQueryHashHolder;
     }
     if (lane_cols.empty()) return execute_impl(seg, &base.q, out, nullptr, nullptr, 0, nullptr);
@@ -5691,7 +5707,7 @@ static pg_status plan_pass_keys(const pg_segment* seg, const pg_query* q, const 
   if (hash_plan.kind != 0) return fail(PG_ERR_UNSUPPORTED, "%s grouped over a key space of kind %d (raw keys beyond an int: the hashed holders) -- CPU plan", who, hash_plan.kind);
   *product = 1;
   for (int card : cards) *product *= (unsigned long long)std::max(card, 1);
-  const long long limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
+  const long long limit = groups_limit(q);
   if (*product > (unsigned long long)limit)
     return fail(PG_ERR_UNSUPPORTED, "%s grouped over %llu raw keys, above numGroupsLimit %lld (the limit could bind) -- CPU plan", who, *product, limit);
   return PG_OK;

@@ -49,22 +49,23 @@ SEED_BASE = F.SEED_BASE
 SEEDS = list(range(24))
 SIZES = [1, 2047, 2049, 8191, 8192, 8193, 20_011, 65_535, 65_537, 70_001, 131_073, 140_000]
 
-# the planner's arithmetic, mirrored (pg_engine.hip run_group_by "Key spaces above the LDS table", :4672-4685; pg_device.h :405-435)
-ARRAY_BASED_THRESHOLD = F.ARRAY_BASED_THRESHOLD   # pg_engine.hip:4508  map_based = product > 10000 || first_appearance
-DEFAULT_GROUPS_LIMIT = F.DEFAULT_GROUPS_LIMIT     # pg_engine.hip:4507  num_groups_limit > 0 ? num_groups_limit : 100000
-MAX_PARTITIONS = 512                              # pg_device.h:405     kMaxPartitions
-MAX_PARTITION_AGGS = 3                            # pg_device.h:407     kMaxPartitionAggs
-MAX_FINE_PER_COARSE = 1024                        # pg_device.h:434     kMaxFinePerCoarse
-REPARTITION_CHUNK = 1 << 16                       # pg_device.h:435     kRepartitionChunk
-SCATTER_ROUND_DOCS = 8192                         # pg_group_partition.h:83 kScatterDocsPerRound
+# the planner's arithmetic, mirrored (pg_group_plan.h partition_plan, the limits of pg_device.h; tests/test_group_plan_cpu.py holds `plan` and
+# the four partition limits below against the header's stand-alone check)
+ARRAY_BASED_THRESHOLD = F.ARRAY_BASED_THRESHOLD   # pg_engine.hip bind_group_keys  map_based = product > 10000 || first_appearance
+DEFAULT_GROUPS_LIMIT = F.DEFAULT_GROUPS_LIMIT     # pg_engine.hip groups_limit     num_groups_limit > 0 ? num_groups_limit : 100000
+MAX_PARTITIONS = 512                              # pg_device.h         kMaxPartitions
+MAX_PARTITION_AGGS = 3                            # pg_device.h         kMaxPartitionAggs
+MAX_FINE_PER_COARSE = 1024                        # pg_device.h         kMaxFinePerCoarse
+REPARTITION_CHUNK = 1 << 16                       # pg_device.h         kRepartitionChunk
+SCATTER_ROUND_DOCS = 8192                         # pg_group_partition.h kScatterDocsPerRound
 TILE_DOCS = 2048
-WIDE_KEYS = 1 << 24                               # pg_engine.hip:4537  gp.wide_keys = product > (1ll << 24)
+WIDE_KEYS = 1 << 24                               # pg_engine.hip bind_group_aggs  gp.wide_keys = product > (1ll << 24)
 SCATTER_KERNEL = "group_partition_scatter_kernel"
 
 
 def plan(product, accumulators):
     """(shift, fine partitions, log2_fine_per_coarse, scatter partitions) of a key space: entry bytes = 4 + 8 x accumulators; shift 12
-    when the entry is at most 20 bytes, else 11 (pg_engine.hip:4672-4673); one level up to 512 partitions (:4679-4682)."""
+    when the entry is at most 20 bytes, else 11; one level up to 512 partitions (pg_group_plan.h partition_plan)."""
     entry_bytes = 4 + 8 * accumulators
     shift = 12 if entry_bytes <= 20 else 11
     fine = (product + (1 << shift) - 1) >> shift
@@ -187,7 +188,7 @@ def _key_column(rng, name, kind, card, digits):
 
 
 def _plane_bits(values):
-    """compute_plane_shape (pg_engine.hip:739-760): the width of the gcd-scaled offset field of an INT dictionary."""
+    """compute_plane_shape (pg_engine.hip): the width of the gcd-scaled offset field of an INT dictionary."""
     v = np.asarray(values, dtype=np.int64)
     g = int(np.gcd.reduce(v - v[0])) or 1
     top, w = int(v[-1] - v[0]) // g, 1
@@ -288,7 +289,7 @@ class GroupInfo:
     NULL digit; `accumulators`: distinct (column, SUM | MIN | MAX) pairs of the launch that decides the groups (under null handling the
     aggregations over nullable columns run in lanes of their own: execute_null_handling, pg_engine.hip); `klass`: lds / one-level /
     two-level / wide; `shift`, `log2_fine_per_coarse`; `map_based`; `int32_inputs`; `packed_bits` (0: separate key / value columns);
-    `partitionable`: what PINOT_GPU_GROUP_PARTITION=force partitions (run_group_by's use_partition, with every filter leaf lane-private
+    `partitionable`: what PINOT_GPU_GROUP_PARTITION=force partitions (choose_group_route's use_partition, with every filter leaf lane-private
     as they all are here).  `lane_plans`: (partitionable, log2_fine_per_coarse) of every launch the query is answered from -- one, or under
     null handling the base lane and one lane per nullable aggregated column; Result.dominant_kernel is the kernel of the lane whose
     kernel ran longest, a measured time, so it can be foretold only where the lanes agree."""
@@ -327,13 +328,13 @@ def key_cards(seg, fq):
 
 def _int32_domain(col, kind):
     """An accumulator the 32-bit record format holds: MIN / MAX of any dictionary column fold dictIds; a SUM needs INT values, or a LONG
-    dictionary whose range fits 31 bits (an offset dictionary: the 32-bit machinery applies to value - min, pg_engine.hip:2262-2267)."""
+    dictionary whose range fits 31 bits (an offset dictionary: the 32-bit machinery applies to value - min, pg_segment_open in pg_engine.hip)."""
     if col.kind == F.RAW_INT or col.kind == F.DICT_INT or (kind != "sum" and col.is_dict):
         return True
     return col.kind == F.DICT_LONG and int(col.dict_values[-1]) - int(col.dict_values[0]) < 2 ** 31
 
 
-LDS_TABLE_BYTES = 96 * 1024                       # pg_engine.hip:4610  in_lds = table_bytes <= 96 * 1024 (group_private_kernel's LDS table)
+LDS_TABLE_BYTES = 96 * 1024                       # pg_engine.hip size_group_launch  in_lds = table_bytes <= 96 * 1024 (group_private_kernel's LDS table)
 
 
 def _lane_plan(seg, product, map_based, accumulators):

@@ -667,6 +667,35 @@ def test_items_with_dictid_sets_share_the_launch_of_their_kind():
         assert largest.get(name, 0) >= items - 2, (name, largest, proc.stderr[-1500:])
 
 
+def test_the_shared_group_by_launch_converts_every_kind_of_holder_value():
+    """The rows of a group-by that took the shared launch are converted by the item's own closure (defer_group_item), through the same
+    group_agg_value as pg_execute's rows after the zero-identity bias of MIN / MAX is removed.  tools/batch_group_probe.py pins what that
+    closure can be asked for: COUNT, SUM, MIN, MAX and AVG over a plane-encoded and over a plain dictionary column, keyed by a dictionary
+    column and by a raw INT column with numGroupsLimit above its key space -- 3 segments of 5000 docs, 1000 groups, against the oracle and
+    pg_execute.  PINOT_GPU_BATCH_TRACE says that all three items of every call shared one group-by launch."""
+    import json
+    import re
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PINOT_GPU_BATCH_TRACE="1")
+    proc = subprocess.run([sys.executable, os.path.join(root, "tools", "batch_group_probe.py")], capture_output=True, text=True, env=env, timeout=300)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    report = json.loads(proc.stdout.strip().splitlines()[-1])
+    assert report["failed"] == [], report["failed"][:10]
+    assert sorted(report["shapes"]) == ["dictionary-key", "raw-int-key", "raw-int-key-filtered"]
+    shape, launches = None, {}
+    for line in proc.stderr.splitlines():
+        if line.startswith("== shape "):
+            shape = line[len("== shape "):]
+        m = re.search(r"deferred group-by launch on device \d+: (\d+) items", line)
+        if m and shape:
+            launches.setdefault(shape, []).append(int(m.group(1)))
+    for name, items in report["shapes"].items():
+        # both calls: one launch with every item (a pg_execute of the probe may take the one-item form of the same launch)
+        assert [k for k in launches.get(name, []) if k > 1] == [items, items], (name, launches, proc.stderr[-1500:])
+
+
 @pytest.mark.parametrize("bits", [1, 2, 5, 6, 9, 10, 13, 16])
 def test_one_in_list_in_front_of_one_column_alone_and_in_a_batch(engine, bits):
     """`SUM(v) ... WHERE f IN (...)` / `NOT IN (...)` has scan_simple_kernel's shape: alone it takes scan_simple_set_kernel, as items of a batch
