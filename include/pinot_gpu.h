@@ -57,7 +57,8 @@ extern "C" {
                             *    (still 5) PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns, pg_result_value_counts: no struct layout changed, one function added;
                             *    (still 5) PG_DISTINCT_LDS_MAX_DICT_IDS: a diagnostic constant beside PG_PERCENTILE_LDS_MAX_COUNTERS, nothing else;
                             *    (still 5) PG_AGG_DISTINCTCOUNTHLL / PG_AGG_HLL(log2m), pg_result_hll_registers: no struct layout changed, one enumerator and one function added;
-                            *    (still 5) PG_STAGED_SET_LDS_WORDS: a diagnostic constant beside PG_DISTINCT_LDS_MAX_DICT_IDS, nothing else */
+                            *    (still 5) PG_STAGED_SET_LDS_WORDS: a diagnostic constant beside PG_DISTINCT_LDS_MAX_DICT_IDS, nothing else;
+                            *    (still 5) LZ4 / SNAPPY chunks behind PG_FWD_RAW_FIXED_BYTE, PG_CHUNK_DECODE_MAX_BYTES (a diagnostic constant): no struct layout changed, no function added */
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -81,7 +82,11 @@ typedef enum pg_data_type {
 /* Forward-index encodings (segl/segment/index/forward/ForwardIndexReaderFactory.java:75-117). */
 typedef enum pg_fwd_encoding {
   PG_FWD_FIXED_BIT_DICT = 0,   /* FixedBitSVForwardIndexReaderV2: big-endian MSB-first bit-packed dictIds, no header */
-  PG_FWD_RAW_FIXED_BYTE = 1    /* FixedByteChunkSVForwardIndexReader, PASS_THROUGH: chunk header + big-endian values */
+  PG_FWD_RAW_FIXED_BYTE = 1    /* FixedByteChunkSVForwardIndexReader (versions 1 to 4): chunk header + offset table + big-endian values.  The codec is read from
+                                * the file's header, as the reference does: PASS_THROUGH chunks are resident as they are; LZ4 and SNAPPY chunks (version 1:
+                                * always SNAPPY) are decoded once by pg_segment_open into the same dense value area and only that stays resident --
+                                * afterwards the column is the PASS_THROUGH column of the same values.  ZSTANDARD, GZIP and LZ4_LENGTH_PREFIXED:
+                                * PG_ERR_UNSUPPORTED.  A malformed header, offset table or chunk: PG_ERR_INVALID_ARGUMENT. */
 } pg_fwd_encoding;
 
 typedef struct pg_config {
@@ -216,14 +221,14 @@ typedef enum pg_agg_function {
                                 * pg_agg_value.count = the set's cardinality, sum = 0, sum_exact = 0, min = +inf, max = -inf; the set itself comes
                                 * from pg_result_distinct_dict_ids.  No filter (or one that matches everything), no GROUP BY, every function
                                 * answerable that way: the whole dictionary, nothing scanned (NonScanBasedAggregationOperator.java:106-112).
-                                * On a raw (PG_FWD_RAW_FIXED_BYTE, uncompressed) INT / LONG / FLOAT / DOUBLE column, under PINOT_GPU_COLLECT=1 (without the
+                                * On a raw (PG_FWD_RAW_FIXED_BYTE) INT / LONG / FLOAT / DOUBLE column, under PINOT_GPU_COLLECT=1 (without the
                                 * switch such a column is PG_ERR_UNSUPPORTED at plan time): the set of the matching docs' VALUES
                                 * (the Int / Long / Float / DoubleOpenHashSet), always scanned; pg_agg_value.count = the distinct values, the set comes
                                 * from pg_result_value_counts (the run values; pg_result_distinct_dict_ids answers PG_ERR_INVALID_ARGUMENT).
                                 * PG_ERR_UNSUPPORTED at plan time: PG_QUERY_NULL_HANDLING when the column carries a null vector; a
                                 * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four DISTINCTCOUNT columns; raw and
-                                * dictionary DISTINCTCOUNT columns in one query; a raw column's lists above PG_COLLECT_MAX_BYTES (STRING / BYTES and chunk-
-                                * compressed raw columns are never resident: pg_segment_open declines them); GROUP BY
+                                * dictionary DISTINCTCOUNT columns in one query; a raw column's lists above PG_COLLECT_MAX_BYTES (STRING / BYTES raw
+                                * columns are never resident: pg_segment_open declines them; LZ4 / SNAPPY chunks are decoded at open); GROUP BY
                                 * unless group_key_kind is 0, group_id_upper_bound <= numGroupsLimit (the limit can never bind), the keys are
                                 * dictionary columns or raw INT / LONG columns keyed by offset, without null docs under PG_QUERY_NULL_HANDLING,
                                 * at most four of them, and the bit matrices fit PG_DISTINCT_GROUP_MAX_BYTES. */
@@ -233,13 +238,13 @@ typedef enum pg_agg_function {
                                 * pg_agg_value.count = the docs aggregated (the list's length), sum = 0, sum_exact = 0, min = +inf, max = -inf; the list
                                 * comes from pg_result_percentile_counts.  No metadata fast path: the reference scans even without a filter, and
                                 * numEntriesScannedPostFilter = docs scanned x the distinct columns the whole query projects.
-                                * On a raw (PG_FWD_RAW_FIXED_BYTE, uncompressed) INT / LONG / FLOAT / DOUBLE column, under PINOT_GPU_COLLECT=1 (without the
+                                * On a raw (PG_FWD_RAW_FIXED_BYTE) INT / LONG / FLOAT / DOUBLE column, under PINOT_GPU_COLLECT=1 (without the
                                 * switch such a column is PG_ERR_UNSUPPORTED at plan time): the same list as sorted (value,
                                 * count) runs from pg_result_value_counts (pg_result_percentile_counts answers PG_ERR_INVALID_ARGUMENT).
                                 * PG_ERR_UNSUPPORTED at plan time: PG_QUERY_NULL_HANDLING when the column carries a null vector; a
                                 * range predicate on a raw LONG / FLOAT / DOUBLE column beside it; more than four PERCENTILE columns; raw and
-                                * dictionary PERCENTILE columns in one query; a raw column's lists above PG_COLLECT_MAX_BYTES (STRING / BYTES and chunk-
-                                * compressed raw columns are never resident: pg_segment_open declines them); a
+                                * dictionary PERCENTILE columns in one query; a raw column's lists above PG_COLLECT_MAX_BYTES (STRING / BYTES raw
+                                * columns are never resident: pg_segment_open declines them; LZ4 / SNAPPY chunks are decoded at open); a
                                 * PG_AGG_DISTINCTCOUNT in the same query; GROUP BY outside the conditions PG_AGG_DISTINCTCOUNT sets, or counter
                                 * matrices above PG_PERCENTILE_GROUP_MAX_BYTES. */
   PG_AGG_DISTINCTCOUNTHLL = 7  /* DistinctCountHLLAggregationFunction.java: the HyperLogLog sketch of the matching docs' values -- 2^log2m registers of one
@@ -252,7 +257,7 @@ typedef enum pg_agg_function {
                                 * shared with a DISTINCTCOUNT and with HLLs of other log2m on the same column), folded into registers on the device
                                 * (hll_fold_kernel: the reference's convertToHyperLogLog); only the register rows are copied.  No filter (or one that
                                 * matches everything), no GROUP BY, every function answerable from metadata: the whole dictionary is folded, nothing scanned.
-                                * On a raw (PG_FWD_RAW_FIXED_BYTE, uncompressed) INT / LONG / FLOAT / DOUBLE column: one pass of scan_hll_kernel /
+                                * On a raw (PG_FWD_RAW_FIXED_BYTE) INT / LONG / FLOAT / DOUBLE column: one pass of scan_hll_kernel /
                                 * group_hll_kernel, always scanned, no PINOT_GPU_COLLECT and no sort.  Hashed is the value as stored: FLOAT by its 32 bits.
                                 * PG_ERR_UNSUPPORTED at plan time: everything PG_AGG_DISTINCTCOUNT names; raw and dictionary HLL columns in one query; a raw
                                 * HLL beside any DISTINCTCOUNT (it would need a second pass); any HLL beside a PERCENTILE; more than four (column, log2m) pairs; registers of the raw form beyond the LDS
@@ -287,6 +292,10 @@ typedef enum pg_agg_function {
 /* Diagnostics: the 32-bit words of a workgroup's LDS that hold the dictId sets of a filter's IN / NOT IN leaves when they are staged there
  * (PINOT_GPU_SET_LDS, on by default): the "2048 fewer" above, and the room scan_hll_kernel needs beside its registers behind such a leaf. */
 #define PG_STAGED_SET_LDS_WORDS 2048
+/* Diagnostics: the largest decoded chunk (numDocsPerChunk x sizeOfEntry bytes) of an LZ4 / SNAPPY raw forward index that chunk_decode_kernel
+ * builds in LDS; files with larger chunks (a hand-set targetDocsPerChunk), and every file under PINOT_GPU_CHUNK_DECODE=host, are decoded on
+ * the host at pg_segment_open and uploaded as values.  The resident column is the same either way. */
+#define PG_CHUNK_DECODE_MAX_BYTES 65536
 
 typedef struct pg_aggregation {
   int32_t function;            /* pg_agg_function */

@@ -128,6 +128,13 @@ void ph_raw_write_fixed_v2(const void* values, int32_t num_docs, int32_t num_doc
 int64_t ph_roaring_serialize(const int32_t* sorted_doc_ids, int64_t n, int32_t run_optimize, uint8_t* out);     /* out NULL: size only */
 int64_t ph_inverted_build(const int32_t* dict_ids, int32_t num_docs, int32_t cardinality, int32_t run_optimize, uint8_t* out);
 
+/* ---- chunk-compressed raw forward indexes (pinot_amd/csrc/pg_chunk_codec.h: the parsers the device kernel shares, and the host decoder) ----
+ * codec: ChunkCompressionType value, 1 SNAPPY | 3 LZ4.  ph_chunk_decode: one chunk into exactly `expect` bytes; 1 when it decoded to exactly
+ * that size, otherwise the parser's error code (2..10).  ph_raw_decode_file: a whole version 1..4 file of num_docs docs into its
+ * num_docs * sizeOfEntry big-endian value bytes; 0 ok, 1 header / offset table rejected, 2 codec not decoded, 3 malformed chunk. */
+int32_t ph_chunk_decode(int32_t codec, const uint8_t* src, uint32_t size, uint8_t* dst, uint32_t expect);
+int32_t ph_raw_decode_file(const uint8_t* file, uint64_t size, int64_t num_docs, uint8_t* out_values);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@
  *
  * <p>What reaches the device per column (pg_column_desc, include/pinot_gpu.h:88-105): single-value columns of stored type INT / LONG /
  * FLOAT / DOUBLE with a dictionary (fixed-bit forward index + big-endian dictionary file, + the bitmap inverted index and the null value
- * vector when they exist) or raw (PASS_THROUGH fixed-byte chunks); STRING columns with a dictionary travel as their dictIds under a
+ * vector when they exist) or raw (fixed-byte chunks, PASS_THROUGH or compressed with LZ4 / SNAPPY -- the defaults of every raw DIMENSION,
+ * TIME and DATE_TIME column; the device decodes them when the segment is opened); STRING columns with a dictionary travel as their dictIds under a
  * placeholder dictionary {0..cardinality-1} (their values never reach the device: predicates are lowered to dictIds here, group keys
  * are mapped back through the Java dictionary).  Sorted columns store [start, end] docId pairs instead of a dictId per doc
  * (SortedIndexReaderImpl): the fixed-bit stream the device scans is packed here from those pairs, in the layout of
@@ -297,9 +298,12 @@ final class GpuSegment implements Closeable {
             dict = new long[]{PinotGpuNative.directBufferAddress(placeholder), placeholder.capacity()};
           }
         } else {
-          if (forwardIndex.getCompressionType() != ChunkCompressionType.PASS_THROUGH) {
-            continue;                                            // compressed raw chunks are decoded on the CPU plan
+          ChunkCompressionType compression = forwardIndex.getCompressionType();
+          if (compression != ChunkCompressionType.PASS_THROUGH && compression != ChunkCompressionType.LZ4
+              && compression != ChunkCompressionType.SNAPPY) {
+            continue;                                            // ZSTANDARD / GZIP / LZ4_LENGTH_PREFIXED chunks are decoded on the CPU plan
           }
+          // LZ4 and SNAPPY chunks travel as they are: pg_segment_open reads the codec from the file's header and decodes them on the device
           encoding = FWD_RAW_FIXED_BYTE;
           fwd = addressOf(reader.getIndexFor(column, StandardIndexes.forward()));
         }

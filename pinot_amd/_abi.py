@@ -45,6 +45,7 @@ PG_COLLECT_MAX_BYTES = 1 << 30               # PERCENTILE / DISTINCTCOUNT on raw
 PG_PERCENTILE_LDS_MAX_COUNTERS = 39036      # scan_counts_kernel's LDS tier without a staged filter set (with one: kSetLdsWords = 2048 fewer)
 PG_DISTINCT_LDS_MAX_DICT_IDS = 1277952      # scan_distinct_kernel's LDS tier without a staged filter set (with one: 65536 dictIds fewer)
 PG_STAGED_SET_LDS_WORDS = 2048              # the 32-bit words of LDS a filter's staged dictId sets take (scan_hll_kernel: beside its registers)
+PG_CHUNK_DECODE_MAX_BYTES = 65536          # the largest decoded chunk of an LZ4 / SNAPPY raw forward index that is decoded on the device (larger ones: on the host, at open)
 PG_CFG_TIME_KERNELS = 1
 PG_CFG_PROFILE_WAVES = 2
 

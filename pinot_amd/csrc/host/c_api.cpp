@@ -10,6 +10,7 @@
 #include "pinot_host.h"
 #include "../pg_raw_set_table.h"
 #include "../pg_hll.h"
+#include "../pg_chunk_codec.h"
 
 using namespace pinot;
 
@@ -827,5 +828,33 @@ int32_t ph_value_set_from_device(int32_t stored_type, const int64_t* value_bits,
 // GroupByUtils.getTableCapacity / getIndexedTableTrimThreshold (core/util/GroupByUtils.java:48-73)
 int32_t ph_group_by_table_capacity(int32_t limit, int32_t min_num_groups) { return GroupByUtils::getTableCapacity(limit, min_num_groups); }
 int32_t ph_group_by_trim_threshold(int32_t trim_size, int32_t trim_threshold) { return GroupByUtils::getIndexedTableTrimThreshold(trim_size, trim_threshold); }
+
+// The host decoder of pg_chunk_codec.h (what pg_segment_open runs under PINOT_GPU_CHUNK_DECODE=host and for chunks above the device cap; the device
+// kernel walks the same parsers).  codec: ChunkCompressionType value, 1 SNAPPY | 3 LZ4; `dst` has exactly `expect` bytes.  Returns 1 (pgcodec::kEnd)
+// when the chunk decoded to exactly `expect` bytes, otherwise the parser's error code (2..10).
+int32_t ph_chunk_decode(int32_t codec, const uint8_t* src, uint32_t size, uint8_t* dst, uint32_t expect) {
+  return pgcodec::decode_chunk_host(codec, src, size, dst, expect);
+}
+// A whole LZ4 / SNAPPY fixed-byte chunk file (versions 1 to 4) of `num_docs` docs -> its num_docs * sizeOfEntry value bytes, big-endian as stored.
+// Returns 0; 1: the header or the offset table fails the checks made before any chunk is decoded (ph_last_error says which); 2: a codec that is
+// not decoded here; 3: a malformed chunk.
+int32_t ph_raw_decode_file(const uint8_t* file, uint64_t size, int64_t num_docs, uint8_t* out_values) {
+  pgcodec::ChunkFile cf;
+  int r = pgcodec::parse_chunk_header(file, size, &cf);
+  if (r == pgcodec::kFileOk && cf.codec != pgcodec::kLz4 && cf.codec != pgcodec::kSnappy) {
+    g_hostError = std::string("compressionType ") + pgcodec::codec_name(cf.codec) + " is not decoded";
+    return 2;
+  }
+  if (r == pgcodec::kFileOk) r = pgcodec::validate_chunk_table(cf, file, size, num_docs);
+  if (r != pgcodec::kFileOk) {
+    g_hostError = r == pgcodec::kFileBadOffsets ? "chunk offsets decrease or point outside the file" : r == pgcodec::kFileBadChunkCount ? "numChunks does not match numDocs and numDocsPerChunk"
+                  : r == pgcodec::kFileTruncated ? "header or offset table truncated" : "bad header";
+    return 1;
+  }
+  int bad = 0;
+  r = pgcodec::decode_file_host(cf, file, size, num_docs, out_values, &bad);
+  if (r != pgcodec::kEnd) { g_hostError = "chunk " + std::to_string(bad) + " is malformed (error " + std::to_string(r) + ")"; return 3; }
+  return 0;
+}
 
 }  // extern "C"

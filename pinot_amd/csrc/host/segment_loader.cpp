@@ -24,6 +24,7 @@
 #include <sstream>
 
 #include "pinot_host.h"
+#include "../pg_chunk_codec.h"
 
 namespace pinot {
 
@@ -268,7 +269,15 @@ std::unique_ptr<ImmutableSegment> loadSegmentDirectory(const std::string& indexD
       if (ds.dataType == DataType::STRING) { skip("raw STRING column"); continue; }
       const Slice fwd = index.get(col, ".sv.raw.fwd", "forward_index", &keep);
       if (!fwd.data) { skip("raw forward index not found"); continue; }
-      if (fwd.size >= 28 && beInt(fwd.data + 20) != 0) { skip("compressed raw forward index"); continue; }   // PASS_THROUGH only
+      // PASS_THROUGH chunks are resident as they are; LZ4 and SNAPPY chunks (a version-1 file is always SNAPPY) are decoded by
+      // pg_segment_open into the same value area (pg_chunk_codec.h).  The other codecs need an entropy decoder or are never written here.
+      if (fwd.size >= 28 && beInt(fwd.data) > 1) {
+        const int codec = beInt(fwd.data + 20);
+        if (codec != pgcodec::kPassThrough && codec != pgcodec::kLz4 && codec != pgcodec::kSnappy) {
+          skip(std::string("compressed raw forward index (") + pgcodec::codec_name(codec) + ")");
+          continue;
+        }
+      }
       ds.forwardIndex = fwd.data; ds.forwardIndexSize = fwd.size;
       ds.bitsPerElement = 8 * valueBytes;
       const Slice nulls = index.get(col, ".bitmap.nullvalue", "nullvalue_vector", &keep);

@@ -33,6 +33,7 @@
 #include "pg_hll.h"
 #include "pg_set_pass_layout.h"
 #include "pg_group_plan.h"
+#include "pg_chunk_decode.h"
 
 namespace {
 
@@ -82,6 +83,7 @@ struct Engine {
   bool poll_result = true;   // PINOT_GPU_POLL_RESULT=0: pg_execute always waits with hipStreamSynchronize instead of spinning on the pinned record's sequence number
   bool distinct_lds = true;  // PINOT_GPU_DISTINCT_LDS=0: DISTINCTCOUNT keeps its dictId bitsets in HBM at every cardinality (scan_distinct_kernel<false>; tests of that tier on small dictionaries)
   bool collect = false;        // PINOT_GPU_COLLECT=1: PERCENTILE / DISTINCTCOUNT on raw columns take the collect pass (pg_scan_collect.h); unset: declined as before, the CPU plan keeps them
+  bool chunk_decode_host = false;      // PINOT_GPU_CHUNK_DECODE=host: compressed raw chunks are decoded by the host decoder of pg_chunk_codec.h and uploaded as values (what chunks above PG_CHUNK_DECODE_MAX_BYTES always take)
   bool percentile_lds = true;  // PINOT_GPU_PERCENTILE_LDS=0: PERCENTILE keeps its dictId counters in HBM at every cardinality (scan_counts_kernel<false>; tests of that tier on small dictionaries)
   bool set_lds = true;       // PINOT_GPU_SET_LDS=0: dictId-set leaves (IN lists) of the lane-private scan kernels read their words from memory per doc (rounds 2-6a)
   bool lane_skip = true;     // PINOT_GPU_LANE_SKIP=0: the aggregating kernels load a tile's value bytes for every lane, matches or not
@@ -2031,6 +2033,7 @@ pg_status pg_init(const pg_config* config) {
   g_engine.distinct_lds = env_on("PINOT_GPU_DISTINCT_LDS");
   g_engine.percentile_lds = env_on("PINOT_GPU_PERCENTILE_LDS");
   { const char* cv = getenv("PINOT_GPU_COLLECT"); g_engine.collect = cv != nullptr && cv[0] == '1'; }
+  { const char* cd = getenv("PINOT_GPU_CHUNK_DECODE"); g_engine.chunk_decode_host = cd != nullptr && strcmp(cd, "host") == 0; }
   g_engine.partition_two_level = env_on("PINOT_GPU_PARTITION_TWO_LEVEL");
   g_engine.fsm_perm = env_on("PINOT_GPU_FSM_PERM");
   g_engine.fsm_stats = env_on("PINOT_GPU_FSM_STATS");
@@ -2182,6 +2185,55 @@ pg_status pg_measure_stream_read(int32_t device_id, uint64_t bytes, int32_t laun
   return PG_OK;
 }
 
+// The chunks of an LZ4 / SNAPPY raw forward index (validated: pgcodec::validate_chunk_table) -> `d_values`, the column's dense value area.
+// On the device: the file is uploaded as it is, chunk_decode_kernel decodes every chunk (pg_chunk_decode.h), and the compressed copy is freed
+// before this returns.  Chunks above PG_CHUNK_DECODE_MAX_BYTES (a hand-set targetDocsPerChunk) and everything under PINOT_GPU_CHUNK_DECODE=host
+// take the host decoder of pg_chunk_codec.h and are uploaded as values.
+static pg_status decode_raw_chunks(const pg_segment* seg, const ColumnDev& col, const pgcodec::ChunkFile& cf, const uint8_t* file, uint64_t file_size, uint8_t* d_values) {
+  const uint64_t chunk_bytes = (uint64_t)cf.docs_per_chunk * (uint64_t)cf.entry_size;
+  const uint64_t value_area = (uint64_t)seg->num_docs * (uint64_t)cf.entry_size;
+  auto malformed = [&](int chunk, int code) {
+    return fail(PG_ERR_INVALID_ARGUMENT, "column %s: chunk %d of %d is not a well-formed %s chunk (error %d)", col.name.c_str(), chunk, cf.num_chunks, pgcodec::codec_name(cf.codec), code);
+  };
+  if (g_engine.chunk_decode_host || chunk_bytes > PG_CHUNK_DECODE_MAX_BYTES) {
+    std::vector<uint8_t> values((size_t)value_area);
+    int bad = 0;
+    const int r = pgcodec::decode_file_host(cf, file, file_size, seg->num_docs, values.data(), &bad);
+    if (r != pgcodec::kEnd) return malformed(bad, r);
+    const hipError_t e = h2d_copy(d_values, values.data(), values.size(), phys_device(seg->device));
+    if (e != hipSuccess) return fail(PG_ERR_DEVICE, "column %s: H2D copy: %s", col.name.c_str(), hipGetErrorString(e));
+    return PG_OK;
+  }
+  const size_t status_at = ((size_t)file_size + 8 + 7) / 8 * 8;      // (8 readable bytes behind the file, then the status word)
+  uint8_t* d_file = nullptr;
+  hipError_t e = hipMalloc((void**)&d_file, status_at + 8);
+  if (e != hipSuccess) return fail(PG_ERR_OUT_OF_MEMORY, "column %s: hipMalloc(%zu) for the compressed chunks: %s", col.name.c_str(), status_at + 8, hipGetErrorString(e));
+  unsigned long long status = ~0ull;
+  e = hipMemset(d_file + file_size, 0, status_at - (size_t)file_size);
+  if (e == hipSuccess) e = hipMemcpy(d_file + status_at, &status, 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = h2d_copy(d_file, file, (size_t)file_size, phys_device(seg->device));
+  if (e == hipSuccess) {
+    ChunkDecodeParams p;
+    p.file = d_file; p.file_size = file_size; p.header_start = cf.header_start; p.offset_bytes = cf.offset_bytes; p.num_chunks = cf.num_chunks;
+    p.chunk_bytes = (unsigned int)chunk_bytes;
+    p.last_chunk_bytes = (unsigned int)pgcodec::chunk_expect_bytes(cf, seg->num_docs, cf.num_chunks - 1);
+    p.lds_stride = (unsigned int)((chunk_bytes + 15) / 16 * 16);
+    p.out = d_values;
+    p.status = reinterpret_cast<unsigned long long*>(d_file + status_at);
+    // as many chunks per workgroup as fit 64 KiB of LDS (at most four), as many workgroups per CU as fit its 160 KiB (at most eight)
+    const int waves = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)kChunkDecodeMaxWaves, (uint64_t)PG_CHUNK_DECODE_MAX_BYTES / p.lds_stride, (uint64_t)cf.num_chunks}));
+    const int per_cu = (int)std::max<uint64_t>(1, std::min<uint64_t>(8, (160u * 1024u) / ((uint64_t)waves * p.lds_stride)));
+    const int blocks = (int)std::min<long long>(((long long)cf.num_chunks + waves - 1) / waves, (long long)seg->num_cus * per_cu);
+    launch_chunk_decode(cf.codec, blocks, waves, 0, p);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(&status, d_file + status_at, 8, hipMemcpyDeviceToHost);      // (waits for the kernel)
+  }
+  (void)hipFree(d_file);
+  if (e != hipSuccess) return fail(PG_ERR_DEVICE, "column %s: chunk decode: %s", col.name.c_str(), hipGetErrorString(e));
+  if (status != ~0ull) return malformed((int)(status >> 8), (int)(status & 255));
+  return PG_OK;
+}
+
 pg_status pg_segment_open(const pg_segment_desc* desc, pg_segment** out_segment) {
   if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
   if (!desc || !out_segment) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
@@ -2285,36 +2337,49 @@ pg_status pg_segment_open(const pg_segment_desc* desc, pg_segment** out_segment)
       if (e != hipSuccess) return bail(fail(PG_ERR_DEVICE, "column %s: dictionary upload: %s", col.name.c_str(), hipGetErrorString(e)));
       seg->device_bytes += col.fwd_alloc_bytes + C * (col.vkind == kValI32 ? 4 : 8);
     } else if (cd.fwd_encoding == PG_FWD_RAW_FIXED_BYTE) {
-      // BaseChunkForwardIndexReader header (BaseChunkForwardIndexReader.java:61-111)
+      // BaseChunkForwardIndexReader header (BaseChunkForwardIndexReader.java:61-111; pg_chunk_codec.h)
       if (cd.fwd_size < 16) return bail(fail(PG_ERR_INVALID_ARGUMENT, "column %s: raw forward index too small", col.name.c_str()));
-      int off = 0;
-      const int version = (int)be32(fwd + off); off += 4;
-      const int num_chunks = (int)be32(fwd + off); off += 4;
-      off += 4;  // numDocsPerChunk
-      const int entry_size = (int)be32(fwd + off); off += 4;
-      int data_header_start = off;
-      int compression = 2;
-      if (version > 1) {
-        if (cd.fwd_size < 28) return bail(fail(PG_ERR_INVALID_ARGUMENT, "column %s: raw forward index header truncated", col.name.c_str()));
-        off += 4;  // totalDocs
-        compression = (int)be32(fwd + off); off += 4;
-        data_header_start = (int)be32(fwd + off);
-      }
-      if (compression != 0) return bail(fail(PG_ERR_UNSUPPORTED, "column %s: only PASS_THROUGH raw chunks are offloaded (compressionType=%d)", col.name.c_str(), compression));
+      if ((int)be32(fwd) > 1 && cd.fwd_size < 28) return bail(fail(PG_ERR_INVALID_ARGUMENT, "column %s: raw forward index header truncated", col.name.c_str()));
+      pgcodec::ChunkFile cf;
+      if (pgcodec::parse_chunk_header(fwd, cd.fwd_size, &cf) != pgcodec::kFileOk)
+        return bail(fail(PG_ERR_INVALID_ARGUMENT, "column %s: raw forward index header holds a negative count", col.name.c_str()));
+      const int compression = cf.codec;
+      // LZ4 and SNAPPY chunks are decoded below, once, into the value area a PASS_THROUGH file has.  ZSTANDARD and GZIP need an entropy decoder;
+      // the fixed-byte writers never produce LZ4_LENGTH_PREFIXED.
+      if (compression != pgcodec::kPassThrough && compression != pgcodec::kLz4 && compression != pgcodec::kSnappy)
+        return bail(fail(PG_ERR_UNSUPPORTED, "column %s: %s raw chunks are not offloaded (compressionType=%d): only PASS_THROUGH, LZ4 and SNAPPY are", col.name.c_str(), pgcodec::codec_name(compression), compression));
+      const bool compressed = compression != pgcodec::kPassThrough;
+      const int entry_size = cf.entry_size;
       if (entry_size != value_bytes) return bail(fail(PG_ERR_UNSUPPORTED, "column %s: raw entry size %d for stored type %d", col.name.c_str(), entry_size, cd.stored_type));
       col.vkind = cd.stored_type == PG_TYPE_INT ? kValI32 : (cd.stored_type == PG_TYPE_LONG ? kValI64 : (cd.stored_type == PG_TYPE_FLOAT ? kValF32 : kValF64));
-      const uint64_t raw_start = (uint64_t)data_header_start + (uint64_t)num_chunks * (version <= 2 ? 4 : 8);
-      if (raw_start + (uint64_t)desc->num_docs * (uint64_t)value_bytes > cd.fwd_size) return bail(fail(PG_ERR_INVALID_ARGUMENT, "column %s: raw forward index shorter than numDocs", col.name.c_str()));
+      const uint64_t raw_start = cf.data_start;
+      const uint64_t value_area = (uint64_t)desc->num_docs * (uint64_t)value_bytes;
+      if (!compressed && raw_start + value_area > cd.fwd_size) return bail(fail(PG_ERR_INVALID_ARGUMENT, "column %s: raw forward index shorter than numDocs", col.name.c_str()));
+      if (compressed && desc->num_docs > 0) {
+        // header and offset table, before anything touches the device
+        const int vs = pgcodec::validate_chunk_table(cf, fwd, cd.fwd_size, desc->num_docs);
+        if (vs != pgcodec::kFileOk)
+          return bail(fail(PG_ERR_INVALID_ARGUMENT, "column %s: %s raw forward index: %s", col.name.c_str(), pgcodec::codec_name(compression),
+                           vs == pgcodec::kFileBadOffsets ? "chunk offsets decrease or point outside the file"
+                           : vs == pgcodec::kFileBadChunkCount ? "numChunks does not match numDocs and numDocsPerChunk"
+                           : vs == pgcodec::kFileTruncated ? "the chunk offset table does not lie inside the file" : "the header is not one of versions 1 to 4 with positive sizes"));
+      }
+      // The resident image of a compressed column is its PASS_THROUGH twin's: the same header and offset table sizes, then the dense values.
+      const uint64_t image_size = compressed ? raw_start + value_area : cd.fwd_size;
       // padded so that whole 2048-doc tiles can be read past numDocs (the lane-private kernels never clamp docIds)
       // The file is placed so that the VALUES (not the header) start on a 256-byte boundary: a lane's 32 docs are then whole,
       // aligned 16-byte loads and a tile's rows whole cache lines (the header is 28 + 4 * numChunks bytes: any multiple of 4).
       const size_t lead = (256 - (size_t)(raw_start % 256)) % 256;
-      col.fwd_alloc_bytes = lead + std::max<size_t>((size_t)cd.fwd_size, (size_t)raw_start + (size_t)std::max(seg->num_tiles, 1) * 2048 * (size_t)value_bytes) + 64;
+      col.fwd_alloc_bytes = lead + std::max<size_t>((size_t)image_size, (size_t)raw_start + (size_t)std::max(seg->num_tiles, 1) * 2048 * (size_t)value_bytes) + 64;
       hipError_t e = hipMalloc((void**)&col.d_fwd_alloc, col.fwd_alloc_bytes);
       if (e != hipSuccess) return bail(fail(PG_ERR_OUT_OF_MEMORY, "column %s: hipMalloc(%zu): %s", col.name.c_str(), col.fwd_alloc_bytes, hipGetErrorString(e)));
       e = hipMemset(col.d_fwd_alloc, 0, col.fwd_alloc_bytes);
-      if (e == hipSuccess) e = h2d_copy(col.d_fwd_alloc + lead, fwd, (size_t)cd.fwd_size, phys_device(seg->device));
+      if (e == hipSuccess && !compressed) e = h2d_copy(col.d_fwd_alloc + lead, fwd, (size_t)cd.fwd_size, phys_device(seg->device));
       if (e != hipSuccess) return bail(fail(PG_ERR_DEVICE, "column %s: H2D copy: %s", col.name.c_str(), hipGetErrorString(e)));
+      if (compressed && desc->num_docs > 0) {
+        const pg_status dst = decode_raw_chunks(seg, col, cf, fwd, cd.fwd_size, col.d_fwd_alloc + lead + raw_start);
+        if (dst != PG_OK) return bail(dst);
+      }
       col.d_fwd = col.d_fwd_alloc + lead + raw_start;
       col.bits = 32;
       col.cardinality = 0;
@@ -5617,8 +5682,8 @@ static pg_status plan_collect_bytes(const pg_segment* seg, const char* function,
     return fail(PG_ERR_UNSUPPORTED, "%s value lists of %llu bytes over raw columns exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES)", function, bytes, (unsigned long long)g_engine.group_table_bytes);
   return PG_OK;
 }
-// A raw column the pass can read: fixed-width numeric values.  (pg_segment_open keeps nothing else resident -- chunk-compressed, STRING and BYTES
-// columns are refused there -- so this is a safety net behind it.)
+// A raw column the pass can read: fixed-width numeric values.  (pg_segment_open keeps nothing else resident -- STRING and BYTES columns are
+// refused there, LZ4 / SNAPPY chunks are decoded there -- so this is a safety net behind it.)
 static pg_status plan_collect_column(const ColumnDev& col, const char* function) {
   // The pass is opt-in (PINOT_GPU_COLLECT=1): a deployment that has not asked for it sees the decline it has always seen, and its plans do not change
   // under it -- the lists cost up to 16 bytes of HBM per doc and column for the length of a query, which the dictionary forms never did.

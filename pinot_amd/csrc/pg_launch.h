@@ -171,5 +171,10 @@ void launch_group_typed_direct(int blocks, hipStream_t stream, const GroupParams
 int waves_group_partition_scatter();
 int blocks_per_cu_group_partition_scatter_packed(int num_partitions);
 
+// chunk_decode_kernel<LZ4 | SNAPPY>: the chunks of a compressed raw forward index -> the dense value area, one wave per chunk, `waves` chunks per
+// workgroup in waves * p.lds_stride bytes of dynamic LDS (pg_chunk_decode.h; codec: pgcodec::kLz4 | kSnappy)
+struct ChunkDecodeParams;
+void launch_chunk_decode(int codec, int blocks, int waves, hipStream_t stream, const ChunkDecodeParams& p);
+
 }  // namespace pg
 #endif

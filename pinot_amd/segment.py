@@ -48,6 +48,10 @@ def load_host_library():
     lib.ph_roaring_serialize.argtypes = [i32p, C.c_int64, C.c_int32, u8p]
     lib.ph_inverted_build.restype = C.c_int64
     lib.ph_inverted_build.argtypes = [i32p, C.c_int32, C.c_int32, C.c_int32, u8p]
+    lib.ph_chunk_decode.restype = C.c_int32
+    lib.ph_chunk_decode.argtypes = [C.c_int32, u8p, C.c_uint32, u8p, C.c_uint32]
+    lib.ph_raw_decode_file.restype = C.c_int32
+    lib.ph_raw_decode_file.argtypes = [u8p, C.c_uint64, C.c_int64, u8p]
     _host_lib = lib
     return lib
 
@@ -176,6 +180,13 @@ class Column:
         fwd = np.zeros(int(lib.ph_raw_size_fixed_v2(n, docs_per_chunk, es)), dtype=np.uint8)
         lib.ph_raw_write_fixed_v2(values.ctypes.data, n, docs_per_chunk, es, _u8p(fwd))
         return Column(name, _abi.PG_FWD_RAW_FIXED_BYTE, 8 * es, 0, fwd, stored_type=st)
+
+    @staticmethod
+    def raw_file(name, fwd, dtype):
+        """A raw column over a fixed-byte chunk file as it is on disk (versions 1 to 4; PASS_THROUGH, LZ4 or SNAPPY chunks: the engine reads
+        the codec from the file's header); `dtype` is the numpy dtype of the stored values."""
+        st = stored_type_of(dtype)
+        return Column(name, _abi.PG_FWD_RAW_FIXED_BYTE, 8 * np.dtype(dtype).itemsize, 0, np.ascontiguousarray(fwd, dtype=np.uint8), stored_type=st)
 
     @staticmethod
     def synthetic_uniform(name, num_docs, dict_values, seed):

@@ -522,6 +522,32 @@ def main():
                     except AssertionError as e:
                         failed.append({"id": eid, "error": str(e)[:300]})
                 ran += 1
+    # ---- LZ4 / SNAPPY raw columns (pg_chunk_decode.h): chunk_decode_kernel<codec> at pg_segment_open, more chunks than waves in flight (1 000-doc
+    # chunks: 101 of them for the 32 waves of one CU, 12 301 for the 8 192 of the whole chip).  The oracle declines compressed files: the raw-range SUM
+    # on the compressed column is held against the oracle on the same values written PASS_THROUGH.  The chunks repeat sixteen contents, so that
+    # the Python compressors of tests/chunk_codec_cases.py see 16 000 docs whatever the regime.
+    if only is None or only.search("chunk-codec"):
+        import chunk_codec_cases as CC
+        dpc, kinds = 1000, 16
+        pool = (np.cumsum(np.random.default_rng(5).integers(0, 3, dpc * kinds)) * 7 - 20000).astype(np.int32)
+        values = np.tile(pool, n // (dpc * kinds) + 1)[:n]
+        raw_chunks = CC.split_chunks(CC.big_endian_bytes(values), dpc * 4)
+        twin = S.SegmentData("chunk_twin", n, [S.Column.raw_file("r", CC.write_file(2, CC.PASS_THROUGH, dpc, 4, n, raw_chunks), np.int32)])
+        spec = Q.QuerySpec([(Q.SUM, 0), (Q.COUNT, -1)], filter=Q.leaf(Q.Pred.raw_range(0, -5000, 9000)))
+        want = oracle.execute(twin, spec)
+        for codec, cname in ((CC.LZ4, "lz4"), (CC.SNAPPY, "snappy")):
+            packed = {c: CC.COMPRESSORS[codec](c) for c in set(raw_chunks)}
+            chunks = [packed[c] for c in raw_chunks]
+            zseg = S.SegmentData("chunk_" + cname, n, [S.Column.raw_file("r", CC.write_file(2, codec, dpc, 4, n, chunks), np.int32)])
+            for env in ({}, {"PINOT_GPU_CHUNK_DECODE": "host"}):
+                engine.reinit(**env)
+                try:
+                    with engine.open(zseg) as g:
+                        for rep in range(2):
+                            check("chunk-codec-%s%s" % (cname, "-host" if env else ""), g.execute(spec), want, "scan_raw_kernel")
+                finally:
+                    engine.reinit(**{k: flipped.get(k) for k in env})
+            ran += 1
     # ---- the transducer's kernels: byte-function walks, then table walks of the same machines ----
     if only is None or only.search("fsm"):
         count = args.fsm_trees if args.fsm_trees >= 0 else (400 if args.regime == "tiny" else 40)

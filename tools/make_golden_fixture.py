@@ -174,8 +174,25 @@ def export_raw_chunk_fixture():
     print("wrote", path, len(data), "bytes")
 
 
+def export_compressed_chunk_fixtures():
+    """pinot-segment-local/src/test/resources/data/fixedByteCompressed.v2 (version 2, SNAPPY, 2 x 1000 doubles, value i = i + 100.2356) and
+    fixedByteSVRDoubles.v1 (version 1 -- SNAPPY by definition -- 3 chunks of 5003 docs, 10009 doubles, value i = i): the compressed chunk files
+    the reference keeps for FixedByteChunkSVForwardIndexTest.java:344-375 (testBackwardCompatibilityV1 / V2).  Data, base64 in JSON like
+    fixedByteRaw_v2.json: they pin the Snappy decoder, the version-1 header and the short last chunk."""
+    import base64
+    for fname, num_docs, start in (("fixedByteCompressed.v2", 2000, 100.2356), ("fixedByteSVRDoubles.v1", 10009, 0.0)):
+        src = "/root/reference/pinot-segment-local/src/test/resources/data/" + fname
+        data = open(src, "rb").read()
+        path = os.path.join(os.path.dirname(OUT), fname.replace(".", "_") + ".json")
+        with open(path, "w") as f:
+            json.dump({"_source": src, "num_docs": num_docs, "start_value": start, "stored_type": "DOUBLE",
+                       "file_base64": base64.b64encode(data).decode()}, f)
+        print("wrote", path, len(data), "bytes")
+
+
 if __name__ == "__main__":
     main()
     export_prebuilt_segment()
     export_raw_chunk_fixture()
+    export_compressed_chunk_fixtures()
     export_segment_directories()
