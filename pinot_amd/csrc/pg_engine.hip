@@ -95,6 +95,9 @@ struct Engine {
                              // scan_simple_valid_kernel whose tiles without a valid doc skip the filter column too (pg_scan_simple.h)
   int scan_simple_pipe = 1;   // PINOT_GPU_SCAN_SIMPLE_PIPE: 0 never scan_simple_pipe_kernel, 1 by the estimated selectivity of the leaf (choose_scan_kernel), 2 whenever
                              // the shape allows, whatever the estimate (pg_scan_simple_pipe.h)
+  int scan_simple_dma = 1;    // PINOT_GPU_SCAN_SIMPLE_DMA: 0 never scan_simple_dma_kernel, 1 by rule (choose_scan_kernel), 2 whenever the shape allows (pg_scan_simple_dma.h)
+  int dma_nt = -1;            // PINOT_GPU_SCAN_SIMPLE_DMA_NT: 0 / 1 forces the default / the non-temporal cache policy; unset = by the columns' size
+  int dma_blocks_per_cu = 0;  // PINOT_GPU_SCAN_SIMPLE_DMA_BLOCKS_PER_CU: workgroups per CU (what registers and LDS admit still bounds it); 0 = the rule's
   bool scan_simple = true;   // PINOT_GPU_SCAN_SIMPLE=0: one-leaf / one-column queries stay in scan_private_kernel (half the waves per SIMD)
   bool scan_sparse = true;   // PINOT_GPU_SCAN_SPARSE=0: index-led aggregations scan their listed tiles in scan_private_kernel (one tile per wave and iteration)
   // (read at every pg_init like the rest: they were function-local statics, fixed at their first use in the process, until the kernel
@@ -2021,6 +2024,12 @@ pg_status pg_init(const pg_config* config) {
   g_engine.scan_simple_valid = ssv ? (ssv[0] == '0' ? 0 : (ssv[0] == '2' ? 2 : 1)) : 1;
   const char* spp = getenv("PINOT_GPU_SCAN_SIMPLE_PIPE");
   g_engine.scan_simple_pipe = spp ? (spp[0] == '0' ? 0 : (spp[0] == '2' ? 2 : 1)) : 1;
+  const char* sdm = getenv("PINOT_GPU_SCAN_SIMPLE_DMA");
+  g_engine.scan_simple_dma = sdm ? (sdm[0] == '0' ? 0 : (sdm[0] == '2' ? 2 : 1)) : 1;
+  const char* sdn = getenv("PINOT_GPU_SCAN_SIMPLE_DMA_NT");
+  g_engine.dma_nt = sdn ? (sdn[0] == '0' ? 0 : 1) : -1;
+  const char* sdb = getenv("PINOT_GPU_SCAN_SIMPLE_DMA_BLOCKS_PER_CU");
+  g_engine.dma_blocks_per_cu = sdb && atoi(sdb) > 0 ? atoi(sdb) : 0;
   const char* srw = getenv("PINOT_GPU_SCAN_RAW");
   g_engine.scan_raw = !(srw && srw[0] == '0');
   const char* srs = getenv("PINOT_GPU_SCAN_RAW_SET");
@@ -3072,11 +3081,32 @@ struct ScanChoice {
   int hist_slot = -1, hist_cw = 0;         // Hist: the aggregation slot the histogram counts, its counter bits ...
   bool hist_guarded = false;               // ... and whether they are the guarded tier's
   bool pipe = false;                       // Simple: scan_simple_pipe_kernel, the form with both columns' loads pipelined across tiles (same id, same batch kind)
+  bool dma = false, dma_nt = false;        // Simple: scan_simple_dma_kernel, the two columns through a wave-private LDS ring (same id, same batch kind); goes before `pipe`
+  int dma_blocks_per_cu = 0;               // ... its workgroups per CU
 };
 // scan_simple_pipe_kernel always loads the aggregated column: it wins where scan_simple_kernel's lane skip and sparse walk have nothing to
 // skip.  The leaf's selectivity is estimated as span / cardinality of its column (1 - that for an exclusive leaf); at or above this many
 // per cent the pipelined form is taken (DESIGN.md 4.1g has the table the figure comes from).
 constexpr int kPipeMinSelectivityPct = 5;
+// scan_simple_dma_kernel (pg_scan_simple_dma.h) takes the pipelined kernel's queries -- same conditions, every width pair -- when a ring is
+// worth filling and the shape is one that was measured: at least kDmaMinTilesPerWave tiles for every resident wave (2.4 lose to the pipelined
+// kernel, 12 win), slots of at least kDmaMinSlotBytes (the headline's: what a wave keeps in flight is one slot, and narrower pairs were not
+// measured) and room for kDmaBlocksPerCu workgroups of four waves per CU (one workgroup per CU is slower than the pipelined kernel: the
+// decode of four waves does not cover the CU's stream).  Non-temporal loads when the two columns together exceed the Infinity Cache (a smaller
+// segment queried again is served from it).  DESIGN.md 4.1g has the tables the figures come from.
+constexpr int kDmaMinTilesPerWave = 8;
+constexpr int kDmaMinSlotBytes = 6912;
+constexpr int kDmaBlocksPerCu = 2;
+constexpr long long kInfinityCacheBytes = 256ll << 20;
+static void plan_scan_simple_dma(const pg_segment* seg, int filter_bits, int value_bits, bool dense, ScanChoice* k) {
+  const int bpc = std::min(blocks_scan_simple_dma(filter_bits, value_bits, kLdsBudget), g_engine.dma_blocks_per_cu > 0 ? g_engine.dma_blocks_per_cu : kDmaBlocksPerCu);
+  if (bpc < 1) return;      // (does not happen: one workgroup's rings of the widest pair are half the budget)
+  k->dma_blocks_per_cu = bpc;
+  const long long tiles = doc_tiles(seg), slot_bytes = 256ll * (filter_bits + value_bits);
+  k->dma_nt = g_engine.dma_nt >= 0 ? g_engine.dma_nt == 1 : tiles * slot_bytes > kInfinityCacheBytes;
+  const long long resident_waves = (long long)seg->num_cus * bpc * (kBlockThreads / 64);
+  k->dma = g_engine.scan_simple_dma == 2 || (dense && slot_bytes >= kDmaMinSlotBytes && bpc >= kDmaBlocksPerCu && tiles >= kDmaMinTilesPerWave * resident_waves);
+}
 static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, int hist_col, bool typed, bool want_bitmap, bool want_result) {
   const PlanParams& pl = lw.plan; const ScanParams& sp = lw.sp;
   const bool profile = (g_engine.flags & PG_CFG_PROFILE_WAVES) != 0;
@@ -3172,11 +3202,13 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
                 (leaf == nullptr || ((leaf->kind == kLeafDictRange || set) && leaf->bits >= 1 && leaf->bits <= kSimpleMaxBits));
   if (simple && ac != nullptr)
     simple = ac->bits >= 1 && ac->bits <= kSimpleMaxBits && !ac->is_raw && !(leaf != nullptr && leaf->fwd == ac->fwd && leaf->bits == ac->bits && ac->need_sum != 0 && ac->need_minmax == 0 && leaf->exclusive == 0);
-  if (simple && !set && leaf != nullptr && ac != nullptr && g_engine.scan_simple_pipe != 0 && scan_simple_pipe_shape(leaf->bits, ac->bits)) {
+  if (simple && !set && leaf != nullptr && leaf->kind == kLeafDictRange && ac != nullptr) {
     const DevColumn& fc = pl.cols[pl.leaves[pl.nodes[0].leaf].col];
     const unsigned long long values = fc.is_plane ? 1ull << leaf->bits : (unsigned long long)std::max(fc.cardinality, 1);      // (a range over a value plane: span is in plane units)
     const unsigned long long inside = std::min<unsigned long long>(leaf->span, values), taken = leaf->exclusive ? values - inside : inside;
-    k.pipe = g_engine.scan_simple_pipe == 2 || taken * 100ull >= (unsigned long long)kPipeMinSelectivityPct * values;
+    const bool dense = taken * 100ull >= (unsigned long long)kPipeMinSelectivityPct * values;
+    if (g_engine.scan_simple_pipe != 0 && scan_simple_pipe_shape(leaf->bits, ac->bits)) k.pipe = g_engine.scan_simple_pipe == 2 || dense;
+    if (g_engine.scan_simple_dma != 0) plan_scan_simple_dma(seg, leaf->bits, ac->bits, dense, &k);
   }
   if (simple) return pick(set ? ScanKernel::SimpleSet : ScanKernel::Simple);
   // The same idea for raw INT columns (BASELINE.json configs[0]'s scan pair): one raw-range leaf (or no filter) in front of at most one
@@ -3316,7 +3348,13 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Lowe
     case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
     case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
-    case ScanKernel::Simple: case ScanKernel::SimpleSet: lean_grid(seg, k.pipe ? waves_scan_simple_pipe() : waves_scan_simple(), &g); break;
+    case ScanKernel::Simple: case ScanKernel::SimpleSet:
+      if (k.dma) {
+        // the rings are dynamic LDS: the workgroups per CU are those plan_scan_simple_dma found room for; small grids as lean_grid
+        g.lds = scan_simple_dma_lds(sp.nodes[0].bits, sp.agg_cols[0].bits);
+        g.blocks = grid_blocks(seg, tiles, wpb, k.dma_blocks_per_cu, false);
+      } else lean_grid(seg, k.pipe ? waves_scan_simple_pipe() : waves_scan_simple(), &g);
+      break;
     case ScanKernel::SimpleValid: lean_grid(seg, waves_scan_simple_valid(), &g); break;
     case ScanKernel::Raw: lean_grid(seg, waves_scan_raw(), &g); break;
     case ScanKernel::RawSet: {
@@ -3357,7 +3395,8 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Narrow: case ScanKernel::NarrowSingle: launch_scan_narrow(k.kernel == ScanKernel::NarrowSingle, g.blocks, stream, sp); break;
     case ScanKernel::Sparse: launch_scan_sparse(one, g.blocks, stream, sp); break;
     case ScanKernel::Simple: case ScanKernel::SimpleSet:
-      if (k.pipe) launch_scan_simple_pipe(g.blocks, lean_threads, stream, sp);
+      if (k.dma) launch_scan_simple_dma(g.blocks, k.dma_nt, stream, sp);
+      else if (k.pipe) launch_scan_simple_pipe(g.blocks, lean_threads, stream, sp);
       else launch_scan_simple(g.blocks, lean_threads, stream, sp, k.kernel == ScanKernel::SimpleSet);
       break;
     case ScanKernel::SimpleValid: launch_scan_simple_valid(g.blocks, lean_threads, stream, sp, g_engine.scan_simple_valid == 2); break;

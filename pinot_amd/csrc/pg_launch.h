@@ -54,6 +54,13 @@ int waves_scan_simple();
 bool scan_simple_pipe_shape(int filter_bits, int value_bits);
 void launch_scan_simple_pipe(int blocks, int threads, hipStream_t stream, const ScanParams& p);
 int waves_scan_simple_pipe();          // the least over the instantiations
+// scan_simple_dma_kernel<N, aux>: the pipelined kernel's queries with the two columns streamed through a wave-private ring of kDmaSlots LDS
+// slots by LDS-DMA loads (pg_scan_simple_dma.h); every width pair up to kSimpleMaxBits.  nt: the loads are non-temporal (columns read once and
+// larger than the Infinity Cache).  Workgroups of kBlockThreads; the dynamic LDS is scan_simple_dma_lds(...).
+constexpr int kDmaSlots = 2;      // (three slots leave room for one workgroup per CU at the headline's widths: measured slower)
+size_t scan_simple_dma_lds(int filter_bits, int value_bits);
+void launch_scan_simple_dma(int blocks, bool nt, hipStream_t stream, const ScanParams& p);
+int blocks_scan_simple_dma(int filter_bits, int value_bits, size_t lds_budget);      // resident workgroups per CU: registers and LDS
 // scan_simple_valid_kernel: the same shape behind one PG_PRED_DOC_SET leaf (p.bitmaps[0] = the doc set; p.nodes[0] = the range leaf, if any);
 // skip_empty_tiles: the form whose tiles without a valid doc skip the filter column too
 void launch_scan_simple_valid(int blocks, int threads, hipStream_t stream, const ScanParams& p, bool skip_empty_tiles);

@@ -1,9 +1,11 @@
-"""A/B of scan_simple_kernel against scan_simple_pipe_kernel on a RESIDENT C2b segment (bench.py's: v 17-bit, f 10-bit over 1000 values):
-SELECT SUM(v) WHERE f < t at a list of selectivities, PINOT_GPU_SCAN_SIMPLE_PIPE flipped between 0 (scan_simple_kernel) and 2 (the
-pipelined kernel whatever the estimate) in one process -- Engine.reinit re-reads the switch, the segment stays open.  The settings
-alternate within every round, so that a drift of the clocks falls on both.
+"""A/B of scan_simple_kernel, scan_simple_pipe_kernel and scan_simple_dma_kernel on a RESIDENT C2b segment (bench.py's: v 17-bit, f 10-bit
+over 1000 values): SELECT SUM(v) WHERE f < t at a list of selectivities, the switches flipped in one process -- `simple`
+(PINOT_GPU_SCAN_SIMPLE_PIPE=0, PINOT_GPU_SCAN_SIMPLE_DMA=0), `pipe` (the pipelined kernel whatever the estimate) and `dma` (the LDS-ring
+kernel whatever the rule says; --dma-configs adds other launches of it: `blocks_per_cu[:nt]`, e.g. 1,2:0,2:1).  Engine.reinit
+re-reads the switches, the segment stays open.  The settings alternate within every round, so that a drift of the clocks falls on all.
 
-  python tools/ab_scan_simple.py [--rows N] [--steps K] [--warmup W] [--rounds R] [--selectivities 1,2,3,5,7,10,25,50] [--out file.jsonl]
+  python tools/ab_scan_simple.py [--rows N] [--steps K] [--warmup W] [--rounds R] [--selectivities 1,2,3,5,7,10,25,50] [--settings simple,pipe,dma]
+                                 [--dma-configs 1,2:0] [--out file.jsonl]
 
 Every answer is held against the oracle once, on a segment of --check-rows rows with the same columns (both settings), and on the large
 segment the two settings must give the same answer.  One JSON line per (round, selectivity, setting), and a last line per selectivity
@@ -20,8 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-SWITCH = "PINOT_GPU_SCAN_SIMPLE_PIPE"
-SETTINGS = (("simple", "0"), ("pipe", "2"))
+PIPE, DMA, BPC, NT = "PINOT_GPU_SCAN_SIMPLE_PIPE", "PINOT_GPU_SCAN_SIMPLE_DMA", "PINOT_GPU_SCAN_SIMPLE_DMA_BLOCKS_PER_CU", "PINOT_GPU_SCAN_SIMPLE_DMA_NT"
+UNSET = {PIPE: None, DMA: None, BPC: None, NT: None}
+BASE_SETTINGS = {"simple": dict(UNSET, **{PIPE: "0", DMA: "0"}), "pipe": dict(UNSET, **{PIPE: "2", DMA: "0"}), "dma": dict(UNSET, **{DMA: "2"})}
 
 
 def main():
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--selectivities", default="1,2,3,5,7,10,25,50", help="per cent of f's 1000 dictIds")
+    ap.add_argument("--settings", default="simple,pipe,dma")
+    ap.add_argument("--dma-configs", default="", help="further launches of the ring kernel, blocks_per_cu[:nt], comma separated")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -45,6 +50,10 @@ def main():
     from pinot_amd.engine import Engine
 
     percents = [int(x) for x in args.selectivities.split(",") if x]
+    SETTINGS = [(name, BASE_SETTINGS[name]) for name in args.settings.split(",") if name]
+    for cfg in [c for c in args.dma_configs.split(",") if c]:
+        parts = cfg.split(":")
+        SETTINGS.append(("dma-b%s%s" % (parts[0], "-nt" + parts[1] if len(parts) > 1 else ""), dict(UNSET, **{DMA: "2", BPC: parts[0], NT: parts[1] if len(parts) > 1 else None})))
     spec_of = lambda pct: Q.QuerySpec([(Q.SUM, 0)], filter=Q.leaf(Q.Pred.dict_range(1, 0, pct * 10)))
     answer = lambda r: (r.stats[0], [(a.count, a.sum_i64) for a in r.aggregations])
     engine = Engine(device_id=0, time_kernels=True)
@@ -67,7 +76,7 @@ def main():
                 want = oracle.execute(small, spec_of(pct))
                 exact[pct] = True
                 for _name, value in SETTINGS:
-                    engine.reinit(**{SWITCH: value})
+                    engine.reinit(**value)
                     try:
                         H.assert_results_equal(g.execute(spec_of(pct)), want, True)
                     except AssertionError:
@@ -82,30 +91,31 @@ def main():
         nbytes = seg.columns[0].fwd.nbytes + seg.columns[1].fwd.nbytes
         samples = {}
         with engine.open(seg) as g:
-            engine.reinit(**{SWITCH: "0"})
+            engine.reinit(**BASE_SETTINGS["simple"])
             timer.run(g, spec_of(10), 1, 48)             # the clock transient after idle (bench.py's settle launches)
             same = {}
             for rnd in range(args.rounds):
                 for pct in percents:
                     for name, value in SETTINGS:
-                        engine.reinit(**{SWITCH: value})
+                        engine.reinit(**value)
                         t = timer.run(g, spec_of(pct), args.steps, args.warmup)
                         if rnd == 0:
                             same.setdefault(pct, []).append(answer(g.execute(spec_of(pct))))
                         samples.setdefault((pct, name), []).append(t["kernel_ms"])
-                        emit({"round": rnd, "selectivity_pct": pct, "setting": name, SWITCH: value, "rows": args.rows, "kernel": t["kernel"], "kernel_ms": t["kernel_ms"],
+                        emit({"round": rnd, "selectivity_pct": pct, "setting": name, "rows": args.rows, "kernel": t["kernel"], "kernel_ms": t["kernel_ms"],
                               "all_kernels_ms": t["all_kernels_ms"], "host_clock_ms": t["step_ms_host_clock"], "TBps": nbytes / t["kernel_ms"] / 1e9})
+        names = [name for name, _ in SETTINGS]
         for pct in percents:
-            a, b = samples[(pct, "simple")], samples[(pct, "pipe")]
-            emit({"summary": True, "selectivity_pct": pct, "rows": args.rows, "rounds": args.rounds, "steps": args.steps,
-                  "simple_ms": {"median": statistics.median(a), "min": min(a), "max": max(a)}, "pipe_ms": {"median": statistics.median(b), "min": min(b), "max": max(b)},
-                  "pipe_over_simple": statistics.median(b) / statistics.median(a), "pipe_faster_in_every_round": max(b) < min(a),
-                  "same_answer": same[pct][0] == same[pct][1], "exact_vs_oracle_at_check_rows": exact[pct]})
-        differ = [pct for pct in percents if same[pct][0] != same[pct][1]]
+            stats = {name: {"median": statistics.median(samples[(pct, name)]), "min": min(samples[(pct, name)]), "max": max(samples[(pct, name)])} for name in names}
+            emit({"summary": True, "selectivity_pct": pct, "rows": args.rows, "rounds": args.rounds, "steps": args.steps, "kernel_ms": stats,
+                  "over_first": {name: stats[name]["median"] / stats[names[0]]["median"] for name in names[1:]},
+                  "fastest_in_every_round": [name for name in names if all(stats[name]["max"] < stats[o]["min"] for o in names if o != name)],
+                  "same_answer": all(a == same[pct][0] for a in same[pct]), "exact_vs_oracle_at_check_rows": exact[pct]})
+        differ = [pct for pct in percents if any(a != same[pct][0] for a in same[pct])]
         if differ:
-            sys.exit("ab_scan_simple: the two settings answer differently at %s %%" % differ)
+            sys.exit("ab_scan_simple: the settings answer differently at %s %%" % differ)
     finally:
-        engine.reinit(**{SWITCH: None})
+        engine.reinit(**UNSET)
 
 
 if __name__ == "__main__":

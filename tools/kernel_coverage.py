@@ -94,6 +94,15 @@ def table(Q, n):
             if (nf4, nv4) not in ((4, 5), (5, 3), (5, 4), (5, 5)):
                 add("pipe-%d-%d" % (nf4, nv4), {"PINOT_GPU_SCAN_SIMPLE_PIPE": "2"}, "scan_simple_kernel",
                     Q.QuerySpec([(Q.MAX, vcol), (Q.COUNT, -1)] + ([(Q.SUM, V)] if vcol == V else []), filter=L(Q.Pred.dict_range(fcol, lo, hi))))
+    # scan_simple_dma_kernel<N, aux>: the same queries through a wave-private LDS ring, N = the LDS-DMA instructions of a tile (the two
+    # columns' sixteen-byte-load classes added up, 2 .. 10), aux 0 / 2 (default / non-temporal loads).  With the switch at 2 every
+    # instance; by the rule neither regime's segment is large enough for it (f < 100 above stays with the pipelined kernel).
+    dma_pairs = [(1, 1), (1, 2), (2, 2), (2, 3), (3, 3), (3, 4), (4, 4), (4, 5), (5, 5)]
+    for nf4, nv4 in dma_pairs:
+        (fcol, lo, hi), vcol = pipe_filters[nf4 - 1], pipe_values[nv4 - 1]
+        for nt in (0, 1):
+            add("dma-%d-nt%d" % (nf4 + nv4, nt), {"PINOT_GPU_SCAN_SIMPLE_DMA": "2", "PINOT_GPU_SCAN_SIMPLE_DMA_NT": str(nt)},
+                "scan_simple_kernel", Q.QuerySpec([(Q.MAX, vcol), (Q.COUNT, -1)] + ([(Q.SUM, V)] if vcol == V else []), filter=L(Q.Pred.dict_range(fcol, lo, hi))))
     add("simple-set", {}, "scan_simple_kernel", Q.QuerySpec([(Q.SUM, V), (Q.COUNT, -1)], filter=L(Q.Pred.dict_set(F, list(range(0, 300, 3)), 1000))))      # scan_simple_set_kernel: the one leaf an IN list, its words in LDS
     add("raw", {}, "scan_raw_kernel", Q.QuerySpec([(Q.COUNT, -1)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))
     add("raw-sum", {}, "scan_raw_kernel", Q.QuerySpec([(Q.SUM, RI), (Q.MAX, RI)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))

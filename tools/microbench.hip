@@ -50,6 +50,86 @@ __global__ __launch_bounds__(256) void stream_read_dma(const uint8_t* __restrict
   if (acc == 0x1234567ull) out[0] = acc;
 }
 
+// 1c. the one-leaf scan's request shape through a wave-private LDS ring ("Gate 0"; `microbench ring`).
+// One wave per workgroup, kS slots of 6 912 bytes per wave.  A tile is one 2 560-byte piece of `f` (a 10-bit column's 2048 docs) and one
+// 4 352-byte piece of `v` (17 bits), each moved by 1 KiB-per-instruction LDS-DMA loads, the last one partial (32 and 16 lanes): 3 + 5 = 8
+// instructions per tile, every one inside the tile.  kS - 1 tiles stay in flight behind a counted vmcnt; each lane then reads its own
+// 10 and 17 dwords (byte offsets 40 * lane and 68 * lane: 4-byte aligned only) back from the slot and xors them into a sink.
+constexpr int kRingFBytes = 2560, kRingVBytes = 4352, kRingSlotBytes = kRingFBytes + kRingVBytes, kRingLoadsPerTile = 8;
+
+template <int kAux>
+__device__ __forceinline__ void ring_issue(const uint8_t* __restrict__ f, const uint8_t* __restrict__ v, size_t tile, uint8_t* slot, int lane) {
+  const uint8_t* fp = f + tile * kRingFBytes + lane * 16;
+  const uint8_t* vp = v + tile * kRingVBytes + lane * 16;
+  __builtin_amdgcn_global_load_lds((gbl_void_t*)(fp), (lds_void_t*)(slot), 16, 0, kAux);
+  __builtin_amdgcn_global_load_lds((gbl_void_t*)(fp + 1024), (lds_void_t*)(slot + 1024), 16, 0, kAux);
+  if (lane < 32) __builtin_amdgcn_global_load_lds((gbl_void_t*)(fp + 2048), (lds_void_t*)(slot + 2048), 16, 0, kAux);
+  uint8_t* vs = slot + kRingFBytes;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) __builtin_amdgcn_global_load_lds((gbl_void_t*)(vp + j * 1024), (lds_void_t*)(vs + j * 1024), 16, 0, kAux);
+  if (lane < 16) __builtin_amdgcn_global_load_lds((gbl_void_t*)(vp + 4096), (lds_void_t*)(vs + 4096), 16, 0, kAux);
+}
+
+__device__ __forceinline__ uint32_t ring_consume(const uint8_t* slot, int lane) {
+  const uint32_t* fd = reinterpret_cast<const uint32_t*>(slot + lane * 40);
+  const uint32_t* vd = reinterpret_cast<const uint32_t*>(slot + kRingFBytes + lane * 68);
+  uint32_t x = 0;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) x ^= fd[i];
+#pragma unroll
+  for (int i = 0; i < 17; ++i) x ^= vd[i];
+  return x;
+}
+
+template <int kS, int kAux>
+__global__ __launch_bounds__(64) void stream_ring_dma(const uint8_t* __restrict__ f, const uint8_t* __restrict__ v, uint32_t num_tiles, unsigned long long* out) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t ring[];
+  const int lane = threadIdx.x;
+  const uint32_t wave = blockIdx.x, waves = gridDim.x;
+  const uint32_t n = wave < num_tiles ? (num_tiles - wave + waves - 1) / waves : 0;   // tiles wave, wave + waves, ...
+  uint32_t acc = 0;
+  if (n >= (uint32_t)kS) {                      // (the benchmark's grids give every wave far more; a shorter wave reads nothing here)
+#pragma unroll
+    for (int k = 0; k < kS - 1; ++k) ring_issue<kAux>(f, v, wave + (size_t)k * waves, ring + k * kRingSlotBytes, lane);
+    uint32_t rd = 0, wr = kS - 1, i = 0;
+    for (; i + (kS - 1) < n; ++i) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slot about to be refilled was read in the iteration before
+      ring_issue<kAux>(f, v, wave + (size_t)(i + kS - 1) * waves, ring + wr * kRingSlotBytes, lane);
+      if (kS == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      acc ^= ring_consume(ring + rd * kRingSlotBytes, lane);
+      rd = rd + 1 == (uint32_t)kS ? 0 : rd + 1;
+      wr = wr + 1 == (uint32_t)kS ? 0 : wr + 1;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    for (; i < n; ++i) {
+      acc ^= ring_consume(ring + rd * kRingSlotBytes, lane);
+      rd = rd + 1 == (uint32_t)kS ? 0 : rd + 1;
+    }
+  }
+  if (acc == 0x12345678u) out[0] = acc;
+}
+static_assert(kRingLoadsPerTile == 8, "the counted waits above are 8 * (kS - 1)");
+
+// 1d. the same two pieces per tile by plain lane-contiguous loads straight to registers, nothing decoded: the request shape of
+// scan_simple_kernel / scan_simple_pipe_kernel, and the figure the ring has to beat.
+__global__ __launch_bounds__(256) void lane_contiguous_pair(const uint8_t* __restrict__ f, const uint8_t* __restrict__ v, uint32_t num_tiles, unsigned long long* out) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+  uint32_t acc = 0;
+  for (uint32_t t = wave; t < num_tiles; t += waves) {
+    const uint32_t* fp = reinterpret_cast<const uint32_t*>(f + (size_t)t * kRingFBytes + lane * 40);
+    const uint32_t* vp = reinterpret_cast<const uint32_t*>(v + (size_t)t * kRingVBytes + lane * 68);
+    uint32_t d[27];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) d[i] = fp[i];
+#pragma unroll
+    for (int i = 0; i < 17; ++i) d[10 + i] = vp[i];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) acc ^= d[i];
+  }
+  if (acc == 0x12345678u) out[0] = acc;
+}
+
 // 2. gather from a table in global memory (L2 resident): `active_pct` percent of lanes do a real gather,
 // the others present an out-of-range buffer offset (returns 0, no memory access).
 template <int kAux>
@@ -305,6 +385,49 @@ int main(int argc, char** argv) {
     printf("{\"bench\": \"sparse_read\", \"buffer_bytes\": %zu, \"ms\": {\"8B_per_128B_line\": %.3f, \"8B_per_64B_half\": %.3f, \"8B_per_256B\": %.3f, \"16B_per_512B\": %.3f, \"stream_16B_per_lane\": %.3f},"
            " \"lines_touched\": {\"8B_per_128B_line\": %zu, \"8B_per_64B_half\": %zu, \"8B_per_256B\": %zu, \"16B_per_512B\": %zu, \"stream_16B_per_lane\": %zu}}\n",
            bytes, a, b, c, d, e, bytes / 128, bytes / 128, bytes / 256, bytes / 512, bytes / 128);
+    return 0;
+  }
+
+  if (argc > 1 && !strcmp(argv[1], "ring")) {
+    // The headline's segment: 1 B docs = 488 282 tiles of 2048, a 10-bit and a 17-bit column in buffers of their own.
+    const uint32_t tiles = 488282;
+    const size_t fbytes = (size_t)tiles * kRingFBytes, vbytes = (size_t)tiles * kRingVBytes, total = fbytes + vbytes;
+    uint8_t *d_f, *d_v;
+    CHECK(hipMalloc((void**)&d_f, fbytes));
+    CHECK(hipMalloc((void**)&d_v, vbytes));
+    CHECK(hipMemset(d_f, 0x5a, fbytes));
+    CHECK(hipMemset(d_v, 0xa5, vbytes));
+    const int lds_cu = 160 * 1024, reps = 10;
+    for (int round = 0; round < 3; ++round) {
+      for (int bpc : {4, 8}) {
+        double ms = time_ms([&] { stream_read<<<cus * bpc, 256>>>((const uint4*)d_v, vbytes / 16, d_out); }, reps);
+        printf("{\"bench\": \"stream_read_dwordx4\", \"round\": %d, \"blocks_per_cu\": %d, \"GBps\": %.1f, \"ms_for_headline_bytes\": %.4f}\n", round, bpc,
+               vbytes / ms / 1e6, ms * total / vbytes);
+      }
+      {
+        double m10 = time_ms([&] { lane_contiguous_read<10><<<cus * 5, 256>>>(d_f, tiles, d_out); }, reps);
+        double m17 = time_ms([&] { lane_contiguous_read<17><<<cus * 5, 256>>>(d_v, tiles, d_out); }, reps);
+        printf("{\"bench\": \"lane_contiguous_read\", \"round\": %d, \"blocks_per_cu\": 5, \"GBps\": {\"10dw\": %.1f, \"17dw\": %.1f}, \"ms_for_headline_bytes\": %.4f}\n", round,
+               fbytes / m10 / 1e6, vbytes / m17 / 1e6, m10 + m17);
+      }
+      for (int bpc : {4, 5, 8}) {
+        double ms = time_ms([&] { lane_contiguous_pair<<<cus * bpc, 256>>>(d_f, d_v, tiles, d_out); }, reps);
+        printf("{\"bench\": \"lane_contiguous_pair\", \"round\": %d, \"waves_per_cu\": %d, \"ms\": %.4f, \"GBps\": %.1f}\n", round, bpc * 4, ms, total / ms / 1e6);
+      }
+      // The ring: dynamic LDS sized so that exactly `wpc` one-wave workgroups fit a CU's 160 KB.
+#define RINGRUN(S, A, WPC) { const int lds = (lds_cu / (WPC)) & ~255; \
+      if (lds >= (S) * kRingSlotBytes) { \
+        CHECK(hipFuncSetAttribute((const void*)stream_ring_dma<S, A>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
+        double ms = time_ms([&] { stream_ring_dma<S, A><<<cus * (WPC), 64, lds>>>(d_f, d_v, tiles, d_out); }, reps); \
+        printf("{\"bench\": \"stream_ring_dma\", \"round\": %d, \"slots\": %d, \"aux\": %d, \"waves_per_cu\": %d, \"lds_per_wave\": %d, \"ms\": %.4f, \"GBps\": %.1f}\n", \
+               round, S, A, WPC, lds, ms, total / ms / 1e6); } }
+      RINGRUN(2, 0, 4) RINGRUN(2, 0, 6) RINGRUN(2, 0, 8) RINGRUN(2, 0, 10) RINGRUN(2, 0, 11)
+      RINGRUN(3, 0, 4) RINGRUN(3, 0, 6) RINGRUN(3, 0, 7)
+      RINGRUN(2, 2, 4) RINGRUN(2, 2, 6) RINGRUN(2, 2, 8) RINGRUN(2, 2, 10) RINGRUN(2, 2, 11)
+      RINGRUN(3, 2, 4) RINGRUN(3, 2, 6) RINGRUN(3, 2, 7)
+#undef RINGRUN
+      fflush(stdout);
+    }
     return 0;
   }
 
