@@ -33,6 +33,7 @@
 #include "pg_hll.h"
 #include "pg_set_pass_layout.h"
 #include "pg_group_plan.h"
+#include "pg_dma_pairs.h"
 #include "pg_chunk_decode.h"
 
 namespace {
@@ -96,6 +97,7 @@ struct Engine {
   int scan_simple_pipe = 1;   // PINOT_GPU_SCAN_SIMPLE_PIPE: 0 never scan_simple_pipe_kernel, 1 by the estimated selectivity of the leaf (choose_scan_kernel), 2 whenever
                              // the shape allows, whatever the estimate (pg_scan_simple_pipe.h)
   int scan_simple_dma = 1;    // PINOT_GPU_SCAN_SIMPLE_DMA: 0 never scan_simple_dma_kernel, 1 by rule (choose_scan_kernel), 2 whenever the shape allows (pg_scan_simple_dma.h)
+  int dma_pair = 1;           // PINOT_GPU_SCAN_SIMPLE_DMA_PAIR: 0 the ring kernel's generic form for every width pair; otherwise scan_simple_dma_pair_kernel where the pair has an instance
   int dma_nt = -1;            // PINOT_GPU_SCAN_SIMPLE_DMA_NT: 0 / 1 forces the default / the non-temporal cache policy; unset = by the columns' size
   int dma_blocks_per_cu = 0;  // PINOT_GPU_SCAN_SIMPLE_DMA_BLOCKS_PER_CU: workgroups per CU (what registers and LDS admit still bounds it); 0 = the rule's
   bool scan_simple = true;   // PINOT_GPU_SCAN_SIMPLE=0: one-leaf / one-column queries stay in scan_private_kernel (half the waves per SIMD)
@@ -2026,6 +2028,8 @@ pg_status pg_init(const pg_config* config) {
   g_engine.scan_simple_pipe = spp ? (spp[0] == '0' ? 0 : (spp[0] == '2' ? 2 : 1)) : 1;
   const char* sdm = getenv("PINOT_GPU_SCAN_SIMPLE_DMA");
   g_engine.scan_simple_dma = sdm ? (sdm[0] == '0' ? 0 : (sdm[0] == '2' ? 2 : 1)) : 1;
+  const char* sdp = getenv("PINOT_GPU_SCAN_SIMPLE_DMA_PAIR");
+  g_engine.dma_pair = sdp && sdp[0] == '0' ? 0 : 1;
   const char* sdn = getenv("PINOT_GPU_SCAN_SIMPLE_DMA_NT");
   g_engine.dma_nt = sdn ? (sdn[0] == '0' ? 0 : 1) : -1;
   const char* sdb = getenv("PINOT_GPU_SCAN_SIMPLE_DMA_BLOCKS_PER_CU");
@@ -3082,6 +3086,7 @@ struct ScanChoice {
   bool hist_guarded = false;               // ... and whether they are the guarded tier's
   bool pipe = false;                       // Simple: scan_simple_pipe_kernel, the form with both columns' loads pipelined across tiles (same id, same batch kind)
   bool dma = false, dma_nt = false;        // Simple: scan_simple_dma_kernel, the two columns through a wave-private LDS ring (same id, same batch kind); goes before `pipe`
+  bool dma_pair = false;                   // ... in its form with both widths compile-time constants (scan_simple_dma_pair_kernel)
   int dma_blocks_per_cu = 0;               // ... its workgroups per CU
 };
 // scan_simple_pipe_kernel always loads the aggregated column: it wins where scan_simple_kernel's lane skip and sparse walk have nothing to
@@ -3094,15 +3099,17 @@ constexpr int kPipeMinSelectivityPct = 5;
 // measured) and room for kDmaBlocksPerCu workgroups of four waves per CU (one workgroup per CU is slower than the pipelined kernel: the
 // decode of four waves does not cover the CU's stream).  Non-temporal loads when the two columns together exceed the Infinity Cache (a smaller
 // segment queried again is served from it).  DESIGN.md 4.1g has the tables the figures come from.
+// kDmaMinSlotBytes, kDmaBlocksPerCu and the LDS budget are pg_dma_pairs.h's: the pairs that pass them are the pairs scan_simple_dma_pair_kernel,
+// the form with a straight-line tile, is instantiated for (dma_pair_admitted); every other pair the switch at 2 sends here keeps the generic form.
 constexpr int kDmaMinTilesPerWave = 8;
-constexpr int kDmaMinSlotBytes = 6912;
-constexpr int kDmaBlocksPerCu = 2;
+static_assert(kDmaLdsBudget == kLdsBudget, "pg_dma_pairs.h prices the rings against this budget");
 constexpr long long kInfinityCacheBytes = 256ll << 20;
 static void plan_scan_simple_dma(const pg_segment* seg, int filter_bits, int value_bits, bool dense, ScanChoice* k) {
   const int bpc = std::min(blocks_scan_simple_dma(filter_bits, value_bits, kLdsBudget), g_engine.dma_blocks_per_cu > 0 ? g_engine.dma_blocks_per_cu : kDmaBlocksPerCu);
   if (bpc < 1) return;      // (does not happen: one workgroup's rings of the widest pair are half the budget)
   k->dma_blocks_per_cu = bpc;
-  const long long tiles = doc_tiles(seg), slot_bytes = 256ll * (filter_bits + value_bits);
+  const long long tiles = doc_tiles(seg), slot_bytes = dma_slot_bytes(filter_bits, value_bits);
+  k->dma_pair = g_engine.dma_pair != 0 && scan_simple_dma_pair_shape(filter_bits, value_bits);
   k->dma_nt = g_engine.dma_nt >= 0 ? g_engine.dma_nt == 1 : tiles * slot_bytes > kInfinityCacheBytes;
   const long long resident_waves = (long long)seg->num_cus * bpc * (kBlockThreads / 64);
   k->dma = g_engine.scan_simple_dma == 2 || (dense && slot_bytes >= kDmaMinSlotBytes && bpc >= kDmaBlocksPerCu && tiles >= kDmaMinTilesPerWave * resident_waves);
@@ -3395,7 +3402,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::Narrow: case ScanKernel::NarrowSingle: launch_scan_narrow(k.kernel == ScanKernel::NarrowSingle, g.blocks, stream, sp); break;
     case ScanKernel::Sparse: launch_scan_sparse(one, g.blocks, stream, sp); break;
     case ScanKernel::Simple: case ScanKernel::SimpleSet:
-      if (k.dma) launch_scan_simple_dma(g.blocks, k.dma_nt, stream, sp);
+      if (k.dma) launch_scan_simple_dma(g.blocks, k.dma_nt, k.dma_pair, stream, sp);
       else if (k.pipe) launch_scan_simple_pipe(g.blocks, lean_threads, stream, sp);
       else launch_scan_simple(g.blocks, lean_threads, stream, sp, k.kernel == ScanKernel::SimpleSet);
       break;

@@ -59,7 +59,16 @@ int waves_scan_simple_pipe();          // the least over the instantiations
 // larger than the Infinity Cache).  Workgroups of kBlockThreads; the dynamic LDS is scan_simple_dma_lds(...).
 constexpr int kDmaSlots = 2;      // (three slots leave room for one workgroup per CU at the headline's widths: measured slower)
 size_t scan_simple_dma_lds(int filter_bits, int value_bits);
-void launch_scan_simple_dma(int blocks, bool nt, hipStream_t stream, const ScanParams& p);
+// scan_simple_dma_pair_kernel<FB, VB, aux>: the same ring with both widths compile-time constants, a straight-line tile; one instance per pair
+// the rule admits (pg_dma_pairs.h).  scan_simple_dma_pair_shape: the pair has one.  pair: launch it (the generic kernel otherwise).
+// Its instances are spread over kDmaPairParts translation units (pg_unit_scan_simple_dma_pair*.hip); part k keeps the table's entries k, k + 3, ...
+bool scan_simple_dma_pair_shape(int filter_bits, int value_bits);
+typedef void (*DmaKernel)(const ScanParams);
+constexpr int kDmaPairParts = 3;
+DmaKernel scan_simple_dma_pair_part0(int at, bool nt);
+DmaKernel scan_simple_dma_pair_part1(int at, bool nt);
+DmaKernel scan_simple_dma_pair_part2(int at, bool nt);
+void launch_scan_simple_dma(int blocks, bool nt, bool pair, hipStream_t stream, const ScanParams& p);
 int blocks_scan_simple_dma(int filter_bits, int value_bits, size_t lds_budget);      // resident workgroups per CU: registers and LDS
 // scan_simple_valid_kernel: the same shape behind one PG_PRED_DOC_SET leaf (p.bitmaps[0] = the doc set; p.nodes[0] = the range leaf, if any);
 // skip_empty_tiles: the form whose tiles without a valid doc skip the filter column too

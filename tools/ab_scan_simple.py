@@ -1,7 +1,8 @@
 """A/B of scan_simple_kernel, scan_simple_pipe_kernel and scan_simple_dma_kernel on a RESIDENT C2b segment (bench.py's: v 17-bit, f 10-bit
 over 1000 values): SELECT SUM(v) WHERE f < t at a list of selectivities, the switches flipped in one process -- `simple`
-(PINOT_GPU_SCAN_SIMPLE_PIPE=0, PINOT_GPU_SCAN_SIMPLE_DMA=0), `pipe` (the pipelined kernel whatever the estimate) and `dma` (the LDS-ring
-kernel whatever the rule says; --dma-configs adds other launches of it: `blocks_per_cu[:nt]`, e.g. 1,2:0,2:1).  Engine.reinit
+(PINOT_GPU_SCAN_SIMPLE_PIPE=0, PINOT_GPU_SCAN_SIMPLE_DMA=0), `pipe` (the pipelined kernel whatever the estimate), `dma` (the LDS-ring
+kernel's generic form whatever the rule says, PINOT_GPU_SCAN_SIMPLE_DMA_PAIR=0; --dma-configs adds other launches of it: `blocks_per_cu[:nt]`,
+e.g. 1,2:0,2:1) and `pair` (the ring kernel's instance for the two widths, scan_simple_dma_pair_kernel; --settings dma,pair).  Engine.reinit
 re-reads the switches, the segment stays open.  The settings alternate within every round, so that a drift of the clocks falls on all.
 
   python tools/ab_scan_simple.py [--rows N] [--steps K] [--warmup W] [--rounds R] [--selectivities 1,2,3,5,7,10,25,50] [--settings simple,pipe,dma]
@@ -23,8 +24,12 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 PIPE, DMA, BPC, NT = "PINOT_GPU_SCAN_SIMPLE_PIPE", "PINOT_GPU_SCAN_SIMPLE_DMA", "PINOT_GPU_SCAN_SIMPLE_DMA_BLOCKS_PER_CU", "PINOT_GPU_SCAN_SIMPLE_DMA_NT"
-UNSET = {PIPE: None, DMA: None, BPC: None, NT: None}
-BASE_SETTINGS = {"simple": dict(UNSET, **{PIPE: "0", DMA: "0"}), "pipe": dict(UNSET, **{PIPE: "2", DMA: "0"}), "dma": dict(UNSET, **{DMA: "2"})}
+PAIR = "PINOT_GPU_SCAN_SIMPLE_DMA_PAIR"
+UNSET = {PIPE: None, DMA: None, BPC: None, NT: None, PAIR: None}
+# `dma`: the ring kernel's generic form (scan_simple_dma_kernel<N, aux>); `pair`: its form with both widths compile-time constants
+# (scan_simple_dma_pair_kernel<10, 17, aux> here), which is what the switch at 2 alone launches for this segment
+BASE_SETTINGS = {"simple": dict(UNSET, **{PIPE: "0", DMA: "0"}), "pipe": dict(UNSET, **{PIPE: "2", DMA: "0"}), "dma": dict(UNSET, **{DMA: "2", PAIR: "0"}),
+                 "pair": dict(UNSET, **{DMA: "2"})}
 
 
 def main():
@@ -53,7 +58,7 @@ def main():
     SETTINGS = [(name, BASE_SETTINGS[name]) for name in args.settings.split(",") if name]
     for cfg in [c for c in args.dma_configs.split(",") if c]:
         parts = cfg.split(":")
-        SETTINGS.append(("dma-b%s%s" % (parts[0], "-nt" + parts[1] if len(parts) > 1 else ""), dict(UNSET, **{DMA: "2", BPC: parts[0], NT: parts[1] if len(parts) > 1 else None})))
+        SETTINGS.append(("dma-b%s%s" % (parts[0], "-nt" + parts[1] if len(parts) > 1 else ""), dict(UNSET, **{DMA: "2", PAIR: "0", BPC: parts[0], NT: parts[1] if len(parts) > 1 else None})))
     spec_of = lambda pct: Q.QuerySpec([(Q.SUM, 0)], filter=Q.leaf(Q.Pred.dict_range(1, 0, pct * 10)))
     answer = lambda r: (r.stats[0], [(a.count, a.sum_i64) for a in r.aggregations])
     engine = Engine(device_id=0, time_kernels=True)

@@ -31,6 +31,12 @@ SIZES = {"tiny": 100_003, "large": 12_300_017}
 
 # column numbers of the table's segment
 V, F, K, W8, W16, W32, A, B, C2, RI, RL, RD, DL, X, Y, Z, K1, K2, K3, WN, K4 = range(21)
+# ... and one column per width 7 .. 20 behind them, for scan_simple_dma_pair_kernel's instances (values = dictIds: affine, so that a SUM reads the
+# packed column itself); 10 and 17 bits are F and V
+PAIR_BITS = range(7, 21)
+PAIR_COL = {bits: 21 + i for i, bits in enumerate(b for b in PAIR_BITS if b not in (10, 17))}
+PAIR_COL.update({10: F, 17: V})
+pair_cardinality = lambda bits: 2 ** bits - 5
 
 
 def irregular(card, seed, lo=-2 ** 31, hi=2 ** 31 - 1):
@@ -43,7 +49,10 @@ def irregular(card, seed, lo=-2 ** 31, hi=2 ** 31 - 1):
 def build_segment(S, n, seed=1):
     ids = lambda s, card: S.synthetic_dict_ids(seed * 1000 + s, 0, n, card)
     rng = np.random.default_rng(seed)
-    cols = [None] * 21
+    cols = [None] * (21 + len(PAIR_BITS) - 2)
+    for bits, at in PAIR_COL.items():
+        if at >= 21:
+            cols[at] = S.Column.synthetic_uniform("p%d" % bits, n, np.arange(pair_cardinality(bits), dtype=np.int32), seed=seed * 1000 + 100 + bits)
     cols[V] = S.Column.synthetic_uniform("v", n, (np.arange(100000, dtype=np.int64) * 7 + 3).astype(np.int32), seed=seed * 1000 + 1)
     cols[F] = S.Column.synthetic_uniform("f", n, np.arange(1000, dtype=np.int32), seed=seed * 1000 + 2)
     cols[K] = S.Column.synthetic_uniform("k", n, np.arange(1000, dtype=np.int32) * 3 - 7, seed=seed * 1000 + 3)
@@ -96,13 +105,25 @@ def table(Q, n):
                     Q.QuerySpec([(Q.MAX, vcol), (Q.COUNT, -1)] + ([(Q.SUM, V)] if vcol == V else []), filter=L(Q.Pred.dict_range(fcol, lo, hi))))
     # scan_simple_dma_kernel<N, aux>: the same queries through a wave-private LDS ring, N = the LDS-DMA instructions of a tile (the two
     # columns' sixteen-byte-load classes added up, 2 .. 10), aux 0 / 2 (default / non-temporal loads).  With the switch at 2 every
-    # instance; by the rule neither regime's segment is large enough for it (f < 100 above stays with the pipelined kernel).
+    # instance; by the rule neither regime's segment is large enough for it (f < 100 above stays with the pipelined kernel).  (The pair
+    # switch at 0: N = 8, 9 and 10 here are pairs with an instance of the pair kernel below.)
     dma_pairs = [(1, 1), (1, 2), (2, 2), (2, 3), (3, 3), (3, 4), (4, 4), (4, 5), (5, 5)]
     for nf4, nv4 in dma_pairs:
         (fcol, lo, hi), vcol = pipe_filters[nf4 - 1], pipe_values[nv4 - 1]
         for nt in (0, 1):
-            add("dma-%d-nt%d" % (nf4 + nv4, nt), {"PINOT_GPU_SCAN_SIMPLE_DMA": "2", "PINOT_GPU_SCAN_SIMPLE_DMA_NT": str(nt)},
+            add("dma-%d-nt%d" % (nf4 + nv4, nt), {"PINOT_GPU_SCAN_SIMPLE_DMA": "2", "PINOT_GPU_SCAN_SIMPLE_DMA_NT": str(nt), "PINOT_GPU_SCAN_SIMPLE_DMA_PAIR": "0"},
                 "scan_simple_kernel", Q.QuerySpec([(Q.MAX, vcol), (Q.COUNT, -1)] + ([(Q.SUM, V)] if vcol == V else []), filter=L(Q.Pred.dict_range(fcol, lo, hi))))
+    # scan_simple_dma_pair_kernel<FB, VB, aux>: the ring kernel with both widths compile-time constants, one instance per pair the rule admits
+    # (pinot_amd/csrc/pg_dma_pairs.h: 27 <= FB + VB <= 38, both up to 20) and cache policy; the entries above set its switch to 0 to reach the generic
+    # form.  The two policies of a pair share one query and one oracle answer (`want_key`).
+    for fb in PAIR_BITS:
+        for vb in PAIR_BITS:
+            if 27 <= fb + vb <= 38:
+                card = 1000 if fb == 10 else (100000 if fb == 17 else pair_cardinality(fb))
+                spec = Q.QuerySpec([(Q.MAX, PAIR_COL[vb]), (Q.COUNT, -1), (Q.SUM, PAIR_COL[vb])], filter=L(Q.Pred.dict_range(PAIR_COL[fb], card // 4, card // 2)))
+                spec.want_key = "pair-%d-%d" % (fb, vb)
+                for nt in (0, 1):
+                    add("pair-%d-%d-nt%d" % (fb, vb, nt), {"PINOT_GPU_SCAN_SIMPLE_DMA": "2", "PINOT_GPU_SCAN_SIMPLE_DMA_NT": str(nt)}, "scan_simple_kernel", spec)
     add("simple-set", {}, "scan_simple_kernel", Q.QuerySpec([(Q.SUM, V), (Q.COUNT, -1)], filter=L(Q.Pred.dict_set(F, list(range(0, 300, 3)), 1000))))      # scan_simple_set_kernel: the one leaf an IN list, its words in LDS
     add("raw", {}, "scan_raw_kernel", Q.QuerySpec([(Q.COUNT, -1)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))
     add("raw-sum", {}, "scan_raw_kernel", Q.QuerySpec([(Q.SUM, RI), (Q.MAX, RI)], filter=L(Q.Pred.raw_range(RI, -1000, 250000))))
@@ -300,6 +321,7 @@ def main():
     wants = {}
 
     def want_of(key, spec):
+        key = getattr(spec, "want_key", key)
         if key not in wants:
             wants[key] = oracle.execute(seg, getattr(spec, "oracle_spec", spec))      # (raw IN lists: the equivalent range, see table())
         return wants[key]

@@ -81,6 +81,105 @@ __device__ __forceinline__ uint32_t ring_consume(const uint8_t* slot, int lane) 
   return x;
 }
 
+// 1c'. what a decode behind the ring costs (`microbench ring-decode`): the same ring, the lane's 27 dwords consumed three ways --
+//   kDecode 0   folded by xor, nothing decoded (ring_consume above)
+//   kDecode 1   the per-value VALU of the two decodes at compile-time widths: 32 ten-bit values compared with a bound and shifted into a mask,
+//               32 seventeen-bit values summed under the mask with a 24-bit multiply-add (the scan kernels' per-value code, all 27 reads first)
+//   kDecode 2   the same two decodes, each behind a switch on a run-time width in halves of sixteen values, as scan_simple_dma_kernel has them
+// The bound is a kernel argument (span = 100 of 1024); the buffers are memset bytes, so every lane decodes the same values.
+template <int B, int H>
+__device__ __forceinline__ void ring_decode16(const uint32_t* w, uint32_t (&v)[16]) {
+  constexpr int first_bit = 16 * B * H, w0 = first_bit >> 5, w1 = (16 * B * (H + 1) - 1) >> 5, NW = w1 - w0 + 1;
+  uint32_t d[NW];
+#pragma unroll
+  for (int i = 0; i < NW; ++i) d[i] = __builtin_bswap32(w[w0 + i]);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int bit = first_bit + j * B - w0 * 32, i = bit >> 5, o = bit & 31;
+    if (o + B <= 32) v[j] = __builtin_amdgcn_ubfe(d[i], 32 - o - B, B);
+    else v[j] = __builtin_amdgcn_alignbit(d[i], d[(i + 1) < NW ? (i + 1) : i], 64 - o - B) & ((1u << B) - 1u);
+  }
+}
+template <int B, int H, typename WP>
+__device__ __forceinline__ void ring_range16(WP w, uint32_t span, uint32_t& m) {
+  uint32_t v[16];
+  uint32_t r[(16 * B * (H + 1) - 1) / 32 + 1];
+#pragma unroll
+  for (int i = (16 * B * H) >> 5; i <= (16 * B * (H + 1) - 1) >> 5; ++i) r[i] = w[i];
+  ring_decode16<B, H>(r, v);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) asm("v_cmp_gt_u32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m) : "v"(v[j]), "s"(span) : "vcc");
+}
+template <int B, int H, typename WP>
+__device__ __forceinline__ void ring_sum16(WP w, uint32_t m, uint32_t& psum) {
+  uint32_t v[16];
+  uint32_t r[(16 * B * (H + 1) - 1) / 32 + 1];
+#pragma unroll
+  for (int i = (16 * B * H) >> 5; i <= (16 * B * (H + 1) - 1) >> 5; ++i) r[i] = w[i];
+  ring_decode16<B, H>(r, v);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) psum = __umul24(v[j], __builtin_amdgcn_ubfe(m, 16 * H + j, 1)) + psum;
+}
+typedef const __attribute__((address_space(3))) uint32_t* RingLdsWords;
+template <int kDecode>
+__device__ __forceinline__ uint32_t ring_consume_decoded(const uint8_t* slot, int lane, uint32_t span, int fb, int vb) {
+  const RingLdsWords fw = (RingLdsWords)reinterpret_cast<const uint32_t*>(slot + lane * 40);
+  const RingLdsWords vw = (RingLdsWords)reinterpret_cast<const uint32_t*>(slot + kRingFBytes + lane * 68);
+  uint32_t m = 0, psum = 0;
+  if (kDecode == 1) {
+    uint32_t fd[10], vd[17];      // every read first, each dword once
+#pragma unroll
+    for (int i = 0; i < 10; ++i) fd[i] = fw[i];
+#pragma unroll
+    for (int i = 0; i < 17; ++i) vd[i] = vw[i];
+    ring_range16<10, 0>((const uint32_t*)fd, span, m); ring_range16<10, 1>((const uint32_t*)fd, span, m);
+    m = __builtin_bitreverse32(m);
+    ring_sum16<17, 0>((const uint32_t*)vd, m, psum); ring_sum16<17, 1>((const uint32_t*)vd, m, psum);
+  } else {
+    switch (fb) {
+#define RING_CASE(B) case B: ring_range16<B, 0>(fw, span, m); ring_range16<B, 1>(fw, span, m); break;
+      RING_CASE(1) RING_CASE(2) RING_CASE(3) RING_CASE(4) RING_CASE(5) RING_CASE(6) RING_CASE(7) RING_CASE(8) RING_CASE(9) RING_CASE(10)
+      RING_CASE(11) RING_CASE(12) RING_CASE(13) RING_CASE(14) RING_CASE(15) RING_CASE(16) RING_CASE(17) RING_CASE(18) RING_CASE(19) RING_CASE(20)
+#undef RING_CASE
+      default: break;
+    }
+    m = __builtin_bitreverse32(m);
+    switch (vb) {
+#define RING_CASE(B) case B: ring_sum16<B, 0>(vw, m, psum); ring_sum16<B, 1>(vw, m, psum); break;
+      RING_CASE(1) RING_CASE(2) RING_CASE(3) RING_CASE(4) RING_CASE(5) RING_CASE(6) RING_CASE(7) RING_CASE(8) RING_CASE(9) RING_CASE(10)
+      RING_CASE(11) RING_CASE(12) RING_CASE(13) RING_CASE(14) RING_CASE(15) RING_CASE(16) RING_CASE(17) RING_CASE(18) RING_CASE(19) RING_CASE(20)
+#undef RING_CASE
+      default: break;
+    }
+  }
+  return psum + (uint32_t)__builtin_popcount(m);
+}
+
+// (kS = 2; fb / vb: the two widths as run-time values, 10 and 17 at every call)
+template <int kDecode, int kAux>
+__global__ __launch_bounds__(64) void stream_ring_decode(const uint8_t* __restrict__ f, const uint8_t* __restrict__ v, uint32_t num_tiles, uint32_t span, int fb, int vb,
+                                                         unsigned long long* out) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t ring[];
+  const int lane = threadIdx.x;
+  const uint32_t wave = blockIdx.x, waves = gridDim.x;
+  const uint32_t n = wave < num_tiles ? (num_tiles - wave + waves - 1) / waves : 0;
+  uint32_t acc = 0;
+  if (n >= 2u) {
+    ring_issue<kAux>(f, v, wave, ring, lane);
+    uint32_t rd = 0, i = 0;
+    for (; i + 1 < n; ++i) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      ring_issue<kAux>(f, v, wave + (size_t)(i + 1) * waves, ring + (1 - rd) * kRingSlotBytes, lane);
+      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      acc += kDecode == 0 ? ring_consume(ring + rd * kRingSlotBytes, lane) : ring_consume_decoded<kDecode>(ring + rd * kRingSlotBytes, lane, span, fb, vb);
+      rd = 1 - rd;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    acc += kDecode == 0 ? ring_consume(ring + rd * kRingSlotBytes, lane) : ring_consume_decoded<kDecode>(ring + rd * kRingSlotBytes, lane, span, fb, vb);
+  }
+  if (acc == 0x12345678u) out[0] = acc;
+}
+
 template <int kS, int kAux>
 __global__ __launch_bounds__(64) void stream_ring_dma(const uint8_t* __restrict__ f, const uint8_t* __restrict__ v, uint32_t num_tiles, unsigned long long* out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t ring[];
@@ -426,6 +525,33 @@ int main(int argc, char** argv) {
       RINGRUN(2, 2, 4) RINGRUN(2, 2, 6) RINGRUN(2, 2, 8) RINGRUN(2, 2, 10) RINGRUN(2, 2, 11)
       RINGRUN(3, 2, 4) RINGRUN(3, 2, 6) RINGRUN(3, 2, 7)
 #undef RINGRUN
+      fflush(stdout);
+    }
+    return 0;
+  }
+
+  if (argc > 1 && !strcmp(argv[1], "ring-decode")) {
+    // The headline's shape (10 + 17 bits, 2 slots x 8 waves per CU, nt): what the LDS reads, the arithmetic and the run-time switches cost
+    // behind the ring's stream.  Three rounds of ten launches, the variants alternating within a round.
+    const uint32_t tiles = 488282;
+    const size_t fbytes = (size_t)tiles * kRingFBytes, vbytes = (size_t)tiles * kRingVBytes, total = fbytes + vbytes;
+    uint8_t *d_f, *d_v;
+    CHECK(hipMalloc((void**)&d_f, fbytes));
+    CHECK(hipMalloc((void**)&d_v, vbytes));
+    CHECK(hipMemset(d_f, 0x5a, fbytes));
+    CHECK(hipMemset(d_v, 0xa5, vbytes));
+    const int wpc = 8, lds = ((160 * 1024) / wpc) & ~255, reps = 10;
+    const int fb = argc > 2 ? atoi(argv[2]) : 10, vb = argc > 3 ? atoi(argv[3]) : 17;      // (run-time values to the compiler)
+    CHECK(hipFuncSetAttribute((const void*)stream_ring_decode<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    CHECK(hipFuncSetAttribute((const void*)stream_ring_decode<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    CHECK(hipFuncSetAttribute((const void*)stream_ring_decode<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    time_ms([&] { stream_ring_decode<0, 2><<<cus * wpc, 64, lds>>>(d_f, d_v, tiles, 100u, fb, vb, d_out); }, 48);      // (the clock transient after idle)
+    for (int round = 0; round < 3; ++round) {
+#define DECODERUN(D, WHAT) { double ms = time_ms([&] { stream_ring_decode<D, 2><<<cus * wpc, 64, lds>>>(d_f, d_v, tiles, 100u, fb, vb, d_out); }, reps); \
+      printf("{\"bench\": \"stream_ring_decode\", \"round\": %d, \"variant\": \"%s\", \"slots\": 2, \"aux\": 2, \"waves_per_cu\": %d, \"ms\": %.4f, \"GBps\": %.1f}\n", \
+             round, WHAT, wpc, ms, total / ms / 1e6); }
+      DECODERUN(0, "i: 27 ds_reads folded by xor") DECODERUN(1, "ii: + both decodes at compile-time widths") DECODERUN(2, "iii: + the run-time width switches")
+#undef DECODERUN
       fflush(stdout);
     }
     return 0;
