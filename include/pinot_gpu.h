@@ -57,6 +57,7 @@ extern "C" {
                             *    (still 5) PG_AGG_PERCENTILE / PG_AGG_DISTINCTCOUNT on raw columns, pg_result_value_counts: no struct layout changed, one function added;
                             *    (still 5) PG_DISTINCT_LDS_MAX_DICT_IDS: a diagnostic constant beside PG_PERCENTILE_LDS_MAX_COUNTERS, nothing else;
                             *    (still 5) PG_AGG_DISTINCTCOUNTHLL / PG_AGG_HLL(log2m), pg_result_hll_registers: no struct layout changed, one enumerator and one function added;
+                            *    (still 5) PG_AGG_VARIANCE, pg_result_moments: no struct layout changed, one enumerator and one function added;
                             *    (still 5) PG_STAGED_SET_LDS_WORDS: a diagnostic constant beside PG_DISTINCT_LDS_MAX_DICT_IDS, nothing else;
                             *    (still 5) LZ4 / SNAPPY chunks behind PG_FWD_RAW_FIXED_BYTE, PG_CHUNK_DECODE_MAX_BYTES (a diagnostic constant): no struct layout changed, no function added */
 
@@ -247,7 +248,7 @@ typedef enum pg_agg_function {
                                 * columns are never resident: pg_segment_open declines them; LZ4 / SNAPPY chunks are decoded at open); a
                                 * PG_AGG_DISTINCTCOUNT in the same query; GROUP BY outside the conditions PG_AGG_DISTINCTCOUNT sets, or counter
                                 * matrices above PG_PERCENTILE_GROUP_MAX_BYTES. */
-  PG_AGG_DISTINCTCOUNTHLL = 7  /* DistinctCountHLLAggregationFunction.java: the HyperLogLog sketch of the matching docs' values -- 2^log2m registers of one
+  PG_AGG_DISTINCTCOUNTHLL = 7, /* DistinctCountHLLAggregationFunction.java: the HyperLogLog sketch of the matching docs' values -- 2^log2m registers of one
                                 * rank each (DESIGN.md section 4.1s states the hash, the rank rule and the estimator).  log2m travels in the function word:
                                 * PG_AGG_HLL(log2m); the plain enumerator means log2m 8 (CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M).  log2m outside
                                 * [PG_HLL_MIN_LOG2M, PG_HLL_MAX_LOG2M], or bits above the low byte on any other function: PG_ERR_INVALID_ARGUMENT.
@@ -262,6 +263,22 @@ typedef enum pg_agg_function {
                                 * PG_ERR_UNSUPPORTED at plan time: everything PG_AGG_DISTINCTCOUNT names; raw and dictionary HLL columns in one query; a raw
                                 * HLL beside any DISTINCTCOUNT (it would need a second pass); any HLL beside a PERCENTILE; more than four (column, log2m) pairs; registers of the raw form beyond the LDS
                                 * budget; GROUP BY register matrices above PG_HLL_GROUP_MAX_BYTES. */
+  PG_AGG_VARIANCE = 8          /* VarianceAggregationFunction.java (:42-201) -- VAR_POP, VAR_SAMP, STDDEV_POP and STDDEV_SAMP: one enumerator, because all four
+                                * share the intermediate VarianceTuple(count, sum, m2) (segment-local customobject/VarianceTuple.java:29-64).  On a
+                                * dictionary-encoded or raw (PG_FWD_RAW_FIXED_BYTE) INT / LONG / FLOAT / DOUBLE column; the value is converted to double as
+                                * StatisticalAggregationFunctionUtils.getValSet does.  pg_agg_value.count = the docs aggregated; sum / sum_i64 / sum_exact =
+                                * exactly what a PG_AGG_SUM on the same column yields in the same query; min = +inf, max = -inf.  count, sum and
+                                * m2 = sum((x - mean)^2) come from pg_result_moments.  The final value (m2 / n, m2 / (n - 1), their square roots;
+                                * Double.NEGATIVE_INFINITY for count 0, and for count 1 in the sample forms: extractFinalResult :181-201) is taken where tuples
+                                * are merged, not here.  Two runs: the ordinary query with the function turned into AVG, then one
+                                * pass of scan_moments_kernel / group_moments_kernel behind the same filter that accumulates sum(x - c) and sum((x - c)^2)
+                                * around c = sum / count; m2 = S2 - S1^2 / n, raised to 0 if it comes out negative.  A NaN or an infinity among the values
+                                * makes m2 NaN (where VarianceTuple.apply :35-42 ends too).  count 0: m2 = 0, the pass is not launched.  There is no metadata
+                                * fast path: the reference always scans, and numEntriesScannedPostFilter counts the column as projected.
+                                * PG_ERR_UNSUPPORTED at plan time: the column carries a null value vector under PG_QUERY_NULL_HANDLING; a PG_AGG_DISTINCTCOUNT,
+                                * PG_AGG_PERCENTILE or PG_AGG_DISTINCTCOUNTHLL in the same query; more than four distinct VARIANCE columns; a range
+                                * predicate on a raw LONG / FLOAT / DOUBLE column beside it; GROUP BY outside the conditions PG_AGG_DISTINCTCOUNT states, or
+                                * moment matrices above PG_MOMENTS_GROUP_MAX_BYTES; whatever the ordinary query itself declines. */
 } pg_agg_function;
 
 #define PG_AGG_HLL(log2m) (PG_AGG_DISTINCTCOUNTHLL | ((log2m) << 8))
@@ -271,6 +288,9 @@ typedef enum pg_agg_function {
 /* GROUP BY with PG_AGG_DISTINCTCOUNTHLL: group_id_upper_bound x 2^log2m x 4 bytes (the registers are staged as 32-bit words), summed over the query's
  * HLL aggregations (dictionary form) or columns (raw form), may not exceed this; PINOT_GPU_GROUP_TABLE_BYTES bounds it too. */
 #define PG_HLL_GROUP_MAX_BYTES (1ull << 30)
+/* GROUP BY with PG_AGG_VARIANCE: group_id_upper_bound x 24 bytes (S1, S2 and the pivot, a double each) x the query's distinct VARIANCE columns may not
+ * exceed this; PINOT_GPU_GROUP_TABLE_BYTES bounds it too. */
+#define PG_MOMENTS_GROUP_MAX_BYTES (1ull << 30)
 
 /* GROUP BY with PG_AGG_DISTINCTCOUNT: group_id_upper_bound x ceil(cardinality / 32) x 4 bytes, summed over the query's DISTINCTCOUNT columns,
  * may not exceed this (a capacity limit: it bounds the host copy of the result; PINOT_GPU_GROUP_TABLE_BYTES bounds the device's). */
@@ -390,6 +410,8 @@ typedef enum pg_kernel_id {
   PG_KERNEL_GROUP_COLLECT = 19,    /* group_collect_kernel: the same under GROUP BY, every doc's raw group id beside its images */
   PG_KERNEL_SCAN_HLL = 20,         /* scan_hll_kernel: DISTINCTCOUNTHLL of raw columns, 2^log2m 32-bit registers per column in LDS, max-merged into the query's row in HBM */
   PG_KERNEL_GROUP_HLL = 21,        /* group_hll_kernel: the same under GROUP BY, one register row per raw group id in HBM */
+  PG_KERNEL_SCAN_MOMENTS = 22,     /* scan_moments_kernel: VARIANCE's pass, sum(x - c) and sum((x - c)^2) of raw or dictionary columns, one record per workgroup combined in workgroup order */
+  PG_KERNEL_GROUP_MOMENTS = 23,    /* group_moments_kernel: the same under GROUP BY, one {S1, S2} row per raw group id in HBM (double atomics: the last bits may differ run to run) */
   PG_KERNEL_SCAN_HIST = 6          /* scan_hist_kernel: lane-private scan, SUM = sum_d matches[d] * dictionary[d] through an LDS histogram */
 } pg_kernel_id;
 
@@ -515,6 +537,12 @@ pg_status pg_result_value_counts(const pg_result* result, int32_t aggregation, i
  * aggregation index or row: PG_ERR_INVALID_ARGUMENT.  (Registers of equal log2m merge by the register-wise maximum, across segments too.) */
 pg_status pg_result_hll_registers(const pg_result* result, int32_t aggregation, int32_t group_row,
                                   const uint8_t** out_registers, int32_t* out_num_registers);
+
+/* The VarianceTuple behind a PG_AGG_VARIANCE aggregation: *out_count docs aggregated, *out_sum their sum as a double (pg_agg_value.sum),
+ * *out_m2 = sum((x - mean)^2) -- 0 for count 0, NaN when a value is NaN or infinite.  group_row = -1 for an aggregation-only query, else a row of
+ * group_aggregations.  Any other aggregation index or row: PG_ERR_INVALID_ARGUMENT.  (Tuples merge by VarianceTuple.apply(VarianceTuple) :55-64.) */
+pg_status pg_result_moments(const pg_result* result, int32_t aggregation, int32_t group_row,
+                            int64_t* out_count, double* out_sum, double* out_m2);
 
 /* How a group-by column's entries of pg_result.group_key_dict_ids turn into key values.  A dictionary column: *out_is_offset = 0, the
  * entry is a dictId (GroupKeyGenerator.getGroupKeys looks it up, DictionaryBasedGroupKeyGenerator.java:260-290).  A raw (no-dictionary)

@@ -97,6 +97,13 @@ char* ph_combine_counts(const char* sql, int32_t num_blocks, const int64_t* bloc
 char* ph_combine_hll(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
                      const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
                      const double* mins, const double* maxs, const uint8_t* is_null, const int64_t* register_offsets, const uint8_t* registers, int32_t* status);
+/* The combine of VarianceTuples (VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP): cell (row, function) of such a function holds the tuple (counts[at],
+ * sums[at], m2s[at]); the combine merges tuples with VarianceTuple.apply(VarianceTuple), the final result is m2 / n, m2 / (n - 1) or their square
+ * root (-Infinity for no doc, and for one doc in the sample forms).  GROUP BY: as ph_group_by_combine; aggregation only: one row per block,
+ * {"combined": <block>}. */
+char* ph_combine_moments(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                         const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                         const double* mins, const double* maxs, const uint8_t* is_null, const double* m2s, int32_t* status);
 /* HyperLogLog.cardinality() of num_registers = 2^log2m registers; -1 when num_registers is not such a count. */
 int64_t ph_hll_cardinality(const uint8_t* registers, int32_t num_registers);
 /* The registers (2^log2m bytes) after offering `num` longs to an empty sketch, computed with the header the kernels include; 0, or 1 for a bad log2m. */

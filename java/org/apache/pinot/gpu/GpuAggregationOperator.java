@@ -47,6 +47,7 @@ import org.apache.pinot.core.query.aggregation.groupby.ObjectGroupByResultHolder
 import org.apache.pinot.core.query.request.context.QueryContext;
 import org.apache.pinot.core.util.GroupByUtils;
 import org.apache.pinot.segment.local.customobject.AvgPair;
+import org.apache.pinot.segment.local.customobject.VarianceTuple;
 import org.apache.pinot.segment.spi.AggregationFunctionType;
 import org.apache.pinot.segment.spi.IndexSegment;
 import org.apache.pinot.segment.spi.index.reader.Dictionary;
@@ -85,6 +86,7 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     Object[] _percentileCounts;   // ... and the int[] of how many matching docs carry each
     Object[] _valueBits;          // DISTINCTCOUNT / PERCENTILE lanes over RAW columns: long[] ascending value bits of aggregation a, row r at a * rows + r; else null
     Object[] _valueCounts;        // ... and the int[] of how many matching docs carry each
+    double[] _m2s;                // variance lanes: m2 of aggregation a, row r at a * rows + r (0 for other functions); else null
     Object[] _hllRegisters;       // DISTINCTCOUNTHLL lanes: byte[] registers of aggregation a, row r at a * rows + r (null for other functions); else null
   }
 
@@ -177,7 +179,10 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       throw new UnsupportedOperationException("segment " + _segment.getSegmentName() + " is no longer resident on the device");
     }
     try {
-      Object[] raw = q._hasHll
+      Object[] raw = q._hasMoments
+          ? PinotGpuNative.executeWithMoments(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
+              q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
+          : q._hasHll
           ? PinotGpuNative.executeWithHllRegisters(_segment.handle(), q._filterNodes, q._predInts, q._predLongs, q._setOffsets, q._setWords,
               q._aggregations, q._groupBy, q._numGroupsLimit, q._flags)
           : q._rawValueLists
@@ -220,6 +225,14 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
       hllRegisters = (Object[]) raw[PinotGpuNative.PGM_HLL_REGISTERS];
       raw = (Object[]) raw[PinotGpuNative.PGM_HLL_RESULT];
     }
+    double[] m2s = null;
+    if (q._hasMoments) {
+      if (raw == null || raw.length != PinotGpuNative.PGM_MOMENTS_SLOTS) {
+        throw new IllegalStateException("native variance result does not match jni/pinot_gpu_jni.c");
+      }
+      m2s = (double[]) raw[PinotGpuNative.PGM_MOMENTS_M2];
+      raw = (Object[]) raw[PinotGpuNative.PGM_MOMENTS_RESULT];
+    }
     Object[] distinctSets = null;
     if (q._hasDistinctCount && !q._rawValueLists) {
       if (raw == null || raw.length != PinotGpuNative.PGM_DISTINCT_SLOTS) {
@@ -256,6 +269,7 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
     result._valueBits = valueBits;
     result._valueCounts = valueCounts;
     result._hllRegisters = hllRegisters;
+    result._m2s = m2s;
     result._rows = _queryContext.getGroupByExpressions() == null ? 1 : result._groupIds.length;
     if (result._header.length != PinotGpuNative.PGM_HEADER_LEN) {
       throw new IllegalStateException("native result header does not match jni/pg_marshal.h");
@@ -273,10 +287,31 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
         AggregationFunctionType type = _functions[positions[i]].getType();
         out[positions[i]] = type == AggregationFunctionType.DISTINCTCOUNT ? valueSet(positions[i], result, i, 0)
             : type == AggregationFunctionType.DISTINCTCOUNTHLL ? sketch(positions[i], result, i, 0)
+            : isVariance(type) ? varianceTuple(result, i, 0, nullHandling)
             : type == AggregationFunctionType.PERCENTILE ? valueList(positions[i], result, i, 0, nullHandling) : intermediate(type, result, i, nullHandling);
       }
     }
     return new AggregationResultsBlock(_functions, Arrays.asList(out), _queryContext);
+  }
+
+  private static boolean isVariance(AggregationFunctionType type) {
+    return type == AggregationFunctionType.VARPOP || type == AggregationFunctionType.VARSAMP || type == AggregationFunctionType.STDDEVPOP
+        || type == AggregationFunctionType.STDDEVSAMP;
+  }
+
+  /**
+   * VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: aggregation {@code at}, row {@code row} of the lane -> the VarianceTuple the reference's function hands
+   * on (extractAggregationResult :143-150 / extractGroupByResult :153-155); null under null handling when no value reached the holder.
+   */
+  private VarianceTuple varianceTuple(LaneResult result, int at, int row, boolean nullHandling) {
+    if (result._m2s == null) {
+      throw new IllegalStateException("native variance result carries no m2");
+    }
+    int cell = row * result._width + at;
+    if (nullHandling && result._counts[cell] == 0) {
+      return null;
+    }
+    return new VarianceTuple(result._counts[cell], result._sums[cell], result._m2s[at * result._rows + row]);
   }
 
   /**
@@ -477,6 +512,16 @@ final class GpuAggregationOperator extends BaseOperator<BaseResultsBlock> {
           ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);
           for (int g = 0; g < rowOf.length; g++) {
             holder.setValueForKey(rowOf[g], sketch(positions[i], r, i, g));
+          }
+          holders[positions[i]] = holder;
+        } else if (isVariance(type)) {
+          // one VarianceTuple per group (setGroupByResult :106-114 keeps one per group key; a group without a value stays null under null handling)
+          ObjectGroupByResultHolder holder = new ObjectGroupByResultHolder(capacity, capacity);
+          for (int g = 0; g < rowOf.length; g++) {
+            VarianceTuple tuple = varianceTuple(r, i, g, nullHandling);
+            if (tuple != null) {
+              holder.setValueForKey(rowOf[g], tuple);
+            }
           }
           holders[positions[i]] = holder;
         } else if (type == AggregationFunctionType.DISTINCTCOUNT) {

@@ -194,7 +194,7 @@ public class GpuPlanMaker extends InstancePlanMakerImplV2 {
     boolean percentile = false;
     boolean hll = false;
     for (GpuAggregationOperator.Lane lane : lanes) {
-      hll |= lane._query._hasHll;
+      hll |= lane._query._hasHll || lane._query._hasMoments;      // (a variance lane likewise runs alone: PinotGpuNative.executeWithMoments)
       distinctCount |= lane._query._hasDistinctCount;
       percentile |= lane._query._hasPercentile;
     }

@@ -66,6 +66,7 @@ final class GpuQueryLowering {
   static final int AGG_DISTINCTCOUNT = PinotGpuNative.PG_AGG_DISTINCTCOUNT;
   static final int AGG_PERCENTILE = PinotGpuNative.PG_AGG_PERCENTILE;
   static final int AGG_DISTINCTCOUNTHLL = PinotGpuNative.PG_AGG_DISTINCTCOUNTHLL;
+  static final int AGG_VARIANCE = PinotGpuNative.PG_AGG_VARIANCE;
   private static final int NODE_INTS = PinotGpuNative.PGM_FILTER_NODE_INTS;
   private static final int PRED_INTS = PinotGpuNative.PGM_PRED_INTS;
   private static final int PRED_LONGS = PinotGpuNative.PGM_PRED_LONGS;
@@ -92,6 +93,7 @@ final class GpuQueryLowering {
     int _flags;
     boolean _hasDistinctCount;      // a DISTINCTCOUNT among the aggregations: executed alone through executeWithDistinctSets, never in a batch
     boolean _hasPercentile;         // a PERCENTILE among the aggregations: executed alone through executeWithPercentileCounts, never in a batch
+    boolean _hasMoments;            // a VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP among the aggregations: executed alone through executeWithMoments, never in a batch
     boolean _hasHll;                // a DISTINCTCOUNTHLL among the aggregations: executed alone through executeWithHllRegisters, never in a batch
     boolean _rawValueLists;         // those DISTINCTCOUNT / PERCENTILE columns are RAW (no dictionary): executed through executeWithValueLists instead
   }
@@ -223,6 +225,14 @@ final class GpuQueryLowering {
           out._hasHll = true;
           break;
         }
+        case VARPOP:
+        case VARSAMP:
+        case STDDEVPOP:
+        case STDDEVSAMP:
+          // VarianceAggregationFunction: one intermediate for all four, VarianceTuple(count, sum, m2); the final value stays with the function object
+          code = AGG_VARIANCE;
+          out._hasMoments = true;
+          break;
         case PERCENTILE:
           // the exact PercentileAggregationFunction (PERCENTILE50(col) / PERCENTILE(col, 50)); the percentile itself stays with the function object:
           // the device returns the whole value list whatever it is
@@ -269,6 +279,9 @@ final class GpuQueryLowering {
     if (out._hasHll && (out._hasDistinctCount || out._hasPercentile)) {
       // one native call returns one kind of intermediate result (and the engine declines most of these mixes itself)
       throw new NotOffloadable("DISTINCTCOUNTHLL beside DISTINCTCOUNT / PERCENTILE in one query");
+    }
+    if (out._hasMoments && (out._hasDistinctCount || out._hasPercentile || out._hasHll)) {
+      throw new NotOffloadable("a variance function beside DISTINCTCOUNT / PERCENTILE / DISTINCTCOUNTHLL in one query");
     }
     // ---- group-by keys: dictionary-encoded identifiers ----
     List<ExpressionContext> groupBy = _queryContext.getGroupByExpressions();

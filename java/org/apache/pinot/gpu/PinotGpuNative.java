@@ -90,6 +90,11 @@ public final class PinotGpuNative {
    * value means log2m 8.  The registers come back through executeWithHllRegisters.
    */
   public static final int PG_AGG_DISTINCTCOUNTHLL = 7;
+  /**
+   * VarianceAggregationFunction -- VAR_POP, VAR_SAMP, STDDEV_POP and STDDEV_SAMP share the intermediate VarianceTuple(count, sum, m2): count and sum are
+   * the aggregation's count and sum, m2 comes back through executeWithMoments.
+   */
+  public static final int PG_AGG_VARIANCE = 8;
   /** PG_AGG_HLL(log2m) of include/pinot_gpu.h: the function word of DISTINCTCOUNTHLL with its log2m; PG_HLL_MIN_LOG2M .. PG_HLL_MAX_LOG2M are offloaded. */
   public static final int PG_HLL_MIN_LOG2M = 4;
   public static final int PG_HLL_MAX_LOG2M = 14;
@@ -245,6 +250,19 @@ public final class PinotGpuNative {
    * registers (one rank each) for a DISTINCTCOUNTHLL aggregation and null for every other function; rows = 1 without GROUP BY, else the groups.
    */
   static native Object[] executeWithHllRegisters(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
+      int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
+
+  /** Slots of executeWithMoments' Object[]: the Object[PGM_RESULT_ARRAYS] of execute(), then the VarianceTuples' m2. */
+  public static final int PGM_MOMENTS_SLOTS = 2;
+  public static final int PGM_MOMENTS_RESULT = 0;
+  public static final int PGM_MOMENTS_M2 = 1;
+
+  /**
+   * pg_execute of a query with PG_AGG_VARIANCE aggregations plus pg_result_moments over its result.  Returns Object[PGM_MOMENTS_SLOTS]: what execute()
+   * returns, and a double[aggregations * rows] whose element {@code aggregation * rows + row} is the m2 of a VARIANCE aggregation's VarianceTuple (its
+   * count and sum are the aggregation's own in the first array) and 0 for every other function; rows = 1 without GROUP BY, else the groups.
+   */
+  static native Object[] executeWithMoments(long handle, int[] filterNodes, int[] predInts, long[] predLongs, int[] setOffsets, int[] setWords,
       int[] aggregations, int[] groupBy, int numGroupsLimit, int flags);
 
   /** Slots of executeWithPercentileCounts' Object[]: the Object[PGM_RESULT_ARRAYS] of execute(), then the lists' dictIds and their counts. */

@@ -42,6 +42,8 @@ enum {
 enum { PGM_DISTINCT_SLOTS = 2, PGM_DISTINCT_RESULT = 0, PGM_DISTINCT_SETS = 1 };
 /* PinotGpuNative.executeWithHllRegisters: Object[PGM_HLL_SLOTS] = {the Object[PGM_RESULT_ARRAYS] of execute(), the DISTINCTCOUNTHLL registers} */
 enum { PGM_HLL_SLOTS = 2, PGM_HLL_RESULT = 0, PGM_HLL_REGISTERS = 1 };
+/* PinotGpuNative.executeWithMoments: Object[PGM_MOMENTS_SLOTS] = {the Object[PGM_RESULT_ARRAYS] of execute(), the VarianceTuples' m2 as one double[]} */
+enum { PGM_MOMENTS_SLOTS = 2, PGM_MOMENTS_RESULT = 0, PGM_MOMENTS_M2 = 1 };
 /* PinotGpuNative.executeWithPercentileCounts: Object[PGM_PERCENTILE_SLOTS] = {the Object[PGM_RESULT_ARRAYS] of execute(), the PERCENTILE lists' dictIds, their counts} */
 enum { PGM_PERCENTILE_SLOTS = 3, PGM_PERCENTILE_RESULT = 0, PGM_PERCENTILE_DICT_IDS = 1, PGM_PERCENTILE_COUNTS = 2 };
 /* PinotGpuNative.executeWithValueLists: Object[PGM_VALUES_SLOTS] = {the Object[PGM_RESULT_ARRAYS] of execute(), the raw columns' run values (value bits), their counts} */

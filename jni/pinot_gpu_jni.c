@@ -451,6 +451,49 @@ JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeW
   return out;
 }
 
+/* pg_execute of a query with PG_AGG_VARIANCE aggregations, and pg_result_moments over its result before that is released.
+ * Returns Object[PGM_MOMENTS_SLOTS]: {the Object[PGM_RESULT_ARRAYS] execute() returns, double[aggregations * rows]} -- element (aggregation * rows + row) of
+ * the second array is the m2 of the VarianceTuple of a VARIANCE aggregation (its count and sum are that aggregation's count and sum in the first
+ * array), 0 for every other function; rows = 1 for an aggregation-only query, else the number of groups. */
+JNIEXPORT jobjectArray JNICALL Java_org_apache_pinot_gpu_PinotGpuNative_executeWithMoments(JNIEnv* env, jclass cls, jlong handle, jintArray filterNodes,
+    jintArray predInts, jlongArray predLongs, jintArray setOffsets, jintArray setWords, jintArray aggregations, jintArray groupBy,
+    jint numGroupsLimit, jint flags) {
+  (void)cls;
+  pinned_query p;
+  if (!pin_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy, numGroupsLimit, flags)) return NULL;
+  const int32_t num_group_by = pgm_query_get(p.built)->num_group_by;
+  pg_result result;
+  const pg_status status = pg_execute((pg_segment*)(intptr_t)handle, pgm_query_get(p.built), &result);
+  release_query(env, &p, filterNodes, predInts, predLongs, setOffsets, setWords, aggregations, groupBy);
+  if (status != PG_OK) { throw_status(env, status); return NULL; }     /* pg_execute freed the result */
+  const jsize rows = num_group_by > 0 ? (jsize)result.num_groups : 1;
+  const jsize na = (jsize)result.num_aggregations;
+  jdoubleArray m2s = (*env)->NewDoubleArray(env, na * rows);
+  jdouble* m = m2s ? (*env)->GetDoubleArrayElements(env, m2s, NULL) : NULL;
+  if (m) {
+    for (jsize a = 0; a < na; ++a) {
+      for (jsize r = 0; r < rows; ++r) {
+        int64_t count = 0;
+        double sum = 0.0, m2 = 0.0;
+        if (pg_result_moments(&result, (int32_t)a, num_group_by > 0 ? (int32_t)r : -1, &count, &sum, &m2) != PG_OK) m2 = 0.0;      /* not a VARIANCE */
+        m[a * rows + r] = m2;
+      }
+    }
+    (*env)->ReleaseDoubleArrayElements(env, m2s, m, 0);
+  }
+  jobjectArray converted = result_to_java(env, &result, num_group_by);      /* releases the result */
+  if (m == NULL || converted == NULL) {
+    if (!(*env)->ExceptionCheck(env)) throw_new(env, "java/lang/OutOfMemoryError", "allocating the VarianceTuples failed");
+    return NULL;
+  }
+  jclass object_class = (*env)->FindClass(env, "java/lang/Object");
+  jobjectArray out = object_class ? (*env)->NewObjectArray(env, PGM_MOMENTS_SLOTS, object_class, NULL) : NULL;
+  if (out == NULL) return NULL;
+  (*env)->SetObjectArrayElement(env, out, PGM_MOMENTS_RESULT, converted);
+  (*env)->SetObjectArrayElement(env, out, PGM_MOMENTS_M2, m2s);
+  return out;
+}
+
 /* pg_execute of a query with PG_AGG_PERCENTILE aggregations, and pg_result_percentile_counts over its result before that is released.
  * Returns Object[PGM_PERCENTILE_SLOTS]: {the Object[PGM_RESULT_ARRAYS] execute() returns, Object[aggregations * rows], Object[aggregations * rows]} -- element
  * (aggregation * rows + row) of the second array is the int[] of the list's ascending dictIds, of the third the int[] of their counts (non-zero;

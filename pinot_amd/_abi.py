@@ -15,7 +15,8 @@ PG_OK, PG_ERR_INVALID_ARGUMENT, PG_ERR_UNSUPPORTED, PG_ERR_DEVICE, PG_ERR_OUT_OF
 KERNEL_NAMES = {0: "scan_agg_kernel", 1: "scan_private_kernel", 2: "scan_group_kernel", 3: "group_private_kernel",
                 4: "group_partition_scatter_kernel", 5: "scan_private_typed_kernel", 6: "scan_hist_kernel", 7: "index_and_kernel", 8: "scan_narrow_kernel", 9: "scan_sparse_kernel", 10: "scan_simple_kernel", 11: "scan_raw_kernel", 12: "scan_raw_set_kernel", 13: "scan_simple_valid_kernel",
                 14: "scan_distinct_kernel", 15: "group_distinct_kernel", 16: "scan_counts_kernel", 17: "group_counts_kernel",
-                18: "scan_collect_kernel", 19: "group_collect_kernel", 20: "scan_hll_kernel", 21: "group_hll_kernel"}
+                18: "scan_collect_kernel", 19: "group_collect_kernel", 20: "scan_hll_kernel", 21: "group_hll_kernel",
+                22: "scan_moments_kernel", 23: "group_moments_kernel"}
 PG_TYPE_INT, PG_TYPE_LONG, PG_TYPE_FLOAT, PG_TYPE_DOUBLE = range(4)
 PG_FWD_FIXED_BIT_DICT, PG_FWD_RAW_FIXED_BYTE = 0, 1
 # pg_predicate_kind / pg_leaf_eval
@@ -32,6 +33,8 @@ PG_AGG_COUNT, PG_AGG_SUM, PG_AGG_MIN, PG_AGG_MAX, PG_AGG_AVG, PG_AGG_DISTINCTCOU
 PG_AGG_DISTINCTCOUNTHLL = 7                  # the low byte of the function word; log2m travels above it: PG_AGG_HLL(log2m)
 PG_HLL_MIN_LOG2M, PG_HLL_MAX_LOG2M, PG_HLL_DEFAULT_LOG2M = 4, 14, 8
 PG_HLL_GROUP_MAX_BYTES = 1 << 30             # GROUP BY with DISTINCTCOUNTHLL: group_id_upper_bound x 2^log2m x 4 bytes over the query's HLL aggregations
+PG_AGG_VARIANCE = 8                          # VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: one intermediate, VarianceTuple(count, sum, m2) -- pg_result_moments
+PG_MOMENTS_GROUP_MAX_BYTES = 1 << 30         # GROUP BY with VARIANCE: group_id_upper_bound x 24 bytes x the query's distinct VARIANCE columns
 
 
 def PG_AGG_HLL(log2m):
@@ -136,6 +139,7 @@ ABI_SYMBOLS = [
     ("pg_result_percentile_counts", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(_P(C.c_int32)), _P(_P(C.c_uint32)), _P(C.c_int32)]),
     ("pg_result_value_counts", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(_P(C.c_int64)), _P(_P(C.c_uint32)), _P(C.c_int32)]),
     ("pg_result_hll_registers", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(_P(C.c_uint8)), _P(C.c_int32)]),
+    ("pg_result_moments", C.c_int, [_P(pg_result), C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_double), _P(C.c_double)]),
     ("pg_group_key_info", C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
     ("pg_group_key_values", C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64), C.c_int32, _P(C.c_int32)]),
     ("pg_execute_batch", C.c_int, [_P(C.c_void_p), _P(_P(pg_query)), C.c_int32, _P(pg_result), _P(C.c_int)]),

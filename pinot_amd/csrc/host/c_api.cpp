@@ -67,6 +67,10 @@ std::string intermediateJson(const IntermediateResult& r) {
     for (size_t i = 0; i < l.counts.size(); ++i) out += (i ? ", " : "") + std::to_string(l.counts[i]);
     return out + "]}";
   }
+  if (std::holds_alternative<VarianceTuple>(r)) {
+    const VarianceTuple& t = std::get<VarianceTuple>(r);
+    return "{\"count\": " + std::to_string(t.count) + ", \"sum\": " + num(t.sum) + ", \"m2\": " + num(t.m2) + "}";
+  }
   const AvgPair& p = std::get<AvgPair>(r);
   return "[" + num(p.sum) + ", " + std::to_string(p.count) + "]";
 }
@@ -151,7 +155,7 @@ ResultsBlock blockFromArrays(bool is_group_by, const std::vector<AggregationFunc
                              const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums, const double* mins,
                              const double* maxs, const uint8_t* is_null, const int64_t* set_offsets = nullptr, const int64_t* set_values = nullptr,
                              const int64_t* run_offsets = nullptr, const double* run_values = nullptr, const int64_t* run_counts = nullptr,
-                             const int64_t* register_offsets = nullptr, const uint8_t* registers = nullptr) {
+                             const int64_t* register_offsets = nullptr, const uint8_t* registers = nullptr, const double* m2s = nullptr) {
   ResultsBlock block;
   block.isGroupBy = is_group_by;
   const int num_functions = (int)functions.size();
@@ -191,6 +195,9 @@ ResultsBlock blockFromArrays(bool is_group_by, const std::vector<AggregationFunc
         }
         return l;
       }
+      // cell `at` of a variance function holds the VarianceTuple (counts[at], sums[at], m2s[at])
+      case AggregationFunctionType::VARPOP: case AggregationFunctionType::VARSAMP: case AggregationFunctionType::STDDEVPOP: case AggregationFunctionType::STDDEVSAMP:
+        return VarianceTuple{counts[at], sums[at], m2s ? m2s[at] : 0.0};
       case AggregationFunctionType::COUNT: return counts[at];
       case AggregationFunctionType::SUM: return sums[at];
       case AggregationFunctionType::MIN: return mins[at];
@@ -771,6 +778,44 @@ char* ph_combine_hll(const char* sql, int32_t num_blocks, const int64_t* block_r
       if (!grouped && block_rows[b] != 1) throw QueryException("an aggregation-only block has one row");
       ResultsBlock block = blockFromArrays(grouped, functions, (int32_t)key_names.size(), key_names.data(), key_types, row, row + block_rows[b], key_longs, key_doubles,
                                            key_strings, key_is_null, counts, sums, mins, maxs, is_null, nullptr, nullptr, nullptr, nullptr, nullptr, register_offsets, registers);
+      if (grouped) trimSegmentGroupByBlock(&block, q);
+      blocks.push_back(std::move(block));
+      row += block_rows[b];
+    }
+    if (blocks.empty()) throw QueryException("no blocks");
+    std::ostringstream o;
+    if (!grouped) {
+      ResultsBlock merged = blocks[0];
+      for (size_t i = 1; i < blocks.size(); ++i) mergeResultsBlocks(&merged, blocks[i]);
+      o << "{\"combined\": " << blockJson(merged) << "}";
+    } else {
+      const ResultsBlock combined = combineGroupByBlocks(blocks, q);
+      const std::vector<ReducedRow> reduced = reduceGroupBy(combined, q);
+      o << "{\"combined\": " << blockJson(combined) << ", \"reduced\": " << reducedJson(reduced) << ", \"resultTable\": " << resultTableJson(toResultTable(reduced, combined, q)) << "}";
+    }
+    out = o.str();
+  });
+  return *status == 0 ? strdup(out.c_str()) : nullptr;
+}
+// The combine of VarianceTuples built on the host (no device), the way ph_combine_hll drives the sketches': one block per segment, the cell of a
+// VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP function carries (counts[at], sums[at], m2s[at]).  Same array conventions and results as ph_combine_counts.
+char* ph_combine_moments(const char* sql, int32_t num_blocks, const int64_t* block_rows, const int32_t* key_types, const int64_t* key_longs,
+                         const double* key_doubles, const char* const* key_strings, const uint8_t* key_is_null, const int64_t* counts, const double* sums,
+                         const double* mins, const double* maxs, const uint8_t* is_null, const double* m2s, int32_t* status) {
+  std::string out;
+  *status = guarded([&] {
+    const QueryContext q = getQueryContext(sql);
+    std::vector<AggregationFunction> functions;
+    for (const auto& a : q.aggregations) functions.emplace_back(a, q.nullHandlingEnabled);
+    std::vector<const char*> key_names;
+    for (const auto& g : q.groupByExpressions) key_names.push_back(g.c_str());
+    const bool grouped = !q.groupByExpressions.empty();
+    std::vector<ResultsBlock> blocks;
+    int64_t row = 0;
+    for (int b = 0; b < num_blocks; ++b) {
+      if (!grouped && block_rows[b] != 1) throw QueryException("an aggregation-only block has one row");
+      ResultsBlock block = blockFromArrays(grouped, functions, (int32_t)key_names.size(), key_names.data(), key_types, row, row + block_rows[b], key_longs, key_doubles,
+                                           key_strings, key_is_null, counts, sums, mins, maxs, is_null, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, m2s);
       if (grouped) trimSegmentGroupByBlock(&block, q);
       blocks.push_back(std::move(block));
       row += block_rows[b];

@@ -135,6 +135,7 @@ void put(std::map<int, std::pair<char, std::string>>* m, int id, char type, cons
 void setIntermediate(Builder* b, int column, const AggregationFunction& f, const IntermediateResult& r, std::vector<int32_t>* nullRows, int row, bool isGroupBy) {
   // ObjectSerDeUtils' set formats (IntSet, LongSet, ...: object types 10+) are not written here
   if (f.getType() == AggregationFunctionType::DISTINCTCOUNTHLL) throw UnsupportedOperationException("DataTable V4 bytes of a DISTINCTCOUNTHLL sketch (a serialized HyperLogLog) are not written on this path");
+  if (isVarianceFunction(f.getType())) throw UnsupportedOperationException("DataTable V4 bytes of a VarianceTuple (ObjectSerDeUtils' VarianceTuple object type) are not written on this path");
   if (f.getType() == AggregationFunctionType::PERCENTILE) throw UnsupportedOperationException("DataTable V4 bytes of a PERCENTILE value list (a DoubleArrayList) are not written on this path");
   if (f.getType() == AggregationFunctionType::DISTINCTCOUNT) throw UnsupportedOperationException("DataTable V4 bytes of a DISTINCTCOUNT value set are not written on this path");
   const ColumnType t = intermediateType(f.getType());

@@ -206,7 +206,9 @@ struct FilterContext {                               // common/request/context/F
   Predicate predicate;
 };
 
-enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE, DISTINCTCOUNTHLL };   // sspi/AggregationFunctionType.java (ordinals = pg_agg_function)
+// sspi/AggregationFunctionType.java (ordinals up to DISTINCTCOUNTHLL = pg_agg_function; the four variance functions are one PG_AGG_VARIANCE)
+enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE, DISTINCTCOUNTHLL, VARPOP, VARSAMP, STDDEVPOP, STDDEVSAMP };
+inline bool isVarianceFunction(AggregationFunctionType t) { return t >= AggregationFunctionType::VARPOP && t <= AggregationFunctionType::STDDEVSAMP; }
 // DISTINCTCOUNT(col) / DISTINCT_COUNT(col) (the reference canonicalises function names by dropping underscores): the engine returns a segment's
 // dictId set (PG_AGG_DISTINCTCOUNT, pg_result_distinct_dict_ids), the mirror turns it into the value set that segments merge (ValueSet below).
 
@@ -216,6 +218,10 @@ enum class AggregationFunctionType { COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, P
 
 // DISTINCTCOUNTHLL(col) / DISTINCTCOUNTHLL(col, log2m) (and the underscore spellings): DistinctCountHLLAggregationFunction.  The engine returns a
 // segment's 2^log2m registers (PG_AGG_HLL(log2m), pg_result_hll_registers); the mirror merges them by the register-wise max (HllRegisters below).
+
+// VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (and the spellings without underscores, STD_DEV_POP among them): VarianceAggregationFunction.  The
+// engine returns a segment's (count, sum, m2) (PG_AGG_VARIANCE, pg_result_moments); the mirror merges the tuples and takes the final value
+// (VarianceTuple below).
 
 struct AggregationExpression {
   AggregationFunctionType function;
@@ -323,7 +329,22 @@ struct HllRegisters {
   int log2m() const { int l = 0; while (((size_t)1 << l) < registers.size()) ++l; return l; }
   int64_t cardinality() const;
 };
-using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet, ValueCounts, HllRegisters>;   // Long / Double / AvgPair / null (null handling only) / value set / value list / HLL registers
+// The variance functions' intermediate result: segment-local customobject/VarianceTuple.java.  apply = apply(VarianceTuple) :55-64, the pairwise
+// update around the current average, in the reference's order of operations (no product feeds an addition directly -- a division stands between --
+// so a compiler that contracts a * b + c has nothing to contract here: the merged tuple is the reference's bit for bit).
+struct VarianceTuple {
+  int64_t count = 0;
+  double sum = 0.0, m2 = 0.0;
+  void apply(const VarianceTuple& o) {
+    if (o.count == 0) return;
+    const double currAvg = count == 0 ? 0.0 : sum / (double)count;
+    const double delta = (o.sum / (double)o.count) - currAvg;
+    m2 += o.m2 + delta * delta * (double)o.count * (double)count / (double)(o.count + count);
+    count += o.count;
+    sum += o.sum;
+  }
+};
+using IntermediateResult = std::variant<int64_t, double, AvgPair, std::monostate, ValueSet, ValueCounts, HllRegisters, VarianceTuple>;   // Long / Double / AvgPair / null (null handling only) / value set / value list / HLL registers / VarianceTuple
 inline bool isNullResult(const IntermediateResult& r) { return std::holds_alternative<std::monostate>(r); }
 
 class AggregationFunction {                         // query/aggregation/function/AggregationFunction.java:42-145
@@ -550,6 +571,7 @@ struct GpuAbi {
   decltype(&pg_result_free) result_free;
   decltype(&pg_result_distinct_dict_ids) result_distinct_dict_ids;
   decltype(&pg_result_hll_registers) result_hll_registers;
+  decltype(&pg_result_moments) result_moments;
   decltype(&pg_result_percentile_counts) result_percentile_counts;
   decltype(&pg_result_value_counts) result_value_counts;
   decltype(&pg_filter_bitmap) filter_bitmap;

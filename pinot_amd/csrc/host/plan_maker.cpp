@@ -50,6 +50,7 @@ const GpuAbi& gpuAbi() {
     abi.result_free = (decltype(abi.result_free))sym("pg_result_free");
     abi.result_distinct_dict_ids = (decltype(abi.result_distinct_dict_ids))sym("pg_result_distinct_dict_ids");
     abi.result_hll_registers = (decltype(abi.result_hll_registers))sym("pg_result_hll_registers");
+    abi.result_moments = (decltype(abi.result_moments))sym("pg_result_moments");
     abi.result_percentile_counts = (decltype(abi.result_percentile_counts))sym("pg_result_percentile_counts");
     abi.result_value_counts = (decltype(abi.result_value_counts))sym("pg_result_value_counts");
     abi.filter_bitmap = (decltype(abi.filter_bitmap))sym("pg_filter_bitmap");
@@ -166,7 +167,7 @@ void ImmutableSegment::setQueryableDocIds(const void* roaringBytes, uint64_t siz
 // AggregationFunction
 // ---------------------------------------------------------------------------------------------------------------
 std::string AggregationFunction::getResultColumnName() const {
-  static const char* names[] = {"count", "sum", "min", "max", "avg", "distinctcount", "percentile", "distinctcounthll"};
+  static const char* names[] = {"count", "sum", "min", "max", "avg", "distinctcount", "percentile", "distinctcounthll", "varpop", "varsamp", "stddevpop", "stddevsamp"};
   if (_type == AggregationFunctionType::PERCENTILE) {
     // PercentileAggregationFunction.getResultColumnName :63-66: version 0 "percentile50(col)", version 1 "percentile(col, 50.0)" (Double.toString)
     if (_percentileIntForm) return "percentile" + std::to_string((int)_percentile) + "(" + _column + ")";
@@ -191,6 +192,8 @@ IntermediateResult AggregationFunction::fromDevice(const pg_agg_value& v) const 
     case AggregationFunctionType::DISTINCTCOUNT: return ValueSet{};         // (no doc reached the holder: the empty set; a set comes through fromDeviceSet)
     case AggregationFunctionType::PERCENTILE: return ValueCounts{};         // (the empty list; a list comes through fromDeviceCounts)
     case AggregationFunctionType::DISTINCTCOUNTHLL: return HllRegisters::empty(_hllLog2m);      // (an empty sketch; registers come through fromDeviceRegisters)
+    // (no doc reached the holder: VarianceTuple(0, 0.0, 0.0), extractAggregationResult :143-150; a tuple comes through pg_result_moments)
+    case AggregationFunctionType::VARPOP: case AggregationFunctionType::VARSAMP: case AggregationFunctionType::STDDEVPOP: case AggregationFunctionType::STDDEVSAMP: return VarianceTuple{};
   }
   return 0.0;
 }
@@ -302,6 +305,11 @@ IntermediateResult AggregationFunction::merge(const IntermediateResult& a, const
       }
       return r;
     }
+    case AggregationFunctionType::VARPOP: case AggregationFunctionType::VARSAMP: case AggregationFunctionType::STDDEVPOP: case AggregationFunctionType::STDDEVSAMP: {
+      VarianceTuple r = std::get<VarianceTuple>(a);                                            // VarianceAggregationFunction.merge :158-168 -> VarianceTuple.apply
+      r.apply(std::get<VarianceTuple>(b));
+      return r;
+    }
     case AggregationFunctionType::COUNT: return std::get<int64_t>(a) + std::get<int64_t>(b);   // CountAggregationFunction.merge
     case AggregationFunctionType::SUM: return std::get<double>(a) + std::get<double>(b);        // SumAggregationFunction.merge :223-233
     // Min / MaxAggregationFunction.merge (:237-251): `if (r1 < r2) return r1; return r2;` / `if (r1 > r2) ...` -- a primitive compare, not
@@ -335,6 +343,15 @@ double AggregationFunction::extractFinalResult(const IntermediateResult& r) cons
       int64_t seen = 0;
       for (size_t i = 0; i < list.values.size(); ++i) { seen += list.counts[i]; if (index < seen) return list.values[i]; }
       return list.values.back();
+    }
+    case AggregationFunctionType::VARPOP: case AggregationFunctionType::VARSAMP: case AggregationFunctionType::STDDEVPOP: case AggregationFunctionType::STDDEVSAMP: {
+      // VarianceAggregationFunction.extractFinalResult :181-201: DEFAULT_FINAL_RESULT = Double.NEGATIVE_INFINITY for no doc, and for one doc in the sample forms
+      const VarianceTuple& t = std::get<VarianceTuple>(r);
+      const bool sample = _type == AggregationFunctionType::VARSAMP || _type == AggregationFunctionType::STDDEVSAMP;
+      const bool stdDev = _type == AggregationFunctionType::STDDEVPOP || _type == AggregationFunctionType::STDDEVSAMP;
+      if (t.count == 0 || (sample && t.count == 1)) return -INFINITY;
+      const double variance = t.m2 / (double)(sample ? t.count - 1 : t.count);
+      return stdDev ? std::sqrt(variance) : variance;
     }
     case AggregationFunctionType::AVG: {                                    // AvgAggregationFunction.extractFinalResult :209-218
       const AvgPair& p = std::get<AvgPair>(r);
@@ -625,8 +642,12 @@ std::unique_ptr<LoweredQuery> lowerQuery(const ImmutableSegment& seg, const Quer
       if (a.column == "*") throw QueryException("'*' is only valid in COUNT(*)");
       if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException("DISTINCTCOUNTHLL(" + a.column + ") on a STRING column keeps the CPU plan");
     }
+    if (isVarianceFunction(a.function)) {
+      if (a.column == "*") throw QueryException("'*' is only valid in COUNT(*)");
+      if (!isNumeric(seg.getDataSource(a.column).dataType)) throw UnsupportedOperationException(AggregationFunction(a).getResultColumnName() + " on a STRING column keeps the CPU plan");
+    }
     pg_aggregation pa;
-    pa.function = a.function == AggregationFunctionType::DISTINCTCOUNTHLL ? PG_AGG_HLL(a.hllLog2m) : (int32_t)a.function;
+    pa.function = a.function == AggregationFunctionType::DISTINCTCOUNTHLL ? PG_AGG_HLL(a.hllLog2m) : (isVarianceFunction(a.function) ? PG_AGG_VARIANCE : (int32_t)a.function);
     pa.column = a.column == "*" ? -1 : seg.getColumnIndex(a.column);
     if (pa.column >= 0) {
       const DataSource& ds = seg.getDataSource(a.column);
@@ -838,6 +859,13 @@ class GpuAggregationOperator : public Operator {
       int32_t num = 0;
       checkStatus(gpuAbi().result_hll_registers(&res, aggregation, groupRow, &registers, &num), "reading DISTINCTCOUNTHLL registers");
       return HllRegisters::fromDeviceRegisters(registers, num);
+    }
+    if (isVarianceFunction(f.getType())) {
+      VarianceTuple t;
+      checkStatus(gpuAbi().result_moments(&res, aggregation, groupRow, &t.count, &t.sum, &t.m2), "reading a VarianceTuple");
+      // null handling: the holder stays null until a value arrives (aggregate :89-91)
+      if (_queryContext.nullHandlingEnabled && t.count == 0) return std::monostate{};
+      return t;
     }
     // a raw (no-dictionary) column: the sorted runs of pg_result_value_counts, for either function
     const bool collected = f.getType() == AggregationFunctionType::PERCENTILE || f.getType() == AggregationFunctionType::DISTINCTCOUNT;
@@ -1106,6 +1134,8 @@ std::unique_ptr<PlanNode> GpuPlanMaker::makeSegmentPlanNode(const SegmentContext
     if (a.function == AggregationFunctionType::PERCENTILE) throw UnsupportedOperationException("PERCENTILE in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
   for (const auto& a : qc.aggregations)
     if (a.function == AggregationFunctionType::DISTINCTCOUNTHLL) throw UnsupportedOperationException("DISTINCTCOUNTHLL in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
+  for (const auto& a : qc.aggregations)
+    if (isVarianceFunction(a.function)) throw UnsupportedOperationException(AggregationFunction(a).getResultColumnName() + " in a query with FILTER (WHERE ...) aggregations keeps the CPU plan");
   std::vector<std::string> keys;                       // lane order = first appearance, the unfiltered lane keyed ""
   std::vector<QueryContext> laneQueries;
   std::vector<std::vector<int>> positions;

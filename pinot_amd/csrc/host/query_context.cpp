@@ -393,6 +393,10 @@ QueryContext getQueryContext(const std::string& sql) {
     else if (u == "AVG") e.function = AggregationFunctionType::AVG;
     else if (u == "DISTINCTCOUNT") e.function = AggregationFunctionType::DISTINCTCOUNT;
     else if (u == "DISTINCTCOUNTHLL") e.function = AggregationFunctionType::DISTINCTCOUNTHLL;
+    else if (u == "VARPOP") e.function = AggregationFunctionType::VARPOP;                    // VAR_POP (AggregationFunctionFactory: VarianceAggregationFunction(.., sample, stdDev))
+    else if (u == "VARSAMP") e.function = AggregationFunctionType::VARSAMP;
+    else if (u == "STDDEVPOP") e.function = AggregationFunctionType::STDDEVPOP;              // STDDEV_POP / STD_DEV_POP
+    else if (u == "STDDEVSAMP") e.function = AggregationFunctionType::STDDEVSAMP;
     else if (u.rfind("PERCENTILE", 0) == 0) {
       // AggregationFunctionFactory.java:68-140: PERCENTILE<digits>(col) is the exact function with an int percentile, PERCENTILE(col, p) the same
       // with a double; every other PERCENTILE... spelling (EST, TDIGEST, KLL, RAW..., ...MV, SMARTTDIGEST) is another function
@@ -406,7 +410,7 @@ QueryContext getQueryContext(const std::string& sql) {
         e.percentile = (double)atoi(rest.c_str());
       }
     }
-    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT/DISTINCTCOUNTHLL/PERCENTILE are offloaded, got " + fn.text);
+    else throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/VARPOP/VARSAMP/STDDEVPOP/STDDEVSAMP/DISTINCTCOUNT/DISTINCTCOUNTHLL/PERCENTILE are offloaded, got " + fn.text);
     lx.expectSymbol("(");
     if (lx.acceptSymbol("*")) e.column = "*";
     else {
@@ -508,7 +512,7 @@ QueryContext getQueryContext(const std::string& sql) {
         int found = -1;
         for (size_t a = 0; a < q.aggregations.size() && found < 0; ++a) {
           const AggregationExpression& e = q.aggregations[a];
-          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "PERCENTILE()", "DISTINCTCOUNTHLL"};      // (a PERCENTILE is ordered by through its alias)
+          static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "PERCENTILE()", "DISTINCTCOUNTHLL", "VARPOP", "VARSAMP", "STDDEVPOP", "STDDEVSAMP"};      // (a PERCENTILE is ordered by through its alias)
           if (!e.hasFilter && u == names[(int)e.function] && (e.column == column || (e.function == AggregationFunctionType::COUNT && (column == "*" || e.column == "*")))) found = (int)a;
         }
         if (found < 0) {
@@ -519,7 +523,7 @@ QueryContext getQueryContext(const std::string& sql) {
           static const char* const names[] = {"COUNT", "SUM", "MIN", "MAX", "AVG"};      // (a DISTINCTCOUNT that is only ordered by keeps the CPU plan)
           for (int k = 0; k < 5; ++k) if (u == names[k]) kind = k;
           if (u.rfind("PERCENTILE", 0) == 0) throw UnsupportedOperationException("ORDER BY a PERCENTILE expression keeps the CPU plan (select it with an alias and order by the alias on this path)");
-          if (u == "DISTINCTCOUNT" || u == "DISTINCTCOUNTHLL") throw UnsupportedOperationException("a " + u + " that appears only in ORDER BY keeps the CPU plan (select it to order by it on this path)");
+          if (u == "DISTINCTCOUNT" || u == "DISTINCTCOUNTHLL" || u == "VARPOP" || u == "VARSAMP" || u == "STDDEVPOP" || u == "STDDEVSAMP") throw UnsupportedOperationException("a " + u + " that appears only in ORDER BY keeps the CPU plan (select it to order by it on this path)");
           if (kind < 0) throw UnsupportedOperationException("only COUNT/SUM/MIN/MAX/AVG/DISTINCTCOUNT are offloaded, got " + first.text);
           e.function = (AggregationFunctionType)kind;
           e.column = column;

@@ -299,6 +299,35 @@ struct HllFoldParams {
   int32_t chunks, words_per_chunk;      // workgroup b folds words [chunk * words_per_chunk, ...) of row b / chunks, chunk = b % chunks
 };
 
+// ---- VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (pg_scan_moments.h): the pivoted moments S1 = sum(x - c), S2 = sum((x - c)^2) ----
+// A column is read where it is stored: raw big-endian values, or dictIds and the device copy of the dictionary in the kernels' domain.
+enum MomentsSource : int32_t {
+  kMomentsRawI32 = 0, kMomentsRawF32 = 1, kMomentsRawI64 = 2, kMomentsRawF64 = 3,      // raw INT / FLOAT / LONG / DOUBLE
+  kMomentsDictI32 = 4,      // dictionary of 32-bit entries: value = base + entry (INT; LONG whose range fits 31 bits)
+  kMomentsDictI64 = 5,      // dictionary of longs
+  kMomentsDictF64 = 6       // dictionary of doubles (FLOAT widened at open)
+};
+struct MomentsCol {
+  const uint8_t* fwd;                   // raw: first value byte (padded to whole 2048-doc tiles); dictionary: the packed dictId stream
+  const int32_t* dict32;                // kMomentsDictI32
+  const unsigned long long* dict64;     // kMomentsDictI64 / kMomentsDictF64
+  long long base;                       // kMomentsDictI32: ColumnDev.value_base
+  int32_t source;                       // MomentsSource
+  int32_t bits;                         // dictionary: packed width
+  int32_t cardinality;                  // dictionary: entries (a dictId at or above it reads the last entry, never past the copy)
+  int32_t pad;
+};
+struct MomentsParams {
+  DistinctParams d;                     // scan: the filter and the record; num_cols: VARIANCE columns (cols[] unused); num_keys / keys: group_moments_kernel's raw group ids
+  MomentsCol cols[kMaxAggCols];
+  double pivot[kMaxAggCols];            // scan_moments_kernel: c per column (the ordinary query's sum / count)
+  const double* pivots;                 // group_moments_kernel: [num_rows x num_cols] c per raw group id and column (0 for a row without a doc)
+  double* out;                          // scan_moments_kernel: [gridDim.x x num_cols x 2] one {S1, S2} record per workgroup and column;
+                                        // group_moments_kernel: [num_rows x num_cols x 2], zero before the launch
+  uint32_t num_rows;                    // group_moments_kernel: rows of the matrix (a raw group id at or above it updates nothing)
+  uint32_t pad;
+};
+
 // raw_set_bitmap_kernel (pg_scan_raw_set.h): the match bitmap of one PG_PRED_RAW_SET leaf
 struct RawSetBitmapParams {
   const uint8_t* fwd;                   // the raw column's first value byte (padded to whole 2048-doc tiles)

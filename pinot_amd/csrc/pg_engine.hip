@@ -1038,6 +1038,7 @@ struct Lowered {
   std::vector<int> distinct_slots, distinct_key_slots;
   bool hll_pass = false;                       // kQueryHllPass: the slots are RAW columns with a log2m each (hll_slot_log2m), the kernels scan_hll_kernel / group_hll_kernel (pg_scan_hll.h)
   std::vector<int> hll_slot_log2m;
+  bool moments_pass = false;                   // kQueryMomentsPass: the slots are VARIANCE columns, raw or dictionary-encoded, the kernels scan_moments_kernel / group_moments_kernel (pg_scan_moments.h)
   bool counts_pass = false;                    // kQueryCountsPass: the slots are PERCENTILE columns, the kernels scan_counts_kernel / group_counts_kernel (32-bit counters per dictId)
   bool collect_pass = false;                   // kQueryCollectPass: the slots are RAW columns, the kernels scan_collect_kernel / group_collect_kernel (pg_scan_collect.h)
 };
@@ -2650,7 +2651,13 @@ struct HllSet {
   int rows = 1;                         // one (aggregation only), or one per row of group_aggregations (in transit from the pass: one per raw group id)
   std::vector<uint8_t> registers;       // [rows << log2m]
 };
-struct ResultInternal { std::vector<DistinctSet> distinct; std::vector<CountList> counts; std::vector<ValueList> values; std::vector<HllSet> hll; };
+// The VarianceTuple behind a PG_AGG_VARIANCE aggregation (pg_result_moments).  In transit from the pass: m2 holds {S1, S2} per raw group id.
+struct MomentsSet {
+  int aggregation = 0;
+  int rows = 1;                         // one (aggregation only), or one per row of group_aggregations
+  std::vector<double> m2;               // [rows] (in transit: [rows x 2])
+};
+struct ResultInternal { std::vector<DistinctSet> distinct; std::vector<CountList> counts; std::vector<ValueList> values; std::vector<HllSet> hll; std::vector<MomentsSet> moments; };
 
 void pg_result_free(pg_result* r) {
   if (!r) return;
@@ -2681,7 +2688,11 @@ constexpr int32_t kQueryCollectPass = 1 << 26;
 // internal pg_query.flags bit, set beside kQueryDistinctPass: the pass's aggregations are DISTINCTCOUNTHLLs on RAW columns -- one launch of scan_hll_kernel /
 // group_hll_kernel (pg_scan_hll.h) builds their registers.  (HLLs on dictionary columns ride the bitset pass itself: hll_fold_kernel behind its kernel.)
 constexpr int32_t kQueryHllPass = 1 << 25;
+// internal pg_query.flags bit, set beside kQueryDistinctPass: the pass's aggregations are PG_AGG_VARIANCEs on raw or dictionary columns -- one launch of
+// scan_moments_kernel / group_moments_kernel (pg_scan_moments.h) accumulates their moments around the pivots execute_moments took from the ordinary query.
+constexpr int32_t kQueryMomentsPass = 1 << 24;
 constexpr int32_t kQuerySetPass = kQueryDistinctPass | kQueryCountsPass;
+static inline bool is_moments_function(int32_t function) { return function == PG_AGG_VARIANCE; }
 static inline bool is_hll_function(int32_t function) { return (function & 0xFF) == PG_AGG_DISTINCTCOUNTHLL; }
 // the one function besides COUNT(*) a pass query carries, -1: not a pass
 static inline int set_pass_function(int32_t flags) { return (flags & kQueryCountsPass) ? PG_AGG_PERCENTILE : ((flags & kQueryDistinctPass) ? PG_AGG_DISTINCTCOUNT : -1); }
@@ -2841,7 +2852,7 @@ static pg_status check_query_plan(const pg_segment* seg, const pg_query* q, int 
   std::vector<std::pair<int, int>> group_aggs;     // distinct (column, SUM | MIN | MAX)
   for (int a = 0; a < na; ++a) {
     const pg_aggregation& ag = q->aggregations[a];
-    if (distinct_pass ? (ag.function != PG_AGG_COUNT && ag.function != pass_function && !(pass_function == PG_AGG_DISTINCTCOUNT && is_hll_function(ag.function))) : (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG))
+    if (distinct_pass ? (ag.function != PG_AGG_COUNT && ag.function != pass_function && !(pass_function == PG_AGG_DISTINCTCOUNT && is_hll_function(ag.function)) && !((q->flags & kQueryMomentsPass) && is_moments_function(ag.function))) : (ag.function < PG_AGG_COUNT || ag.function > PG_AGG_AVG))
       return fail(PG_ERR_UNSUPPORTED, "aggregation function %d", ag.function);
     if (ag.function == PG_AGG_COUNT) continue;
     if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
@@ -3069,14 +3080,14 @@ static pg_status execute_impl(pg_segment* seg, const pg_query* q, pg_result* out
 
 // ---- the aggregation-only path's kernel: one value per kernel the path launches.  choose_scan_kernel tries them in order of
 // preference; the grid, the PG_KERNEL_* id, the kind of shared launch, the fold's flags and the launcher all follow from the choice.
-enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Counts, GroupCounts, Collect, GroupCollect, Hll, GroupHll, Agg };
+enum class ScanKernel { Hist, Narrow, NarrowSingle, Sparse, Simple, SimpleSet, SimpleValid, Raw, RawSet, PrivateFsm, Private, PrivateTyped, Distinct, GroupDistinct, Counts, GroupCounts, Collect, GroupCollect, Hll, GroupHll, Moments, GroupMoments, Agg };
 // per ScanKernel: its PG_KERNEL_* id, and whether it evaluates the filter with eval_filter_private over every tile (it can then leave the
 // leaves' bitmaps for the transducer pass; PrivateFsm walks the transducer itself)
 static const struct { int id; bool writes_leaves; } kScanKernels[] = {
   {PG_KERNEL_SCAN_HIST, true}, {PG_KERNEL_SCAN_NARROW, true}, {PG_KERNEL_SCAN_NARROW, false}, {PG_KERNEL_SCAN_SPARSE, false}, {PG_KERNEL_SCAN_SIMPLE, false},
   {PG_KERNEL_SCAN_SIMPLE, false}, {PG_KERNEL_SCAN_SIMPLE_VALID, false}, {PG_KERNEL_SCAN_RAW, false}, {PG_KERNEL_SCAN_RAW_SET, false}, {PG_KERNEL_SCAN_PRIVATE, false}, {PG_KERNEL_SCAN_PRIVATE, true},
   {PG_KERNEL_SCAN_PRIVATE_TYPED, true}, {PG_KERNEL_SCAN_DISTINCT, true}, {PG_KERNEL_GROUP_DISTINCT, true}, {PG_KERNEL_SCAN_COUNTS, true}, {PG_KERNEL_GROUP_COUNTS, true},
-  {PG_KERNEL_SCAN_COLLECT, true}, {PG_KERNEL_GROUP_COLLECT, true}, {PG_KERNEL_SCAN_HLL, true}, {PG_KERNEL_GROUP_HLL, true}, {PG_KERNEL_SCAN_AGG, false}};
+  {PG_KERNEL_SCAN_COLLECT, true}, {PG_KERNEL_GROUP_COLLECT, true}, {PG_KERNEL_SCAN_HLL, true}, {PG_KERNEL_GROUP_HLL, true}, {PG_KERNEL_SCAN_MOMENTS, true}, {PG_KERNEL_GROUP_MOMENTS, true}, {PG_KERNEL_SCAN_AGG, false}};
 static_assert(sizeof(kScanKernels) / sizeof(kScanKernels[0]) == (size_t)ScanKernel::Agg + 1, "one row per ScanKernel");
 // general: the kernel of the query's family -- Private or PrivateTyped, or Agg when neither lane-private kernel takes the query.  A
 // specialised kernel that won keeps it: the index handling, the leap-frog count and the batch's fallbacks go by the family.
@@ -3126,6 +3137,7 @@ static ScanChoice choose_scan_kernel(const pg_segment* seg, const Lowered& lw, i
   // declined the leaves that filter does not evaluate.  Everything that goes by the family (tile lists, the entry counts) is Private's.
   // On raw columns both passes collect the values (pg_scan_collect.h).
   if (!lw.distinct_slots.empty() && lw.hll_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Hll : ScanKernel::GroupHll); }      // DISTINCTCOUNTHLL on raw columns (pg_scan_hll.h)
+  if (!lw.distinct_slots.empty() && lw.moments_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Moments : ScanKernel::GroupMoments); }      // VARIANCE's moments (pg_scan_moments.h)
   if (!lw.distinct_slots.empty() && lw.collect_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Collect : ScanKernel::GroupCollect); }
   if (!lw.distinct_slots.empty() && !lw.counts_pass) { k.general = ScanKernel::Private; return pick(lw.distinct_key_slots.empty() ? ScanKernel::Distinct : ScanKernel::GroupDistinct); }
   // The counts pass of a PERCENTILE query: the same, with 32-bit counters per dictId (pg_scan_counts.h).
@@ -3352,6 +3364,16 @@ static ScanGrid scan_grid(const pg_segment* seg, const ScanChoice& k, const Lowe
       g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, waves_group_hll() / wpb));
       break;
     }
+    case ScanKernel::Moments: case ScanKernel::GroupMoments: {
+      // the accumulators live in registers (the matrices in HBM): workgroups of four wavefronts, the filter's set area (if any) 16 bytes in, the
+      // wavefronts' sums and then the reduction records over the start
+      bool has_set = false;
+      if (g_engine.set_lds) for (int nd = 0; nd < sp.num_nodes; ++nd) has_set |= sp.nodes[nd].op == PG_FILTER_LEAF && sp.nodes[nd].kind == kLeafDictSet;
+      g.hist_set_off = has_set ? 16 : 0;
+      g.lds = std::max((size_t)(has_set ? 16 + kSetLdsWords * 4 : 0), sizeof(BlockPartial) * (size_t)wpb + 16);
+      g.blocks = grid_blocks(seg, tiles, wpb, std::max(1, (k.kernel == ScanKernel::Moments ? waves_scan_moments() : waves_group_moments()) / wpb));
+      break;
+    }
     case ScanKernel::Narrow: g.blocks = grid_blocks(seg, (tiles + kNarrowTiles - 1) / kNarrowTiles, wpb, std::max(1, waves_scan_narrow(false) / wpb)); break;
     case ScanKernel::NarrowSingle: g.blocks = grid_blocks(seg, (tiles + kNarrowSingleTiles - 1) / kNarrowSingleTiles, wpb, std::max(1, waves_scan_narrow(true) / wpb)); break;
     case ScanKernel::Sparse: g.blocks = grid_blocks(seg, tiles, wpb * kSparseTiles, std::max(1, waves_scan_sparse(num_agg_cols <= 1) / wpb)); break;
@@ -3414,7 +3436,7 @@ static void launch_scan_kernel(const ScanChoice& k, const ScanGrid& g, int num_a
     case ScanKernel::PrivateTyped: launch_scan_private_typed(num_agg_cols, g.blocks, stream, sp); break;
     case ScanKernel::Agg: launch_scan_agg(g_engine.use_dma, one, typed, g.blocks, g.threads, g.lds, stream, sp); break;
     case ScanKernel::Distinct: case ScanKernel::GroupDistinct: case ScanKernel::Counts: case ScanKernel::GroupCounts:
-    case ScanKernel::Collect: case ScanKernel::GroupCollect: case ScanKernel::Hll: case ScanKernel::GroupHll: break;      // (launched with their own parameter block: launch_set_pass)
+    case ScanKernel::Collect: case ScanKernel::GroupCollect: case ScanKernel::Hll: case ScanKernel::GroupHll: case ScanKernel::Moments: case ScanKernel::GroupMoments: break;      // (launched with their own parameter block: launch_set_pass)
   }
 }
 // What the phases of execute_impl share about one query
@@ -3573,22 +3595,23 @@ static void fill_hll_dictionary(const ColumnDev& col, HllFoldParams* fp) {
   else fp->dict_kind = col.stored_type == PG_TYPE_FLOAT ? kHllDictFloat : kHllDictDouble;
 }
 // ---- the set passes: what a pass query (kQueryDistinctPass / kQueryCountsPass) adds to the aggregation-only scan ----
-// Four forms, each with kernels and a parameter block of its own, all keeping their device state in the context's d_distinct scratch (GROUP BY: one
+// Five forms, each with kernels and a parameter block of its own, all keeping their device state in the context's d_distinct scratch (GROUP BY: one
 // row per raw group id).  run_aggregation calls the stages below where a scalar query has nothing to do: bind (the columns and keys), arm (keys,
 // layout, scratch, host buffers), launch, enqueue_post (what follows the kernel on the stream), harvest.
 struct CollectLayout { size_t images[kMaxAggCols], work, heads, position, rows, rows_a, rows_b, temp, temp_bytes, total; };
 constexpr size_t kCollectHeadBytes = 256;      // the scratch's first line: the cursor, the flag word, (later) a column's runs
 struct SetPass {
   // Bitsets: DISTINCTCOUNT (and DISTINCTCOUNTHLL, folded behind the kernel) on dictionary columns; Counts: PERCENTILE on dictionary columns;
-  // Collect: either function on raw columns; HllRaw: DISTINCTCOUNTHLL on raw columns
-  enum Form { None, Bitsets, Counts, Collect, HllRaw } form = None;
+  // Collect: either function on raw columns; HllRaw: DISTINCTCOUNTHLL on raw columns; Moments: VARIANCE on raw and dictionary columns
+  enum Form { None, Bitsets, Counts, Collect, HllRaw, Moments } form = None;
   int function = -1;                       // the one function besides COUNT(*) the pass query carries (set_pass_function)
   const char* name = "DISTINCTCOUNT";      // ... as the messages spell it
   std::vector<int> distinct_of;            // per aggregation: its bitset / counter row / list / register set (index into lw.distinct_slots), -1: none
   std::vector<int> hll_log2m_of;           // per aggregation: the log2m of a DISTINCTCOUNTHLL (0: another function)
   std::vector<int> key_cards;              // the key columns' cardinalities
   long long rows = 1;                      // raw group ids: their product
-  DistinctParams dp; HllParams hp; CollectParams cp;      // the form's parameter block (Bitsets and Counts: dp)
+  DistinctParams dp; HllParams hp; CollectParams cp; MomentsParams mp;      // the form's parameter block (Bitsets and Counts: dp)
+  std::vector<double> moments_host;        // Moments: where the {S1, S2} records (one per workgroup and column) or rows (GROUP BY: one per raw group id and column) land
   std::vector<std::vector<uint32_t>> distinct_host;      // Bitsets / Counts: per bitset where its copy lands -- the vector that becomes the result's DistinctSet, no second host copy
   // DISTINCTCOUNTHLL: per aggregation the first staged register word in the scratch (Bitsets: its own matrix's; HllRaw: its slot's); the staged
   // words are packed to bytes behind them and land in hll_host in the same order
@@ -3612,8 +3635,10 @@ static void open_set_pass(QueryRun& r, SetPass* p) {
   lw.counts_pass = on && p->function == PG_AGG_PERCENTILE;
   lw.collect_pass = on && (r.q->flags & kQueryCollectPass) != 0;
   lw.hll_pass = on && (r.q->flags & kQueryHllPass) != 0;
+  lw.moments_pass = on && (r.q->flags & kQueryMomentsPass) != 0;
+  if (lw.moments_pass) p->name = "VARIANCE";
   if (!on) return;
-  p->form = lw.hll_pass ? SetPass::HllRaw : (lw.collect_pass ? SetPass::Collect : (lw.counts_pass ? SetPass::Counts : SetPass::Bitsets));
+  p->form = lw.moments_pass ? SetPass::Moments : lw.hll_pass ? SetPass::HllRaw : (lw.collect_pass ? SetPass::Collect : (lw.counts_pass ? SetPass::Counts : SetPass::Bitsets));
   p->copy.stream = r.ctx->stream;
   p->distinct_of.assign((size_t)std::max(r.na, 1), -1);
   p->hll_log2m_of.assign((size_t)std::max(r.na, 1), 0);
@@ -3624,12 +3649,14 @@ static pg_status bind_set_pass_column(QueryRun& r, SetPass* p, int a, bool* boun
   const pg_segment* seg = r.seg; Lowered& lw = r.lw;
   const pg_aggregation& ag = r.q->aggregations[a];
   const bool hll_agg = p->function == PG_AGG_DISTINCTCOUNT && is_hll_function(ag.function);
-  *bound = p->form != SetPass::None && (hll_agg || (ag.function == p->function && !lw.hll_pass));
+  const bool moments_agg = lw.moments_pass && is_moments_function(ag.function);
+  *bound = p->form != SetPass::None && (moments_agg || hll_agg || (ag.function == p->function && !lw.hll_pass && !lw.moments_pass));
   if (!*bound) return PG_OK;
   if (ag.column < 0 || ag.column >= (int)seg->cols.size()) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
   if (hll_agg) p->hll_log2m_of[(size_t)a] = pg::hll_log2m_of(ag.function);
   const bool raw_form = lw.collect_pass || lw.hll_pass;
-  if (seg->cols[(size_t)ag.column].encoding != (raw_form ? PG_FWD_RAW_FIXED_BYTE : PG_FWD_FIXED_BIT_DICT))
+  // (the moments pass reads a column where it is stored, raw or dictionary-encoded: plan_moments checked it)
+  if (!lw.moments_pass && seg->cols[(size_t)ag.column].encoding != (raw_form ? PG_FWD_RAW_FIXED_BYTE : PG_FWD_FIXED_BIT_DICT))
     return fail(PG_ERR_UNSUPPORTED, "%s on %s column %s", p->name, raw_form ? "dictionary" : "raw", seg->cols[(size_t)ag.column].name.c_str());
   r.add_projected(ag.column);
   const int s = slot_for(&lw, seg, ag.column, false);
@@ -3787,8 +3814,54 @@ static pg_status arm_collect(QueryRun& r, SetPass* p) {
   HIP_TRY(hipMemsetAsync(base, 0, kCollectHeadBytes, ctx->stream));
   return PG_OK;
 }
+// arm, Moments: the kernels' value sources, the pivots execute_moments took from the ordinary query, and the scratch -- without GROUP BY one
+// {S1, S2} record per workgroup and column, which every workgroup writes; under GROUP BY a zeroed [rows x cols] matrix of {S1, S2} and behind it the
+// uploaded [rows x cols] pivots.
+static thread_local const std::vector<double>* t_moments_pivots = nullptr;      // execute_moments -> arm_moments, around the pass's execute_one
+static pg_status arm_moments(QueryRun& r, SetPass* p, const ScanGrid& grid) {
+  ExecCtx* ctx = r.ctx; const Lowered& lw = r.lw; const pg_segment* seg = r.seg;
+  MomentsParams& mp = p->mp;
+  memset(&mp, 0, sizeof(mp));
+  pg_status st = set_pass_keys(lw, p, &mp.d); if (st != PG_OK) return st;
+  const size_t cols = lw.distinct_slots.size();
+  for (int a = 0; a < r.na; ++a) {
+    const int c = p->distinct_of[(size_t)a];
+    if (c < 0) continue;
+    const ColumnDev& col = seg->cols[(size_t)r.q->aggregations[a].column];
+    const DevColumn& dc = lw.plan.cols[lw.distinct_slots[(size_t)c]];
+    MomentsCol& mc = mp.cols[c];
+    mc.fwd = dc.fwd; mc.bits = dc.bits; mc.cardinality = col.cardinality;
+    if (col.encoding == PG_FWD_FIXED_BIT_DICT) {
+      mc.dict32 = col.d_dict; mc.dict64 = col.d_dict64; mc.base = col.value_base;
+      mc.source = col.vkind == kValI32 ? kMomentsDictI32 : (col.vkind == kValI64 ? kMomentsDictI64 : kMomentsDictF64);
+      if ((mc.source == kMomentsDictI32 ? (const void*)mc.dict32 : (const void*)mc.dict64) == nullptr || col.cardinality < 1)
+        return fail(PG_ERR_INTERNAL, "VARIANCE on column %s: no device copy of its dictionary", col.name.c_str());
+    } else {
+      mc.source = col.stored_type == PG_TYPE_INT ? kMomentsRawI32 : (col.stored_type == PG_TYPE_LONG ? kMomentsRawI64 : (col.stored_type == PG_TYPE_FLOAT ? kMomentsRawF32 : kMomentsRawF64));
+    }
+    if (mc.fwd == nullptr) return fail(PG_ERR_INTERNAL, "VARIANCE on column %s: no forward index on the device", col.name.c_str());
+  }
+  const bool grouped = p->grouped(lw);
+  const std::vector<double>* pivots = t_moments_pivots;
+  if (pivots == nullptr || pivots->size() != (size_t)p->rows * cols) return fail(PG_ERR_INTERNAL, "the VARIANCE pass without the pivots of %lld rows x %zu columns", p->rows, cols);
+  const size_t out_doubles = (grouped ? (size_t)p->rows : (size_t)grid.blocks) * cols * 2, pivot_doubles = grouped ? pivots->size() : 0;
+  st = ensure_distinct(r.seg, ctx, (out_doubles + pivot_doubles) * 2); if (st != PG_OK) return st;
+  double* const base = reinterpret_cast<double*>(ctx->d_distinct);
+  mp.out = base;
+  if (grouped) {
+    mp.pivots = base + out_doubles;
+    mp.num_rows = (uint32_t)p->rows;
+    HIP_TRY(hipMemsetAsync(base, 0, out_doubles * 8, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + out_doubles, pivots->data(), pivot_doubles * 8, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    for (size_t c = 0; c < cols; ++c) mp.pivot[c] = (*pivots)[c];
+  }
+  if (r.out) p->moments_host.resize(out_doubles);
+  return PG_OK;
+}
 static pg_status arm_set_pass(QueryRun& r, SetPass* p, const ScanGrid& grid) {
   switch (p->form) {
+    case SetPass::Moments: return arm_moments(r, p, grid);
     case SetPass::Bitsets: case SetPass::Counts: return arm_bitsets(r, p, grid);
     case SetPass::Collect: return arm_collect(r, p);
     case SetPass::HllRaw: return arm_hll_raw(r, p);
@@ -3804,6 +3877,7 @@ static void launch_set_pass(const QueryRun& r, SetPass* p, const ScanGrid& grid)
     case SetPass::Counts: p->dp.scan = sp; grouped ? launch_group_counts(blocks, lds, stream, p->dp) : launch_scan_counts(grid.distinct_lds, blocks, lds, stream, p->dp); break;
     case SetPass::Collect: p->cp.d.scan = sp; grouped ? launch_group_collect(blocks, lds, stream, p->cp) : launch_scan_collect(blocks, lds, stream, p->cp); break;
     case SetPass::HllRaw: p->hp.d.scan = sp; grouped ? launch_group_hll(blocks, lds, stream, p->hp) : launch_scan_hll(blocks, lds, stream, p->hp); break;
+    case SetPass::Moments: p->mp.d.scan = sp; grouped ? launch_group_moments(blocks, lds, stream, p->mp) : launch_scan_moments(blocks, lds, stream, p->mp); break;
     default: break;
   }
 }
@@ -3818,6 +3892,10 @@ static pg_status enqueue_set_pass_post(QueryRun& r, SetPass* p) {
       if (!p->distinct_host[c].empty()) HIP_TRY(hipMemcpyAsync(p->distinct_host[c].data(), p->dp.cols[c].set_bits, p->distinct_host[c].size() * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (p->form == SetPass::Collect) { p->copy.armed = true; HIP_TRY(hipMemcpyAsync(p->collect_head, ctx->d_distinct, 16, hipMemcpyDeviceToHost, ctx->stream)); }
+  if (p->form == SetPass::Moments && !p->moments_host.empty()) {
+    p->copy.armed = true;
+    HIP_TRY(hipMemcpyAsync(p->moments_host.data(), p->mp.out, p->moments_host.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
   if (p->hll_staged_words == 0) return PG_OK;
   for (int a = 0; a < (bitsets ? r.na : 0); ++a) {      // the bitsets' rows -> register rows, one fold per DISTINCTCOUNTHLL aggregation over its column's bitset
     if (p->hll_log2m_of[(size_t)a] == 0 || p->hll_same_as[(size_t)a] >= 0) continue;
@@ -3928,11 +4006,35 @@ static pg_status harvest_collect(QueryRun& r, SetPass* p, unsigned long long mat
   out->internal = lists.release();
   return PG_OK;
 }
+// harvest, Moments: {S1, S2} per VARIANCE aggregation -- without GROUP BY the workgroups' records added in workgroup order (the same grid adds
+// the same numbers in the same order: bit-identical run to run), under GROUP BY the rows of all raw group ids.  execute_moments turns them into m2.
+static void harvest_moments(QueryRun& r, SetPass* p) {
+  const size_t cols = r.lw.distinct_slots.size();
+  const bool grouped = p->grouped(r.lw);
+  const size_t records = p->moments_host.size() / (cols * 2);      // workgroups, or raw group ids
+  std::unique_ptr<ResultInternal> sets(new ResultInternal());
+  for (int a = 0; a < r.na; ++a) {
+    const int dc = p->distinct_of[(size_t)a];
+    if (dc < 0) continue;
+    MomentsSet ms;
+    ms.aggregation = a; ms.rows = grouped ? (int)records : 1;
+    if (grouped) {
+      ms.m2.resize(records * 2);
+      for (size_t row = 0; row < records; ++row) { ms.m2[2 * row] = p->moments_host[(row * cols + (size_t)dc) * 2]; ms.m2[2 * row + 1] = p->moments_host[(row * cols + (size_t)dc) * 2 + 1]; }
+    } else {
+      double s1 = 0.0, s2 = 0.0;
+      for (size_t b = 0; b < records; ++b) { s1 += p->moments_host[(b * cols + (size_t)dc) * 2]; s2 += p->moments_host[(b * cols + (size_t)dc) * 2 + 1]; }
+      ms.m2 = {s1, s2};
+    }
+    sets->moments.push_back(std::move(ms));
+  }
+  r.out->internal = sets.release();
+}
 // harvest: the stream was synchronised -- the copies of enqueue_post have landed.  The sets go to out->internal for execute_distinct / execute_percentile.
 static pg_status harvest_set_pass(QueryRun& r, SetPass* p, const BlockPartial& fp) {
   p->copy.armed = false;
   if (p->form == SetPass::Collect) return harvest_collect(r, p, (unsigned long long)fp.count);
-  if (r.out) harvest_sets(r, p);
+  if (r.out) { if (p->form == SetPass::Moments) harvest_moments(r, p); else harvest_sets(r, p); }
   trim_distinct(r.seg, r.ctx);
   return PG_OK;
 }
@@ -4082,7 +4184,7 @@ static pg_status run_aggregation(QueryRun& r, unsigned long long* d_out_bitmap_r
       const pg_aggregation& ag = q->aggregations[a];
       pg_agg_value& v = out->aggregations[a];
       empty_agg_value(&v, (int64_t)fp.count);
-      if (ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT || ag.function == PG_AGG_PERCENTILE || is_hll_function(ag.function)) continue;      // (a DISTINCTCOUNT's count is its bitset's: filled in behind the copy; a PERCENTILE's is the docs aggregated)
+      if (ag.function == PG_AGG_COUNT || ag.function == PG_AGG_DISTINCTCOUNT || ag.function == PG_AGG_PERCENTILE || is_hll_function(ag.function) || is_moments_function(ag.function)) continue;      // (a DISTINCTCOUNT's count is its bitset's: filled in behind the copy; a PERCENTILE's is the docs aggregated)
       const int ac = agg_slot_of[(size_t)a];
       const ColumnDev& col = seg->cols[(size_t)ag.column];
       const bool plane = lw.plane_cols[(size_t)ag.column] != 0;
@@ -5825,11 +5927,16 @@ static pg_status plan_pass_keys(const pg_segment* seg, const pg_query* q, const 
 }
 // The two queries that answer the caller's: the ordinary query -- every aggregation of the pass (is_pass) turned into COUNT(*) -- and the pass, with
 // everything BUT those turned into COUNT(*) and pass_flags set.  Ends with the plan-time checks of both (check_pass false: only the ordinary one runs).
-static pg_status split_pass_query(const pg_segment* seg, const pg_query* q, PassPlan* plan, bool (*is_pass)(int32_t function), int32_t pass_flags, bool check_pass = true) {
+// base_function: what a pass aggregation becomes in the ordinary query -- COUNT(*), or that function on the same column (VARIANCE: AVG).
+static pg_status split_pass_query(const pg_segment* seg, const pg_query* q, PassPlan* plan, bool (*is_pass)(int32_t function), int32_t pass_flags, bool check_pass = true,
+                                  int32_t base_function = PG_AGG_COUNT) {
   const int na = q->num_aggregations;
   plan->base_aggs.assign(q->aggregations, q->aggregations + na);
   plan->pass_aggs.assign(q->aggregations, q->aggregations + na);
-  for (int a = 0; a < na; ++a) (is_pass(q->aggregations[a].function) ? plan->base_aggs : plan->pass_aggs)[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+  for (int a = 0; a < na; ++a) {
+    if (!is_pass(q->aggregations[a].function)) plan->pass_aggs[(size_t)a] = pg_aggregation{PG_AGG_COUNT, -1};
+    else plan->base_aggs[(size_t)a] = base_function == PG_AGG_COUNT ? pg_aggregation{PG_AGG_COUNT, -1} : pg_aggregation{base_function, q->aggregations[a].column};
+  }
   plan->base = *q; plan->base.aggregations = plan->base_aggs.data();
   plan->pass = *q; plan->pass.aggregations = plan->pass_aggs.data();
   plan->pass.flags |= pass_flags;
@@ -6081,6 +6188,177 @@ static pg_status execute_distinct(pg_segment* seg, const pg_query* q, pg_result*
     if (!kept) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the DISTINCTCOUNTHLL matrix of %d rows, or out of order", (long long)bad_row, m.rows); }
     m.rows = out->num_groups;
     sets->hll.push_back(std::move(m));
+  }
+  out->internal = sets.release();
+  return PG_OK;
+}
+
+// ---- PG_AGG_VARIANCE: VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP as VarianceTuple(count, sum, m2) (pg_scan_moments.h) ----
+// Two runs over the same filter, on the same stream one after the other:
+//   the ordinary query  -- the caller's list with every VARIANCE turned into AVG on the same column: count and sum per row, every other function,
+//                          the statistics and (GROUP BY) the list of groups come from the paths they take today, untouched;
+//   the moments pass    -- everything BUT the VARIANCEs turned into COUNT(*), flagged kQueryDistinctPass | kQueryMomentsPass: one launch of
+//                          scan_moments_kernel / group_moments_kernel behind the same lowered filter, accumulating S1 = sum(x - c) and
+//                          S2 = sum((x - c)^2) around the pivot c = sum / count of every (row, column).
+// m2 = S2 - S1^2 / n: exact in exact arithmetic for ANY c; with c the row's own mean up to SUM's rounding, S1 is small and S2 a sum of non-negative
+// terms of the spread's own size -- where VarianceTuple.apply(double) (:35-42) subtracts numbers of the values' size.  There is no metadata fast
+// path (the reference always scans) and the pass never runs alone.  A row or query without a doc: m2 = 0, nothing launched for it.
+static bool has_moments(const pg_query* q) {
+  if (!q || !q->aggregations) return false;
+  for (int a = 0; a < q->num_aggregations; ++a) if (is_moments_function(q->aggregations[a].function)) return true;
+  return false;
+}
+struct MomentsPlan : PassPlan {
+  std::vector<int> cols;             // the distinct VARIANCE columns, in first-use order (the pass binds them in the same order)
+  unsigned long long rows = 1;       // GROUP BY: raw group ids
+};
+// Every reason a VARIANCE query is declined for, from the query and the segment's metadata alone (pg_query_check and pg_execute both come
+// through here), and the two queries that answer it.
+static pg_status plan_moments(const pg_segment* seg, const pg_query* q, MomentsPlan* plan) {
+  if (!g_engine.initialized) return fail(PG_ERR_NOT_INITIALIZED, "pg_init has not been called");
+  const int num_cols_total = (int)seg->cols.size();
+  const int na = q->num_aggregations, ng = q->num_group_by;
+  const bool null_handling = (q->flags & PG_QUERY_NULL_HANDLING) != 0;
+  if (na < 0 || ng < 0 || (ng > 0 && !q->group_by_columns)) return fail(PG_ERR_INVALID_ARGUMENT, "bad aggregation / group-by lists");
+  if (q->num_filter_nodes > 0 && (!q->filter || !q->predicates)) return fail(PG_ERR_INVALID_ARGUMENT, "filter nodes without predicates");
+  std::vector<int> projected;
+  auto project = [&](int c) { if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c); };
+  for (int a = 0; a < na; ++a) {
+    const pg_aggregation& ag = q->aggregations[a];
+    if (ag.function == PG_AGG_COUNT) { if (null_handling && ag.column >= 0) project(ag.column); continue; }
+    if (ag.function == PG_AGG_DISTINCTCOUNT || ag.function == PG_AGG_PERCENTILE || is_hll_function(ag.function))
+      return fail(PG_ERR_UNSUPPORTED, "%s beside VARIANCE in one query -- CPU plan", ag.function == PG_AGG_PERCENTILE ? "PERCENTILE" : (ag.function == PG_AGG_DISTINCTCOUNT ? "DISTINCTCOUNT" : "DISTINCTCOUNTHLL"));
+    if (ag.column < 0 || ag.column >= num_cols_total) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation column %d out of range", ag.column);
+    project(ag.column);
+    if (!is_moments_function(ag.function)) continue;
+    const ColumnDev& col = seg->cols[(size_t)ag.column];
+    if (null_handling && col.d_null_bitmap != nullptr)
+      return fail(PG_ERR_UNSUPPORTED, "VARIANCE on column %s, which carries a null value vector, under null handling -- CPU plan", col.name.c_str());
+    const bool dict = col.encoding == PG_FWD_FIXED_BIT_DICT;
+    if ((!dict && col.encoding != PG_FWD_RAW_FIXED_BYTE) || col.stored_type < PG_TYPE_INT || col.stored_type > PG_TYPE_DOUBLE || col.d_fwd == nullptr ||
+        (dict && (col.vkind == kValI32 ? (const void*)col.d_dict : (const void*)col.d_dict64) == nullptr))
+      return fail(PG_ERR_UNSUPPORTED, "VARIANCE on column %s: neither a dictionary-encoded nor a raw fixed-width INT / LONG / FLOAT / DOUBLE column -- CPU plan", col.name.c_str());
+    // GROUP BY on a raw LONG column: the ordinary query's table slot is one wrapping int64 (a dictionary column of such values is declined by the
+    // ordinary query itself).  moments_pivot undoes a wrap while numDocs x (max - min) stays below 2^64; beyond that no pivot can be trusted.
+    if (ng > 0 && !dict && col.stored_type == PG_TYPE_LONG && col.raw_max >= col.raw_min &&
+        (double)seg->num_docs * std::max(std::fabs((double)col.raw_min), std::fabs((double)col.raw_max)) >= 9.2e18 &&
+        (double)seg->num_docs * ((double)col.raw_max - (double)col.raw_min) >= 1.8e19)
+      return fail(PG_ERR_UNSUPPORTED, "VARIANCE grouped on raw LONG column %s, whose group sums could wrap int64 beyond repair -- CPU plan", col.name.c_str());
+    if (std::find(plan->cols.begin(), plan->cols.end(), ag.column) == plan->cols.end()) plan->cols.push_back(ag.column);
+  }
+  if ((int)plan->cols.size() > kMaxAggCols) return fail(PG_ERR_UNSUPPORTED, "more than %d VARIANCE columns -- CPU plan", kMaxAggCols);
+  bool match_all = false, filter_stages_set = false;
+  pg_status st = plan_pass_filter(seg, q, "VARIANCE", &match_all, &filter_stages_set); if (st != PG_OK) return st;
+  if (ng > 0) {
+    st = plan_pass_keys(seg, q, "VARIANCE", &projected, &plan->rows); if (st != PG_OK) return st;
+    // S1, S2 and the pivot of every (raw group id, column)
+    const unsigned long long matrix = plan->rows * 24ull * (unsigned long long)plan->cols.size();
+    if (matrix > PG_MOMENTS_GROUP_MAX_BYTES)
+      return fail(PG_ERR_UNSUPPORTED, "VARIANCE moment matrices of %llu bytes exceed PG_MOMENTS_GROUP_MAX_BYTES (%llu) -- CPU plan", matrix, (unsigned long long)PG_MOMENTS_GROUP_MAX_BYTES);
+    if (matrix > g_engine.group_table_bytes)
+      return fail(PG_ERR_UNSUPPORTED, "VARIANCE moment matrices of %llu bytes exceed the %llu-byte budget (PINOT_GPU_GROUP_TABLE_BYTES) -- CPU plan", matrix, (unsigned long long)g_engine.group_table_bytes);
+  }
+  plan->num_projected = (int)projected.size();
+  plan->pass_alone = false;
+  return split_pass_query(seg, q, plan, is_moments_function, kQueryDistinctPass | kQueryMomentsPass, true, PG_AGG_AVG);
+}
+// m2 of n values from the pivoted moments.  Rounding can leave it a hair below zero (a constant column): raised to 0.  NaN stays NaN -- a NaN or an
+// infinity among the values makes sum, the pivot and both moments non-finite, as it makes the reference's m2 (inf - inf).
+static double moments_m2(double s1, double s2, int64_t n) {
+  if (n <= 0) return 0.0;
+  const double m2 = s2 - s1 * s1 / (double)n;
+  return m2 < 0.0 ? 0.0 : m2;
+}
+// The pivot of one row: sum / count as a double.  A group-by's SUM of a raw LONG column is an int64 that wraps without telling (the aggregation-only
+// path reports the double image of a wrapped sum instead); the true sum lies in [count x min, count x max] of the column, and plan_moments kept
+// that interval narrower than 2^64: the one multiple of 2^64 that brings the sum back into it is added here.  (pg_agg_value.sum itself stays what
+// PG_AGG_SUM reports.)
+static double moments_pivot(const ColumnDev& col, const pg_agg_value& v, bool grouped) {
+  if (grouped && col.encoding == PG_FWD_RAW_FIXED_BYTE && col.stored_type == PG_TYPE_LONG && col.raw_max >= col.raw_min) {
+    const __int128 lo = (__int128)v.count * (__int128)col.raw_min, hi = (__int128)v.count * (__int128)col.raw_max, wrap = (__int128)1 << 64;
+    __int128 s = (__int128)v.sum_i64;
+    if (s < lo) s += (lo - s + wrap - 1) / wrap * wrap;
+    else if (s > hi) s -= (s - hi + wrap - 1) / wrap * wrap;
+    return (double)s / (double)v.count;
+  }
+  return v.sum / (double)v.count;
+}
+static void moments_agg_value(pg_agg_value* v) { v->min = std::numeric_limits<double>::infinity(); v->max = -std::numeric_limits<double>::infinity(); }
+
+static pg_status execute_moments(pg_segment* seg, const pg_query* q, pg_result* out) {
+  if (!out) return fail(PG_ERR_INVALID_ARGUMENT, "null result");
+  memset(out, 0, sizeof(*out));
+  if (!seg || !q) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  MomentsPlan plan;
+  pg_status st = plan_moments(seg, q, &plan);
+  if (st != PG_OK) return st;
+  const int na = q->num_aggregations;
+  const bool grouped = q->num_group_by > 0;
+  const size_t cols = plan.cols.size();
+  // 1. the ordinary query: count and sum per row
+  st = execute_one(seg, &plan.base, out, nullptr); if (st != PG_OK) return st;
+  if (grouped && out->group_key_kind != 0) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "VARIANCE: the ordinary query grouped over a key space of kind %d", (int)out->group_key_kind); }
+  // 2. the pivots, by raw group id (rows without a doc keep 0)
+  std::vector<int> col_of((size_t)std::max(na, 1), -1);
+  for (int a = 0; a < na; ++a)
+    if (is_moments_function(q->aggregations[a].function)) col_of[(size_t)a] = (int)(std::find(plan.cols.begin(), plan.cols.end(), q->aggregations[a].column) - plan.cols.begin());
+  std::vector<double> pivots((size_t)plan.rows * cols, 0.0);
+  bool any = false;
+  const int num_rows_out = grouped ? out->num_groups : 1;
+  for (int k = 0; k < num_rows_out; ++k) {
+    const int64_t row = grouped ? out->group_ids[k] : 0;
+    if (row < 0 || (unsigned long long)row >= plan.rows) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the VARIANCE matrix of %llu rows", (long long)row, plan.rows); }
+    for (int a = 0; a < na; ++a) {
+      if (col_of[(size_t)a] < 0) continue;
+      pg_agg_value* v = grouped ? &out->group_aggregations[(size_t)k * (size_t)na + (size_t)a] : &out->aggregations[a];
+      moments_agg_value(v);
+      if (v->count > 0) { pivots[(size_t)row * cols + (size_t)col_of[(size_t)a]] = moments_pivot(seg->cols[(size_t)q->aggregations[a].column], *v, grouped); any = true; }
+    }
+  }
+  std::unique_ptr<ResultInternal> sets(new ResultInternal());
+  if (!any) {
+    // no doc behind the filter: every tuple is (0, 0, 0), nothing is launched
+    for (int a = 0; a < na; ++a) {
+      if (col_of[(size_t)a] < 0) continue;
+      MomentsSet ms;
+      ms.aggregation = a; ms.rows = num_rows_out; ms.m2.assign((size_t)num_rows_out, 0.0);
+      sets->moments.push_back(std::move(ms));
+    }
+    out->internal = sets.release();
+    return PG_OK;
+  }
+  // 3. the moments pass behind the same filter
+  pg_result pass;
+  memset(&pass, 0, sizeof(pass));
+  t_moments_pivots = &pivots;
+  st = execute_one(seg, &plan.pass, &pass, nullptr);
+  t_moments_pivots = nullptr;
+  if (st != PG_OK) { pg_result_free(out); return st; }
+  out->device_ms += pass.device_ms;
+  if (pass.dominant_kernel_ms >= out->dominant_kernel_ms) { out->dominant_kernel_ms = pass.dominant_kernel_ms; out->dominant_kernel = pass.dominant_kernel; }
+  std::unique_ptr<ResultInternal> got(static_cast<ResultInternal*>(pass.internal));
+  pass.internal = nullptr;
+  const int64_t pass_docs = pass.stats.num_docs_scanned;
+  pg_result_free(&pass);
+  if (!got || got->moments.empty()) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "the VARIANCE pass returned no moments"); }
+  if (pass_docs != out->stats.num_docs_scanned) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "the VARIANCE pass saw %lld docs, the ordinary query %lld", (long long)pass_docs, (long long)out->stats.num_docs_scanned); }
+  // 4. the harvest: m2 per row (GROUP BY: the rows of the groups the ordinary query reports)
+  for (MomentsSet& m : got->moments) {
+    if (!grouped) {
+      if (m.m2.size() != 2) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "VARIANCE: %zu moments for one row", m.m2.size()); }
+      m.m2 = {moments_m2(m.m2[0], m.m2[1], out->aggregations[m.aggregation].count)};
+      m.rows = 1;
+    } else {
+      std::vector<double> m2((size_t)out->num_groups, 0.0);
+      int64_t bad_row = 0;
+      const bool kept = keep_group_rows(out, &m.m2, m.rows, 2, &bad_row, [&](int k, const double* row) {
+        m2[(size_t)k] = moments_m2(row[0], row[1], out->group_aggregations[(size_t)k * (size_t)na + (size_t)m.aggregation].count);
+      });
+      if (!kept) { pg_result_free(out); return fail(PG_ERR_INTERNAL, "group id %lld outside the VARIANCE matrix of %d rows, or out of order", (long long)bad_row, m.rows); }
+      m.m2 = std::move(m2);
+      m.rows = out->num_groups;
+    }
+    sets->moments.push_back(std::move(m));
   }
   out->internal = sets.release();
   return PG_OK;
@@ -6859,6 +7137,7 @@ pg_status finish_deferred(DeferredLaunch* L, std::vector<Deferred>& defs, pg_res
 pg_status pg_execute(pg_segment* segment, const pg_query* query, pg_result* out_result) {
   if (reserved_flags(query)) { if (out_result) memset(out_result, 0, sizeof(*out_result)); return fail_reserved_flags(query); }
   if (const pg_aggregation* bad = bad_function_word(query)) { if (out_result) memset(out_result, 0, sizeof(*out_result)); return fail_function_word(bad); }
+  if (has_moments(query)) return execute_moments(segment, query, out_result);
   if (has_percentile(query)) return execute_percentile(segment, query, out_result);
   if (has_distinct(query)) return execute_distinct(segment, query, out_result);
   // (PG_CFG_PROFILE_WAVES: the per-wave phase counters live in the kernels execute_one launches itself, and its HIP events bracket ALL of a
@@ -6944,8 +7223,8 @@ pg_status pg_execute_batch(pg_segment* const* segments, const pg_query* const* q
     const pg_query* q = queries[i];
     std::shared_ptr<const OwnedQuery> copy;
     if (!keys.empty() && !keys[(size_t)i].empty()) { copy = own_query(q); q = &copy->q; }
-    // (a DISTINCTCOUNT / PERCENTILE item runs as a pg_execute of its own: no shared launch)
-    statuses[i] = has_percentile(q) ? execute_percentile(segments[i], q, &results[i]) : has_distinct(q) ? execute_distinct(segments[i], q, &results[i]) : execute_one(segments[i], q, &results[i], g_engine.batch_launch ? &defs[(size_t)i] : nullptr);
+    // (a DISTINCTCOUNT / PERCENTILE / VARIANCE item runs as a pg_execute of its own: no shared launch)
+    statuses[i] = has_moments(q) ? execute_moments(segments[i], q, &results[i]) : has_percentile(q) ? execute_percentile(segments[i], q, &results[i]) : has_distinct(q) ? execute_distinct(segments[i], q, &results[i]) : execute_one(segments[i], q, &results[i], g_engine.batch_launch ? &defs[(size_t)i] : nullptr);
     if (statuses[i] == kDeferred && copy && defs[(size_t)i].cacheable) remember_item(segments[i], std::move(keys[(size_t)i]), copy, &defs[(size_t)i]);
     else if (statuses[i] == kDeferred && copy) std::const_pointer_cast<LoweredItem>(defs[(size_t)i].item)->query = copy;
     if (trace) item_us[(size_t)i] = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t_item).count();
@@ -7112,6 +7391,7 @@ pg_status pg_query_check(const pg_segment* segment, const pg_query* query) {
   if (!segment || !query) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
   if (reserved_flags(query)) return fail_reserved_flags(query);
   if (const pg_aggregation* bad = bad_function_word(query)) return fail_function_word(bad);
+  if (has_moments(query)) { MomentsPlan plan; return plan_moments(segment, query, &plan); }
   if (has_percentile(query)) { PercentilePlan plan; return plan_percentile(segment, query, &plan); }
   if (has_distinct(query)) { DistinctPlan plan; return plan_distinct(segment, query, &plan); }
   return check_ordinary_query(segment, query);
@@ -7146,6 +7426,22 @@ pg_status pg_result_hll_registers(const pg_result* result, int32_t aggregation, 
     return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
   *out_registers = hs->registers.data() + ((size_t)(grouped ? group_row : 0) << hs->log2m);
   *out_num_registers = 1 << hs->log2m;
+  return PG_OK;
+}
+
+pg_status pg_result_moments(const pg_result* result, int32_t aggregation, int32_t group_row, int64_t* out_count, double* out_sum, double* out_m2) {
+  if (!result || !out_count || !out_sum || !out_m2) return fail(PG_ERR_INVALID_ARGUMENT, "null argument");
+  *out_count = 0; *out_sum = 0.0; *out_m2 = 0.0;
+  const ResultInternal* sets = static_cast<const ResultInternal*>(result->internal);
+  if (aggregation < 0 || aggregation >= result->num_aggregations) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d out of range", aggregation);
+  const MomentsSet* ms = nullptr;
+  if (sets) for (const MomentsSet& s : sets->moments) if (s.aggregation == aggregation) ms = &s;
+  if (!ms) return fail(PG_ERR_INVALID_ARGUMENT, "aggregation %d is not a PG_AGG_VARIANCE", aggregation);
+  const bool grouped = result->group_aggregations != nullptr;
+  if (grouped ? (group_row < 0 || group_row >= result->num_groups || group_row >= ms->rows) : group_row != -1)
+    return fail(PG_ERR_INVALID_ARGUMENT, "group row %d out of range", group_row);
+  const pg_agg_value& v = grouped ? result->group_aggregations[(size_t)group_row * (size_t)result->num_aggregations + (size_t)aggregation] : result->aggregations[aggregation];
+  *out_count = v.count; *out_sum = v.sum; *out_m2 = ms->m2[(size_t)(grouped ? group_row : 0)];
   return PG_OK;
 }
 

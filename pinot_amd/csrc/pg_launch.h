@@ -174,6 +174,14 @@ void launch_hll_fold(long long rows, hipStream_t stream, HllFoldParams fp);
 // hll_pack_kernel: n staged 32-bit registers (a multiple of four) -> n bytes
 void launch_hll_pack(const uint32_t* words, uint8_t* bytes, unsigned long long n, int num_cus, hipStream_t stream);
 
+// scan_moments_kernel: the pivoted moments {sum(x - c), sum((x - c)^2)} of up to kMaxAggCols raw or dictionary columns, one record per workgroup and
+// column (workgroups of 256; `lds`: the filter's set area + the reduction scratch) -- pg_scan_moments.h
+void launch_scan_moments(int blocks, size_t lds, hipStream_t stream, const MomentsParams& mp);
+int waves_scan_moments();
+// group_moments_kernel: the same under GROUP BY, one {S1, S2} row per raw group id in HBM, the pivots read from an uploaded array
+void launch_group_moments(int blocks, size_t lds, hipStream_t stream, const MomentsParams& mp);
+int waves_group_moments();
+
 // scan_private_typed_kernel: lane-private scan for raw / 8-byte aggregated columns (pg_scan_typed.h)
 void launch_scan_private_typed(int agg_cols, int blocks, hipStream_t stream, const ScanParams& p);      // instantiated for 1, 2 and kMaxAggCols slots
 int waves_scan_private_typed(int agg_cols);

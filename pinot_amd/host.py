@@ -352,6 +352,44 @@ def combine_hll(sql, blocks, key_types=()):
     return _take_json(lib, lib.ph_combine_hll(sql.encode(), len(blocks), br, kt, kl, kd, ks, kn, counts, sums, mins, maxs, nulls, ro.ctypes.data, rb.ctypes.data, C.byref(st)), st)
 
 
+def combine_moments(sql, blocks, key_types=()):
+    """The combine of VarianceTuples built on the host (no device): ph_combine_moments.  `blocks` as for combine_counts; the cell of a VAR_POP /
+    VAR_SAMP / STDDEV_POP / STDDEV_SAMP function is (count, sum, min, max, is_null, m2): its tuple is (count, sum, m2)."""
+    lib = _lib()
+    P = C.POINTER
+    lib.ph_combine_moments.restype = C.c_void_p
+    lib.ph_combine_moments.argtypes = [C.c_char_p, C.c_int32, P(C.c_int64), P(C.c_int32), P(C.c_int64), P(C.c_double), P(C.c_char_p), P(C.c_uint8), P(C.c_int64),
+                                       P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_uint8), P(C.c_double), P(C.c_int32)]
+    rows = [r for b in blocks for r in b]
+    nk = len(key_types)
+    nf = len(rows[0][1]) if rows else 1
+    nr = len(rows)
+    br = (C.c_int64 * max(len(blocks), 1))(*[len(b) for b in blocks])
+    kt = (C.c_int32 * max(nk, 1))(*key_types)
+    kl, kd, ks, kn = (C.c_int64 * max(nr * nk, 1))(), (C.c_double * max(nr * nk, 1))(), (C.c_char_p * max(nr * nk, 1))(), (C.c_uint8 * max(nr * nk, 1))()
+    counts, sums, m2s = (C.c_int64 * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))()
+    mins, maxs, nulls = (C.c_double * max(nr * nf, 1))(), (C.c_double * max(nr * nf, 1))(), (C.c_uint8 * max(nr * nf, 1))()
+    for r, (key_values, cells) in enumerate(rows):
+        for k, v in enumerate(key_values):
+            at = r * nk + k
+            if v is None:
+                kn[at] = 1
+                ks[at] = b""
+            elif key_types[k] in (KEY_INT, KEY_LONG):
+                kl[at] = int(v)
+            elif key_types[k] == KEY_STRING:
+                ks[at] = str(v).encode()
+            else:
+                kd[at] = float(v)
+        for f, cell in enumerate(cells):
+            c, s, mn, mx, is_null = cell[:5]
+            at = r * nf + f
+            counts[at], sums[at], mins[at], maxs[at], nulls[at] = int(c), float(s), float(mn), float(mx), int(bool(is_null))
+            m2s[at] = float(cell[5]) if len(cell) > 5 else 0.0
+    st = C.c_int32()
+    return _take_json(lib, lib.ph_combine_moments(sql.encode(), len(blocks), br, kt, kl, kd, ks, kn, counts, sums, mins, maxs, nulls, m2s, C.byref(st)), st)
+
+
 def hll_cardinality(registers):
     """HyperLogLog.cardinality() of 2^log2m registers, computed by the host mirror (pinot_amd/csrc/pg_hll.h)."""
     import numpy as np

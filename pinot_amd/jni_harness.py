@@ -193,6 +193,18 @@ class FakeJvm:
         finally:
             self.release(*arrays)
 
+    def execute_with_moments(self, handle, spec):
+        """PinotGpuNative.executeWithMoments: [the Object[PGM_RESULT_ARRAYS] as numpy arrays, the m2 of every VarianceTuple: float64 at aggregation * rows + row]."""
+        arrays, limit, flags = self.query_arrays(spec)
+        try:
+            out = self.call("executeWithMoments", C.c_void_p, C.c_int64(handle), *arrays, C.c_int32(limit), C.c_int32(flags))
+            try:
+                return self.to_python(out)
+            finally:
+                self.release(C.c_void_p(out))
+        finally:
+            self.release(*arrays)
+
     def execute_with_percentile_counts(self, handle, spec):
         """PinotGpuNative.executeWithPercentileCounts: [the Object[PGM_RESULT_ARRAYS] as numpy arrays, the lists' dictIds, their counts: aggregation * rows + row ->
         int32 array or None]."""

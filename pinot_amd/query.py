@@ -119,6 +119,7 @@ COUNT, SUM, MIN, MAX, AVG = _abi.PG_AGG_COUNT, _abi.PG_AGG_SUM, _abi.PG_AGG_MIN,
 DISTINCTCOUNT = _abi.PG_AGG_DISTINCTCOUNT      # on a dictionary-encoded column: the set of dictIds (AggValue.dict_ids); on a raw column: AggValue.value_counts
 PERCENTILE = _abi.PG_AGG_PERCENTILE            # on a dictionary-encoded column: the value list as (dictIds, counts) (AggValue.dict_id_counts); raw: AggValue.value_counts
 DISTINCTCOUNTHLL = _abi.PG_AGG_DISTINCTCOUNTHLL  # on a dictionary-encoded or raw column: the 2^log2m HyperLogLog registers (AggValue.hll_registers)
+VARIANCE = _abi.PG_AGG_VARIANCE                # VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: the VarianceTuple (count, sum, m2) (AggValue.moments)
 
 
 def hll(log2m=_abi.PG_HLL_DEFAULT_LOG2M):
@@ -202,9 +203,9 @@ class QuerySpec:
 
 
 class AggValue:
-    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max", "dict_ids", "dict_id_counts", "value_counts", "hll_registers")
+    __slots__ = ("count", "sum", "sum_i64", "sum_exact", "min", "max", "dict_ids", "dict_id_counts", "value_counts", "hll_registers", "moments")
 
-    def __init__(self, v, dict_ids=None, dict_id_counts=None, value_counts=None, hll_registers=None):
+    def __init__(self, v, dict_ids=None, dict_id_counts=None, value_counts=None, hll_registers=None, moments=None):
         self.count, self.sum, self.sum_i64, self.sum_exact, self.min, self.max = (
             int(v.count), float(v.sum), int(v.sum_i64), bool(v.sum_exact), float(v.min), float(v.max))
         self.dict_ids = dict_ids      # DISTINCTCOUNT: the sorted dictIds of the set (numpy int32); None for every other function
@@ -212,12 +213,15 @@ class AggValue:
         # PERCENTILE / DISTINCTCOUNT on a RAW column: (ascending value bits int64, their non-zero counts uint32) -- pg_result_value_counts; None otherwise
         self.value_counts = value_counts
         self.hll_registers = hll_registers      # DISTINCTCOUNTHLL: the 2^log2m registers, one rank per byte (numpy uint8); None for every other function
+        self.moments = moments                  # VARIANCE: the VarianceTuple (count, sum, m2) of pg_result_moments; None for every other function
 
     def intermediate(self, function):
         """The reference's intermediate result type: COUNT -> Long, SUM/MIN/MAX -> Double, AVG -> (sum, count), DISTINCTCOUNT -> the
         segment's dictId set (the values behind it are what segments merge: dictIds differ from segment to segment)."""
         if is_hll(function):
             return self.hll_registers
+        if function == VARIANCE:
+            return self.moments
         if function == DISTINCTCOUNT:
             return self.dict_ids if self.value_counts is None else self.value_counts[0]
         if function == PERCENTILE:
@@ -292,12 +296,20 @@ class Result:
             _abi.check(the_lib, the_lib.pg_result_hll_registers(C.byref(res), a, row, C.byref(regs), C.byref(n)))
             return np.ctypeslib.as_array(regs, shape=(n.value,)).copy()
 
+        def moments(a, row):
+            if self.functions[a] != VARIANCE:
+                return None
+            the_lib = lib if lib is not None else _abi.load_gpu_library()
+            n, total, m2 = C.c_int64(), C.c_double(), C.c_double()
+            _abi.check(the_lib, the_lib.pg_result_moments(C.byref(res), a, row, C.byref(n), C.byref(total), C.byref(m2)))
+            return int(n.value), float(total.value), float(m2.value)
+
         class _Lists(dict):
             def __missing__(self, key):
                 self[key] = value_counts(*key)
                 return self[key]
         raw_lists = _Lists()
-        self.aggregations = [AggValue(res.aggregations[a], dict_ids(a, -1), dict_id_counts(a, -1), raw_lists[(a, -1)], hll_registers(a, -1)) for a in range(na)] if res.aggregations else []
+        self.aggregations = [AggValue(res.aggregations[a], dict_ids(a, -1), dict_id_counts(a, -1), raw_lists[(a, -1)], hll_registers(a, -1), moments(a, -1)) for a in range(na)] if res.aggregations else []
         self.groups = {}
         self.group_id_upper_bound = int(res.group_id_upper_bound)
         self.num_groups_limit_reached = bool(res.num_groups_limit_reached)
@@ -310,7 +322,7 @@ class Result:
             tup = tuple(int(res.group_key_dict_ids[g * ng + j]) for j in range(ng)) if res.group_key_dict_ids else None
             self.group_keys.append(tup)
             gid = int(res.group_ids[g]) if self.group_key_kind == 0 else tup
-            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a], dict_ids(a, g), dict_id_counts(a, g), raw_lists[(a, g)], hll_registers(a, g)) for a in range(na)]
+            self.groups[gid] = [AggValue(res.group_aggregations[g * na + a], dict_ids(a, g), dict_id_counts(a, g), raw_lists[(a, g)], hll_registers(a, g), moments(a, g)) for a in range(na)]
         self.group_ids64 = [int(res.group_ids64[g]) for g in range(int(res.num_groups))] if (self.group_key_kind == 1 and res.group_ids64) else None
 
     def intermediates(self):

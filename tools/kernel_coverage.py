@@ -553,6 +553,53 @@ def main():
                     except AssertionError as e:
                         failed.append({"id": eid, "error": str(e)[:300]})
                 ran += 1
+    # ---- VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (pg_scan_moments.h): scan_moments_kernel and group_moments_kernel over raw and dictionary
+    # columns, with and without keys, behind a range leaf and behind an IN leaf.  The oracle has no such function: the tuples are held against the exact
+    # model of tests/moments_cases.py (its derived tolerance) over the docs oracle.filter_bitmap matches, every other function against the oracle.
+    if only is None or only.search("moments"):
+        import moments_cases as MC
+        ids = lambda s, card: S.synthetic_dict_ids(1000 + s, 0, n, card)
+        MC.set_values(seg, RI, (ids(10, 1_000_000) - 500_000).astype(np.int32))
+        MC.set_values(seg, RL, (ids(11, 1 << 20).astype(np.int64) - (1 << 19)) * ((1 << 20) + 3))
+        MC.set_values(seg, RD, (ids(12, 1 << 20).astype(np.float64) - (1 << 19)) * 0.37)
+        MC.set_values(seg, W8, irregular(100000, 11)[ids(4, 100000)])
+        MC.set_values(seg, DL, ((np.arange(500, dtype=np.int64) - 250) * (2 ** 33 + 7))[ids(13, 500)])
+        MC.set_values(seg, A, (np.arange(200, dtype=np.int32) * 2 - 100)[ids(7, 200)])
+        in_list = Q.leaf(Q.Pred.dict_set(F, list(range(0, 300, 3)), 1000))
+        f500 = Q.leaf(Q.Pred.dict_range(F, 0, 500))
+        shapes = (("scan-raw", Q.QuerySpec([(Q.VARIANCE, RL), (Q.VARIANCE, RI), (Q.VARIANCE, RD), (Q.SUM, RD), (Q.COUNT, -1)], filter=in_list), "scan_moments_kernel"),
+                  ("scan-dict", Q.QuerySpec([(Q.VARIANCE, W8), (Q.VARIANCE, DL), (Q.VARIANCE, RI), (Q.MAX, W8), (Q.COUNT, -1)], filter=f500), "scan_moments_kernel"),
+                  ("group-raw", Q.QuerySpec([(Q.VARIANCE, RD), (Q.SUM, V), (Q.VARIANCE, RI)], filter=f500, group_by=[B, C2]), "group_moments_kernel"),
+                  ("group-dict", Q.QuerySpec([(Q.VARIANCE, A), (Q.SUM, V), (Q.VARIANCE, W8), (Q.VARIANCE, RL)], filter=in_list, group_by=[B]), "group_moments_kernel"))
+        with engine.open(seg) as g:
+            for sid, spec, family in shapes:
+                eid = "moments-%s" % sid
+                if g.check(spec) != 0:
+                    failed.append({"id": eid, "error": "pg_query_check declined"})
+                    continue
+                oracle_spec = MC.without_variance(spec)
+                for rep in range(2):
+                    got = g.execute(spec)
+                    try:
+                        MC.assert_moments(got, seg, spec, where=eid, quiet=True)
+                        want = want_of(eid, oracle_spec)
+                        for a, (fn, _) in enumerate(spec.aggregations):
+                            if fn == Q.VARIANCE:
+                                continue
+                            if spec.group_by:
+                                assert sorted(got.groups) == sorted(want.groups), "group ids differ"
+                                for gid in want.groups:
+                                    H.assert_agg_equal(got.groups[gid][a], want.groups[gid][a], fn, "group %r agg %d" % (gid, a))
+                            else:
+                                H.assert_agg_equal(got.aggregations[a], want.aggregations[a], fn, "agg %d" % a)
+                        assert got.stats[0] == want.stats[0] and got.stats[3] == want.stats[3], (got.stats, want.stats)
+                        if not flipped:
+                            # the ordinary query runs too: dominant_kernel is the pass's kernel or the ordinary query's own, whichever took longer
+                            ordinary = g.execute(oracle_spec).dominant_kernel
+                            assert got.dominant_kernel in (family, ordinary), "dominant kernel %s, expected %s or %s" % (got.dominant_kernel, family, ordinary)
+                    except AssertionError as e:
+                        failed.append({"id": eid, "error": str(e)[:300]})
+                ran += 1
     # ---- LZ4 / SNAPPY raw columns (pg_chunk_decode.h): chunk_decode_kernel<codec> at pg_segment_open, more chunks than waves in flight (1 000-doc
     # chunks: 101 of them for the 32 waves of one CU, 12 301 for the 8 192 of the whole chip).  The oracle declines compressed files: the raw-range SUM
     # on the compressed column is held against the oracle on the same values written PASS_THROUGH.  The chunks repeat sixteen contents, so that
